@@ -16,13 +16,20 @@ instead of 8 significand bits per stored value: it is the 16-bit mode that meets
 reference arithmetic" (7.4e-4 against the float64 oracle at this very size, tests/test_gpu_fullsize_oracle.py; bf16: 6e-3).  The
 bf16 step is timed the same way and reported under extras.bf16_mode; the line's "precision" object states mode and tolerance.
 
-Timing: ``--blocks`` (default 5) blocks of exactly K steps, each bracketed by barrier + torch.cuda.synchronize() on both sides, the
-maximum over ranks per block; the line reports the MEDIAN block (steps = K, ms_per_step = median block / K) and lists all blocks:
-one 60 ms block alone decides nothing below the +-3 % the boxes differ by.
+Timing: W warm-up steps, then K timed steps, bracketed by barrier + torch.cuda.synchronize() on both sides, the maximum over ranks;
+ms_per_step = that time / K.  ``--blocks B`` (default 1) repeats the timed block B times (B x K timed steps) and reports the MEDIAN
+block: one 60 ms block alone decides nothing below the +-3 % that machines differ by.
 
-Extra objects on the JSON line: "roofline" (dominant GEMM family, HIP events on the launch stream), "precision", "timing",
-"data_parallel" (N > 1: backend, per-rank ms, un-hidden all-reduce time) and "cpu_baseline" (the CPU oracle's fp32 training step on
-a bounded sample, rank 0 at N = 1 only).
+A plain run does only that: set up, warm up, time, write ``--dump-outputs DIR`` if given, print the line ("metric", "value", "timing",
+and "data_parallel" at N > 1: backend, per-rank ms, un-hidden all-reduce time).  ``--full`` adds everything measured beside the headline,
+each after the timed region: "roofline" (dominant GEMM family from a serial attribution pass, HIP events on the launch stream; traffic
+from two rocprofv3 --pmc passes; the sustained MFMA rate; the vendor GEMM), "precision" and "extras" (other storage modes, losses,
+configurations and the evaluation figures) and "cpu_baseline" (the CPU oracle's fp32 training step on a bounded sample); the last
+three at rank 0, N = 1 only.
+
+``--dump-outputs DIR``: what the last timed step handed its caller, as float32 .npy files in DIR (12.4 MB at cfg-A): loss_acc,
+pred (one distance per pair), emb (both towers' embeddings), and the state the step left -- params, adam_m, adam_v (flat fp32
+buffers) and bn_moving (BatchNorm moving statistics).  Inputs and initial weights are seeded, so equal arguments give equal inputs.
 """
 import argparse
 import json
@@ -78,6 +85,17 @@ def timed(fn, reps=10, warm=2):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t1) / reps
+
+
+def dump_outputs(d, eng, pl, pairs):
+    """--dump-outputs: what the last timed step handed its caller (the plan's head outputs and the engine's state after the update),
+    float32, one DIR/<name>.npy per array."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"loss_acc": pl["loss_acc"], "pred": pl["pred"][:pairs], "emb": pl["emb"],
+              "params": eng.P, "adam_m": eng.M, "adam_v": eng.V, "bn_moving": eng.NT}
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 def snapshot(eng):
@@ -220,7 +238,7 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=5, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--blocks", type=int, default=1, help="timed blocks of --steps steps; the median block is reported")
     ap.add_argument("--pairs", type=int, default=128, help="pairs per GPU (cfg: 128)")
     ap.add_argument("--dtype", default="f16", help="storage mode of the headline: f16 (default) | bf16 | f32s | f32")
     ap.add_argument("--loss", default="contrastive")
@@ -235,6 +253,9 @@ def main():
     ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed profiles/pmc_traffic.json instead of two "
                     "rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) run by this process on the serial step")
     ap.add_argument("--allow-nonfinite", action="store_true", help="timing experiments with ablated builds (tools/build_variant.sh): results are wrong by design")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure roofline, precision, extras and cpu_baseline "
+                    "(the --no-* switches above thin this out); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed to DIR/<name>.npy (float32)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "RANK" not in os.environ:
@@ -357,6 +378,8 @@ def main():
     # which more than a tenth of the steps did not update is not a training run
     n_skipped = int(eng.skipped_steps())
     assert n_skipped * 10 <= a.warmup + a.steps * len(block_s) or a.allow_nonfinite, "loss-scaled steps were skipped (non-finite gradients): %d" % n_skipped
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, eng, pl, pairs)
 
     value = 2 * pairs * n_gpus * a.steps * 3.0 / dt
     ms = dt / a.steps * 1e3
@@ -403,6 +426,87 @@ def main():
                                 "note": "rank_ms: each rank's own median block (before the closing barrier); unhidden: the optimizer-step "
                                         "stream's time inside / waiting for the two collectives (HIP events)"}
 
+    if a.full:
+        out["roofline"] = roofline(a, eng, step, dt, pairs, rank, n_gpus, dev)
+
+    if a.breakdown and rank == 0 and n_gpus == 1:  # its steps contain collectives: single-process runs only
+        names = ["vm_decimate_whiten", "vm_conv1_fused_fwd", "vm_conv1_fused_bwd", "vm_conv1_fwd", "vm_conv_fwd", "vm_bn_finalize", "vm_bn_drop_pool_fwd", "vm_bn_drop_pool_gmax_fwd",
+                 "vm_global_maxpool_fwd", "vm_dense_fwd", "vm_siamese_head_loss", "vm_dense_bwd", "vm_global_maxpool_bwd",
+                 "vm_bn_pool_bwd_reduce", "vm_bn_pool_bwd_reduce_pooled", "vm_bn_pool_bwd_reduce_gmax", "vm_bn_bwd_gmax_finalize", "vm_bn_bwd_from_sums", "vm_bn_bwd_from_sums_finalize", "vm_bn_bwd_finalize", "vm_bn_pool_bwd_apply",
+                 "vm_bn_pool_bwd_apply_gmax", "vm_colsum", "vm_du_tower_sums", "vm_fold_bn_weights", "vm_conv_wgrad",
+                 "vm_conv_dgrad", "vm_conv1_wgrad", "vm_grad_sqnorm", "vm_adam_clip_step", "vm_prep_conv_weights", "vm_prep_conv_weights_batch",
+                 "vm_bn_drop_pool_gmax_partials", "vm_tail_fwd_bwd", "vm_tail_param_grads", "vm_pack_nt_weights_batch", "vm_conv_wgrad_fold_finish"]
+        eng.timed = {nm: [] for nm in names}
+        was_overlap, eng.overlap_wgrad = eng.overlap_wgrad, False  # serial, so that every entry point is attributable
+        was_split2, eng.split_towers = eng.split_towers, False
+        snap1 = snapshot(eng)
+        reps = 3
+        for _ in range(reps):
+            step()
+        torch.cuda.synchronize()
+        rows = []
+        for nm in names:
+            r_ = eng.timed[nm]
+            tot = sum(e0.elapsed_time(e1) for e0, e1, _ in r_) / reps
+            rows.append((nm, len(r_) // reps, tot))
+        eng.timed = {}
+        eng.overlap_wgrad = was_overlap
+        eng.split_towers = was_split2
+        restore(eng, snap1)
+        with open(a.breakdown, "w") as f:
+            f.write("entry_point,launches_per_step,ms_per_step\n")
+            for nm, cnt, tot in sorted(rows, key=lambda r: -r[2]):
+                f.write("%s,%d,%.4f\n" % (nm, cnt, tot))
+            f.write("TOTAL_EVENT_MS,,%.4f\nWALL_MS_PER_STEP,,%.4f\n" % (sum(r[2] for r in rows), ms))
+            f.write("# breakdown steps run with the wgrad side stream off; WALL is the timed region (overlap %s); dtype %s\n" % ("on" if was_overlap else "off", a.dtype))
+
+    if a.full and rank == 0 and n_gpus == 1 and not a.no_extras:
+        out["extras"] = extras(a, eng, step, pl, xcat, y, pairs, dev, make_engine, make_step, time_blocks, out)
+
+    if a.full and rank == 0 and n_gpus == 1 and not a.no_cpu_baseline:
+        from oracle import voicemap_oracle as O
+        arch = O.EncoderArch.baseline(F, E, dropout=0.0)
+        cpu_pairs, cpu_steps = 8, 4
+        sec, threads = O.time_cpu_train_steps(arch, cpu_pairs, cpu_steps, loss=a.loss, threads=None)
+        trials = getattr(O.time_cpu_train_steps, "last_trials", {})
+        out["cpu_baseline"] = {"value": 2 * cpu_pairs * 3.0 / sec, "unit": "audio-s/s", "cores": threads, "kind": "port",
+                               "host_cpu_count": os.cpu_count() or 1,
+                               "threads_tried_ms_per_step": {str(k): round(v * 1e3, 1) for k, v in sorted(trials.items())},
+                               "full_batch_note": "the 128-pair batch of the GPU step is the CPU path's WORSE operating point: 10.0 / 11.3 / 17.8 s "
+                                                  "per step on 32 / 64 / 128 threads of the same 256-cpu host = 77 audio-s/s at best "
+                                                  "(tools/probe/cpu_full_batch.py, round 6) against 150-200 at 8 pairs -- the sample below is "
+                                                  "the batch that favours the CPU",
+                               "sample": "<=%d steps of %d pairs, cfg-A, same step definition (fp32 torch-CPU oracle, best of the "
+                                         "intra-op thread counts listed in threads_tried on a %d-cpu host: a batch of %d pairs does "
+                                         "not scale to every core; %.0f ms/step)"
+                                         % (cpu_steps, cpu_pairs, os.cpu_count() or 1, cpu_pairs, sec * 1e3)}
+        # the other two legs BASELINE.md 3 names, on the same host with the thread count the search above chose (bounded: ~10 s):
+        # the inference embedding pass (voicemap/utils.py:141-156) and BASELINE.json config 1, the classifier step at batch 8
+        # (experiments/train_classifier.py:110-127) -- each beside the GPU figure of the same work from this run's extras
+        try:
+            legs = {}
+            n_emb = 16
+            t_e = O.time_cpu_embed_only(arch, n_emb, 3, threads)
+            legs["embed_only"] = {"value": n_emb * 3.0 / t_e, "unit": "audio-s/s", "cores": threads, "kind": "port",
+                                  "sample": "%d windows of 3 s per pass, inference BatchNorm, fp32 (%.0f ms per pass)" % (n_emb, t_e * 1e3),
+                                  "gpu_value_this_run": (out.get("extras") or {}).get("embed_only_audio_s_per_s")}
+            n_cls, classes = 8, 40
+            t_c = O.time_cpu_classifier_steps(arch, n_cls, classes, 3, threads)
+            legs["classifier_step_batch8"] = {"value": n_cls * 3.0 / t_c, "unit": "audio-s/s", "cores": threads, "kind": "port",
+                                              "sample": "BASELINE.json config 1: train_on_batch of the speaker classifier (cfg-A encoder + "
+                                                        "Dense(%d, softmax), categorical CE, Adam(clipnorm 1)), batch %d of 3 s windows, "
+                                                        "fp32 (%.0f ms per step)" % (classes, n_cls, t_c * 1e3),
+                                              "gpu_value_this_run": (out.get("extras") or {}).get("classifier_batch8_audio_s_per_s")}
+            out["cpu_baseline"]["legs"] = legs
+        except Exception as e:   # a side figure never takes the line down
+            out["cpu_baseline"]["legs_error"] = repr(e)
+    if rank == 0:
+        print(json.dumps(out))
+
+
+def roofline(a, eng, step, dt, pairs, rank, n_gpus, dev):
+    """--full: the "roofline" object -- the dominant GEMM family of a serial attribution pass, its traffic, the sustained MFMA rate and
+    the vendor GEMM beside it.  Runs extra steps after the timed region and restores the state the timed steps left."""
     # ---- serial attribution pass (untimed, after the timed region): the same step with the weight-gradient GEMMs on the main
     # stream, every GEMM launch bracketed by HIP events on its launch stream; median over the repetitions per launch shape ----
     esize = 2 if a.dtype in ("bf16", "f16") else 4
@@ -531,81 +635,7 @@ def main():
             roof["vendor_gemm"] = {"error": repr(e)}
     roof["step_hbm_frac"] = TRAIN_BYTES_PER_WINDOW * (2 * pairs * a.steps / dt) / (HBM_PEAK_GBS * 1e9)
     roof["step_mfma_frac"] = TRAIN_FLOPS_PER_WINDOW * (2 * pairs * a.steps / dt) / (MFMA_16BIT_PEAK_TF * 1e12)
-    out["roofline"] = roof
-
-    if a.breakdown and rank == 0 and n_gpus == 1:  # its steps contain collectives: single-process runs only
-        names = ["vm_decimate_whiten", "vm_conv1_fused_fwd", "vm_conv1_fused_bwd", "vm_conv1_fwd", "vm_conv_fwd", "vm_bn_finalize", "vm_bn_drop_pool_fwd", "vm_bn_drop_pool_gmax_fwd",
-                 "vm_global_maxpool_fwd", "vm_dense_fwd", "vm_siamese_head_loss", "vm_dense_bwd", "vm_global_maxpool_bwd",
-                 "vm_bn_pool_bwd_reduce", "vm_bn_pool_bwd_reduce_pooled", "vm_bn_pool_bwd_reduce_gmax", "vm_bn_bwd_gmax_finalize", "vm_bn_bwd_from_sums", "vm_bn_bwd_from_sums_finalize", "vm_bn_bwd_finalize", "vm_bn_pool_bwd_apply",
-                 "vm_bn_pool_bwd_apply_gmax", "vm_colsum", "vm_du_tower_sums", "vm_fold_bn_weights", "vm_conv_wgrad",
-                 "vm_conv_dgrad", "vm_conv1_wgrad", "vm_grad_sqnorm", "vm_adam_clip_step", "vm_prep_conv_weights", "vm_prep_conv_weights_batch",
-                 "vm_bn_drop_pool_gmax_partials", "vm_tail_fwd_bwd", "vm_tail_param_grads", "vm_pack_nt_weights_batch", "vm_conv_wgrad_fold_finish"]
-        eng.timed = {nm: [] for nm in names}
-        was_overlap, eng.overlap_wgrad = eng.overlap_wgrad, False  # serial, so that every entry point is attributable
-        was_split2, eng.split_towers = eng.split_towers, False
-        snap1 = snapshot(eng)
-        reps = 3
-        for _ in range(reps):
-            step()
-        torch.cuda.synchronize()
-        rows = []
-        for nm in names:
-            r_ = eng.timed[nm]
-            tot = sum(e0.elapsed_time(e1) for e0, e1, _ in r_) / reps
-            rows.append((nm, len(r_) // reps, tot))
-        eng.timed = {}
-        eng.overlap_wgrad = was_overlap
-        eng.split_towers = was_split2
-        restore(eng, snap1)
-        with open(a.breakdown, "w") as f:
-            f.write("entry_point,launches_per_step,ms_per_step\n")
-            for nm, cnt, tot in sorted(rows, key=lambda r: -r[2]):
-                f.write("%s,%d,%.4f\n" % (nm, cnt, tot))
-            f.write("TOTAL_EVENT_MS,,%.4f\nWALL_MS_PER_STEP,,%.4f\n" % (sum(r[2] for r in rows), ms))
-            f.write("# breakdown steps run with the wgrad side stream off; WALL is the timed region (overlap %s); dtype %s\n" % ("on" if was_overlap else "off", a.dtype))
-
-    if rank == 0 and n_gpus == 1 and not a.no_extras:
-        out["extras"] = extras(a, eng, step, pl, xcat, y, pairs, dev, make_engine, make_step, time_blocks, out)
-
-    if rank == 0 and n_gpus == 1 and not a.no_cpu_baseline:
-        from oracle import voicemap_oracle as O
-        arch = O.EncoderArch.baseline(F, E, dropout=0.0)
-        cpu_pairs, cpu_steps = 8, 4
-        sec, threads = O.time_cpu_train_steps(arch, cpu_pairs, cpu_steps, loss=a.loss, threads=None)
-        trials = getattr(O.time_cpu_train_steps, "last_trials", {})
-        out["cpu_baseline"] = {"value": 2 * cpu_pairs * 3.0 / sec, "unit": "audio-s/s", "cores": threads, "kind": "port",
-                               "host_cpu_count": os.cpu_count() or 1,
-                               "threads_tried_ms_per_step": {str(k): round(v * 1e3, 1) for k, v in sorted(trials.items())},
-                               "full_batch_note": "the 128-pair batch of the GPU step is the CPU path's WORSE operating point: 10.0 / 11.3 / 17.8 s "
-                                                  "per step on 32 / 64 / 128 threads of the same 256-cpu host = 77 audio-s/s at best "
-                                                  "(tools/probe/cpu_full_batch.py, round 6) against 150-200 at 8 pairs -- the sample below is "
-                                                  "the batch that favours the CPU",
-                               "sample": "<=%d steps of %d pairs, cfg-A, same step definition (fp32 torch-CPU oracle, best of the "
-                                         "intra-op thread counts listed in threads_tried on a %d-cpu host: a batch of %d pairs does "
-                                         "not scale to every core; %.0f ms/step)"
-                                         % (cpu_steps, cpu_pairs, os.cpu_count() or 1, cpu_pairs, sec * 1e3)}
-        # the other two legs BASELINE.md 3 names, on the same host with the thread count the search above chose (bounded: ~10 s):
-        # the inference embedding pass (voicemap/utils.py:141-156) and BASELINE.json config 1, the classifier step at batch 8
-        # (experiments/train_classifier.py:110-127) -- each beside the GPU figure of the same work from this run's extras
-        try:
-            legs = {}
-            n_emb = 16
-            t_e = O.time_cpu_embed_only(arch, n_emb, 3, threads)
-            legs["embed_only"] = {"value": n_emb * 3.0 / t_e, "unit": "audio-s/s", "cores": threads, "kind": "port",
-                                  "sample": "%d windows of 3 s per pass, inference BatchNorm, fp32 (%.0f ms per pass)" % (n_emb, t_e * 1e3),
-                                  "gpu_value_this_run": (out.get("extras") or {}).get("embed_only_audio_s_per_s")}
-            n_cls, classes = 8, 40
-            t_c = O.time_cpu_classifier_steps(arch, n_cls, classes, 3, threads)
-            legs["classifier_step_batch8"] = {"value": n_cls * 3.0 / t_c, "unit": "audio-s/s", "cores": threads, "kind": "port",
-                                              "sample": "BASELINE.json config 1: train_on_batch of the speaker classifier (cfg-A encoder + "
-                                                        "Dense(%d, softmax), categorical CE, Adam(clipnorm 1)), batch %d of 3 s windows, "
-                                                        "fp32 (%.0f ms per step)" % (classes, n_cls, t_c * 1e3),
-                                              "gpu_value_this_run": (out.get("extras") or {}).get("classifier_batch8_audio_s_per_s")}
-            out["cpu_baseline"]["legs"] = legs
-        except Exception as e:   # a side figure never takes the line down
-            out["cpu_baseline"]["legs_error"] = repr(e)
-    if rank == 0:
-        print(json.dumps(out))
+    return roof
 
 
 def extras(a, eng, step, pl, xcat, y, pairs, dev, make_engine, make_step, time_blocks, out):

@@ -14,6 +14,8 @@ Outputs (committed, data only -- no reference source text):
   iterations, keyed like the weights (Keras ``trainable_weights`` order), plus ``vhat_max`` (the 20 amsgrad
   placeholders are all zero).  These and the BatchNorm moving statistics are the only numbers in the reference tree that
   its own forward / backward pass computed; tests/test_oracle_reference_pin.py holds the oracle to them.
+* ``ckpt_cfgCK.hdf5``          -- that checkpoint file itself, byte for byte (tests/test_hdf5_checkpoints.py reads it with
+  this package's own HDF5 reader and compares with the arrays above).
 * ``ckpt_cfgCK_meta.json``    -- layer geometry read from its ``model_config``
   attribute (kernel sizes, pool sizes, BN eps/momentum, head type) and the
   optimizer config from ``training_config``.
@@ -28,6 +30,7 @@ import io
 import json
 import os
 import re
+import shutil
 import struct
 import sys
 
@@ -74,6 +77,7 @@ def main():
     import h5py
 
     path = os.path.join(REF, "models/n_seconds/siamese__nseconds_3.0__filters_32__embed_64__drop_0.05__r_0.hdf5")
+    shutil.copyfile(path, os.path.join(OUT, "ckpt_cfgCK.hdf5"))
     f = h5py.File(path, "r")
     weights = {}
     enc = f["model_weights/sequential_1/sequential_1"]

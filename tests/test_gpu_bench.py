@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ def _last_json_line(text):
 
 
 def test_bench_single_process_line_contract():
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--blocks", "3", "--pairs", "16", "--no-extras",
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--blocks", "3", "--pairs", "16", "--full", "--no-extras",
                         "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _last_json_line(r.stdout)
@@ -37,6 +38,37 @@ def test_bench_single_process_line_contract():
     assert set(roof["families_serial"]) == {"vm_conv_fwd", "vm_conv_dgrad", "vm_conv_wgrad"}
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """A plain run times exactly --steps steps (one block), carries no side figures, and --dump-outputs writes what its last step
+    computed: float32 arrays of the documented shapes, finite, at most 64 MB, and the same bits from a second run with the same
+    arguments (seeded inputs and weights, deterministic step)."""
+    pairs = 16
+    lines = []
+    for tag in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--pairs", str(pairs), "--dump-outputs",
+                            str(tmp_path / tag)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_last_json_line(r.stdout))
+    out = lines[0]
+    assert out["steps"] == 3 and out["timing"]["blocks"] == 1 and len(out["timing"]["block_ms_per_step"]) == 1
+    assert abs(out["timing"]["block_ms_per_step"][0] - out["ms_per_step"]) < 1e-3 * out["ms_per_step"] + 1e-4
+    assert abs(out["value"] - 2 * pairs * 3 * 3.0 / (out["ms_per_step"] * 3 / 1e3)) < 1e-6 * out["value"]
+    for key in ("roofline", "precision", "extras", "cpu_baseline"):
+        assert key not in out, key
+    shapes = {"loss_acc": (2,), "pred": (pairs,), "emb": (2 * pairs, 64)}
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(n + ".npy" for n in ("loss_acc", "pred", "emb", "params", "adam_m", "adam_v", "bn_moving"))
+    total = 0
+    for n in names:
+        x, x2 = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        total += x.nbytes
+        assert x.dtype == np.float32 and np.isfinite(x).all(), n
+        assert x.shape == shapes.get(n[:-4], x.shape), n
+        assert np.array_equal(x, x2), n
+    assert total <= 64 << 20
+    assert float(np.load(tmp_path / "a" / "loss_acc.npy")[0]) == out["config"]["final_loss"]
+
+
 def test_bench_counts_the_dominant_launch_traffic_in_the_run():
     """roofline.traffic is COUNTED by the run that reports it: bench.py, at the headline batch, runs the two
     rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) on a child process of itself and folds them with tools/pmc_traffic.py; the
@@ -45,7 +77,7 @@ def test_bench_counts_the_dominant_launch_traffic_in_the_run():
     if shutil.which("rocprofv3") is None and not os.path.exists("/opt/rocm/bin/rocprofv3"):
         pytest.skip("no rocprofv3 on this box")
     env = {k: v for k, v in os.environ.items() if not k.startswith(("ROCP_", "ROCPROF"))}
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--blocks", "1", "--no-extras", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--blocks", "1", "--full", "--no-extras", "--no-cpu-baseline"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     roof = _last_json_line(r.stdout)["roofline"]

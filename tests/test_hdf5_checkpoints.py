@@ -2,8 +2,8 @@
 voicemap_amd/keras_hdf5.py (Keras' layout).  CPU only.
 
 Pins: (1) a file written by libhdf5 itself in Keras' layout (tests/golden/keras_layout_h5py.hdf5, made by
-tests/golden/make_h5py_fixture.py under the container's h5py) reads back exactly; (2) in the build container the
-reference's own shipped checkpoint reads to the arrays that h5py extracted from it (tests/golden/ckpt_cfgCK_weights.npz);
+tests/golden/make_h5py_fixture.py under the container's h5py) reads back exactly; (2) the reference's own shipped checkpoint
+(a copy: tests/golden/ckpt_cfgCK.hdf5) reads to the arrays that h5py extracted from it (tests/golden/ckpt_cfgCK_weights.npz);
 (3) what this package writes is read identically by its own reader and -- where an h5py interpreter exists -- by libhdf5."""
 import json
 import os
@@ -16,7 +16,7 @@ from voicemap_amd import hdf5_lite as H
 from voicemap_amd import keras_hdf5 as KH
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF_CKPT = "/root/reference/models/n_seconds/siamese__nseconds_3.0__filters_32__embed_64__drop_0.05__r_0.hdf5"
+REF_CKPT = os.path.join(GOLDEN, "ckpt_cfgCK.hdf5")   # the reference's models/n_seconds/siamese__nseconds_3.0__filters_32__embed_64__drop_0.05__r_0.hdf5
 H5PY_PYTHON = "/opt/conda/bin/python3.9"
 
 
@@ -81,7 +81,6 @@ def test_reader_on_a_file_written_by_libhdf5():
         f["model_weights/conv1d_9"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CKPT), reason="the reference tree is only mounted in the build container")
 def test_reader_on_the_reference_checkpoint_equals_h5py_extraction():
     ck = KH.read_checkpoint(REF_CKPT)
     ref = np.load(os.path.join(GOLDEN, "ckpt_cfgCK_weights.npz"))

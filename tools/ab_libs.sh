@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}; cd $R; OUT=gpurun_out/${1:-ab}; mkdir -p $OUT; ROUNDS=${3:-3}
 for rep in $(seq 1 $ROUNDS); do for v in $2; do
   L=""; [ "$v" != "default" ] && L=$R/voicemap_amd/lib/libvoicemap_hip_$v.so
-  VOICEMAP_HIP_LIB=$L python bench.py --no-extras --no-cpu-baseline --blocks 5 2>> $OUT/bench.err | python -c "
+  VOICEMAP_HIP_LIB=$L python bench.py --full --no-extras --no-cpu-baseline --blocks 5 2>> $OUT/bench.err | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$v', d['ms_per_step'], ' '.join('%s=%.3f' % (k[8:], v['ms_per_step']) for k, v in d['roofline'].get('families_serial', {}).items()))" | tee -a $OUT/runs.txt
 done; done

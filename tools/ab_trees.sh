@@ -2,7 +2,7 @@
 # Interleaved A/B of two checkouts of the repository on ONE box: bash tools/ab_trees.sh <dirA> <dirB> [rounds]   (each with its own built library)
 A=$1; B=$2; ROUNDS=${3:-3}; R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out; mkdir -p $O; : > $O/ab_trees.txt
 for rep in $(seq 1 $ROUNDS); do for d in $A $B; do
-  (cd $R/$d && python bench.py --no-extras --no-cpu-baseline --blocks 5 2>/dev/null | python -c "
+  (cd $R/$d && python bench.py --full --no-extras --no-cpu-baseline --blocks 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$d', d['ms_per_step'], ' '.join('%s=%.3f' % (k[8:], v['ms_per_step']) for k, v in d['roofline'].get('families_serial', {}).items()))") | tee -a $O/ab_trees.txt
 done; done

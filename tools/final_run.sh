@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 timeout 600 python -m pytest tests -m gpu -x -q > $O/pytest_$TAG.log 2>&1; echo "pytest rc=$?"
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke_$TAG.log 2>&1; echo "smoke rc=$?"
-timeout 400 python bench.py --steps 20 --warmup 5 --breakdown $O/breakdown_$TAG.csv > $O/bench_$TAG.log 2>&1; echo "bench rc=$?"
+timeout 400 python bench.py --steps 20 --warmup 5 --full --breakdown $O/breakdown_$TAG.csv > $O/bench_$TAG.log 2>&1; echo "bench rc=$?"
 timeout 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras --no-overlap-wgrad --tune split_towers=0 > $O/bench_${TAG}_serial.log 2>&1
 export TMPDIR=/tmp; cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/rocprof_$TAG.log 2>&1; echo "rocprof rc=$?"

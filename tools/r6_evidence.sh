@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-timeout 500 python bench.py --steps 20 --warmup 5 --breakdown $O/breakdown_$TAG.csv > $O/bench_$TAG.log 2> $O/bench_$TAG.err; echo "bench rc=$?"; head -c 700 $O/bench_$TAG.log; echo
+timeout 500 python bench.py --steps 20 --warmup 5 --full --breakdown $O/breakdown_$TAG.csv > $O/bench_$TAG.log 2> $O/bench_$TAG.err; echo "bench rc=$?"; head -c 700 $O/bench_$TAG.log; echo
 B="python $R/bench.py --steps 20 --warmup 5 --blocks 1 --no-cpu-baseline --no-extras"
 S="$B --no-overlap-wgrad --tune split_towers=0"
 export TMPDIR=/tmp; cd /tmp
