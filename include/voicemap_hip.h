@@ -47,9 +47,12 @@ enum { VM_OK = 0, VM_ERR_ARG = -1, VM_ERR_LAUNCH = -2, VM_ERR_UNSUPPORTED = -3 }
 enum { VM_LOSS_CONTRASTIVE = 0, VM_LOSS_BCE = 1 };
 enum { VM_HEAD_UNIFORM_EUCLIDEAN = 0, VM_HEAD_WEIGHTED_L1 = 1 };
 enum { VM_DIST_EUCLIDEAN = 0, VM_DIST_COSINE = 1, VM_DIST_DOT = 2 };
+/* score kinds of vm_pair_score_hist beside the three VM_DIST_*: the weighted_l1 head's sum (voicemap/models.py:55-60 before its bias and
+ * sigmoid), and the uniform_euclidean head's distance negated (the order of sigmoid(w d + b) when the head kernel w is negative). */
+enum { VM_SCORE_WEIGHTED_L1 = 3, VM_SCORE_NEG_EUCLIDEAN = 4 };
 
 const char* vm_last_error(void);
-/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
+/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
  * vm_conv_dgrad_bnred; `bias`, `wf_packed` and the fourth hb row of vm_fold_bn_weights), the centred block-1 extreme (`center_bias` /
  * `shift_adj` / `mean_adj` of vm_bn_finalize) (round 4).  Earlier: 1 = round 1; 2 = vm_bn_finalize gained the zero-debias arguments (round 2); 3 = VM_F16, `dtype` in vm_conv1_fused_*,
  * `grad_scale` in the loss entry points, `skip_nonfinite` in vm_adam_clip_step, vm_embed_* / vm_pairdist_* (round 3); 4 = the folded-BatchNorm training forward
@@ -550,6 +553,19 @@ int vm_nshot_indexed(const float* emb, int64_t n_rows, const int32_t* query_idx,
 int64_t vm_pairdist_workspace_bytes(int64_t M, int64_t N);
 int vm_pairdist_argmin(const float* q, const float* ref, int64_t M, int64_t N, int E, int dist_kind, int64_t q_row0, float* dist,
                        float* best_val, int32_t* best_idx, void* ws, void* stream);
+/* vm_pair_score_hist: all-pairs speaker verification -- what the reference's experiments/verification_accuracy.py (a stub: "determines the
+ * best verification distance threshold on the validation set and then ... estimate the true verification accuracy on the test set")
+ * needs, without the N x N matrix.  Every pair {i, j}, row_lo <= i < row_hi, i < j < N, of emb (N, E) is scored -- score_kind
+ * VM_DIST_* bit-identical to dist[i][j] of vm_pairdist_argmin, VM_SCORE_WEIGHTED_L1 = sum_e weights[e] |a_e - b_e| (ascending e, fmaf),
+ * VM_SCORE_NEG_EUCLIDEAN = -euclidean -- and counted by class (0: label[i] == label[j], 1: otherwise) into the bins of each of
+ * n_windows (<= 4) windows on the order-preserving uint32 key of the score (-0.0 taken as +0.0; bits | 2^31 if non-negative, ~bits if
+ * negative).  host_windows (n_windows, 2) int64 on the HOST: key_lo, shift (<= 31): key k goes to bin (k - key_lo) >> shift if k >= key_lo
+ * and that is < bins, else to slot bins (k < key_lo) or bins + 1; a NaN score to slot bins + 2.  hist (n_windows, 2, bins + 3) uint64 is
+ * ACCUMULATED (row ranges / ranks sum).  n_windows * 2 * (bins + 3) <= 8216 (4 windows x 1024 bins, 1 x 4096).  weights (E) only for
+ * VM_SCORE_WEIGHTED_L1.  ws >= vm_pair_score_hist_workspace_bytes(N, E).  E <= 256, N < 2^31. */
+int64_t vm_pair_score_hist_workspace_bytes(int64_t N, int E);
+int vm_pair_score_hist(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, const float* weights, int64_t row_lo,
+                       int64_t row_hi, const int64_t* host_windows, int n_windows, int bins, uint64_t* hist, void* ws, void* stream);
 
 /* ---- a10 / f4: log-mel front-end and the 2-D CNN encoder variant (BASELINE.json config 4) -------------------
  * NOT in the reference (nothing to cite under /root/reference); the specification is DESIGN.md section 9 and the

@@ -23,6 +23,7 @@ ABI_VERSION = 11  # include/voicemap_hip.h vm_abi_version(): checked when the li
 VM_LOSS_CONTRASTIVE, VM_LOSS_BCE = 0, 1
 VM_HEAD_UNIFORM_EUCLIDEAN, VM_HEAD_WEIGHTED_L1 = 0, 1
 VM_DIST_EUCLIDEAN, VM_DIST_COSINE, VM_DIST_DOT = 0, 1, 2
+VM_SCORE_WEIGHTED_L1, VM_SCORE_NEG_EUCLIDEAN = 3, 4
 
 P, I, L, F, D = c_void_p, c_int, c_int64, c_float, c_double
 
@@ -119,6 +120,8 @@ SIGNATURES = {
     "vm_nshot_indexed": (I, [P, L, P, P, L, I, I, I, I, P, P, P]),
     "vm_pairdist_workspace_bytes": (L, [L, L]),
     "vm_pairdist_argmin": (I, [P, P, L, L, I, I, L, P, P, P, P, P]),
+    "vm_pair_score_hist_workspace_bytes": (L, [L, I]),
+    "vm_pair_score_hist": (I, [P, P, L, I, I, P, L, L, P, I, I, P, P, P]),
     "vm_stft_frames": (L, [L, I, I]),
     "vm_stft_logmel": (I, [P, I, L, L, I, I, P, P, I, F, I, P, P]),
     "vm_stft_split_basis_bytes": (L, [I]),

@@ -389,6 +389,16 @@ __global__ __launch_bounds__(256) void pairdist_final_kernel(const float* __rest
     best_idx[m] = bi == 0x7fffffff ? -1 : bi;
 }
 
+// launchers of the two preparation kernels above for verif.hip (the pair-score histogram stages its queries the same way)
+void launch_rowsq(const float* x, int64_t rows, int E, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(rowsq_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, rows, E, out);
+}
+void launch_pairdist_qt(const float* q, int64_t M, int E, float* qT, hipStream_t st) {
+    const int EP = ((E + 3) / 4) * 4;
+    const int64_t qt_n = ((M + 7) / 8) * 8 * (int64_t)EP;
+    hipLaunchKernelGGL(pairdist_qt_kernel, dim3((unsigned)((qt_n + 255) / 256)), dim3(256), 0, st, q, M, E, EP, qT);
+}
+
 static int pd_splits(int64_t M, int64_t N) {
     const int64_t mt = (M + PD_T - 1) / PD_T, nt = (N + PD_RT - 1) / PD_RT;
     int64_t s = (2048 + mt - 1) / mt;  // aim for >= 2048 workgroups (8 per CU)

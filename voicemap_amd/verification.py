@@ -1,0 +1,459 @@
+"""All-pairs speaker verification over a cached embedding matrix: EER, ROC and a decision threshold.
+
+The reference planned this (experiments/verification_accuracy.py: "determines the best verification distance threshold on the
+validation set and then ... uses this to estimate the true verification accuracy on the test set") and never wrote it.  The trials are
+all unordered pairs {i, j}, i < j, of the rows of a ``retrieval.EmbeddingCache``; a pair is a target if both rows have the same speaker.
+A score is lower for more alike rows and a pair is accepted as "same" iff s < t:
+
+* FRR(t) = #{targets, s >= t} / n_target, FAR(t) = #{non-targets, s < t} / n_nontarget; t runs over the distinct finite scores and
+  +inf; NaN scores are counted apart and left out of both rates;
+* EER = (FAR + FRR) / 2 at t* = argmin |FAR - FRR| (smallest t on ties); best balanced accuracy = max 1 - (FAR + FRR) / 2 (smallest t
+  that reaches it) -- the expected accuracy on the reference's own 50 % same / 50 % different verification batches.
+
+``vm_pair_score_hist`` scores every pair on the chip and bins it on the order-preserving uint32 key of the fp32 score, so the N x N
+matrix never exists.  A histogram window gives the EXACT counts of scores below each of its bin edges, so the metrics are found like
+this: pass 1 bins the bulk of the scores (a window placed by a sample of pairs, within cheap bounds; the under / over slots keep
+the counts exact whatever falls outside); then every bin
+that may hold t* or the best threshold is zoomed into (a window over the bin, log2(bins) bits finer) until those bins hold one key
+value each.  EER, t*, the best balanced accuracy and its threshold then equal what a full sort of the fp32 scores gives.
+
+Under torchrun every rank takes one ``triangle_shards`` range of rows and the int64 histograms are all-reduced, so every rank takes the
+same zoom decisions.
+"""
+from __future__ import annotations
+
+import math
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import parallel
+
+SCORES = {"euclidean": 0, "cosine": 1, "dot_product": 2, "weighted_l1": 3}
+VM_SCORE_NEG_EUCLIDEAN = 4
+KEY_SPACE = 1 << 32
+KEY_NEG_INF = 0x007FFFFF        # key(-inf)
+KEY_FIN_LO = 0x00800000         # key(-FLT_MAX): the smallest finite key
+KEY_POS_INF = 0xFF800000        # key(+inf); every finite key is below it
+PASS1_BINS = 4096
+MAX_WINDOWS = 4
+LDS_WORDS = 2 * 4 * (1024 + 3)  # csrc/verif.hip VH_LDS_HIST_WORDS
+
+
+# ---- keys ------------------------------------------------------------------------------------------------------------------------
+def score_keys(s) -> np.ndarray:
+    """uint32 keys of fp32 scores: -0.0 -> +0.0, then bits | 2^31 (non-negative) or ~bits (negative).  NaN maps somewhere: mask it."""
+    u = np.ascontiguousarray(np.asarray(s, dtype=np.float32)).view(np.uint32).copy()
+    u[u == 0x80000000] = 0
+    return np.where(u & 0x80000000, ~u, u | 0x80000000).astype(np.uint32)
+
+
+def key_of(t: float) -> int:
+    return int(score_keys(np.array([t], np.float32))[0])
+
+
+def key_value(k: int) -> float:
+    """The fp32 value whose key is k (inverse of ``score_keys``)."""
+    bits = (k & 0x7FFFFFFF) if k & 0x80000000 else (~k & 0xFFFFFFFF)
+    return float(np.array([bits], np.uint32).view(np.float32)[0])
+
+
+def key_values(k: np.ndarray) -> np.ndarray:
+    """``key_value`` of an array of keys, as float64."""
+    k = np.asarray(k, dtype=np.int64)
+    bits = np.where(k & 0x80000000, k & 0x7FFFFFFF, ~k & 0xFFFFFFFF).astype(np.uint32)
+    return bits.view(np.float32).astype(np.float64)
+
+
+def bin_scores(scores, target, windows: Sequence[Tuple[int, int]], bins: int) -> np.ndarray:
+    """numpy twin of ``vm_pair_score_hist``: (n_windows, 2, bins + 3) int64 counts of the scores (class 0 = target)."""
+    s = np.asarray(scores, dtype=np.float32).ravel()
+    cls = np.where(np.asarray(target, dtype=bool).ravel(), 0, 1)
+    nan = np.isnan(s)
+    k = score_keys(s).astype(np.int64)
+    out = np.zeros((len(windows), 2, bins + 3), dtype=np.int64)
+    for v, (lo, sh) in enumerate(windows):
+        b = (k - lo) >> sh
+        slot = np.where(k < lo, bins, np.where(b < bins, b, bins + 1))
+        slot = np.where(nan, bins + 2, slot)
+        out[v] = np.bincount(cls * (bins + 3) + slot, minlength=2 * (bins + 3)).reshape(2, bins + 3)
+    return out
+
+
+# ---- rows of the triangle --------------------------------------------------------------------------------------------------------
+def _pairs_before(i, N):
+    """Pairs {i', j}, i' < i, j > i'."""
+    return i * (N - 1) - i * (i - 1) // 2
+
+
+def triangle_shards(N: int, world: int) -> List[Tuple[int, int]]:
+    """Contiguous row ranges [lo, hi) of the triangle {i < j < N} with near-equal PAIR counts (the early rows hold the most pairs): each
+    boundary is the row whose pair prefix is nearest to an even split of the pairs left to the remaining shards."""
+    total = _pairs_before(N, N)
+    bounds = [0]
+    for k in range(1, world):
+        done = _pairs_before(bounds[-1], N)
+        goal = done + (total - done) / (world - k + 1)
+        lo, hi = bounds[-1], N
+        while lo < hi:   # first row i with prefix >= goal
+            mid = (lo + hi) // 2
+            if _pairs_before(mid, N) >= goal:
+                hi = mid
+            else:
+                lo = mid + 1
+        if lo > bounds[-1] and goal - _pairs_before(lo - 1, N) < _pairs_before(lo, N) - goal:
+            lo -= 1
+        bounds.append(lo)
+    bounds.append(N)
+    return list(zip(bounds[:-1], bounds[1:]))
+
+
+# ---- the device histogram --------------------------------------------------------------------------------------------------------
+def _score_kind(cache, score: str, model) -> Tuple[int, Optional[torch.Tensor], Optional[Tuple[float, float]]]:
+    """(kernel score kind, weights, (w, b) of a uniform_euclidean head)."""
+    if score in ("euclidean", "cosine", "dot_product"):
+        return SCORES[score], None, None
+    if score == "weighted_l1":
+        raise ValueError('score "weighted_l1" takes its weights from a model: use score="head" with a weighted_l1 siamese net')
+    if score != "head":
+        raise ValueError("score must be one of (euclidean, cosine, dot_product, head)")
+    from .retrieval import _siamese_head_engine
+    eng = _siamese_head_engine(model) if model is not None else None
+    if eng is None:
+        raise ValueError('score="head" needs a siamese model with a uniform_euclidean or weighted_l1 head')
+    kern = eng.view("head.kernel").reshape(-1).float()
+    bias = float(eng.view("head.bias").reshape(-1)[0].item())
+    if eng.head == "weighted_l1":
+        return SCORES["weighted_l1"], kern.to(cache.emb.device).contiguous(), None
+    w = float(kern[0].item())
+    return (SCORES["euclidean"] if w >= 0 else VM_SCORE_NEG_EUCLIDEAN), None, (w, bias)
+
+
+def _device_hist(cache, kind: int, weights, windows, bins: int, rows: Tuple[int, int]) -> np.ndarray:
+    from . import _lib
+    lib = _lib.lib()
+    dev = cache.emb.device
+    hist = torch.zeros(len(windows), 2, bins + 3, dtype=torch.int64, device=dev)
+    lo, hi = rows
+    if hi > lo:
+        emb = cache.emb.contiguous()
+        ws = torch.empty(lib.query("vm_pair_score_hist_workspace_bytes", cache.n, cache.E) // 4 + 64, dtype=torch.float32, device=dev)
+        win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
+        lib.call("vm_pair_score_hist", emb.data_ptr(), cache.speaker_dev.data_ptr(), cache.n, cache.E, kind,
+                 None if weights is None else weights.data_ptr(), lo, hi, win.ctypes.data, len(windows), bins, hist.data_ptr(), ws.data_ptr(),
+                 torch.cuda.current_stream(dev).cuda_stream)
+    return hist
+
+
+def score_histogram(cache, score: str, windows: Sequence[Tuple[int, int]], bins: int, rows: Optional[Tuple[int, int]] = None,
+                    model=None) -> np.ndarray:
+    """(n_windows, 2, bins + 3) int64 counts of all pair scores of ``cache`` (class 0 = target) in windows (key_lo, shift).  ``rows``:
+    only the pairs with i in [lo, hi); by default this rank's ``triangle_shards`` range, and under torchrun the histograms of all ranks
+    are summed."""
+    kind, weights, _ = _score_kind(cache, score, model)
+    return _histogram(cache, kind, weights, windows, bins, rows)
+
+
+def _histogram(cache, kind, weights, windows, bins, rows=None) -> np.ndarray:
+    if len(windows) > MAX_WINDOWS or len(windows) * 2 * (bins + 3) > LDS_WORDS:
+        raise ValueError("at most %d windows and %d histogram words per launch" % (MAX_WINDOWS, LDS_WORDS))
+    rank, world = parallel.rank_world()
+    if rows is not None:
+        return _device_hist(cache, kind, weights, windows, bins, rows).cpu().numpy()
+    h = _device_hist(cache, kind, weights, windows, bins, triangle_shards(cache.n, world)[rank])
+    if world > 1:
+        import torch.distributed as dist
+        comm = h.to(parallel._comm_device())
+        dist.all_reduce(comm, op=dist.ReduceOp.SUM)
+        h = comm
+    return h.cpu().numpy()
+
+
+# ---- exact metrics from cumulative counts ----------------------------------------------------------------------------------------
+def _ceil_log2(x: int) -> int:
+    return max(0, (int(x) - 1).bit_length())
+
+
+class _Cumulative:
+    """Exact counts (targets, non-targets) of the scores whose key is below each known edge key; 0 and 2^32 are always known."""
+
+    def __init__(self, total_t, total_n):
+        self.c = {0: (0, 0), KEY_SPACE: (total_t, total_n)}
+
+    def add_window(self, h, lo, sh, bins):
+        """h: (2, bins + 3) counts of one window."""
+        ct, cn = int(h[0, bins]), int(h[1, bins])
+        for b in range(bins + 1):
+            e = lo + (b << sh)
+            if e > KEY_SPACE:
+                break
+            if e < KEY_SPACE:
+                self.c[e] = (ct, cn)
+            if b < bins:
+                ct += int(h[0, b])
+                cn += int(h[1, b])
+
+    def segments(self):
+        ks = sorted(self.c)
+        return [(a, b, self.c[a], self.c[b]) for a, b in zip(ks[:-1], ks[1:])]
+
+
+def _finite_part(lo, hi):
+    return max(lo, KEY_FIN_LO) < min(hi, KEY_POS_INF)
+
+
+def _plan(cum: _Cumulative, nT: int, nN: int):
+    """One step of the zoom: (result or None, segments [lo, hi) to refine).  Items in key order: known candidates (a single-key
+    finite segment that holds scores, and +inf) and 'open' segments (several keys, holding scores, some of them finite)."""
+    items = []   # (kind, lo, hi, c_lo, c_hi): kind 'c' = candidate at key lo, 'o' = open segment
+    pinf = None
+    refine = []
+    for lo, hi, c0, c1 in cum.segments():
+        n = (c1[0] - c0[0]) + (c1[1] - c0[1])
+        if lo <= KEY_POS_INF < hi or lo == KEY_POS_INF:
+            if lo == KEY_POS_INF or n == 0:
+                pinf = c0
+            else:   # +inf's position is inside a segment holding scores: split it there
+                refine.append((lo, hi))
+        if n == 0 or not _finite_part(lo, hi):
+            continue
+        if hi - lo == 1:
+            items.append(("c", lo, hi, c0, c1))
+        else:
+            items.append(("o", lo, hi, c0, c1))
+    if refine:
+        return None, refine
+    items.append(("c", KEY_POS_INF, KEY_SPACE, pinf, pinf))
+    g = lambda c: c[0] * nN - c[1] * nT                     # (1 - (FAR + FRR) / 2 - 1/2) x 2 nT nN: balanced accuracy
+    d = lambda c: c[1] * nT + c[0] * nN - nT * nN          # (FAR - FRR) x nT nN: strictly increasing over the candidates
+    # best balanced accuracy
+    # the best value known to be reached: at a candidate, or at the first score of an open segment (its lower edge) when that score
+    # is finite -- the segment then holds that candidate, key unknown; best_at = the first item known to reach it
+    best, best_at = None, None
+    for it in items:
+        if (it[0] == "c" or it[1] >= KEY_FIN_LO) and (best is None or g(it[3]) > best):
+            best, best_at = g(it[3]), it
+    for it in items:
+        if it[0] == "o":
+            ub = it[4][0] * nN - it[3][1] * nT           # every target of the segment below t, none of its non-targets
+            if ub > best or (ub == best and it[1] <= best_at[1]):
+                refine.append((it[1], it[2]))
+    # EER: the first item that holds (or may hold) a candidate with d >= 0, and the item before it
+    # (+inf's d is negative when +inf scores exist: then no candidate reaches d >= 0 and t* is the last one)
+    first = next((i for i, it in enumerate(items) if (d(it[3]) >= 0 if it[0] == "c" else d(it[4]) >= 0)), len(items))
+    for it in items[max(0, first - 1):first + 1]:
+        if it[0] == "o":
+            refine.append((it[1], it[2]))
+    if refine:
+        # the open neighbours of every segment to refine go into the same pass: once a zoom has split a segment, the candidate next
+        # to the one found is often in the segment beside it, and a pass costs a full sweep of the triangle while a window costs little
+        need = set(refine)
+        opens = [it for it in items if it[0] == "o"]
+        for k, it in enumerate(opens):
+            if (it[1], it[2]) in need:
+                for nb in opens[max(0, k - 1):k + 2]:
+                    refine.append((nb[1], nb[2]))
+        return None, sorted(set(refine))
+    tb = items[first] if first < len(items) else None
+    ta = items[first - 1] if first > 0 else None
+    eer_it = ta if ta is not None and (tb is None or -d(ta[3]) <= d(tb[3])) else tb
+    return (eer_it, best_at), []
+
+
+def _windows_for(refine, bins=1024, gain=16):
+    """Key ranges [lo, hi) of the windows that refine the segments: neighbouring segments share a window while its bins stay at least
+    ``gain`` times narrower than the widest of them; a segment that holds +inf's key starts its window there (it is split at +inf)."""
+    out = []
+    for lo, hi in sorted(refine):
+        if lo < KEY_POS_INF < hi:
+            lo = KEY_POS_INF
+        if out and hi - out[-1][0] <= (bins // gain) * max(out[-1][2], hi - lo):
+            out[-1] = (out[-1][0], hi, max(out[-1][2], hi - lo))
+        else:
+            out.append((lo, hi, hi - lo))
+    return [(lo, hi) for lo, hi, _ in out]
+
+
+def exact_sweep(hist_fn: Callable, pass1: Tuple[int, int], max_passes: int = 10000) -> Dict:
+    """The zoom loop on any histogram source ``hist_fn(windows, bins) -> (n_windows, 2, bins + 3) int64`` (the device histogram, or
+    ``bin_scores`` on a score array in the CPU tests).  Returns the metrics dict of ``verification_metrics`` (without the model part)."""
+    h1 = hist_fn([pass1], PASS1_BINS)
+    n_nan = int(h1[0, 0, -1] + h1[0, 1, -1])
+    nT, nN = int(h1[0, 0, :-1].sum()), int(h1[0, 1, :-1].sum())
+    cum = _Cumulative(nT, nN)
+    cum.add_window(h1[0], pass1[0], pass1[1], PASS1_BINS)
+    out = {"n_target": nT, "n_nontarget": nN, "n_nan": n_nan}
+    # ROC at the pass-1 edges
+    edges = [pass1[0] + (b << pass1[1]) for b in range(PASS1_BINS + 1) if pass1[0] + (b << pass1[1]) <= KEY_POS_INF]
+    roc_t = key_values(np.array(edges, dtype=np.int64))
+    keep = ~np.isnan(roc_t)
+    cs = np.array([cum.c[e] for e in edges], dtype=np.float64).reshape(-1, 2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["roc"] = {"threshold": roc_t[keep], "far": (cs[:, 1] / nN)[keep], "frr": ((nT - cs[:, 0]) / nT)[keep]}
+    passes = 1
+    if nT == 0 or nN == 0:
+        nan = float("nan")
+        out.update(eer=nan, eer_threshold=nan, best_balanced_accuracy=nan, best_threshold=nan, far_at_eer=nan, frr_at_eer=nan,
+                   far_at_best=nan, frr_at_best=nan, auc=nan, auc_bound=nan, passes=passes)
+        return out
+    while True:
+        res, refine = _plan(cum, nT, nN)
+        if res is not None:
+            break
+        wins = _windows_for(refine)
+        for c in range(0, len(wins), MAX_WINDOWS):
+            if passes >= max_passes:
+                raise RuntimeError("verification zoom did not converge in %d passes" % max_passes)
+            chunk = wins[c:c + MAX_WINDOWS]
+            bins = 1 << (min(PASS1_BINS // len(chunk), LDS_WORDS // (2 * len(chunk)) - 3).bit_length() - 1)
+            chunk = [(lo, _ceil_log2(-(-(hi - lo) // bins))) for lo, hi in chunk]
+            h = hist_fn(chunk, bins)
+            for v, (lo, sh) in enumerate(chunk):
+                cum.add_window(h[v], lo, sh, bins)
+            passes += 1
+    (eer_it, best_it) = res
+    rate = lambda c: (c[1] / nN, (nT - c[0]) / nT)
+    far_e, frr_e = rate(eer_it[3])
+    far_b, frr_b = rate(best_it[3])
+    thr = lambda it: math.inf if it[1] == KEY_POS_INF else key_value(it[1])
+    # AUC (P(target score < non-target score) + P(tie) / 2) on the final partition; within a multi-key segment the order is unknown
+    auc2, bound2 = 0, 0
+    for lo, hi, c0, c1 in cum.segments():
+        t, n = c1[0] - c0[0], c1[1] - c0[1]
+        auc2 += 2 * t * (nN - c1[1]) + t * n
+        if hi - lo > 1:
+            bound2 += t * n
+    out.update(eer=(far_e + frr_e) / 2, eer_threshold=thr(eer_it), far_at_eer=far_e, frr_at_eer=frr_e,
+               best_balanced_accuracy=1.0 - (far_b + frr_b) / 2, best_threshold=thr(best_it), far_at_best=far_b, frr_at_best=frr_b,
+               auc=auc2 / (2 * nT * nN), auc_bound=bound2 / (2 * nT * nN), passes=passes)
+    return out
+
+
+def sorted_metrics(scores, target) -> Dict:
+    """The definition, by a full sort (tests and small sets): EER, t*, best balanced accuracy and its threshold, n_nan."""
+    s = np.asarray(scores, dtype=np.float32).ravel()
+    tg = np.asarray(target, dtype=bool).ravel()
+    ok = ~np.isnan(s)
+    st, sn = np.sort(s[ok & tg]), np.sort(s[ok & ~tg])
+    nT, nN = len(st), len(sn)
+    fin = s[ok & np.isfinite(s)]
+    cand = np.concatenate([np.unique(fin), np.array([np.inf], np.float32)])
+    cT = np.searchsorted(st, cand, side="left").astype(object)
+    cN = np.searchsorted(sn, cand, side="left").astype(object)
+    d = [int(a) * nT + int(b) * nN - nT * nN for a, b in zip(cN, cT)]
+    g = [int(b) * nN - int(a) * nT for a, b in zip(cN, cT)]
+    ie = min(range(len(cand)), key=lambda i: (abs(d[i]), i))
+    ib = min(range(len(cand)), key=lambda i: (-g[i], i))
+    rate = lambda i: (int(cN[i]) / nN, (nT - int(cT[i])) / nT)
+    fe, re_ = rate(ie)
+    fb, rb = rate(ib)
+    return {"eer": (fe + re_) / 2, "eer_threshold": float(cand[ie]), "far_at_eer": fe, "frr_at_eer": re_,
+            "best_balanced_accuracy": 1.0 - (fb + rb) / 2, "best_threshold": float(cand[ib]), "far_at_best": fb, "frr_at_best": rb,
+            "n_target": nT, "n_nontarget": nN, "n_nan": int((~ok).sum())}
+
+
+# ---- pass-1 bounds ---------------------------------------------------------------------------------------------------------------
+def _pass1_window(lo_val: float, hi_val: float, bins: int = PASS1_BINS) -> Tuple[int, int]:
+    """A window whose bins cover [lo_val, hi_val] (keys), aligned to its bin width."""
+    klo, khi = key_of(lo_val), key_of(hi_val)
+    sh = min(31, _ceil_log2(-(-(khi - klo + 1) // bins)))
+    while True:
+        lo = (klo >> sh) << sh
+        if lo + (bins << sh) > khi:
+            return lo, sh
+        sh += 1
+
+
+def _bounds(cache, kind) -> Tuple[float, float]:
+    if kind == SCORES["cosine"]:
+        return 0.0, 2.0
+    norms = torch.linalg.vector_norm(cache.emb.double(), dim=1)
+    r = float(norms.max().item()) if cache.n else 0.0
+    r = r * 1.001 + 1e-30
+    if kind == SCORES["euclidean"]:
+        return 0.0, 2 * r
+    if kind == VM_SCORE_NEG_EUCLIDEAN:
+        return -2 * r, 0.0
+    return -r * r, r * r   # dot product (and weighted_l1 below)
+
+
+def _sampled_window(cache, kind, weights, lo: float, hi: float, n_sample: int = 1 << 16) -> Tuple[int, int]:
+    """Pass 1's window: the 1e-4 .. 1 - 1e-4 quantiles of the scores of a seeded sample of pairs (torch arithmetic: it only places the
+    window -- whatever falls outside lands in the under / over slots and the counts stay exact), clipped to the cheap bounds [lo, hi].
+    The bins then cover the bulk of the scores, not the key range of the bounds, and one zoom pass usually reaches single keys.  Under
+    torchrun rank 0's window is broadcast: every rank bins into the same window."""
+    rank, world = parallel.rank_world()
+    win = torch.zeros(2, dtype=torch.int64)
+    if rank == 0:
+        win[0], win[1] = _pass1_window(lo, hi)
+        if cache.n >= 2:
+            g = torch.Generator().manual_seed(0)
+            i = torch.randint(0, cache.n, (n_sample,), generator=g)
+            j = (i + torch.randint(1, cache.n, (n_sample,), generator=g)) % cache.n
+            a = cache.emb[i.to(cache.emb.device)].double()
+            b = cache.emb[j.to(cache.emb.device)].double()
+            if kind in (SCORES["euclidean"], VM_SCORE_NEG_EUCLIDEAN):
+                sc = torch.linalg.vector_norm(a - b, dim=1) * (1 if kind == SCORES["euclidean"] else -1)
+            elif kind == SCORES["cosine"]:
+                sc = 1 - (a * b).sum(1) / (torch.linalg.vector_norm(a, dim=1) * torch.linalg.vector_norm(b, dim=1))
+            elif kind == SCORES["dot_product"]:
+                sc = -(a * b).sum(1)
+            else:
+                sc = ((a - b).abs() * weights.double()).sum(1)
+            sc = sc[torch.isfinite(sc)].cpu().numpy()
+            if len(sc) > 100:
+                q0, q1 = np.quantile(sc, [1e-4, 1 - 1e-4])
+                pad = 0.05 * (q1 - q0) + 1e-6 * max(abs(q0), abs(q1)) + 1e-30
+                q0, q1 = max(lo, q0 - pad), min(hi, q1 + pad)
+                if q0 < q1:
+                    win[0], win[1] = _pass1_window(float(q0), float(q1))
+    if world > 1:
+        import torch.distributed as dist
+        comm = win.to(parallel._comm_device())
+        dist.all_reduce(comm, op=dist.ReduceOp.SUM)
+        win = comm.cpu()
+    return int(win[0]), int(win[1])
+
+
+def verification_metrics(cache, score: str = "euclidean", model=None, bins: int = PASS1_BINS) -> Dict:
+    """All-pairs verification metrics of ``cache`` (module docstring): ``eer``, ``eer_threshold``, ``best_balanced_accuracy``,
+    ``best_threshold``, FAR / FRR at both, ``auc`` and ``auc_bound`` (the true AUC lies within it), ``roc`` (pass-1 edges as float
+    thresholds with FAR and FRR), ``n_target``, ``n_nontarget``, ``n_nan`` and ``passes``.  score="head": the siamese model's own head
+    (a uniform_euclidean head is monotone in the distance; the thresholds are then also reported as head outputs p, ``*_p``)."""
+    if bins != PASS1_BINS:
+        raise ValueError("pass 1 takes %d bins" % PASS1_BINS)
+    kind, weights, head = _score_kind(cache, score, model)
+    if kind == SCORES["weighted_l1"]:
+        wsum = float(weights.abs().double().sum().item())
+        amax = float(cache.emb.abs().max().item()) if cache.n else 0.0
+        lo, hi = -2 * amax * wsum * 1.001 - 1e-30, 2 * amax * wsum * 1.001 + 1e-30
+    else:
+        lo, hi = _bounds(cache, kind)
+    out = exact_sweep(lambda wins, b: _histogram(cache, kind, weights, wins, b), _sampled_window(cache, kind, weights, lo, hi))
+    if head is not None:
+        w, b = head
+        out["eer_threshold_p"] = _head_p(out["eer_threshold"], w, b)
+        out["best_threshold_p"] = _head_p(out["best_threshold"], w, b)
+    return out
+
+
+def _head_p(t: float, w: float, b: float) -> float:
+    """The uniform_euclidean head's output sigmoid(w d + b) at a threshold t on the head score (d, or -d when w < 0)."""
+    if math.isinf(t):
+        return 1.0 if w != 0 else 1.0 / (1.0 + math.exp(-b))   # t = +inf: every finite distance is accepted
+    a = w * (t if w >= 0 else -t) + b
+    return 1.0 / (1.0 + math.exp(-a)) if a > -700 else 0.0
+
+
+def accuracy_at_threshold(cache, t: float, score: str = "euclidean", model=None) -> Dict:
+    """Balanced accuracy, FAR and FRR at a fixed threshold t (in score units): one pass with key_lo = key(t), whose under slot is then
+    exactly {s < t}."""
+    kind, weights, _ = _score_kind(cache, score, model)
+    k = key_of(t) if not math.isnan(t) else KEY_SPACE - 1
+    h = _histogram(cache, kind, weights, [(k, 31)], 1)[0]
+    nT, nN = int(h[0, :-1].sum()), int(h[1, :-1].sum())
+    far = float(h[1, 1]) / nN if nN else float("nan")
+    frr = float(nT - h[0, 1]) / nT if nT else float("nan")
+    return {"balanced_accuracy": 1.0 - (far + frr) / 2, "far": far, "frr": frr, "n_target": nT, "n_nontarget": nN,
+            "n_nan": int(h[0, -1] + h[1, -1])}
