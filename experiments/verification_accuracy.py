@@ -3,9 +3,13 @@ docstring "determines the best verification distance threshold on the validation
 verification accuracy on the test set".  Each set is embedded once (retrieval.embed_corpus: one first-fragment window per file, each
 window whitened alone -- the deviation documented there); the best-balanced-accuracy threshold of the validation set's all-pairs trials
 is applied to the test set's (voicemap_amd/verification.py).  Results go to logs/verification_accuracy_<valid>_<test>_<score>.csv.
-    python -m experiments.verification_accuracy --siamese models/x.hdf5 [--score euclidean|cosine|dot_product|head] [--synthetic]"""
+With --score-norm s-norm / as-norm both sets are normalised against the same cohort (a seeded random subset of --cohort-set's files;
+as-norm over the --top-k cohort rows most like each row) and the file name gains _<score-norm>[_k<top-k>]_c<cohort-size>.
+    python -m experiments.verification_accuracy --siamese models/x.hdf5 [--score euclidean|cosine|dot_product|head] [--synthetic]
+        [--score-norm none|s-norm|as-norm --cohort-set train-clean-100 --cohort-size 5000 --top-k 300]"""
 import argparse
 
+import numpy as np
 import pandas as pd
 
 from config import PATH
@@ -14,24 +18,69 @@ from voicemap_amd.librispeech import LibriSpeechDataset, SyntheticSpeechDataset
 from voicemap_amd.utils import BatchPreProcessor, preprocess_instances
 
 
-def evaluate(net, valid, test, pre, score="euclidean"):
-    """Embed both sets once, take the best-balanced-accuracy threshold of the validation trials and apply it to the test trials."""
+class CohortSubset:
+    """The files ``index`` of a dataset, in that order, as far as ``retrieval.embed_corpus`` reads a dataset."""
+
+    def __init__(self, dataset, index):
+        self.base, self.index = dataset, np.asarray(index, dtype=np.int64)
+        self.fragment_length, self.pad = dataset.fragment_length, dataset.pad
+        self._code = np.asarray(dataset._code)[self.index]
+
+    def __len__(self):
+        return len(self.index)
+
+    def _load(self, i):
+        return self.base._load(int(self.index[i]))
+
+
+def cohort_subset(dataset, size, seed=0):
+    """A seeded random subset of ``size`` files of ``dataset`` (all of them if it has fewer), in file order."""
+    n = len(dataset)
+    if size >= n:
+        return CohortSubset(dataset, np.arange(n))
+    return CohortSubset(dataset, np.sort(np.random.default_rng(seed).choice(n, size, replace=False)))
+
+
+def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort=None, top_k=300):
+    """Embed both sets once, take the best-balanced-accuracy threshold of the validation trials and apply it to the test trials.
+    ``score_norm`` "s-norm" / "as-norm": both sets' scores are normalised against the embeddings of ``cohort`` (a dataset)."""
     model = net if score == "head" else None
     cv = retrieval.embed_corpus(net, valid, pre, "siamese")
     ct = retrieval.embed_corpus(net, test, pre, "siamese")
-    mv = verification.verification_metrics(cv, score, model=model)
-    mt = verification.verification_metrics(ct, score, model=model)
-    at = verification.accuracy_at_threshold(ct, mv["best_threshold"], score, model=model)
+    nv = nt = None
+    if score_norm != "none":
+        cc = retrieval.embed_corpus(net, cohort, pre, "siamese")
+        k = None if score_norm == "s-norm" else top_k
+        nv = verification.score_norm(cv, cc, score, top_k=k, model=model)
+        nt = verification.score_norm(ct, cc, score, top_k=k, model=model)
+    mv = verification.verification_metrics(cv, score, model=model, norm=nv)
+    mt = verification.verification_metrics(ct, score, model=model, norm=nt)
+    at = verification.accuracy_at_threshold(ct, mv["best_threshold"], score, model=model, norm=nt)
     row = {"score": score, "threshold": mv["best_threshold"], "valid_balanced_accuracy": mv["best_balanced_accuracy"],
            "valid_eer": mv["eer"], "valid_eer_threshold": mv["eer_threshold"], "test_balanced_accuracy": at["balanced_accuracy"],
            "test_far": at["far"], "test_frr": at["frr"], "test_eer": mt["eer"], "test_eer_threshold": mt["eer_threshold"],
            "valid_pairs": mv["n_target"] + mv["n_nontarget"], "test_pairs": mt["n_target"] + mt["n_nontarget"]}
     if "best_threshold_p" in mv:
         row["threshold_p"] = mv["best_threshold_p"]
+    if score_norm != "none":
+        row.update(score_norm=score_norm, top_k=top_k if score_norm == "as-norm" else None, cohort_size=len(cohort))
     return row
 
 
-def main(argv=None):
+def result_name(a):
+    """logs/ file name of a run (``a``: the parsed arguments)."""
+    name = "verification_accuracy_{}_{}_{}".format("synthetic" if a.synthetic else a.validation_set,
+                                                   "synthetic" if a.synthetic else a.test_set, a.score)
+    if a.score_norm != "none":
+        name += "_" + a.score_norm.replace("-", "") + ("_k%d" % a.top_k if a.score_norm == "as-norm" else "") + "_c%d" % a.cohort_size
+    return name + ".csv"
+
+
+def parse_args(argv=None):
+    return _parser().parse_args(argv)
+
+
+def _parser():
     p = argparse.ArgumentParser(description=__doc__)
     p.add_argument("--siamese", default=None, help="a saved siamese network (not needed with --synthetic)")
     p.add_argument("--validation-set", default="dev-clean")
@@ -40,6 +89,15 @@ def main(argv=None):
     p.add_argument("--downsampling", type=int, default=4)
     p.add_argument("--score", default="euclidean", choices=["euclidean", "cosine", "dot_product", "head"])
     p.add_argument("--synthetic", action="store_true", help="two generated speaker sets and a freshly built model")
+    p.add_argument("--score-norm", default="none", choices=["none", "s-norm", "as-norm"], help="cohort score normalisation")
+    p.add_argument("--cohort-set", default="train-clean-100", help="the cohort's subset (a third generated set with --synthetic)")
+    p.add_argument("--cohort-size", type=int, default=5000, help="files of the cohort set taken (seeded random subset)")
+    p.add_argument("--top-k", type=int, default=300, help="as-norm: cohort rows per side")
+    return p
+
+
+def main(argv=None):
+    p = _parser()
     a = p.parse_args(argv)
     from experiments._common import setup
     rank, _ = setup()
@@ -49,6 +107,10 @@ def main(argv=None):
                                        subset="synthetic-valid")
         test = SyntheticSpeechDataset(num_speakers=20, files_per_speaker=8, seconds=a.n_seconds, stochastic=False, seed=2,
                                       subset="synthetic-test")
+        cohort = None
+        if a.score_norm != "none":
+            cohort = SyntheticSpeechDataset(num_speakers=20, files_per_speaker=8, seconds=a.n_seconds, stochastic=False, seed=3,
+                                            subset="synthetic-cohort")
         if a.siamese:
             net = models.load_model(a.siamese)
         else:
@@ -61,12 +123,16 @@ def main(argv=None):
         net = load_model(a.siamese)
         valid = LibriSpeechDataset(a.validation_set, a.n_seconds, stochastic=False)
         test = LibriSpeechDataset(a.test_set, a.n_seconds, stochastic=False)
+        cohort = None
+        if a.score_norm != "none":
+            cohort = LibriSpeechDataset(a.cohort_set, a.n_seconds, stochastic=False)
+    if cohort is not None:
+        cohort = cohort_subset(cohort, a.cohort_size)
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
-    row = evaluate(net, valid, test, pre, a.score)
+    row = evaluate(net, valid, test, pre, a.score, a.score_norm, cohort, a.top_k)
     results = pd.DataFrame([row])
     if rank == 0:
-        results.to_csv(PATH + "/logs/verification_accuracy_{}_{}_{}.csv".format(
-            "synthetic" if a.synthetic else a.validation_set, "synthetic" if a.synthetic else a.test_set, a.score), index=False)
+        results.to_csv(PATH + "/logs/" + result_name(a), index=False)
         print(results.to_string(index=False))
     return results
 

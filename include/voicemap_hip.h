@@ -52,7 +52,7 @@ enum { VM_DIST_EUCLIDEAN = 0, VM_DIST_COSINE = 1, VM_DIST_DOT = 2 };
 enum { VM_SCORE_WEIGHTED_L1 = 3, VM_SCORE_NEG_EUCLIDEAN = 4 };
 
 const char* vm_last_error(void);
-/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
+/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms), vm_cohort_topk_stats / vm_cohort_stats_workspace_bytes / vm_pair_score_hist_norm (cohort score normalisation, S-norm / AS-norm); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
  * vm_conv_dgrad_bnred; `bias`, `wf_packed` and the fourth hb row of vm_fold_bn_weights), the centred block-1 extreme (`center_bias` /
  * `shift_adj` / `mean_adj` of vm_bn_finalize) (round 4).  Earlier: 1 = round 1; 2 = vm_bn_finalize gained the zero-debias arguments (round 2); 3 = VM_F16, `dtype` in vm_conv1_fused_*,
  * `grad_scale` in the loss entry points, `skip_nonfinite` in vm_adam_clip_step, vm_embed_* / vm_pairdist_* (round 3); 4 = the folded-BatchNorm training forward
@@ -566,6 +566,32 @@ int vm_pairdist_argmin(const float* q, const float* ref, int64_t M, int64_t N, i
 int64_t vm_pair_score_hist_workspace_bytes(int64_t N, int E);
 int vm_pair_score_hist(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, const float* weights, int64_t row_lo,
                        int64_t row_hi, const int64_t* host_windows, int n_windows, int bins, uint64_t* hist, void* ws, void* stream);
+/* vm_cohort_topk_stats: per-row cohort statistics for score normalisation (S-norm: K = C; AS-norm: the top K).  Query rows q (M, E),
+ * cohort rows cohort (C, E).
+ * Scores.  For query row m and cohort row c, s_mc is the same score vm_pair_score_hist would give the pair, bit for bit: for VM_DIST_*
+ * bit-identical to dist[m][c] of vm_pairdist_argmin(q, cohort, ...); VM_SCORE_NEG_EUCLIDEAN the negated euclidean; VM_SCORE_WEIGHTED_L1
+ * the ascending-e fmaf sum with `weights`.  E <= 256.
+ * Exclusion.  If self_row0 >= 0, query row m is cohort row self_row0 + m and that pair is skipped (the convention of q_row0 of
+ * vm_pairdist_argmin).  NaN scores are skipped.
+ * Selection.  Let V be the remaining scores and K' = min(K, |V|).  The selection is the K' smallest of V by (uint32 key of the score,
+ * cohort index) ascending; the key is vm_pair_score_hist's, with -0.0 taken as +0.0.  "Smallest" means most alike.  Ties at the K-th key
+ * are broken by the lower cohort index, so exactly K' are chosen.  K = C means S-norm over the whole cohort.  K >= 1.
+ * Outputs.  count[m] = K'.  mu[m] and sigma[m] are the mean and the population standard deviation of the selected scores, accumulated in
+ * float64 and rounded to fp32 once.  rsig[m] = (float)(1.0 / (double)sigma[m]).  If K' = 0, mu, sigma and rsig are NaN; if sigma = 0,
+ * rsig = +inf.  topk_idx (M, K) int32 is optional (NULL: not written): the selected cohort indices in (key, index) order, padded with -1.
+ * Determinism.  Bit-identical from run to run: a fixed summation order, no float atomics.
+ * ws >= vm_cohort_stats_workspace_bytes(M, C, E) (a score tile of at most ~192 MB).  M, C < 2^31. */
+int64_t vm_cohort_stats_workspace_bytes(int64_t M, int64_t C, int E);
+int vm_cohort_topk_stats(const float* q, int64_t M, const float* cohort, int64_t C, int E, int score_kind, const float* weights,
+                         int64_t self_row0, int64_t K, float* mu, float* sigma, float* rsig, int32_t* count, int32_t* topk_idx, void* ws,
+                         void* stream);
+/* vm_pair_score_hist_norm: vm_pair_score_hist on normalised scores.  mu, rsig (N) fp32 on the device, indexed by row (vm_cohort_topk_stats
+ * of the rows of emb).  The pair {i, j} is binned on  a = s - mu[i];  b = s - mu[j];  s' = 0.5f * (a * rsig[i] + b * rsig[j])  in fp32,
+ * in exactly that order, every operation rounded on its own (no contraction into fma).  Everything else as vm_pair_score_hist; ws >=
+ * vm_pair_score_hist_workspace_bytes(N, E). */
+int vm_pair_score_hist_norm(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, const float* weights, int64_t row_lo,
+                            int64_t row_hi, const int64_t* host_windows, int n_windows, int bins, const float* mu, const float* rsig,
+                            uint64_t* hist, void* ws, void* stream);
 
 /* ---- a10 / f4: log-mel front-end and the 2-D CNN encoder variant (BASELINE.json config 4) -------------------
  * NOT in the reference (nothing to cite under /root/reference); the specification is DESIGN.md section 9 and the

@@ -122,6 +122,9 @@ SIGNATURES = {
     "vm_pairdist_argmin": (I, [P, P, L, L, I, I, L, P, P, P, P, P]),
     "vm_pair_score_hist_workspace_bytes": (L, [L, I]),
     "vm_pair_score_hist": (I, [P, P, L, I, I, P, L, L, P, I, I, P, P, P]),
+    "vm_pair_score_hist_norm": (I, [P, P, L, I, I, P, L, L, P, I, I, P, P, P, P, P]),
+    "vm_cohort_stats_workspace_bytes": (L, [L, L, I]),
+    "vm_cohort_topk_stats": (I, [P, L, P, L, I, I, P, L, L, P, P, P, P, P, P, P]),
     "vm_stft_frames": (L, [L, I, I]),
     "vm_stft_logmel": (I, [P, I, L, L, I, I, P, P, I, F, I, P, P]),
     "vm_stft_split_basis_bytes": (L, [I]),

@@ -13,6 +13,10 @@
 // to dist[i][j] of vm_pairdist_argmin.  Only reference tiles that hold some j > i are visited and the pairs j <= i are masked.  Counts go
 // into per-workgroup u32 LDS histograms (ds_add_u32: integer adds, order-independent) and each workgroup flushes its non-zero bins once
 // with 64-bit agent-scope atomic adds into the u64 global counts: results are bit-identical from run to run.
+//
+// vm_pair_score_hist_norm (NORM): the same pass on cohort-normalised scores (cohort.hip computes the per-row statistics): the pair
+// {i, j} is binned on 0.5 (a rsig[i] + b rsig[j]), a = s - mu[i], b = s - mu[j], each operation rounded on its own (no fma contraction,
+// so numpy's fp32 reproduces it).  The query side's mu / rsig are wave-uniform registers, the reference side's are read beside its labels.
 #include "common.hpp"
 
 namespace vm {
@@ -33,18 +37,30 @@ __device__ inline uint32_t vh_key(float s) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// the normalised score: fp32, every operation rounded on its own
+__device__ inline float vh_norm(float s, float mi, float ri, float mj, float rj) {
+#pragma clang fp contract(off)
+    const float a = s - mi;
+    const float b = s - mj;
+    const float x = a * ri;
+    const float y = b * rj;
+    return 0.5f * (x + y);
+}
+
 __global__ __launch_bounds__(256) void vh_pad_weights_kernel(const float* __restrict__ w, int E, float* __restrict__ wpad) {
     const int e = threadIdx.x;
     if (e < VH_MAX_E) wpad[e] = (w != nullptr && e < E) ? w[e] : 0.f;
 }
 
 // grid (query blocks of 64 rows of [row_lo, row_lo + M), splits of the block's reference tiles); 512 threads; the first
-// n_win * 2 * (bins + 3) words of the LDS histogram are used.  ghist (n_win, 2, bins + 3) u64, accumulated.
-template <int KIND>
+// n_win * 2 * (bins + 3) words of the LDS histogram are used.  ghist (n_win, 2, bins + 3) u64, accumulated.  NORM: the score is
+// normalised with mu / rsig (N) first (the plain pass, NORM = false, never reads them).
+template <int KIND, bool NORM = false>
 __global__ __launch_bounds__(512) void pair_hist_kernel(const float* __restrict__ qT, const float* __restrict__ ref,
                                                         const int32_t* __restrict__ label, int64_t N, int E, int64_t row_lo, int64_t M,
                                                         const float* __restrict__ rsq, const float* __restrict__ wpad, VhWindows win,
-                                                        int n_win, int bins, int splits, unsigned long long* __restrict__ ghist) {
+                                                        int n_win, int bins, int splits, unsigned long long* __restrict__ ghist,
+                                                        const float* __restrict__ mu, const float* __restrict__ rsig) {
     constexpr int RT = VH_RT, RP = VH_EC + 4;
     __shared__ __attribute__((aligned(16))) float rs[RT * RP];
     __shared__ uint32_t hist[VH_LDS_HIST_WORDS];
@@ -76,6 +92,15 @@ __global__ __launch_bounds__(512) void pair_hist_kernel(const float* __restrict_
         const bool ok = m0 + i < row_hi;
         qn[i] = (KIND == VM_DIST_COSINE && ok) ? sqrtf(rsq[m0 + i]) : 1.f;
         ql[i] = ok ? label[m0 + i] : 0;
+    }
+    float qmu[8], qrs[8];
+    if constexpr (NORM) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bool ok = m0 + i < row_hi;
+            qmu[i] = ok ? mu[m0 + i] : 0.f;
+            qrs[i] = ok ? rsig[m0 + i] : 0.f;
+        }
     }
     const int nchunk = (EP + VH_EC - 1) / VH_EC;
     const int n_stage = (t_hi - t_lo) * nchunk;
@@ -162,6 +187,15 @@ __global__ __launch_bounds__(512) void pair_hist_kernel(const float* __restrict_
             if (KIND == VM_DIST_COSINE) rn[j] = sqrtf(nn < N ? rsq[nn] : 1.f);
             rl[j] = nn < N ? label[nn] : 0;
         }
+        float rmu[2], rrs[2];
+        if constexpr (NORM) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int64_t nn = n0 + lane + 64 * j;
+                rmu[j] = nn < N ? mu[nn] : 0.f;
+                rrs[j] = nn < N ? rsig[nn] : 0.f;
+            }
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int64_t nn = n0 + lane + 64 * j;
@@ -180,6 +214,7 @@ __global__ __launch_bounds__(512) void pair_hist_kernel(const float* __restrict_
                 } else {
                     d = acc[i][j];
                 }
+                if constexpr (NORM) d = vh_norm(d, qmu[i], qrs[i], rmu[j], rrs[j]);
                 if (nn < N && nn > m && m < row_hi) {
                     const bool tgt = rl[j] == ql[i];
                     const int cls = tgt ? 0 : 1;
@@ -249,25 +284,24 @@ extern "C" int64_t vm_pair_score_hist_workspace_bytes(int64_t N, int E) {
     return N * 4 + 256 + vm::VH_MAX_E * 4 + 256 + ((N + 7) / 8) * 8 * EP * 4 + 256;
 }
 
-extern "C" int vm_pair_score_hist(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, const float* weights,
-                                  int64_t row_lo, int64_t row_hi, const int64_t* host_windows, int n_windows, int bins, uint64_t* hist,
-                                  void* ws, void* stream) {
-    using namespace vm;
-    VM_REQUIRE(emb && label && host_windows && hist && ws, "vm_pair_score_hist: null pointer");
-    VM_REQUIRE(N > 0 && N < (1LL << 31) && E > 0 && E <= VH_MAX_E, "vm_pair_score_hist: bad sizes (N < 2^31, E <= %d)", VH_MAX_E);
-    VM_REQUIRE(score_kind >= VM_DIST_EUCLIDEAN && score_kind <= VM_SCORE_NEG_EUCLIDEAN, "vm_pair_score_hist: unknown score_kind %d",
-               score_kind);
-    VM_REQUIRE(score_kind != VM_SCORE_WEIGHTED_L1 || weights, "vm_pair_score_hist: weighted_l1 needs weights");
-    VM_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= N, "vm_pair_score_hist: bad row range");
-    VM_REQUIRE(n_windows >= 1 && n_windows <= VH_MAX_WIN && bins >= 1, "vm_pair_score_hist: 1..%d windows, bins >= 1", VH_MAX_WIN);
-    VM_REQUIRE((int64_t)n_windows * 2 * (bins + 3) <= VH_LDS_HIST_WORDS, "vm_pair_score_hist: %d windows x %d bins exceed %d LDS words",
-               n_windows, bins, VH_LDS_HIST_WORDS);
-    VM_REQUIRE((E & 3) != 0 || (((uintptr_t)emb) & 15) == 0, "vm_pair_score_hist: emb must be 16-byte aligned when E %% 4 == 0");
+namespace vm {
+
+static int vh_run(const char* what, const float* emb, const int32_t* label, int64_t N, int E, int score_kind, const float* weights,
+                  int64_t row_lo, int64_t row_hi, const int64_t* host_windows, int n_windows, int bins, uint64_t* hist, const float* mu,
+                  const float* rsig, void* ws, void* stream) {
+    VM_REQUIRE(emb && label && host_windows && hist && ws, "%s: null pointer", what);
+    VM_REQUIRE(N > 0 && N < (1LL << 31) && E > 0 && E <= VH_MAX_E, "%s: bad sizes (N < 2^31, E <= %d)", what, VH_MAX_E);
+    VM_REQUIRE(score_kind >= VM_DIST_EUCLIDEAN && score_kind <= VM_SCORE_NEG_EUCLIDEAN, "%s: unknown score_kind %d", what, score_kind);
+    VM_REQUIRE(score_kind != VM_SCORE_WEIGHTED_L1 || weights, "%s: weighted_l1 needs weights", what);
+    VM_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= N, "%s: bad row range", what);
+    VM_REQUIRE(n_windows >= 1 && n_windows <= VH_MAX_WIN && bins >= 1, "%s: 1..%d windows, bins >= 1", what, VH_MAX_WIN);
+    VM_REQUIRE((int64_t)n_windows * 2 * (bins + 3) <= VH_LDS_HIST_WORDS, "%s: %d windows x %d bins exceed %d LDS words", what, n_windows, bins,
+               VH_LDS_HIST_WORDS);
+    VM_REQUIRE((E & 3) != 0 || (((uintptr_t)emb) & 15) == 0, "%s: emb must be 16-byte aligned when E %% 4 == 0", what);
     VhWindows win{};
     for (int v = 0; v < n_windows; ++v) {
         const int64_t lo = host_windows[2 * v], sh = host_windows[2 * v + 1];
-        VM_REQUIRE(lo >= 0 && lo <= 0xffffffffLL && sh >= 0 && sh <= 31, "vm_pair_score_hist: window %d: key_lo in [0, 2^32), shift in [0, 31]",
-                   v);
+        VM_REQUIRE(lo >= 0 && lo <= 0xffffffffLL && sh >= 0 && sh <= 31, "%s: window %d: key_lo in [0, 2^32), shift in [0, 31]", what, v);
         win.lo[v] = (uint32_t)lo;
         win.shift[v] = (uint32_t)sh;
     }
@@ -283,15 +317,39 @@ extern "C" int vm_pair_score_hist(const float* emb, const int32_t* label, int64_
     const int splits = vh_splits(M, N);
     const dim3 grid((unsigned)((M + VH_T - 1) / VH_T), (unsigned)splits);
     unsigned long long* gh = (unsigned long long*)hist;
-#define VM_VH(K) hipLaunchKernelGGL(pair_hist_kernel<K>, grid, dim3(512), 0, st, qT, emb, label, N, E, row_lo, M, rsq, wpad, win, n_windows, \
-                                    bins, splits, gh)
-    switch (score_kind) {
-        case VM_DIST_EUCLIDEAN: VM_VH(VM_DIST_EUCLIDEAN); break;
-        case VM_DIST_COSINE: VM_VH(VM_DIST_COSINE); break;
-        case VM_DIST_DOT: VM_VH(VM_DIST_DOT); break;
-        case VM_SCORE_WEIGHTED_L1: VM_VH(VM_SCORE_WEIGHTED_L1); break;
-        default: VM_VH(VM_SCORE_NEG_EUCLIDEAN); break;
+#define VM_VH(K, NM) hipLaunchKernelGGL((pair_hist_kernel<K, NM>), grid, dim3(512), 0, st, qT, emb, label, N, E, row_lo, M, rsq, wpad, win, \
+                                        n_windows, bins, splits, gh, mu, rsig)
+#define VM_VH_KIND(NM)                                                 \
+    switch (score_kind) {                                              \
+        case VM_DIST_EUCLIDEAN: VM_VH(VM_DIST_EUCLIDEAN, NM); break;   \
+        case VM_DIST_COSINE: VM_VH(VM_DIST_COSINE, NM); break;         \
+        case VM_DIST_DOT: VM_VH(VM_DIST_DOT, NM); break;               \
+        case VM_SCORE_WEIGHTED_L1: VM_VH(VM_SCORE_WEIGHTED_L1, NM); break; \
+        default: VM_VH(VM_SCORE_NEG_EUCLIDEAN, NM); break;             \
     }
+    if (mu == nullptr) {
+        VM_VH_KIND(false);
+    } else {
+        VM_VH_KIND(true);
+    }
+#undef VM_VH_KIND
 #undef VM_VH
-    return check_launch("vm_pair_score_hist");
+    return check_launch(what);
+}
+
+}  // namespace vm
+
+extern "C" int vm_pair_score_hist(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, const float* weights,
+                                  int64_t row_lo, int64_t row_hi, const int64_t* host_windows, int n_windows, int bins, uint64_t* hist,
+                                  void* ws, void* stream) {
+    return vm::vh_run("vm_pair_score_hist", emb, label, N, E, score_kind, weights, row_lo, row_hi, host_windows, n_windows, bins, hist,
+                      nullptr, nullptr, ws, stream);
+}
+
+extern "C" int vm_pair_score_hist_norm(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, const float* weights,
+                                       int64_t row_lo, int64_t row_hi, const int64_t* host_windows, int n_windows, int bins,
+                                       const float* mu, const float* rsig, uint64_t* hist, void* ws, void* stream) {
+    VM_REQUIRE(mu && rsig, "vm_pair_score_hist_norm: null pointer");
+    return vm::vh_run("vm_pair_score_hist_norm", emb, label, N, E, score_kind, weights, row_lo, row_hi, host_windows, n_windows, bins, hist,
+                      mu, rsig, ws, stream);
 }

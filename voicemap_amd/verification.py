@@ -19,6 +19,11 @@ value each.  EER, t*, the best balanced accuracy and its threshold then equal wh
 
 Under torchrun every rank takes one ``triangle_shards`` range of rows and the int64 histograms are all-reduced, so every rank takes the
 same zoom decisions.
+
+Cohort score normalisation (``score_norm``, ``norm=``): S-norm and AS-norm.  ``vm_cohort_topk_stats`` gives every row i the mean mu_i
+and the standard deviation sigma_i of its scores against the K cohort rows most like it (K = C: S-norm), and the pair {i, j} is scored
+s' = 0.5 ((s - mu_i) / sigma_i + (s - mu_j) / sigma_j), in fp32 exactly as ``normalise_scores_numpy`` evaluates it
+(``vm_pair_score_hist_norm``).  The exact metrics then work on s' unchanged.
 """
 from __future__ import annotations
 
@@ -81,6 +86,124 @@ def bin_scores(scores, target, windows: Sequence[Tuple[int, int]], bins: int) ->
     return out
 
 
+# ---- cohort score normalisation: the numpy twins -----------------------------------------------------------------------------------
+def cohort_select_numpy(scores, top_k: int, self_row0: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """numpy twin of ``vm_cohort_topk_stats``'s selection on an (M, C) fp32 score matrix: (topk_idx (M, top_k) int32 in (key, index) order
+    padded with -1, count (M) int32).  NaN scores and, with ``self_row0``, the pairs (m, self_row0 + m) are skipped."""
+    s = np.asarray(scores, dtype=np.float32)
+    M, C = s.shape
+    idx = np.full((M, top_k), -1, dtype=np.int32)
+    cnt = np.zeros(M, dtype=np.int32)
+    cols = np.arange(C)
+    for m in range(M):
+        ok = ~np.isnan(s[m])
+        if self_row0 is not None and self_row0 >= 0 and 0 <= self_row0 + m < C:
+            ok[self_row0 + m] = False
+        c = cols[ok]
+        order = c[np.lexsort((c, score_keys(s[m, c])))][:top_k]
+        idx[m, :len(order)] = order
+        cnt[m] = len(order)
+    return idx, cnt
+
+
+def cohort_stats_numpy(scores, top_k: int, self_row0: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """numpy twin of ``vm_cohort_topk_stats``: ``mu``, ``sigma`` (float64 mean and population standard deviation of the selected scores,
+    rounded to fp32 once), ``rsig`` = fp32(1 / float64(sigma)), ``count`` and ``topk_idx``."""
+    s = np.asarray(scores, dtype=np.float32)
+    idx, cnt = cohort_select_numpy(s, top_k, self_row0)
+    M = s.shape[0]
+    mu, sig = np.full(M, np.nan, np.float32), np.full(M, np.nan, np.float32)
+    for m in range(M):
+        if cnt[m]:
+            v = s[m, idx[m, :cnt[m]]].astype(np.float64)
+            mean = v.sum() / cnt[m]
+            mu[m] = np.float32(mean)
+            sig[m] = np.float32(np.sqrt(((v - mean) ** 2).sum() / cnt[m]))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rsig = (1.0 / sig.astype(np.float64)).astype(np.float32)
+    return {"mu": mu, "sigma": sig, "rsig": rsig, "count": cnt, "topk_idx": idx}
+
+
+def normalise_scores_numpy(s, i, j, mu, rsig) -> np.ndarray:
+    """The normalised pair score of ``vm_pair_score_hist_norm`` in fp32: a = s - mu[i]; b = s - mu[j]; 0.5 (a rsig[i] + b rsig[j]), each
+    operation rounded on its own."""
+    s = np.asarray(s, dtype=np.float32)
+    mu, rsig = np.asarray(mu, dtype=np.float32), np.asarray(rsig, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        a = s - mu[i]
+        b = s - mu[j]
+        return np.float32(0.5) * (a * rsig[i] + b * rsig[j])
+
+
+class ScoreNorm:
+    """Per-row cohort statistics of an ``EmbeddingCache`` (``score_norm``): ``mu``, ``sigma``, ``rsig`` (fp32) and ``count`` (int32) on the
+    device, with the ``score`` they were computed for, ``top_k`` (None: S-norm over the whole cohort) and ``cohort_size``."""
+
+    def __init__(self, mu, sigma, rsig, count, score, top_k, cohort_size):
+        self.mu, self.sigma, self.rsig, self.count = mu, sigma, rsig, count
+        self.score, self.top_k, self.cohort_size = score, top_k, cohort_size
+
+    @property
+    def n(self) -> int:
+        return int(self.mu.shape[0])
+
+
+def cohort_topk_stats(q: torch.Tensor, cohort: torch.Tensor, kind: int, weights, top_k: int, self_row0: int = -1,
+                      return_topk: bool = False):
+    """``vm_cohort_topk_stats`` on device tensors: (mu, sigma, rsig, count[, topk_idx])."""
+    from . import _lib
+    lib = _lib.lib()
+    dev = q.device
+    M, E = q.shape
+    C = cohort.shape[0]
+    q, cohort = q.contiguous(), cohort.contiguous()
+    mu, sig, rsig = (torch.empty(M, dtype=torch.float32, device=dev) for _ in range(3))
+    cnt = torch.empty(M, dtype=torch.int32, device=dev)
+    topk = torch.empty(M, top_k, dtype=torch.int32, device=dev) if return_topk else None
+    if M > 0:
+        ws = torch.empty(lib.query("vm_cohort_stats_workspace_bytes", M, C, E) // 4 + 64, dtype=torch.float32, device=dev)
+        lib.call("vm_cohort_topk_stats", q.data_ptr(), M, cohort.data_ptr(), C, E, kind, None if weights is None else weights.data_ptr(),
+                 self_row0, top_k, mu.data_ptr(), sig.data_ptr(), rsig.data_ptr(), cnt.data_ptr(),
+                 None if topk is None else topk.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return (mu, sig, rsig, cnt, topk) if return_topk else (mu, sig, rsig, cnt)
+
+
+def score_norm(cache, cohort, score: str = "euclidean", top_k: Optional[int] = 300, model=None) -> ScoreNorm:
+    """Cohort statistics of every row of ``cache`` for S-norm (``top_k=None``: the whole cohort) or AS-norm (the ``top_k`` cohort rows most
+    like the row).  ``cohort``: an ``EmbeddingCache`` or a (C, E) tensor; ``cohort is cache`` excludes each row from its own cohort.
+    score="head" takes the siamese model's head score like ``verification_metrics``.  Under torchrun every rank computes its
+    ``parallel.shard_range`` rows and the rows are all-gathered: every rank holds all N."""
+    from .retrieval import all_gather_rows
+    kind, weights, _ = _score_kind(cache, score, model)
+    self_ex = cohort is cache
+    ce = cohort.emb if hasattr(cohort, "emb") else torch.as_tensor(cohort)
+    ce = ce.to(device=cache.emb.device, dtype=torch.float32).contiguous()
+    if ce.dim() != 2 or ce.shape[1] != cache.E or ce.shape[0] < 1:
+        raise ValueError("the cohort must be a non-empty (C, %d) matrix" % cache.E)
+    C = int(ce.shape[0])
+    if top_k is not None and top_k < 1:
+        raise ValueError("top_k must be >= 1 (or None for S-norm)")
+    K = C if top_k is None else min(int(top_k), C)
+    rank, world = parallel.rank_world()
+    lo, hi = parallel.shard_range(cache.n, rank, world)
+    mu, sig, rsig, cnt = cohort_topk_stats(cache.emb[lo:hi], ce, kind, weights, K, lo if self_ex else -1)
+    if world > 1:
+        loc = torch.stack([mu.double(), sig.double(), rsig.double(), cnt.double()], 1)
+        allr = all_gather_rows(loc, cache.n)
+        mu, sig, rsig = (allr[:, k].float().contiguous() for k in range(3))
+        cnt = allr[:, 3].to(torch.int32).contiguous()
+    return ScoreNorm(mu, sig, rsig, cnt, score, top_k, C)
+
+
+def _check_norm(cache, score, norm):
+    if norm is None:
+        return
+    if norm.score != score:
+        raise ValueError("the ScoreNorm was computed for score %r, not %r" % (norm.score, score))
+    if norm.n != cache.n:
+        raise ValueError("the ScoreNorm holds %d rows, the cache %d" % (norm.n, cache.n))
+
+
 # ---- rows of the triangle --------------------------------------------------------------------------------------------------------
 def _pairs_before(i, N):
     """Pairs {i', j}, i' < i, j > i'."""
@@ -130,7 +253,7 @@ def _score_kind(cache, score: str, model) -> Tuple[int, Optional[torch.Tensor], 
     return (SCORES["euclidean"] if w >= 0 else VM_SCORE_NEG_EUCLIDEAN), None, (w, bias)
 
 
-def _device_hist(cache, kind: int, weights, windows, bins: int, rows: Tuple[int, int]) -> np.ndarray:
+def _device_hist(cache, kind: int, weights, windows, bins: int, rows: Tuple[int, int], norm=None) -> np.ndarray:
     from . import _lib
     lib = _lib.lib()
     dev = cache.emb.device
@@ -140,28 +263,34 @@ def _device_hist(cache, kind: int, weights, windows, bins: int, rows: Tuple[int,
         emb = cache.emb.contiguous()
         ws = torch.empty(lib.query("vm_pair_score_hist_workspace_bytes", cache.n, cache.E) // 4 + 64, dtype=torch.float32, device=dev)
         win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
-        lib.call("vm_pair_score_hist", emb.data_ptr(), cache.speaker_dev.data_ptr(), cache.n, cache.E, kind,
-                 None if weights is None else weights.data_ptr(), lo, hi, win.ctypes.data, len(windows), bins, hist.data_ptr(), ws.data_ptr(),
-                 torch.cuda.current_stream(dev).cuda_stream)
+        if norm is None:
+            lib.call("vm_pair_score_hist", emb.data_ptr(), cache.speaker_dev.data_ptr(), cache.n, cache.E, kind,
+                     None if weights is None else weights.data_ptr(), lo, hi, win.ctypes.data, len(windows), bins, hist.data_ptr(), ws.data_ptr(),
+                     torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            lib.call("vm_pair_score_hist_norm", emb.data_ptr(), cache.speaker_dev.data_ptr(), cache.n, cache.E, kind,
+                     None if weights is None else weights.data_ptr(), lo, hi, win.ctypes.data, len(windows), bins, norm.mu.data_ptr(),
+                     norm.rsig.data_ptr(), hist.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     return hist
 
 
 def score_histogram(cache, score: str, windows: Sequence[Tuple[int, int]], bins: int, rows: Optional[Tuple[int, int]] = None,
-                    model=None) -> np.ndarray:
+                    model=None, norm: Optional[ScoreNorm] = None) -> np.ndarray:
     """(n_windows, 2, bins + 3) int64 counts of all pair scores of ``cache`` (class 0 = target) in windows (key_lo, shift).  ``rows``:
     only the pairs with i in [lo, hi); by default this rank's ``triangle_shards`` range, and under torchrun the histograms of all ranks
-    are summed."""
+    are summed.  ``norm``: the counts of the normalised scores (``score_norm``)."""
     kind, weights, _ = _score_kind(cache, score, model)
-    return _histogram(cache, kind, weights, windows, bins, rows)
+    _check_norm(cache, score, norm)
+    return _histogram(cache, kind, weights, windows, bins, rows, norm)
 
 
-def _histogram(cache, kind, weights, windows, bins, rows=None) -> np.ndarray:
+def _histogram(cache, kind, weights, windows, bins, rows=None, norm=None) -> np.ndarray:
     if len(windows) > MAX_WINDOWS or len(windows) * 2 * (bins + 3) > LDS_WORDS:
         raise ValueError("at most %d windows and %d histogram words per launch" % (MAX_WINDOWS, LDS_WORDS))
     rank, world = parallel.rank_world()
     if rows is not None:
-        return _device_hist(cache, kind, weights, windows, bins, rows).cpu().numpy()
-    h = _device_hist(cache, kind, weights, windows, bins, triangle_shards(cache.n, world)[rank])
+        return _device_hist(cache, kind, weights, windows, bins, rows, norm).cpu().numpy()
+    h = _device_hist(cache, kind, weights, windows, bins, triangle_shards(cache.n, world)[rank], norm)
     if world > 1:
         import torch.distributed as dist
         comm = h.to(parallel._comm_device())
@@ -378,7 +507,7 @@ def _bounds(cache, kind) -> Tuple[float, float]:
     return -r * r, r * r   # dot product (and weighted_l1 below)
 
 
-def _sampled_window(cache, kind, weights, lo: float, hi: float, n_sample: int = 1 << 16) -> Tuple[int, int]:
+def _sampled_window(cache, kind, weights, lo: float, hi: float, n_sample: int = 1 << 16, norm=None) -> Tuple[int, int]:
     """Pass 1's window: the 1e-4 .. 1 - 1e-4 quantiles of the scores of a seeded sample of pairs (torch arithmetic: it only places the
     window -- whatever falls outside lands in the under / over slots and the counts stay exact), clipped to the cheap bounds [lo, hi].
     The bins then cover the bulk of the scores, not the key range of the bounds, and one zoom pass usually reaches single keys.  Under
@@ -401,6 +530,10 @@ def _sampled_window(cache, kind, weights, lo: float, hi: float, n_sample: int = 
                 sc = -(a * b).sum(1)
             else:
                 sc = ((a - b).abs() * weights.double()).sum(1)
+            if norm is not None:   # the sample's normalised scores (float64: only the window depends on them)
+                ii, jj = i.to(norm.mu.device), j.to(norm.mu.device)
+                mu, rs = norm.mu.double(), norm.rsig.double()
+                sc = 0.5 * ((sc - mu[ii]) * rs[ii] + (sc - mu[jj]) * rs[jj])
             sc = sc[torch.isfinite(sc)].cpu().numpy()
             if len(sc) > 100:
                 q0, q1 = np.quantile(sc, [1e-4, 1 - 1e-4])
@@ -416,20 +549,42 @@ def _sampled_window(cache, kind, weights, lo: float, hi: float, n_sample: int = 
     return int(win[0]), int(win[1])
 
 
-def verification_metrics(cache, score: str = "euclidean", model=None, bins: int = PASS1_BINS) -> Dict:
+def _norm_bounds(norm: ScoreNorm, lo: float, hi: float) -> Tuple[float, float]:
+    """Bounds of the normalised scores of raw scores in [lo, hi]: each half (s - mu_i) rsig_i lies in [(lo - mu_i) rsig_i, (hi - mu_i)
+    rsig_i] (rsig >= 0); rows whose statistics are not finite are left out (their scores are NaN or infinite: the NaN / over slots)."""
+    mu, rs = norm.mu.double(), norm.rsig.double()
+    a, b = (lo - mu) * rs, (hi - mu) * rs
+    ok = torch.isfinite(a) & torch.isfinite(b)
+    if not bool(ok.any()):
+        return -1.0, 1.0
+    lo2, hi2 = float(a[ok].min().item()), float(b[ok].max().item())
+    pad = 1e-5 * max(abs(lo2), abs(hi2)) + 1e-30
+    lo2, hi2 = lo2 - pad, hi2 + pad
+    big = float(np.finfo(np.float32).max)
+    return max(lo2, -big), min(hi2, big)
+
+
+def verification_metrics(cache, score: str = "euclidean", model=None, bins: int = PASS1_BINS, norm: Optional[ScoreNorm] = None) -> Dict:
     """All-pairs verification metrics of ``cache`` (module docstring): ``eer``, ``eer_threshold``, ``best_balanced_accuracy``,
     ``best_threshold``, FAR / FRR at both, ``auc`` and ``auc_bound`` (the true AUC lies within it), ``roc`` (pass-1 edges as float
     thresholds with FAR and FRR), ``n_target``, ``n_nontarget``, ``n_nan`` and ``passes``.  score="head": the siamese model's own head
-    (a uniform_euclidean head is monotone in the distance; the thresholds are then also reported as head outputs p, ``*_p``)."""
+    (a uniform_euclidean head is monotone in the distance; the thresholds are then also reported as head outputs p, ``*_p``).
+    ``norm``: the metrics of the cohort-normalised scores (``score_norm``); the thresholds are then in normalised units."""
     if bins != PASS1_BINS:
         raise ValueError("pass 1 takes %d bins" % PASS1_BINS)
     kind, weights, head = _score_kind(cache, score, model)
+    _check_norm(cache, score, norm)
     if kind == SCORES["weighted_l1"]:
         wsum = float(weights.abs().double().sum().item())
         amax = float(cache.emb.abs().max().item()) if cache.n else 0.0
         lo, hi = -2 * amax * wsum * 1.001 - 1e-30, 2 * amax * wsum * 1.001 + 1e-30
     else:
         lo, hi = _bounds(cache, kind)
+    if norm is not None:
+        lo, hi = _norm_bounds(norm, lo, hi)
+        out = exact_sweep(lambda wins, b: _histogram(cache, kind, weights, wins, b, norm=norm),
+                          _sampled_window(cache, kind, weights, lo, hi, norm=norm))
+        return out
     out = exact_sweep(lambda wins, b: _histogram(cache, kind, weights, wins, b), _sampled_window(cache, kind, weights, lo, hi))
     if head is not None:
         w, b = head
@@ -446,12 +601,13 @@ def _head_p(t: float, w: float, b: float) -> float:
     return 1.0 / (1.0 + math.exp(-a)) if a > -700 else 0.0
 
 
-def accuracy_at_threshold(cache, t: float, score: str = "euclidean", model=None) -> Dict:
-    """Balanced accuracy, FAR and FRR at a fixed threshold t (in score units): one pass with key_lo = key(t), whose under slot is then
-    exactly {s < t}."""
+def accuracy_at_threshold(cache, t: float, score: str = "euclidean", model=None, norm: Optional[ScoreNorm] = None) -> Dict:
+    """Balanced accuracy, FAR and FRR at a fixed threshold t (in score units; with ``norm``, in normalised units): one pass with key_lo =
+    key(t), whose under slot is then exactly {s < t}."""
     kind, weights, _ = _score_kind(cache, score, model)
+    _check_norm(cache, score, norm)
     k = key_of(t) if not math.isnan(t) else KEY_SPACE - 1
-    h = _histogram(cache, kind, weights, [(k, 31)], 1)[0]
+    h = _histogram(cache, kind, weights, [(k, 31)], 1, norm=norm)[0]
     nT, nN = int(h[0, :-1].sum()), int(h[1, :-1].sum())
     far = float(h[1, 1]) / nN if nN else float("nan")
     frr = float(nT - h[0, 1]) / nT if nT else float("nan")
