@@ -10,7 +10,8 @@ experiments/train_siamese.py:54-57.  Figures land in gpurun_out/parity_report.cs
 Bounds: the north star asks for embeddings within 1e-3 (relative) of the reference arithmetic.  'f32' / 'f32s' meet it by three
 orders of magnitude, 'f16' (half storage, the bf16 kernels with 11 significand bits) meets it, 'bf16' does not (5e-3) and is held to
 its own documented bound.  Gradient errors at this size are max-pool re-routing: direction (cosine) is asserted,
-the per-tensor figures are reported.
+and in the fresh state the fp32-storage modes are also held per tensor; the other per-tensor figures are reported.  The worst single
+embedding (per row) is reported for every mode and held to 1e-4 in the fp32-storage modes.
 """
 import os
 import time
@@ -20,13 +21,21 @@ import pytest
 import torch
 
 from oracle import voicemap_oracle as O
-from tests.gpu_util import cosine, rel_err, report
+from tests.gpu_util import cosine, grad_close, rel_err, report, row_rel_err
 
 pytestmark = pytest.mark.gpu
 
 PAIRS, F, E = 128, 128, 64
 EMB_TOL = {"f32": 1e-4, "f32s": 1e-4, "f16": 1e-3, "bf16": 3e-2}
 GRAD_COS = {"f32": 0.9999, "f32s": 0.9999, "f16": 0.99, "bf16": 0.9}
+# the worst single embedding (max over rows of ||e_i - e_ref_i|| / ||e_ref_i||) of the fp32-storage modes, in both states
+ROW_TOL = {"f32": 1e-4, "f32s": 1e-4}
+# per gradient tensor, fresh state: about 10 x what r06 measured at 3 s (5e-4 f32, 4e-3 f32s; tests/test_gpu_fragment_lengths.py
+# holds every fragment length to the same).  dense.bias and bn4.beta are analytically zero (the twin towers' contributions cancel):
+# an absolute bound.  In the trained-like state the fp32 oracle routes a few max-pool gradients differently (r06
+# measured 1.0e-2 for conv1.kernel in f32 AND f32s alike), so there the per-tensor figures are reported and the cosine is asserted.
+GRAD_TOL = {"f32": 5e-3, "f32s": 3e-2}
+ZERO_GRADS, ZERO_ATOL = ("dense.bias", "bn4.beta"), 1e-6
 # second state (VERDICT r3 weak #1a): the same batch through a net whose BatchNorm gamma (15 % negative), beta and conv / dense biases
 # are those of a trained network, not of a fresh one -- the 16-bit modes are held to what they MEASURE there (bounds below; the
 # figures go to the parity report and bench.py's precision object quotes them), the fp32-storage modes to the same 1e-4
@@ -114,6 +123,10 @@ def test_cfgA_full_batch_against_the_cpu_oracle(dtype, oracle_full_size):
     d_emb = rel_err(emb, o["emb"])
     report(tag, "emb_rel_err_vs_fp64_oracle", d_emb)
     report(tag, "emb_max_abs_err_over_max_abs", float(np.abs(emb - o["emb"]).max() / np.abs(o["emb"]).max()))
+    r_emb = row_rel_err(emb, o["emb"])
+    report(tag, "emb_row_rel_err_vs_fp64_oracle", r_emb)
+    if dtype in ROW_TOL:
+        assert r_emb < ROW_TOL[dtype], (dtype, r_emb)
     loss = float(pl["loss_acc"][0].item())
     report(tag, "loss_abs_err_vs_fp64_oracle", abs(loss - o["loss"]))
     assert d_emb < EMB_TOL[dtype], (dtype, d_emb)
@@ -136,9 +149,13 @@ def test_cfgA_full_batch_against_the_cpu_oracle(dtype, oracle_full_size):
     cos = cosine(flat_h, flat_o)
     report(tag, "grad_cosine_vs_fp32_oracle", cos)
     report(tag, "grad_rel_err_vs_fp32_oracle", rel_err(flat_h, flat_o))
+    far = []
     for k, g in o["grads"].items():
         report(tag, "grad_rel_err[%s]" % k, rel_err(grads[k], g))
+        if dtype in GRAD_TOL and not grad_close(grads[k], g, GRAD_TOL[dtype], atol=ZERO_ATOL if k in ZERO_GRADS else 0.0):
+            far.append((k, rel_err(grads[k], g)))
     assert cos > GRAD_COS[dtype], (dtype, cos)
+    assert not far, (dtype, far)
     del eng, pl
     torch.cuda.empty_cache()
 
@@ -159,6 +176,10 @@ def test_cfgA_full_batch_trained_like_batchnorm_state(dtype, oracle_full_size):
     d_emb = rel_err(emb, t["emb"])
     report(tag, "emb_rel_err_vs_fp32_oracle", d_emb)
     report(tag, "emb_max_abs_err_over_max_abs", float(np.abs(emb - t["emb"]).max() / np.abs(t["emb"]).max()))
+    r_emb = row_rel_err(emb, t["emb"])
+    report(tag, "emb_row_rel_err_vs_fp32_oracle", r_emb)
+    if dtype in ROW_TOL:
+        assert r_emb < ROW_TOL[dtype], (dtype, r_emb)
     loss = float(pl["loss_acc"][0].item())
     report(tag, "loss_abs_err_vs_fp32_oracle", abs(loss - t["loss"]))
     grads = eng.get_grads()

@@ -1294,3 +1294,175 @@ def test_tail_fwd_bwd_equals_the_six_launches_and_the_oracle(head, loss, pairs, 
     assert rel_err(dgmax.cpu().numpy() / gs, gg.numpy()) < 1e-4 and rel_err(g_dw.cpu().numpy() / gs, gdw.numpy()) < 1e-4
     assert grad_close(g_db.cpu().numpy() / gs, gdb.numpy(), 1e-4, atol=1e-6)     # the twin towers' contributions cancel: ~0
     assert rel_err(g_hw.cpu().numpy() / gs, ghw.numpy().ravel()) < 1e-4 and rel_err(g_hb.cpu().numpy() / gs, ghb.numpy()) < 1e-4
+
+
+# ----------------------------------------------------------------------------------------------------------
+# Window counts past 65 535.  With apply_order 1 or 2 (2 is the default) the BatchNorm-backward apply pass puts the windows in
+# gridDim.y, order 0 in gridDim.x; the whitening apply pass always puts them in gridDim.y.  The 2-D variant passes 65 535 windows at
+# 1 024 clips.  Outputs start as NaN (halo rows zero), so a window that no workgroup reached cannot pass as a small error.
+BIG_WINDOWS = [65535, 65536, 70000]
+APPLY_ORDERS = (0, 1, 2)
+APPLY_ORDER_DEFAULT = 2   # tests/test_abi.py pins the defaults
+
+
+def _sentinel(shape, tdt, halo):
+    t = torch.full(shape, float("nan"), dtype=tdt, device="cuda")
+    if halo:
+        t[:, 0] = 0
+        t[:, -1] = 0
+    return t
+
+
+def _at_each_apply_order(launch, du_shape, tdt, pdu_shape):
+    """launch(du, pdu) under apply_order 0, 1 and 2; returns [(du, pdu)] per order.  The default order is restored whatever happens."""
+    outs = []
+    try:
+        for order in APPLY_ORDERS:
+            L().call("vm_set_tuning", b"apply_order", order)
+            du = _sentinel(du_shape, tdt, True)
+            pdu = _sentinel(pdu_shape, torch.float32, False)
+            launch(du, pdu)
+            torch.cuda.synchronize()
+            outs.append((du, pdu))
+    finally:
+        L().call("vm_set_tuning", b"apply_order", APPLY_ORDER_DEFAULT)
+    return outs
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=["dense", "gmax"])
+@pytest.mark.parametrize("dt", ["f32", "f16"])
+@pytest.mark.parametrize("n", BIG_WINDOWS)
+def test_bn_pool_bwd_apply_past_65535_windows(n, dt, sparse):
+    """vm_bn_pool_bwd_apply / _apply_gmax at n_windows around 2^16 under every apply_order, against the float64 BatchNorm -> max-pool
+    backward of _bn_block_oracle: every window is written, the windows past 65 535 as accurate as the rest, and the three orders give
+    the same bits (the kernel's claim: same blocks, same sums)."""
+    vm, tdt = DTYPES[dt]
+    r = rng(n)
+    l, c, pool = 8, 16, 2
+    lq = l // pool
+    towers = 3 if n % 3 == 0 else 2
+    wpt = n // towers
+    f32 = dict(dtype=torch.float32, device="cuda")
+    z = quant(np.maximum(r.normal(0.2, 1.0, (n, l, c)), 0.0), dt)
+    gamma = torch.tensor(r.normal(1.0, 0.3, c) * np.where(r.random(c) < 0.2, -1, 1), dtype=torch.float64)
+    beta = torch.tensor(r.normal(0, 0.3, c), dtype=torch.float64)
+    zd = z.to("cuda", tdt).contiguous()
+    ssum = z.sum(1).to("cuda", torch.float32).contiguous()
+    ssq = (z * z).sum(1).to("cuda", torch.float32).contiguous()
+    mean, invstd, scale, shift = (torch.empty(towers, c, **f32) for _ in range(4))
+    mm, mv = torch.zeros(c, **f32), torch.ones(c, **f32)
+    crws = torch.empty(L().query("vm_colreduce_workspace_bytes", towers, c) // 8, dtype=torch.float64, device="cuda")
+    L().call("vm_bn_finalize", p(ssum), p(ssq), wpt, towers, c, float(wpt * l), p(dev(gamma)), p(dev(beta)), 1e-3, 0.99, 1,
+             p(mm), p(mv), p(mean), p(invstd), p(scale), p(shift), p(crws), None, 0.0, None, None, None, None, stream())
+    zr = z.clone().requires_grad_(True)
+    out_ref, _ = _bn_block_oracle(zr, gamma, beta, None, pool, wpt)
+    if sparse:   # dp of GlobalMaxPool1D's backward: one routed value per (window, channel), as the dense tensor would hold it
+        dg = r.normal(0, 1, (n, c)).astype(np.float32)
+        gidx = r.integers(0, lq, (n, c)).astype(np.int32)
+        dp = torch.zeros(n, lq, c, dtype=torch.float64)
+        dp.scatter_(1, torch.from_numpy(gidx.astype(np.int64))[:, None, :], quant(dg, dt)[:, None, :])
+        head = (p(zd), p(dev(dg)), p(dev(gidx, torch.int32)))
+    else:
+        dp = quant(r.normal(0, 1, (n, lq, c)), dt)
+        head = (p(zd), p(dev(dp, tdt)))
+    gz = torch.autograd.grad((out_ref * dp).sum(), [zr])[0] * (z > 0)
+    rows = L().query("vm_bn_part_rows")
+    pa, pb = torch.zeros(n * rows, c, **f32), torch.zeros(n * rows, c, **f32)
+    c1, c2 = torch.empty(towers, c, **f32), torch.empty(towers, c, **f32)
+    ggam, gbet = torch.empty(c, **f32), torch.empty(c, **f32)
+    bn = (p(scale), p(shift), p(mean), p(invstd), None)
+    L().call("vm_bn_pool_bwd_reduce_gmax" if sparse else "vm_bn_pool_bwd_reduce", *head, *bn, n, wpt, l, c, pool, vm, p(pa), p(pb),
+             stream())
+    L().call("vm_bn_bwd_finalize", p(pa), p(pb), n, wpt, c, float(wpt * l), p(c1), p(c2), p(ggam), p(gbet), p(crws), stream())
+    name = "vm_bn_pool_bwd_apply_gmax" if sparse else "vm_bn_pool_bwd_apply"
+    outs = _at_each_apply_order(lambda du, pdu: L().call(name, *head, *bn, p(c1), p(c2), n, wpt, l, c, pool, vm, p(du), p(pdu), stream()),
+                                (n, l + 2, c), tdt, (n * rows, c))
+    for order, (du, pdu) in zip(APPLY_ORDERS, outs):
+        assert torch.equal(du, outs[0][0]) and torch.equal(pdu, outs[0][1]), order
+    du, pdu = outs[0]
+    d = du.float().cpu().numpy()
+    assert np.all(d[:, 0] == 0) and np.all(d[:, -1] == 0)
+    assert np.isfinite(d).all() and torch.isfinite(pdu).all()
+    tol = 5e-5 if dt == "f32" else 1e-2
+    g = gz.numpy()
+    assert rel_err(d[:, 1:-1], g) < tol
+    assert rel_err(d[65535 - 8:, 1:-1], g[65535 - 8:]) < tol   # the windows at and past the 16-bit grid edge on their own
+    gbias = torch.empty(c, **f32)
+    L().call("vm_colsum", p(pdu), n * rows, c, p(gbias), p(crws), stream())
+    assert rel_err(gbias.cpu().numpy(), d[:, 1:-1].astype(np.float64).sum((0, 1))) < 1e-5
+
+
+@pytest.mark.parametrize("sparse", [False, True], ids=["dense", "gmax"])
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+def test_bn_pool_bwd_apply_pairs_equals_apply_on_z_past_65535_windows(dtype, sparse):
+    """vm_bn_pool_bwd_apply_pairs / _pairs_gmax on (e, o) at 70 000 windows == vm_bn_pool_bwd_apply / _gmax on the z they encode, bit
+    for bit, under every apply_order (tests/test_gpu_fold.py checks the same at 4 windows)."""
+    vm, tdt = DTYPES[dtype]
+    r = rng(17)
+    n, wpt, Lw, c = 70000, 35000, 8, 16
+    z = quant(np.maximum(r.normal(0, 1, (n, Lw, c)), 0.0), dtype)
+    z[:, 2:4] = z[:, 2:3]                                            # a tie in every channel
+    dp = quant(r.normal(0, 1, (n, Lw // 2, c)), dtype)
+    dg = r.normal(0, 1, (n, c)).astype(np.float32)
+    gidx = r.integers(0, Lw // 2, (n, c)).astype(np.int32)
+    scale = (r.normal(1.0, 0.3, (2, c)) * np.where(r.random((2, c)) < 0.3, -1, 1)).astype(np.float32)
+    shift, mean = r.normal(0, 0.5, (2, c)).astype(np.float32), r.normal(0.4, 0.1, (2, c)).astype(np.float32)
+    invstd = r.uniform(0.5, 2.0, (2, c)).astype(np.float32)
+    c1, c2 = r.normal(0, 0.01, (2, c)).astype(np.float32), r.normal(0, 0.01, (2, c)).astype(np.float32)
+    zt = z.to("cuda", tdt)
+    pr = zt.view(n, Lw // 2, 2, c)
+    pos = torch.tensor(scale >= 0, device="cuda").repeat_interleave(wpt, 0)[:, None, :]
+    second = torch.where(pos, pr[:, :, 1] > pr[:, :, 0], pr[:, :, 1] < pr[:, :, 0])
+    ext = torch.where(second, pr[:, :, 1], pr[:, :, 0])
+    oth = torch.where(second, pr[:, :, 0], pr[:, :, 1])
+    ep = torch.zeros(n, Lw // 2 + 2, c, dtype=tdt, device="cuda")
+    ep[:, 1:-1] = ext
+    o = (oth.contiguous().view(torch.int16) | (second.to(torch.int16) << 15)).view(tdt).contiguous()
+    prow = L().query("vm_bn_part_rows")
+    src = (p(dev(dg)), p(dev(gidx, torch.int32))) if sparse else (p(dev(dp, tdt)),)
+    bn = (p(dev(scale)), p(dev(shift)), p(dev(mean)), p(dev(invstd)), None, p(dev(c1)), p(dev(c2)), n, wpt, Lw, c)
+    zc = zt.contiguous()
+    if sparse:
+        on_z = lambda du, pdu: L().call("vm_bn_pool_bwd_apply_gmax", p(zc), *src, *bn, 2, vm, p(du), p(pdu), stream())
+        on_pairs = lambda du, pdu: L().call("vm_bn_pool_bwd_apply_pairs_gmax", p(ep), p(o), *src, *bn, vm, p(du), p(pdu), stream())
+    else:
+        on_z = lambda du, pdu: L().call("vm_bn_pool_bwd_apply", p(zc), *src, *bn, 2, vm, p(du), p(pdu), stream())
+        on_pairs = lambda du, pdu: L().call("vm_bn_pool_bwd_apply_pairs", p(ep), p(o), *src, *bn, vm, p(du), p(pdu), None, stream())
+    shapes = ((n, Lw + 2, c), tdt, (n * prow, c))
+    ref = _at_each_apply_order(on_z, *shapes)
+    got = _at_each_apply_order(on_pairs, *shapes)
+    for order, (a, b) in zip(APPLY_ORDERS, zip(ref, got)):
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), order
+        assert torch.equal(a[0], ref[0][0]) and torch.equal(a[1], ref[0][1]), order
+    assert torch.isfinite(ref[0][0]).all() and torch.isfinite(ref[0][1]).all()
+    assert ref[0][0][65535:].abs().sum() > 0
+
+
+@pytest.mark.parametrize("crop", [False, True], ids=["rows", "crop"])
+def test_decimate_whiten_past_65535_windows(crop):
+    """vm_decimate_whiten / vm_crop_decimate_whiten at 70 000 windows (the whitening apply pass has them in gridDim.y) against
+    O.preprocess_instances per tower, every window, halo included."""
+    r = rng(19)
+    n, wpt, raw_len, ds = 70000, 500, 401, 4
+    l0 = (raw_len + ds - 1) // ds
+    if crop:
+        total = 2_000_003
+        audio = (r.normal(0, 0.05, total) + 0.01 * np.sin(np.arange(total) / 900.0)).astype(np.float32)
+        offs = r.integers(0, total - raw_len, n).astype(np.int64)
+        offs[0], offs[-1] = 0, total - raw_len
+        win = audio[offs[:, None] + np.arange(raw_len)[None, :]]
+    else:
+        win = (r.normal(0, 0.05, (n, raw_len)) + r.uniform(-0.01, 0.01, (n, 1))).astype(np.float32)
+    out = torch.full((n, l0 + 31), float("nan"), device="cuda")
+    ws = torch.empty(L().query("vm_decimate_whiten_workspace_bytes", n) // 8, dtype=torch.float64, device="cuda")
+    if crop:
+        L().call("vm_crop_decimate_whiten", p(dev(audio)), 0, p(dev(offs, torch.int64)), n, raw_len, ds, 1, 0.038021, wpt, p(out),
+                 p(ws), stream())
+    else:
+        L().call("vm_decimate_whiten", p(dev(win)), 0, n, raw_len, ds, 1, 0.038021, wpt, p(out), p(ws), stream())
+    pre = O.preprocess_instances(ds)
+    w64 = win.astype(np.float64)
+    ref = np.concatenate([pre(w64[t:t + wpt, :, None]) for t in range(0, n, wpt)])[:, :, 0]
+    o = out.cpu().numpy()
+    assert np.all(o[:, :15] == 0) and np.all(o[:, 15 + l0:] == 0)
+    assert max_err(o[:, 15:15 + l0], ref) < 1e-7
