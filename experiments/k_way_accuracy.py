@@ -27,9 +27,12 @@ def main(argv=None):
     p.add_argument("--cached", action="store_true",
                    help="embed the evaluation set ONCE per model and run every (k, n) cell on the cached (N, E) matrix "
                         "(voicemap_amd/retrieval.py: tasks are row indices, one launch per cell; each window whitened alone)")
+    p.add_argument("--whole-utterance", action="store_true", help="with --cached: embed every file whole, at its own length")
     p.add_argument("--device-sampler", action="store_true", help="with --cached: draw the tasks on the GPU (same distribution, not "
                                                                  "the reference's np.random sequence)")
     a = p.parse_args(argv)
+    if a.whole_utterance and not a.cached:
+        p.error("--whole-utterance needs --cached")
     # under torchrun the tasks of every (k, n) cell are sharded over the ranks (BASELINE.json config 5); rank 0 writes the CSV
     from experiments._common import setup
     rank, _ = setup()
@@ -47,7 +50,7 @@ def main(argv=None):
     if a.cached:
         from voicemap_amd import retrieval
         for method, kind, net in nets:
-            caches[method] = retrieval.embed_corpus(net, valid, pre, kind)      # sharded over ranks + all-gathered under torchrun
+            caches[method] = retrieval.embed_corpus(net, valid, pre, kind, whole_utterance=a.whole_utterance)      # sharded over ranks + all-gathered under torchrun
         if a.device_sampler:
             sampler = retrieval.DeviceTaskSampler(valid, caches["siamese"].emb.device, seed=rank)
     if rank == 0:

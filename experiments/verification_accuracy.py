@@ -6,7 +6,9 @@ is applied to the test set's (voicemap_amd/verification.py).  Results go to logs
 With --score-norm s-norm / as-norm both sets are normalised against the same cohort (a seeded random subset of --cohort-set's files;
 as-norm over the --top-k cohort rows most like each row) and the file name gains _<score-norm>[_k<top-k>]_c<cohort-size>.
     python -m experiments.verification_accuracy --siamese models/x.hdf5 [--score euclidean|cosine|dot_product|head] [--synthetic]
-        [--score-norm none|s-norm|as-norm --cohort-set train-clean-100 --cohort-size 5000 --top-k 300]"""
+        [--score-norm none|s-norm|as-norm --cohort-set train-clean-100 --cohort-size 5000 --top-k 300] [--whole-utterance]
+With --whole-utterance every file is embedded whole, at its own length (retrieval.embed_corpus(whole_utterance=True)), and the file
+name gains _whole."""
 import argparse
 
 import numpy as np
@@ -41,15 +43,16 @@ def cohort_subset(dataset, size, seed=0):
     return CohortSubset(dataset, np.sort(np.random.default_rng(seed).choice(n, size, replace=False)))
 
 
-def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort=None, top_k=300):
+def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort=None, top_k=300, whole_utterance=False):
     """Embed both sets once, take the best-balanced-accuracy threshold of the validation trials and apply it to the test trials.
     ``score_norm`` "s-norm" / "as-norm": both sets' scores are normalised against the embeddings of ``cohort`` (a dataset)."""
     model = net if score == "head" else None
-    cv = retrieval.embed_corpus(net, valid, pre, "siamese")
-    ct = retrieval.embed_corpus(net, test, pre, "siamese")
+    wu = {"whole_utterance": True} if whole_utterance else {}
+    cv = retrieval.embed_corpus(net, valid, pre, "siamese", **wu)
+    ct = retrieval.embed_corpus(net, test, pre, "siamese", **wu)
     nv = nt = None
     if score_norm != "none":
-        cc = retrieval.embed_corpus(net, cohort, pre, "siamese")
+        cc = retrieval.embed_corpus(net, cohort, pre, "siamese", **wu)
         k = None if score_norm == "s-norm" else top_k
         nv = verification.score_norm(cv, cc, score, top_k=k, model=model)
         nt = verification.score_norm(ct, cc, score, top_k=k, model=model)
@@ -62,6 +65,8 @@ def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort
            "valid_pairs": mv["n_target"] + mv["n_nontarget"], "test_pairs": mt["n_target"] + mt["n_nontarget"]}
     if "best_threshold_p" in mv:
         row["threshold_p"] = mv["best_threshold_p"]
+    if whole_utterance:
+        row["whole_utterance"] = True
     if score_norm != "none":
         row.update(score_norm=score_norm, top_k=top_k if score_norm == "as-norm" else None, cohort_size=len(cohort))
     return row
@@ -73,6 +78,8 @@ def result_name(a):
                                                    "synthetic" if a.synthetic else a.test_set, a.score)
     if a.score_norm != "none":
         name += "_" + a.score_norm.replace("-", "") + ("_k%d" % a.top_k if a.score_norm == "as-norm" else "") + "_c%d" % a.cohort_size
+    if getattr(a, "whole_utterance", False):
+        name += "_whole"
     return name + ".csv"
 
 
@@ -93,6 +100,7 @@ def _parser():
     p.add_argument("--cohort-set", default="train-clean-100", help="the cohort's subset (a third generated set with --synthetic)")
     p.add_argument("--cohort-size", type=int, default=5000, help="files of the cohort set taken (seeded random subset)")
     p.add_argument("--top-k", type=int, default=300, help="as-norm: cohort rows per side")
+    p.add_argument("--whole-utterance", action="store_true", help="embed every file whole, at its own length (not its first --n-seconds)")
     return p
 
 
@@ -129,7 +137,7 @@ def main(argv=None):
     if cohort is not None:
         cohort = cohort_subset(cohort, a.cohort_size)
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
-    row = evaluate(net, valid, test, pre, a.score, a.score_norm, cohort, a.top_k)
+    row = evaluate(net, valid, test, pre, a.score, a.score_norm, cohort, a.top_k, a.whole_utterance)
     results = pd.DataFrame([row])
     if rank == 0:
         results.to_csv(PATH + "/logs/" + result_name(a), index=False)

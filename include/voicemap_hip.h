@@ -52,7 +52,7 @@ enum { VM_DIST_EUCLIDEAN = 0, VM_DIST_COSINE = 1, VM_DIST_DOT = 2 };
 enum { VM_SCORE_WEIGHTED_L1 = 3, VM_SCORE_NEG_EUCLIDEAN = 4 };
 
 const char* vm_last_error(void);
-/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms), vm_cohort_topk_stats / vm_cohort_stats_workspace_bytes / vm_pair_score_hist_norm (cohort score normalisation, S-norm / AS-norm); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
+/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms), vm_cohort_topk_stats / vm_cohort_stats_workspace_bytes / vm_pair_score_hist_norm (cohort score normalisation, S-norm / AS-norm), the *_varlen forward entry points (whole utterances in length-masked buckets: vm_crop_decimate_whiten_varlen, vm_conv1_fused_fwd_varlen, vm_conv_fwd_pool_varlen, vm_bn_drop_pool_fwd_varlen, vm_bn_drop_pool_gmax_fwd_varlen, vm_global_maxpool_fwd_varlen); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
  * vm_conv_dgrad_bnred; `bias`, `wf_packed` and the fourth hb row of vm_fold_bn_weights), the centred block-1 extreme (`center_bias` /
  * `shift_adj` / `mean_adj` of vm_bn_finalize) (round 4).  Earlier: 1 = round 1; 2 = vm_bn_finalize gained the zero-debias arguments (round 2); 3 = VM_F16, `dtype` in vm_conv1_fused_*,
  * `grad_scale` in the loss entry points, `skip_nonfinite` in vm_adam_clip_step, vm_embed_* / vm_pairdist_* (round 3); 4 = the folded-BatchNorm training forward
@@ -137,6 +137,20 @@ int vm_decimate_whiten(const void* raw, int raw_is_i16, int64_t n_windows, int64
 int vm_crop_decimate_whiten(const void* audio, int raw_is_i16, const int64_t* offsets, int64_t n_windows, int64_t raw_len,
                             int downsampling, int whitening, float rms, int64_t windows_per_tower, float* out, void* ws,
                             void* stream);
+/* Whole utterances (encoder.predict on a recording of any length, voicemap/models.py:6-41 with input_shape=None): window n is the
+ * raw_lens[n] samples at audio[offsets[n]] (both n_windows int64 on the device), decimated to Ln = ceil(raw_lens[n] / ds) <= L0 samples
+ * and whitened ALONE (windows_per_tower = 1: its own mean and scale, fp64 sums over its own Ln samples).  out: (n_windows, L0 + 31);
+ * every position past Ln is zero (conv 1's SAME padding).  No sample at or past raw_lens[n] is read.  With every raw_lens[n] equal to
+ * raw_len, bit-identical to vm_crop_decimate_whiten(..., windows_per_tower = 1).  ws: vm_decimate_whiten_workspace_bytes(n_windows).
+ *
+ * Length masking, the rule of every *_varlen entry point: the windows of a bucket share the padded length L0 and carry their valid
+ * length lens[n] (int32, device) at the input of the launch.  Every pooled row at or past floor(lens[n] / pool) is written as ZERO --
+ * it is the next convolution's SAME padding -- and the global max sees valid rows only.  Valid rows are then exactly what the
+ * encoder computes on the recording alone: a valid conv row reads at most one row past the valid length, which is that zero.  The
+ * plain GEMM convolutions (vm_conv_fwd, vm_conv1_fwd) need no varlen form: their rows past lens[n] are computed and never read. */
+int vm_crop_decimate_whiten_varlen(const void* audio, int raw_is_i16, const int64_t* offsets, const int64_t* raw_lens,
+                                   int64_t n_windows, int64_t L0, int downsampling, int whitening, float rms, float* out, void* ws,
+                                   void* stream);
 
 /* ---- a1 block 1: Conv1D(filters, 32, padding='same', activation='relu')  (voicemap/models.py:13-16) --
  * x: (n_windows, L + 31) fp32 from vm_decimate_whiten; w: (32, 1, F) fp32 Keras layout; bias (F).
@@ -169,6 +183,10 @@ int vm_conv1_wgrad(const float* x, const void* du, int64_t n_windows, int64_t L,
 int vm_conv1_fused_fwd(const float* x, const float* w, const float* bias, const float* gamma_or_scale, const float* shift,
                        int64_t n_windows, int64_t L, int F, int pool, int inference, int dtype, void* out, float* stat_sum,
                        float* stat_sq, void* stream);
+/* mode 1 (inference) over a length-masked bucket (see vm_crop_decimate_whiten_varlen): lens[n] = the valid positions of window n's
+ * input x; pooled rows at or past lens[n] / pool are zero and a 32-position tile past the last valid pool group runs no MFMA. */
+int vm_conv1_fused_fwd_varlen(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
+                              const int32_t* lens, int64_t n_windows, int64_t L, int F, int pool, int dtype, void* out, void* stream);
 /* Backward of the same block from dp (n_windows, L/pool, F) `dtype`: recomputes the conv tile on the matrix cores,
  * evaluates the pool/dropout/BN/ReLU backward in registers (c1, c2 from vm_bn_pool_bwd_reduce(z = e, pool = 1) +
  * vm_bn_bwd_finalize(count = wpt*L)) and accumulates grad_w (32,1,F) and grad_b (F) (overwritten; fixed order). */
@@ -256,6 +274,12 @@ int vm_pack_nt_weights_batch(int n, const void* const* bt, const int* towers, co
 int vm_conv_fwd_pool_supported(int64_t n_windows, int64_t L, int c_in, int c_out, int dtype);
 int vm_conv_fwd_pool(const void* in, const void* wf, const float* bias, const float* scale, const float* shift,
                      int64_t n_windows, int64_t L, int c_in, int c_out, int dtype, void* act, const void* wf_packed, void* stream);
+/* The same over a length-masked bucket (see vm_crop_decimate_whiten_varlen; models.py:22-35): lens[n] = the valid positions of window n.
+ * Pooled rows at or past lens[n] / 2 are zero; a 254-row tile with no valid pool group writes its zeros and issues no MFMA.  Served
+ * where vm_conv_fwd_pool_supported() says so. */
+int vm_conv_fwd_pool_varlen(const void* in, const void* wf, const float* bias, const float* scale, const float* shift,
+                            const int32_t* lens, int64_t n_windows, int64_t L, int c_in, int c_out, int dtype, void* act,
+                            const void* wf_packed, void* stream);
 /* dgrad: dx[n][t][ci] = sum_{k,co} du[n][t+1-k][co] * W[k][ci][co].  du padded (n_windows, L+2, c_out);
  * wd: (c_in, 3*c_out) `dtype` tap-flipped copy from vm_prep_conv_weights; dx: (n_windows, L, c_in). */
 int vm_conv_dgrad(const void* du, const void* wd, int64_t n_windows, int64_t L, int c_in, int c_out, int dtype,
@@ -424,6 +448,14 @@ int64_t vm_bn_drop_pool_gmax_workspace_bytes(int64_t n_windows, int C);
 int vm_bn_drop_pool_gmax_fwd(const void* z, const float* scale, const float* shift, const float* drop, int64_t n_windows,
                              int64_t windows_per_tower, int64_t L, int C, int pool, int dtype, float* gmax, int32_t* gidx,
                              void* ws, void* stream);
+/* Inference over a length-masked bucket (see vm_crop_decimate_whiten_varlen; models.py:22-37 with learning_phase 0, no dropout):
+ * lens[n] = the valid rows of window n's z, lens[n] >= pool.  vm_bn_drop_pool_fwd_varlen writes zeros at pooled rows >= lens[n] / pool;
+ * vm_bn_drop_pool_gmax_fwd_varlen takes the global max over pooled rows < lens[n] / pool only (gidx a valid row).  Every storage mode
+ * and odd lengths: the shapes the fused launches do not serve. */
+int vm_bn_drop_pool_fwd_varlen(const void* z, const float* scale, const float* shift, const int32_t* lens, int64_t n_windows, int64_t L,
+                               int C, int pool, int dtype, void* out, void* stream);
+int vm_bn_drop_pool_gmax_fwd_varlen(const void* z, const float* scale, const float* shift, const int32_t* lens, int64_t n_windows,
+                                    int64_t L, int C, int pool, int dtype, float* gmax, int32_t* gidx, void* ws, void* stream);
 /* The first launch of vm_bn_drop_pool_gmax_fwd alone: part_v / part_i receive the vm_bn_part_rows() partial (value, position) rows
  * of every window ((n_windows * rows, C) each; two arrays so that the two towers' launches can fill the halves of one pair of
  * arrays); vm_tail_fwd_bwd (below) finishes them inside its own launch. */
@@ -452,6 +484,11 @@ int vm_bn_pool_bwd_apply_pairs_gmax(const void* e, const void* o, const float* d
  * act: padded (n_windows, L+2, C) `dtype`; gmax (n_windows, C) fp32; gidx (n_windows, C) int32 = first argmax. */
 int vm_global_maxpool_fwd(const void* act, int64_t n_windows, int64_t L, int C, int dtype, float* gmax,
                           int32_t* gidx, void* stream);
+/* GlobalMaxPool1D over the valid rows of a length-masked bucket: rows t < lens[n] (>= 1) of window n's padded act only; same values
+ * and first-maximum rows as vm_global_maxpool_fwd on them.  Segment-parallel (a bucket may hold a few very long windows):
+ * ws >= vm_bn_drop_pool_gmax_workspace_bytes(n_windows, C). */
+int vm_global_maxpool_fwd_varlen(const void* act, const int32_t* lens, int64_t n_windows, int64_t L, int C, int dtype, float* gmax,
+                                 int32_t* gidx, void* ws, void* stream);
 /* dp: (n_windows, L, C) `dtype`, zero except dp[n][gidx[n][c]][c] = dg[n][c]. */
 int vm_global_maxpool_bwd(const float* dg, const int32_t* gidx, int64_t n_windows, int64_t L, int C, int dtype,
                           void* dp, void* stream);

@@ -45,11 +45,13 @@ SIGNATURES = {
     "vm_decimate_whiten_workspace_bytes": (L, [L]),
     "vm_decimate_whiten": (I, [P, I, L, L, I, I, F, L, P, P, P]),
     "vm_crop_decimate_whiten": (I, [P, I, P, L, L, I, I, F, L, P, P, P]),
+    "vm_crop_decimate_whiten_varlen": (I, [P, I, P, P, L, L, I, I, F, P, P, P]),
     "vm_conv1_stat_rows": (L, [L]),
     "vm_conv1_fwd": (I, [P, P, P, L, L, I, I, P, P, P, P]),
     "vm_conv1_wgrad_workspace_bytes": (L, [L, I]),
     "vm_conv1_wgrad": (I, [P, P, L, L, I, I, P, P, P]),
     "vm_conv1_fused_fwd": (I, [P, P, P, P, P, L, L, I, I, I, I, P, P, P, P]),
+    "vm_conv1_fused_fwd_varlen": (I, [P, P, P, P, P, P, L, L, I, I, I, P, P]),
     "vm_conv1_fused_bwd_workspace_bytes": (L, [L, L, I]),
     "vm_conv1_fused_bwd": (I, [P, P, P, P, P, P, P, P, P, P, L, L, L, I, I, I, P, P, P, P]),
     "vm_conv_stat_rows": (L, [L]),
@@ -67,6 +69,7 @@ SIGNATURES = {
     "vm_pack_nt_weights_batch": (I, [I, P, P, P, P, I, P, P]),
     "vm_conv_fwd_pool_supported": (I, [L, L, I, I, I]),
     "vm_conv_fwd_pool": (I, [P, P, P, P, P, L, L, I, I, I, P, P, P]),
+    "vm_conv_fwd_pool_varlen": (I, [P, P, P, P, P, P, L, L, I, I, I, P, P, P]),
     "vm_conv_dgrad_bnred_rows": (L, [L]),
     "vm_conv_dgrad_bnred_supported": (I, [L, L, I, I, I]),
     "vm_conv_dgrad_bnred": (I, [P, P, L, L, I, I, I, P, P, I, P, P, P, P]),
@@ -82,6 +85,7 @@ SIGNATURES = {
     "vm_bn_finalize": (I, [P, P, L, I, I, D, P, P, F, F, I, P, P, P, P, P, P, P, P, F, P, P, P, P, P]),
     "vm_bn_infer_affine": (I, [P, P, P, P, F, I, P, P, P]),
     "vm_bn_drop_pool_fwd": (I, [P, P, P, P, L, L, L, I, I, I, P, P]),
+    "vm_bn_drop_pool_fwd_varlen": (I, [P, P, P, P, L, L, I, I, I, P, P]),
     "vm_bn_part_rows": (I, []),
     "vm_bn_pool_bwd_reduce": (I, [P, P, P, P, P, P, P, L, L, L, I, I, I, P, P, P]),
     "vm_bn_pool_bwd_reduce_pooled": (I, [P, P, P, P, P, P, P, P, L, L, L, I, I, I, P, P, P]),
@@ -99,11 +103,13 @@ SIGNATURES = {
     "vm_du_tower_sums": (I, [P, P, L, L, L, I, I, P, P, P, P]),
     "vm_bn_drop_pool_gmax_workspace_bytes": (L, [L, I]),
     "vm_bn_drop_pool_gmax_fwd": (I, [P, P, P, P, L, L, L, I, I, I, P, P, P, P]),
+    "vm_bn_drop_pool_gmax_fwd_varlen": (I, [P, P, P, P, L, L, I, I, I, P, P, P, P]),
     "vm_bn_drop_pool_gmax_partials": (I, [P, P, P, P, L, L, L, I, I, I, P, P, P]),
     "vm_bn_drop_pool_gmax_partials_e": (I, [P, P, P, P, L, L, L, I, I, P, P, P]),
     "vm_bn_bwd_gmax_finalize_e": (I, [P, P, P, P, P, P, P, P, L, L, L, I, I, D, P, P, P, P, P]),
     "vm_bn_pool_bwd_apply_pairs_gmax": (I, [P, P, P, P, P, P, P, P, P, P, P, L, L, L, I, I, P, P, P]),
     "vm_global_maxpool_fwd": (I, [P, L, L, I, I, P, P, P]),
+    "vm_global_maxpool_fwd_varlen": (I, [P, P, L, L, I, I, P, P, P, P]),
     "vm_global_maxpool_bwd": (I, [P, P, L, L, I, I, P, P]),
     "vm_dense_fwd": (I, [P, P, P, L, I, I, P, P]),
     "vm_dense_bwd": (I, [P, P, P, L, I, I, P, P, P, P]),

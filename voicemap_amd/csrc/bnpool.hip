@@ -417,7 +417,8 @@ __global__ void bn_infer_affine_kernel(const float* gamma, const float* beta, co
 template <typename T, int POOL>
 __global__ __launch_bounds__(256) void bn_drop_pool_fwd_kernel(const T* __restrict__ z, const float* __restrict__ scale,
                                                                const float* __restrict__ shift, const float* __restrict__ drop,
-                                                               int64_t wpt, int64_t L, int C, int P, T* __restrict__ out) {
+                                                               int64_t wpt, int64_t L, int C, int P, T* __restrict__ out,
+                                                               const int32_t* __restrict__ valid_len) {
     constexpr int VEC = Elem<T>::kVec;
     const int tid = threadIdx.x;
     const int RP = 256 / P;
@@ -427,6 +428,7 @@ __global__ __launch_bounds__(256) void bn_drop_pool_fwd_kernel(const T* __restri
     const int seg = blockIdx.y;
     const int64_t tw = n / wpt;
     const int64_t Lq = L / POOL;
+    const int64_t Lqv = valid_len ? valid_len[n] / POOL : Lq;   // varlen: pooled rows that hold data; the others are stored as zero
     for (int cv = pl; cv < CV; cv += P) {
         const int c0 = cv * VEC;
         float sc[VEC], sh[VEC], dr[VEC];
@@ -440,6 +442,13 @@ __global__ __launch_bounds__(256) void bn_drop_pool_fwd_kernel(const T* __restri
         const T* zrow = z + n * L * C + c0;
         T* orow = out + (n * (Lq + 2) + 1) * C + c0;
         for (int64_t q = seg + (int64_t)rl * gridDim.y; q < Lq; q += (int64_t)RP * gridDim.y) {
+            if (q >= Lqv) {   // the next conv's SAME padding
+                Vec16<T> zero;
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) zero.set(i, 0.f);
+                store16<T>(orow + q * C, zero);
+                continue;
+            }
             Vec16<T> v[POOL];
 #pragma unroll
             for (int j = 0; j < POOL; ++j) v[j] = load16<T>(zrow + (q * POOL + j) * C);
@@ -464,12 +473,14 @@ __global__ __launch_bounds__(256) void bn_drop_pool_fwd_kernel(const T* __restri
 // pooled tensor of the last block has no other consumer (its BN backward works from z and the sparse (dg, gidx) form), so
 // it is never written: every block keeps the running maximum of the storage-rounded pooled values of its pool groups
 // (first maximum wins, as in vm_global_maxpool_fwd) and a second kernel reduces the BN_SEG segment partials.
-template <typename T, int POOL>
+// AFF = false (vm_global_maxpool_fwd_varlen): no BatchNorm affine and no dropout -- the stored values themselves, -0 included.
+template <typename T, int POOL, bool AFF = true>
 __global__ __launch_bounds__(256) void bn_drop_pool_gmax_fwd_kernel(const T* __restrict__ z, const float* __restrict__ scale,
                                                                     const float* __restrict__ shift,
                                                                     const float* __restrict__ drop, int64_t wpt, int64_t L,
                                                                     int C, int P, float* __restrict__ part_v,
-                                                                    int32_t* __restrict__ part_i, int64_t win_rows, int row0) {
+                                                                    int32_t* __restrict__ part_i, int64_t win_rows, int row0,
+                                                                    const int32_t* __restrict__ valid_len) {
     // win_rows / row0: a window holds win_rows rows of which the L read here start at row0 (L, 0: a plain tensor; L + 2, 1: a
     // padded pool extreme -- vm_bn_drop_pool_gmax_partials_e)
     constexpr int VEC = Elem<T>::kVec;
@@ -482,7 +493,7 @@ __global__ __launch_bounds__(256) void bn_drop_pool_gmax_fwd_kernel(const T* __r
     const int64_t n = blockIdx.x;
     const int seg = blockIdx.y;
     const int64_t tw = n / wpt;
-    const int64_t Lq = L / POOL;
+    const int64_t Lq = valid_len ? valid_len[n] / POOL : L / POOL;   // varlen: only the pooled rows that hold data
     for (int cvb = 0; cvb < CV; cvb += P) {
         const int cv = cvb + pl;
         const bool cok = cv < CV;
@@ -496,8 +507,10 @@ __global__ __launch_bounds__(256) void bn_drop_pool_gmax_fwd_kernel(const T* __r
         }
         if (cok) {
             float sc[VEC], sh[VEC], dr[VEC];
-            loadv<VEC>(scale + tw * C + c0, sc);
-            loadv<VEC>(shift + tw * C + c0, sh);
+            if (AFF) {
+                loadv<VEC>(scale + tw * C + c0, sc);
+                loadv<VEC>(shift + tw * C + c0, sh);
+            }
             if (drop) {
                 loadv<VEC>(drop + n * C + c0, dr);
             } else {
@@ -507,10 +520,10 @@ __global__ __launch_bounds__(256) void bn_drop_pool_gmax_fwd_kernel(const T* __r
             auto group = [&](int64_t q, const Vec16<T> (&v)[POOL]) {
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) {
-                    float y = fmaf(v[0].get(i), sc[i], sh[i]) * dr[i];
+                    float y = AFF ? fmaf(v[0].get(i), sc[i], sh[i]) * dr[i] : v[0].get(i);
 #pragma unroll
                     for (int j = 1; j < POOL; ++j) {
-                        const float yj = fmaf(v[j].get(i), sc[i], sh[i]) * dr[i];
+                        const float yj = AFF ? fmaf(v[j].get(i), sc[i], sh[i]) * dr[i] : v[j].get(i);
                         y = yj > y ? yj : y;
                     }
                     y = Elem<T>::to_f(Elem<T>::from_f(y));  // the value the pooled tensor would have held
@@ -1367,7 +1380,7 @@ extern "C" int vm_bn_drop_pool_fwd(const void* z, const float* scale, const floa
     VM_DISPATCH_DTYPE(dtype, VM_DISPATCH_POOL(pool, {
         const int P = lanes_for(C / Elem<T>::kVec);
         hipLaunchKernelGGL((bn_drop_pool_fwd_kernel<T, POOL>), dim3((unsigned)n_windows, (unsigned)bn_segs(L / POOL, C, Elem<T>::kVec)), dim3(256), 0,
-                           (hipStream_t)stream, (const T*)z, scale, shift, drop, windows_per_tower, L, C, P, (T*)out);
+                           (hipStream_t)stream, (const T*)z, scale, shift, drop, windows_per_tower, L, C, P, (T*)out, nullptr);
     }));
     return check_launch("vm_bn_drop_pool_fwd");
 }
@@ -1386,11 +1399,59 @@ extern "C" int vm_bn_drop_pool_gmax_fwd(const void* z, const float* scale, const
     VM_DISPATCH_DTYPE(dtype, VM_DISPATCH_POOL(pool, {
         const int P = lanes_for(C / Elem<T>::kVec);
         hipLaunchKernelGGL((bn_drop_pool_gmax_fwd_kernel<T, POOL>), dim3((unsigned)n_windows, (unsigned)bn_segs(L / POOL, C, Elem<T>::kVec)), dim3(256), 0,
-                           (hipStream_t)stream, (const T*)z, scale, shift, drop, windows_per_tower, L, C, P, part_v, part_i, L, 0);
+                           (hipStream_t)stream, (const T*)z, scale, shift, drop, windows_per_tower, L, C, P, part_v, part_i, L, 0, nullptr);
     }));
     hipLaunchKernelGGL(gmax_segments_kernel, dim3((unsigned)((n_windows * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        part_v, part_i, n_windows, C, gmax, gidx);
     return check_launch("vm_bn_drop_pool_gmax_fwd");
+}
+
+// ---- inference over a length-masked bucket of whole utterances: lens[n] = the valid rows of window n's z (lens[n] >= pool) ----
+extern "C" int vm_bn_drop_pool_fwd_varlen(const void* z, const float* scale, const float* shift, const int32_t* lens, int64_t n_windows,
+                                          int64_t L, int C, int pool, int dtype, void* out, void* stream) {
+    VM_REQUIRE(z && scale && shift && lens && out, "vm_bn_drop_pool_fwd_varlen: null pointer");
+    VM_REQUIRE(n_windows > 0 && L >= pool && C % 8 == 0, "vm_bn_drop_pool_fwd_varlen: bad sizes");
+    VM_DISPATCH_DTYPE(dtype, VM_DISPATCH_POOL(pool, {
+        const int P = lanes_for(C / Elem<T>::kVec);
+        hipLaunchKernelGGL((bn_drop_pool_fwd_kernel<T, POOL>), dim3((unsigned)n_windows, (unsigned)bn_segs(L / POOL, C, Elem<T>::kVec)), dim3(256), 0,
+                           (hipStream_t)stream, (const T*)z, scale, shift, nullptr, n_windows, L, C, P, (T*)out, lens);
+    }));
+    return check_launch("vm_bn_drop_pool_fwd_varlen");
+}
+
+extern "C" int vm_bn_drop_pool_gmax_fwd_varlen(const void* z, const float* scale, const float* shift, const int32_t* lens,
+                                               int64_t n_windows, int64_t L, int C, int pool, int dtype, float* gmax, int32_t* gidx,
+                                               void* ws, void* stream) {
+    VM_REQUIRE(z && scale && shift && lens && gmax && gidx && ws, "vm_bn_drop_pool_gmax_fwd_varlen: null pointer");
+    VM_REQUIRE(n_windows > 0 && L >= pool && C % 8 == 0, "vm_bn_drop_pool_gmax_fwd_varlen: bad sizes");
+    float* part_v = (float*)ws;
+    int32_t* part_i = (int32_t*)(part_v + n_windows * BN_SEG * (int64_t)C);
+    VM_DISPATCH_DTYPE(dtype, VM_DISPATCH_POOL(pool, {
+        const int P = lanes_for(C / Elem<T>::kVec);
+        hipLaunchKernelGGL((bn_drop_pool_gmax_fwd_kernel<T, POOL>), dim3((unsigned)n_windows, (unsigned)bn_segs(L / POOL, C, Elem<T>::kVec)), dim3(256), 0,
+                           (hipStream_t)stream, (const T*)z, scale, shift, nullptr, n_windows, L, C, P, part_v, part_i, L, 0, lens);
+    }));
+    hipLaunchKernelGGL(gmax_segments_kernel, dim3((unsigned)((n_windows * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       part_v, part_i, n_windows, C, gmax, gidx);
+    return check_launch("vm_bn_drop_pool_gmax_fwd_varlen");
+}
+
+// GlobalMaxPool1D over the valid rows (lens[n] >= 1) of a padded act tensor: the segment-parallel pass above with POOL = 1 and no affine --
+// one workgroup per window would leave the chip idle on a bucket of a few long recordings
+extern "C" int vm_global_maxpool_fwd_varlen(const void* act, const int32_t* lens, int64_t n_windows, int64_t L, int C, int dtype,
+                                            float* gmax, int32_t* gidx, void* ws, void* stream) {
+    VM_REQUIRE(act && lens && gmax && gidx && ws, "vm_global_maxpool_fwd_varlen: null pointer");
+    VM_REQUIRE(n_windows > 0 && L > 0 && C % 8 == 0, "vm_global_maxpool_fwd_varlen: bad sizes");
+    float* part_v = (float*)ws;
+    int32_t* part_i = (int32_t*)(part_v + n_windows * BN_SEG * (int64_t)C);
+    VM_DISPATCH_DTYPE(dtype, {
+        const int P = lanes_for(C / Elem<T>::kVec);
+        hipLaunchKernelGGL((bn_drop_pool_gmax_fwd_kernel<T, 1, false>), dim3((unsigned)n_windows, (unsigned)bn_segs(L, C, Elem<T>::kVec)), dim3(256), 0,
+                           (hipStream_t)stream, (const T*)act, nullptr, nullptr, nullptr, n_windows, L, C, P, part_v, part_i, L + 2, 1, lens);
+    });
+    hipLaunchKernelGGL(gmax_segments_kernel, dim3((unsigned)((n_windows * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       part_v, part_i, n_windows, C, gmax, gidx);
+    return check_launch("vm_global_maxpool_fwd_varlen");
 }
 
 // the first launch of vm_bn_drop_pool_gmax_fwd alone: the BN_SEG partial (value, position) rows per window, into two caller-given
@@ -1403,7 +1464,7 @@ extern "C" int vm_bn_drop_pool_gmax_partials(const void* z, const float* scale, 
     VM_DISPATCH_DTYPE(dtype, VM_DISPATCH_POOL(pool, {
         const int P = lanes_for(C / Elem<T>::kVec);
         hipLaunchKernelGGL((bn_drop_pool_gmax_fwd_kernel<T, POOL>), dim3((unsigned)n_windows, (unsigned)bn_segs(L / POOL, C, Elem<T>::kVec)), dim3(256), 0,
-                           (hipStream_t)stream, (const T*)z, scale, shift, drop, windows_per_tower, L, C, P, part_v, part_i, L, 0);
+                           (hipStream_t)stream, (const T*)z, scale, shift, drop, windows_per_tower, L, C, P, part_v, part_i, L, 0, nullptr);
     }));
     return check_launch("vm_bn_drop_pool_gmax_partials");
 }
@@ -1605,7 +1666,7 @@ extern "C" int vm_bn_drop_pool_gmax_partials_e(const void* e, const float* scale
     VM_DISPATCH_16(dtype, {
         const int P = lanes_for(C / Elem<T>::kVec);
         hipLaunchKernelGGL((bn_drop_pool_gmax_fwd_kernel<T, 1>), dim3((unsigned)n_windows, (unsigned)bn_segs(Lq, C, Elem<T>::kVec)), dim3(256), 0,
-                           (hipStream_t)stream, (const T*)e, scale, shift, drop, windows_per_tower, Lq, C, P, part_v, part_i, Lq + 2, 1);
+                           (hipStream_t)stream, (const T*)e, scale, shift, drop, windows_per_tower, Lq, C, P, part_v, part_i, Lq + 2, 1, nullptr);
     });
     return check_launch("vm_bn_drop_pool_gmax_partials_e");
 }

@@ -216,7 +216,8 @@ __global__ __launch_bounds__(256) void conv1_fused_fwd_kernel(const float* __res
                                                               const float* __restrict__ bias, const float* __restrict__ sgn,
                                                               const float* __restrict__ shift, int64_t L, int F, int chunks,
                                                               int splits, int cps, TS* __restrict__ out, int e_pad,
-                                                              float* __restrict__ stat_sum, float* __restrict__ stat_sq) {
+                                                              float* __restrict__ stat_sum, float* __restrict__ stat_sq,
+                                                              const int32_t* __restrict__ valid_len) {
     // e_pad (training): 1 = the pool extreme is written as a padded activation tensor (n_windows, L / POOL + 2, F), rows 1 .. L / POOL
     __shared__ __attribute__((aligned(16))) F1Copies cp[2];
     __shared__ float red[4][32][2];
@@ -229,6 +230,9 @@ __global__ __launch_bounds__(256) void conv1_fused_fwd_kernel(const float* __res
     const int CT = (min(F - cbase, 128) + 31) / 32;
     const F1Role role = f1_role(wave, CT);
     const int64_t Lq = L / POOL;
+    // varlen (inference, vm_conv1_fused_fwd_varlen): positions [0, Lv) form this window's valid pool groups; a pooled row at or past
+    // Lv / POOL is stored as zero (the next conv's SAME padding) and a 32-position tile wholly past Lv runs no MFMA
+    const int64_t Lv = (INFER && valid_len != nullptr) ? (int64_t)(valid_len[n] / POOL) * POOL : Lq * POOL;
     const int ch_lo = split * cps;
     int ch_hi = ch_lo + cps;
     if (ch_hi > chunks) ch_hi = chunks;
@@ -327,10 +331,22 @@ __global__ __launch_bounds__(256) void conv1_fused_fwd_kernel(const float* __res
         const int64_t t0 = (int64_t)chunk * F1_CHUNK;
         for (int rt = role.rs; role.active && rt < 8; rt += role.RS) {
             if (t0 + 32 * rt >= L) break;
+            if (INFER && t0 + 32 * rt >= Lv) {   // no valid pool group in this tile: zeros, no MFMA
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int64_t tg = t0 + 32 * rt + 8 * g + 4 * hi;
+#pragma unroll
+                    for (int pw = 0; pw < 4 / POOL; ++pw) {
+                        const int64_t q = tg / POOL + pw;
+                        if (cok && q < Lq) out[(n * (Lq + 2) + 1 + q) * F + c] = (TS)0.f;
+                    }
+                }
+                continue;
+            }
             VM_PROF1(const long long pq_t0 = __builtin_amdgcn_s_memtime();)
             f32x16 acc = f1_conv_tile<PROD>(sm, w, rt, lane);
             VM_PROF1(asm volatile("" : "+v"(acc)); const long long pq_t1 = __builtin_amdgcn_s_memtime(); pq_conv += pq_t1 - pq_t0;)
-            if (cok && t0 + 32 * rt + 32 <= Lq * POOL) {
+            if (cok && t0 + 32 * rt + 32 <= Lv) {
                 TS* ob = (INFER ? out + (n * (Lq + 2) + 1 + (t0 + 32 * rt) / POOL) * F
                                 : out + (n * (Lq + 2 * e_pad) + e_pad + (t0 + 32 * rt) / POOL) * F) + lane_off;
                 if (all_max) {
@@ -362,7 +378,8 @@ __global__ __launch_bounds__(256) void conv1_fused_fwd_kernel(const float* __res
                     const int64_t q = tg / POOL + pw;
                     if (cok && q < Lq) {
                         if (INFER) {
-                            out[(n * (Lq + 2) + 1 + q) * F + c] = (TS)fmaf(ext, sg, sh);  // ... and here it is the scale
+                            // ... and here it is the scale; varlen: zero past the valid pool groups
+                            out[(n * (Lq + 2) + 1 + q) * F + c] = q * POOL < Lv ? (TS)fmaf(ext, sg, sh) : (TS)0.f;
                         } else {
                             out[(n * (Lq + 2 * e_pad) + e_pad + q) * F + c] = (TS)(ext - ctr);
                         }
@@ -729,9 +746,9 @@ int f1_set_fwd_blocks(int v) {
 
 using namespace vm;
 
-extern "C" int vm_conv1_fused_fwd(const float* x, const float* w, const float* bias, const float* gamma_or_scale,
-                                  const float* shift, int64_t n_windows, int64_t L, int F, int pool, int inference, int dtype,
-                                  void* out, float* stat_sum, float* stat_sq, void* stream) {
+static int conv1_fused_fwd_impl(const float* x, const float* w, const float* bias, const float* gamma_or_scale,
+                                const float* shift, int64_t n_windows, int64_t L, int F, int pool, int inference, int dtype,
+                                void* out, float* stat_sum, float* stat_sq, void* stream, const int32_t* lens) {
     VM_REQUIRE(x && w && bias && gamma_or_scale && out, "vm_conv1_fused_fwd: null pointer");
     VM_REQUIRE(n_windows > 0 && L > 0 && F > 0 && F % 8 == 0, "vm_conv1_fused_fwd: bad sizes");
     VM_REQUIRE(pool == 2 || pool == 4, "vm_conv1_fused_fwd: pool must be 2 or 4 (got %d)", pool);
@@ -746,7 +763,7 @@ extern "C" int vm_conv1_fused_fwd(const float* x, const float* w, const float* b
     const dim3 grid((unsigned)gx, (unsigned)((F + 127) / 128));
 #define VM_F1_FWD_P(POOL, INF, PROD)                                                                                      \
     hipLaunchKernelGGL((conv1_fused_fwd_kernel<T, POOL, INF, PROD>), grid, dim3(256), 0, (hipStream_t)stream, x, w, bias,  \
-                       gamma_or_scale, shift, L, F, chunks, splits, cps, (T*)out, inference == 2 ? 1 : 0, stat_sum, stat_sq)
+                       gamma_or_scale, shift, L, F, chunks, splits, cps, (T*)out, inference == 2 ? 1 : 0, stat_sum, stat_sq, lens)
 #define VM_F1_FWD(POOL, INF)                                                         \
     if constexpr (std::is_same<T, f16>::value) {                                     \
         if (g_f1_products == 1) VM_F1_FWD_P(POOL, INF, 1);                           \
@@ -765,6 +782,21 @@ extern "C" int vm_conv1_fused_fwd(const float* x, const float* w, const float* b
 #undef VM_F1_FWD
 #undef VM_F1_FWD_P
     return check_launch("vm_conv1_fused_fwd");
+}
+
+extern "C" int vm_conv1_fused_fwd(const float* x, const float* w, const float* bias, const float* gamma_or_scale,
+                                  const float* shift, int64_t n_windows, int64_t L, int F, int pool, int inference, int dtype,
+                                  void* out, float* stat_sum, float* stat_sq, void* stream) {
+    return conv1_fused_fwd_impl(x, w, bias, gamma_or_scale, shift, n_windows, L, F, pool, inference, dtype, out, stat_sum, stat_sq,
+                                stream, nullptr);
+}
+
+// mode 1 (inference) over a length-masked bucket: lens[n] = the valid positions of window n's input
+extern "C" int vm_conv1_fused_fwd_varlen(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
+                                         const int32_t* lens, int64_t n_windows, int64_t L, int F, int pool, int dtype, void* out,
+                                         void* stream) {
+    VM_REQUIRE(lens != nullptr, "vm_conv1_fused_fwd_varlen: null pointer");
+    return conv1_fused_fwd_impl(x, w, bias, scale, shift, n_windows, L, F, pool, 1, dtype, out, nullptr, nullptr, stream, lens);
 }
 
 extern "C" int64_t vm_conv1_fused_bwd_workspace_bytes(int64_t n_windows, int64_t L, int F) {

@@ -238,6 +238,9 @@ struct NtArgs {
     int flat_period = 0, flat_valid = 0;
     // conv_nt3_kernel: bt in MFMA fragment order (vm_pack_nt_weights; all towers).  NULL: conv_nt2r_kernel streams bt through LDS.
     const T* bt_packed = nullptr;
+    // EPI_FWD_POOL (vm_conv_fwd_pool_varlen): valid_len[n] = the conv positions of window n that hold data.  Pooled rows at or past
+    // valid_len[n] / 2 are stored as zero (the next conv's SAME padding); a tile with none below it runs no K loop.  NULL: all L.
+    const int32_t* valid_len = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -657,6 +657,11 @@ __device__ inline void n2_tile_drain(const NtArgs<T>& p, char* lds, int64_t n, i
             }
         }
         const int vq = valid >> 1;
+        int dq = vq;   // varlen: rows at or past the window's valid pooled length are stored as zero
+        if (p.valid_len != nullptr) {
+            const int d = (p.valid_len[n] >> 1) - (t0 >> 1);
+            dq = d < vq ? d : vq;
+        }
         T* pbase = p.out + (n * (int64_t)(p.L / 2 + 2) + 1 + (t0 >> 1)) * (int64_t)p.N + n0 + c8 * 8;
         V8 r0[8], r1[8];
 #pragma unroll
@@ -673,6 +678,10 @@ __device__ inline void n2_tile_drain(const NtArgs<T>& p, char* lds, int64_t n, i
             for (int e = 0; e < 8; ++e) {
                 const float y0 = fmaf((float)r0[jj][e], sc[e], sh[e]), y1 = fmaf((float)r1[jj][e], sc[e], sh[e]);
                 o[e] = (T)(y1 > y0 ? y1 : y0);
+            }
+            if (q >= dq) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[e] = (T)0.f;
             }
             if (q < vq) *reinterpret_cast<V8*>(pbase + (int64_t)q * p.N) = o;
             bar.point();
@@ -1054,6 +1063,26 @@ __device__ unsigned int g_prof[PROF_SLOTS * 8];  // per (workgroup, wave): total
 #define VM_PROF(...)
 #endif
 
+// EPI_FWD_POOL with valid_len (vm_conv_fwd_pool_varlen): a tile whose pooled rows all lie at or past the window's valid pooled
+// length stores zeros there and returns before its first DMA: no K loop, no MFMA.  Uniform over the workgroup (one tile each).
+template <typename T, int EPI>
+__device__ inline bool n2_pool_dead_tile(const NtArgs<T>& p, int64_t n, int t0, int n0, int tid) {
+    if constexpr (EPI != EPI_FWD_POOL) {
+        return false;
+    } else {
+        if (p.valid_len == nullptr || (t0 >> 1) < (p.valid_len[n] >> 1)) return false;
+        using V8 = typename Mfma<T>::Frag;
+        const int rows = ((p.L - t0) < n2r::TROWS ? (p.L - t0) : n2r::TROWS) >> 1;   // this tile's pooled rows
+        const int c8 = tid & 15, rg = tid >> 4;
+        T* pbase = p.out + (n * (int64_t)(p.L / 2 + 2) + 1 + (t0 >> 1)) * (int64_t)p.N + n0 + c8 * 8;
+        V8 zero;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) zero[e] = (T)0.f;
+        for (int q = rg; q < rows; q += 16) *reinterpret_cast<V8*>(pbase + (int64_t)q * p.N) = zero;
+        return true;
+    }
+}
+
 template <typename T, int EPI>
 __global__ __launch_bounds__(256, 2) void conv_nt2r_kernel(NtArgs<T> p, int64_t n_groups) {
     VM_PROF(const long long pt_start = __builtin_amdgcn_s_memtime(); long long pt_first = 0, pt_bar = 0;)
@@ -1085,6 +1114,7 @@ __global__ __launch_bounds__(256, 2) void conv_nt2r_kernel(NtArgs<T> p, int64_t 
     const int tl = (int)(group - nw * (unsigned)p.tilesL);
     const int64_t n = nw;
     const int t0 = tl * TROWS, n0 = tn * TN;
+    if (n2_pool_dead_tile<T, EPI>(p, n, t0, n0, tid)) return;
     if constexpr (EPI == EPI_FWD_FOLD) {  // this window's tower: its folded weights and constants
         const unsigned tw = nw / (unsigned)p.tower_windows;
         p.bt += tw * p.bt_tower_stride;
@@ -1409,6 +1439,7 @@ __global__ __launch_bounds__(256, 2) void conv_nt3_kernel(NtArgs<T> p, int64_t n
     const int tl = (int)(group - nw * (unsigned)p.tilesL);
     const int64_t n = nw;
     const int t0 = tl * n2r::TROWS, n0 = tn * TN;
+    if (n2_pool_dead_tile<T, EPI>(p, n, t0, n0, tid)) return;
     unsigned tw = 0;
     if constexpr (EPI == EPI_FWD_FOLD) {  // this window's tower: its folded weights and constants
         tw = nw / (unsigned)p.tower_windows;
@@ -2052,6 +2083,29 @@ extern "C" int vm_conv_fwd_pool(const void* in, const void* wf, const float* bia
         launch_n2r<T, EPI_FWD_POOL>(a, n_windows, (hipStream_t)stream);
     });
     return check_launch("vm_conv_fwd_pool");
+}
+
+// ---- the same over a length-masked bucket of whole utterances: lens[n] = the valid positions of window n (NtArgs::valid_len);
+// served where vm_conv_fwd_pool_supported says so ----
+extern "C" int vm_conv_fwd_pool_varlen(const void* in, const void* wf, const float* bias, const float* scale, const float* shift,
+                                       const int32_t* lens, int64_t n_windows, int64_t L, int c_in, int c_out, int dtype, void* act,
+                                       const void* wf_packed, void* stream) {
+    VM_REQUIRE(in && wf && bias && scale && shift && lens && act, "vm_conv_fwd_pool_varlen: null pointer");
+    VM_REQUIRE(n_windows > 0 && L > 0, "vm_conv_fwd_pool_varlen: bad sizes");
+    VM_REQUIRE((L + 2) * (int64_t)c_in < (1LL << 31) && 3LL * c_in * c_out < (1LL << 31), "vm_conv_fwd_pool_varlen: window too large");
+    if (!vm_conv_fwd_pool_supported(n_windows, L, c_in, c_out, dtype)) {
+        set_error("vm_conv_fwd_pool_varlen: shape/dtype/tuning not served by the 256 x 128 input-resident kernel (ask vm_conv_fwd_pool_supported)");
+        return VM_ERR_UNSUPPORTED;
+    }
+    VM_DISPATCH_16(dtype, {
+        NtArgs<T> a = fwd_args<T>(in, wf, bias, act, nullptr, nullptr, L, c_in, c_out, dtype);
+        a.aff_scale = scale;
+        a.aff_shift = shift;
+        a.bt_packed = (const T*)wf_packed;
+        a.valid_len = lens;
+        launch_n2r<T, EPI_FWD_POOL>(a, n_windows, (hipStream_t)stream);
+    });
+    return check_launch("vm_conv_fwd_pool_varlen");
 }
 
 // ---- dgrad with the BatchNorm-backward partial sums of the layer below fused into its epilogue (conv_nt2r_kernel only) ----

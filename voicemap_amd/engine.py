@@ -1867,6 +1867,158 @@ class HipEncoderEngine:
                         offsets=offsets.to(self.device, torch.int64).contiguous(), raw_len=raw_len)
         return self.forward(pl, n, None)
 
+    # ---- whole utterances (voicemap/models.py:6-41 with input_shape=None) -------------------------------------------------------
+    def embed_varlen(self, audio, offsets=None, raw_lens=None, downsampling: int = 4, whitening: bool = True, rms: float = 0.038021,
+                     row_budget: Optional[int] = None, max_pad_frac: Optional[float] = None, names=None) -> torch.Tensor:
+        """Inference-mode embeddings of whole recordings of any length -> (n, E) fp32 device tensor, rows in input order.  Row i is
+        what the encoder computes on recording i alone (voicemap_amd/utterances.py).  ``audio``: a resident 1-D int16 / fp32 device
+        buffer with ``offsets`` / ``raw_lens`` (n int64, host or device) -- or a list of host waveforms (offsets None).  Recordings are
+        sorted by length and packed into length-masked buckets (``plan_buckets``); every bucket runs on views of ONE arena of
+        ``row_budget`` decimated rows, so the engine holds one plan whatever the corpus."""
+        from .utterances import DEFAULT_MAX_PAD_FRAC, DEFAULT_ROW_BUDGET, plan_buckets, pool_quantum, valid_lengths
+        if offsets is None:
+            waves = [np.asarray(w).reshape(-1) for w in audio]
+            rl = np.array([len(w) for w in waves], dtype=np.int64)
+            offs = np.concatenate([[0], np.cumsum(rl)[:-1]]).astype(np.int64) if len(rl) else np.zeros(0, np.int64)
+            i16 = len(waves) > 0 and all(w.dtype == np.int16 for w in waves)
+            if not i16:   # a mixed list: int16 PCM in the kernel's float units (x / 32768, as vm_crop_decimate_whiten reads int16)
+                waves = [w.astype(np.float32) / np.float32(32768.0) if w.dtype == np.int16 else w for w in waves]
+            host = np.concatenate(waves) if waves else np.zeros(0)
+            audio = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int16 if i16 else np.float32)).to(self.device)
+        else:
+            offs = np.asarray(offsets.cpu() if torch.is_tensor(offsets) else offsets, dtype=np.int64).reshape(-1)
+            rl = np.asarray(raw_lens.cpu() if torch.is_tensor(raw_lens) else raw_lens, dtype=np.int64).reshape(-1)
+            assert audio.dim() == 1 and audio.is_cuda and audio.dtype in (torch.int16, torch.float32)
+            audio = audio.contiguous()
+            if len(rl) and (offs.min() < 0 or int((offs + rl).max()) > audio.numel()):
+                raise ValueError("a recording lies outside the audio buffer")
+        n = len(rl)
+        if len(offs) != n:
+            raise ValueError("offsets and raw_lens differ in length")
+        ds = int(downsampling)
+        l0s = (rl + ds - 1) // ds
+        q = pool_quantum(self.blocks)
+        budget = int(row_budget or DEFAULT_ROW_BUDGET)
+        bp = plan_buckets(l0s, budget, max_pad_frac or DEFAULT_MAX_PAD_FRAC, q, names)
+        self.last_bucket_plan = bp
+        out = torch.empty(n, self.E, dtype=torch.float32, device=self.device)
+        if n == 0:
+            return out
+        ar = self._varlen_arena(budget, q)
+        lens_all = valid_lengths(l0s, self.blocks)
+        self._ensure_wfp()
+        # ONE host -> device copy for the whole call (a copy per bucket would stall the host on the stream between buckets): per
+        # bucket its offsets, raw lengths and per-block valid lengths, then the output row of every bucket row
+        segs, pos, row0 = [], 0, 0
+        for L0, idx in bp.buckets:
+            m = len(idx)
+            segs.append((pos, row0, m))
+            pos += 2 * m + (self.nb + 1) * m // 2 + 1
+            row0 += m
+        stage = np.zeros(pos + n, dtype=np.int64)
+        for (s0, _, m), (L0, idx) in zip(segs, bp.buckets):
+            stage[s0:s0 + m], stage[s0 + m:s0 + 2 * m] = offs[idx], rl[idx]
+            stage[s0 + 2 * m:].view(np.int32)[:(self.nb + 1) * m] = lens_all[:, idx].reshape(-1)
+        stage[pos:] = bp.order
+        st_all = torch.from_numpy(stage).to(self.device)
+        for i, (_, c, _) in enumerate(self.blocks):
+            self._call("vm_bn_infer_affine", _p(self.view(f"bn{i+1}.gamma")), _p(self.view(f"bn{i+1}.beta")),
+                       _p(self.view(f"bn{i+1}.moving_mean")), _p(self.view(f"bn{i+1}.moving_variance")), self.bn_eps, c,
+                       ar["aff"][i, 0].data_ptr(), ar["aff"][i, 1].data_ptr(), self.stream())
+        for (s0, r0, m), (L0, idx) in zip(segs, bp.buckets):
+            self._forward_varlen(ar, audio, st_all[s0:], m, L0, ds, whitening, rms)
+            out.index_copy_(0, st_all[pos + r0:pos + r0 + m], ar["emb"][:m])
+        return out
+
+    def plan_count(self) -> int:
+        """Plans the engine holds (fixed-length plans + the whole-utterance arena)."""
+        return len(self._plans) + (1 if getattr(self, "_varlen", None) is not None else 0)
+
+    def _varlen_arena(self, budget: int, q: int) -> dict:
+        """Buffers of embed_varlen, sized by the row budget alone: each bucket (n, L0) with n * L0 <= budget takes views of them."""
+        ar = getattr(self, "_varlen", None)
+        if ar is not None and ar["budget"] == budget:
+            return ar
+        self._varlen = None
+        dev, tdt, f32 = self.device, self.tdt, torch.float32
+        nmax = budget // q
+        rows = [budget]                      # rows at the input of each block
+        for (_, _, p) in self.blocks:
+            rows.append(rows[-1] // p)
+        zmax = max([rows[i] * c for i, (_, c, _) in enumerate(self.blocks) if i > 0 or not self.fuse_block1] + [1])
+        cl = self.blocks[-1][1]
+        ar = {"budget": budget, "nmax": nmax,
+              "x0": torch.empty(budget + CONV1_HALO * nmax, dtype=f32, device=dev),
+              "z": torch.empty(zmax, dtype=tdt, device=dev),
+              # one pooled-output buffer per block: its two halo rows per window are zeroed once per bucket shape and no launch
+              # writes them, so consecutive buckets of one length (most of them: the buckets are sorted) zero nothing
+              "act": [torch.empty((rows[i + 1] + 2 * nmax) * c, dtype=tdt, device=dev) for i, (_, c, _) in enumerate(self.blocks)],
+              "halo": [(0, 0)] * self.nb,
+              "aff": torch.empty(self.nb, 2, max(c for _, c, _ in self.blocks), dtype=f32, device=dev),
+              "gmax": torch.empty(nmax, cl, dtype=f32, device=dev),
+              "gidx": torch.empty(nmax, cl, dtype=torch.int32, device=dev),
+              "gmax_ws": torch.empty(self.lib.query("vm_bn_drop_pool_gmax_workspace_bytes", nmax, cl) // 4, dtype=f32, device=dev),
+              "emb": torch.empty(nmax, self.E, dtype=f32, device=dev),
+              "pre_ws": torch.empty(self.lib.query("vm_decimate_whiten_workspace_bytes", nmax) // 8, dtype=torch.float64, device=dev)}
+        self._varlen = ar
+        return ar
+
+    def _forward_varlen(self, ar: dict, audio: torch.Tensor, st_d: torch.Tensor, m: int, L0: int, ds: int, whitening: bool, rms: float):
+        """One bucket of m windows at padded length L0 -> ar['emb'][:m].  Every pooled row past a window's valid length is written as
+        zero by the *_varlen launches (the next conv's SAME padding); the plain GEMM convs compute rows nobody reads."""
+        st, dt = self.stream(), self.dtype
+        offs_p, rl_p = st_d.data_ptr(), st_d.data_ptr() + 8 * m
+
+        def lens(i):   # device int32 (m,): valid length at the input of block i (i = nb: the last block's pooled output)
+            return st_d.data_ptr() + 16 * m + 4 * i * m
+
+        ls = self.lengths(L0)
+        x0 = ar["x0"][:m * (L0 + CONV1_HALO)]
+        self._call("vm_crop_decimate_whiten_varlen", _p(audio), int(audio.dtype == torch.int16), offs_p, rl_p, m, L0, ds, int(whitening),
+                   rms, _p(x0), _p(ar["pre_ws"]), st)
+        z = ar["z"]
+        prev = None
+        cl = self.blocks[-1][1]
+        gmax, gidx = ar["gmax"][:m], ar["gidx"][:m]
+        for i, (k, c, pool) in enumerate(self.blocks):
+            L, last = ls[i], i == self.nb - 1
+            sc, sh = ar["aff"][i, 0].data_ptr(), ar["aff"][i, 1].data_ptr()   # vm_bn_infer_affine, once per embed_varlen call
+            bias = _p(self.view(f"conv{i+1}.bias"))
+            act = ar["act"][i][:m * (ls[i + 1] + 2) * c].view(m, ls[i + 1] + 2, c)
+            hl, hm = ar["halo"][i]
+            if hl != ls[i + 1] or hm < m:       # the two halo rows per window: the views move with the bucket shape
+                act[:, ::ls[i + 1] + 1].zero_()
+                ar["halo"][i] = (ls[i + 1], m)
+            if i == 0 and self.fuse_block1:
+                self._call("vm_conv1_fused_fwd_varlen", _p(x0), _p(self.view("conv1.kernel")), bias, sc, sh, lens(0), m, L, c, pool, dt,
+                           _p(act), st)
+                prev = act
+                if not last:
+                    continue
+                self._call("vm_global_maxpool_fwd_varlen", _p(act), lens(1), m, ls[1], c, dt, _p(gmax), _p(gidx), _p(ar["gmax_ws"]), st)
+                break
+            if i == 0:
+                self._call("vm_conv1_fwd", _p(x0), _p(self.view("conv1.kernel")), bias, m, L, c, dt, _p(z), None, None, st)
+            else:
+                cin = self.blocks[i - 1][1]
+                if (self.fused_infer_pool and pool == 2 and self.lib.query("vm_conv_fwd_pool_supported", m, L, cin, c, dt)):
+                    self._call("vm_conv_fwd_pool_varlen", _p(prev), _p(self.wf[i]), bias, sc, sh, lens(i), m, L, cin, c, dt, _p(act),
+                               _p(self.wfp.get(i)) if self.packed_weights else None, st)
+                    prev = act
+                    if last:
+                        self._call("vm_global_maxpool_fwd_varlen", _p(act), lens(i + 1), m, ls[i + 1], c, dt, _p(gmax), _p(gidx),
+                                   _p(ar["gmax_ws"]), st)
+                    continue
+                self._call("vm_conv_fwd", _p(prev), _p(self.wf[i]), bias, m, L, cin, c, dt, _p(z), None, None, st)
+            if last:
+                self._call("vm_bn_drop_pool_gmax_fwd_varlen", _p(z), sc, sh, lens(i), m, L, c, pool, dt, _p(gmax), _p(gidx),
+                           _p(ar["gmax_ws"]), st)
+            else:
+                self._call("vm_bn_drop_pool_fwd_varlen", _p(z), sc, sh, lens(i), m, L, c, pool, dt, _p(act), st)
+                prev = act
+        self._call("vm_dense_fwd", _p(gmax), _p(self.view("dense.kernel")), _p(self.view("dense.bias")), m, cl, self.E,
+                   _p(ar["emb"][:m]), st)
+
     def siamese_eval(self, x1, x2, y, loss: str = "contrastive", preprocessed: bool = True, downsampling: int = 4,
                      whitening: bool = True):
         """test_on_batch of the siamese model: inference-mode forward + loss / accuracy (no gradients are used; the

@@ -66,11 +66,16 @@ class EmbeddingCache:
         return int(self.emb.shape[1])
 
 
-def embed_corpus(model, dataset, preprocessor, network_type: str = "siamese", batch: int = 256) -> EmbeddingCache:
+def embed_corpus(model, dataset, preprocessor, network_type: str = "siamese", batch: int = 256,
+                 whole_utterance: bool = False) -> EmbeddingCache:
     """Embed the first-fragment window of every file of ``dataset`` (inference mode, each window whitened alone).  With a
     device-resident corpus (``ShardedSpeechDataset.to_device``) windows are start offsets and the crop happens in the preprocessing
     kernel; otherwise windows are loaded on the host like ``dataset[i]`` with ``stochastic=False``.  Under torchrun every rank embeds
-    ``parallel.shard_range`` of the rows and the matrix is all-gathered."""
+    ``parallel.shard_range`` of the rows and the matrix is all-gathered.
+
+    ``whole_utterance``: every file is embedded WHOLE, at its own length, instead of its first fragment -- what the encoder computes
+    on the recording alone (``HipEncoderEngine.embed_varlen``: length-masked buckets, voicemap_amd/utterances.py).  A file too short
+    for the encoder raises ``ValueError`` naming it."""
     eng = _encoder_engine(model, network_type)
     inst = preprocessor.instance_preprocessor if hasattr(preprocessor, "instance_preprocessor") else preprocessor
     n_files = len(dataset)
@@ -82,6 +87,20 @@ def embed_corpus(model, dataset, preprocessor, network_type: str = "siamese", ba
     probe = inst(np.zeros((1, 8, 1)))
     ds, wh = getattr(probe, "downsampling", 1), getattr(probe, "whitening", False)
     lazy_ok = hasattr(probe, "raw")
+    if whole_utterance:
+        if not lazy_ok:
+            raise ValueError("whole_utterance needs a preprocessor that decimates and whitens on the device (utils.preprocess_instances)")
+        if dev_audio is not None:
+            e = eng.embed_varlen(dev_audio, dataset.global_offset[lo:hi], dataset.file_length[lo:hi], ds, wh,
+                                 names=file_names(dataset, lo, hi))
+            local.copy_(e)
+        else:
+            for b0 in range(lo, hi, _WHOLE_FILES):   # host loads, a few thousand files at a time
+                idx = range(b0, min(b0 + _WHOLE_FILES, hi))
+                waves = [np.asarray(dataset._load(int(i)), dtype=np.float32) for i in idx]
+                local[b0 - lo:b0 - lo + len(waves)].copy_(eng.embed_varlen(waves, None, None, ds, wh,
+                                                                           names=file_names(dataset, idx.start, idx.stop)))
+        return EmbeddingCache(all_gather_rows(local, n_files), dataset._code)
     for b0 in range(lo, hi, batch):
         idx = np.arange(b0, min(b0 + batch, hi))
         if dev_audio is not None and lazy_ok:
@@ -100,6 +119,24 @@ def embed_corpus(model, dataset, preprocessor, network_type: str = "siamese", ba
         local[b0 - lo:b0 - lo + len(idx)].copy_(e)
     emb = all_gather_rows(local, n_files)
     return EmbeddingCache(emb, dataset._code)
+
+
+_WHOLE_FILES = 2048
+
+
+def file_names(dataset, lo: int, hi: int):
+    """The names of files [lo, hi) of a dataset for error messages: its index's ``filepath`` column (LibriSpeechDataset,
+    ShardedSpeechDataset, SyntheticSpeechDataset), through a subset's ``index`` into its base dataset, else "file <row>"."""
+    df = getattr(dataset, "df", None)
+    if df is not None and "filepath" in getattr(df, "columns", ()):
+        return [str(v) for v in df["filepath"].values[lo:hi]]
+    base, index = getattr(dataset, "base", None), getattr(dataset, "index", None)
+    if base is not None and index is not None:
+        rows = np.asarray(index)[lo:hi]
+        df = getattr(base, "df", None)
+        if df is not None and "filepath" in getattr(df, "columns", ()):
+            return [str(v) for v in df["filepath"].values[rows]]
+    return ["file %d" % i for i in range(lo, hi)]
 
 
 def _first_fragment(dataset, index: int) -> np.ndarray:
