@@ -1,0 +1,93 @@
+"""Closed-set speaker identification and model-trial verification of a trained siamese network: enrol every speaker of a set as a
+speaker model (voicemap_amd/enrolment.py: the reference's n-shot prototypes with k = every speaker), name the speaker of every utterance
+and verify every utterance against every model.  Prints one JSON line: rank-1 / rank-5 accuracy, mean reciprocal rank, the model-trial
+EER and thresholds.
+    python -m experiments.speaker_identification --siamese models/x.hdf5 [--enrol-set dev-clean] [--test-set test-clean]
+        [--per-speaker N] [--distance euclidean|cosine|dot_product] [--whole-utterance] [--synthetic]
+Without --test-set (or with the same set) the enrolled set is also the test set: leave-one-out (every utterance is scored against its own
+speaker's model built from the speaker's OTHER utterances), or with --per-speaker N a seeded choice of N utterances per speaker is
+enrolled and the others are the queries.  With another --test-set its utterances are scored against the enrolled set's models (its
+speakers that were not enrolled give non-target trials only), and the best threshold of the enrolled set is applied to it.  Under
+torchrun the query rows are sharded like the other evaluation scripts."""
+import argparse
+import json
+
+from voicemap_amd import enrolment, retrieval
+from voicemap_amd.librispeech import LibriSpeechDataset, SyntheticSpeechDataset
+from voicemap_amd.utils import BatchPreProcessor, preprocess_instances
+
+
+def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=None, whole_utterance=False, seed=0):
+    """The result row: identification and model-trial figures of ``test_set`` (None: the enrolled set itself) against the models of
+    ``enrol_set``."""
+    wu = {"whole_utterance": True} if whole_utterance else {}
+    ce = retrieval.embed_corpus(net, enrol_set, pre, "siamese", **wu)
+    models = enrolment.enrol(ce, distance, per_speaker=per_speaker, seed=seed)
+    ct = ce if test_set is None else retrieval.embed_corpus(net, test_set, pre, "siamese", **wu)
+    ident = enrolment.identify(models, ct)
+    mt = enrolment.model_trial_metrics(models, ct)
+    cmc = ident["cmc"]
+    row = {"distance": distance, "speakers": models.S, "per_speaker": per_speaker, "leave_one_out": ident["leave_one_out"],
+           "queries": ident["n_queries"], "unranked": ident["n_unranked"], "rank1_accuracy": ident["rank1_accuracy"],
+           "rank5_accuracy": float(cmc[min(5, len(cmc)) - 1]), "mean_reciprocal_rank": ident["mean_reciprocal_rank"],
+           "trial_eer": mt["eer"], "trial_eer_threshold": mt["eer_threshold"], "trial_best_balanced_accuracy": mt["best_balanced_accuracy"],
+           "trial_best_threshold": mt["best_threshold"], "target_trials": mt["n_target"], "nontarget_trials": mt["n_nontarget"],
+           "whole_utterance": bool(whole_utterance)}
+    if test_set is not None:   # the enrolled set's own threshold applied to the test set, as verification_accuracy.py does for pairs
+        me = enrolment.model_trial_metrics(models, ce)
+        at = enrolment.model_trial_accuracy_at_threshold(models, ct, me["best_threshold"])
+        row.update(enrol_best_threshold=me["best_threshold"], test_balanced_accuracy_at_enrol_threshold=at["balanced_accuracy"],
+                   test_far=at["far"], test_frr=at["frr"])
+    return row
+
+
+def _parser():
+    p = argparse.ArgumentParser(description=__doc__)
+    p.add_argument("--siamese", default=None, help="a saved siamese network (not needed with --synthetic)")
+    p.add_argument("--enrol-set", default="dev-clean")
+    p.add_argument("--test-set", default=None, help="default: the enrolled set itself (leave-one-out, or the rows --per-speaker left out)")
+    p.add_argument("--per-speaker", type=int, default=None, help="enrol a seeded choice of N utterances per speaker")
+    p.add_argument("--distance", default="euclidean", choices=["euclidean", "cosine", "dot_product"])
+    p.add_argument("--n-seconds", type=float, default=3)
+    p.add_argument("--downsampling", type=int, default=4)
+    p.add_argument("--whole-utterance", action="store_true", help="embed every file whole, at its own length")
+    p.add_argument("--synthetic", action="store_true", help="generated speaker sets and a freshly built model")
+    p.add_argument("--seed", type=int, default=0)
+    return p
+
+
+def main(argv=None):
+    p = _parser()
+    a = p.parse_args(argv)
+    from experiments._common import setup
+    rank, _ = setup()
+    same = a.test_set is None or a.test_set == a.enrol_set
+    if a.synthetic:
+        from voicemap_amd import models
+        enrol_set = SyntheticSpeechDataset(num_speakers=20, files_per_speaker=8, seconds=a.n_seconds, stochastic=False, seed=1,
+                                           subset="synthetic-enrol")
+        test_set = None if same else SyntheticSpeechDataset(num_speakers=20, files_per_speaker=8, seconds=a.n_seconds, stochastic=False,
+                                                            seed=1, subset="synthetic-test")
+        if a.siamese:
+            net = models.load_model(a.siamese)
+        else:
+            enc = models.get_baseline_convolutional_encoder(16, 32, dropout=0.0, dtype="f32")
+            net = models.build_siamese_net(enc, (int(a.n_seconds * 16000) // a.downsampling, 1), distance_metric="uniform_euclidean")
+    else:
+        from voicemap_amd.models import load_model
+        if not a.siamese:
+            p.error("--siamese is required without --synthetic")
+        net = load_model(a.siamese)
+        enrol_set = LibriSpeechDataset(a.enrol_set, a.n_seconds, stochastic=False)
+        test_set = None if same else LibriSpeechDataset(a.test_set, a.n_seconds, stochastic=False)
+    pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
+    row = evaluate(net, enrol_set, test_set, pre, a.distance, a.per_speaker, a.whole_utterance, a.seed)
+    row.update(enrol_set="synthetic" if a.synthetic else a.enrol_set,
+               test_set=("synthetic" if a.synthetic else a.enrol_set) if same else a.test_set)
+    if rank == 0:
+        print(json.dumps(row))
+    return row
+
+
+if __name__ == "__main__":
+    main()

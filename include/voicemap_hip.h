@@ -629,6 +629,41 @@ int vm_cohort_topk_stats(const float* q, int64_t M, const float* cohort, int64_t
 int vm_pair_score_hist_norm(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, const float* weights, int64_t row_lo,
                             int64_t row_hi, const int64_t* host_windows, int n_windows, int bins, const float* mu, const float* rsig,
                             uint64_t* hist, void* ws, void* stream);
+/* Speaker models: enrolment, S-way identification and model-trial verification (csrc/enrol.hip, voicemap_amd/enrolment.py) -- the
+ * exhaustive limit of the reference's n-shot k-way metric (voicemap/utils.py:159-206 with k = every speaker, n = every (other) file).
+ * Rows emb (N, E) fp32, label (N) int32: the dense speaker index in [0, S), anything else (-1) = the row is not enrolled.  kind is
+ * VM_DIST_*.  Everything below is float64 until a score is rounded to fp32 ONCE.
+ *   |e_u| = sqrt(sum_e e^2), ascending e, correctly rounded root.  Contribution c_u: euclidean e_u; cosine e_u / |e_u|; dot_product
+ *   e_u / |e_u| and the magnitude |e_u|.
+ *   sum_s = sum of c_u, msum_s = sum of |e_u| (written for every kind) over the enrolled rows of s IN ASCENDING ROW ORDER; count_s.  The
+ *   order is part of the contract: bit-identical from run to run and from rank to rank (no float atomics).
+ *   Model of speaker s as seen by query row m: n = count_s, Sigma = sum_s; with leave_one_out != 0 and q_label[m] == s (query row m is
+ *   then one of the enrolled rows of s): n = count_s - 1, Sigma = sum_s - c_m, msum likewise.  n == 0: no model -- (m, s) is NOT A TRIAL
+ *   and is counted nowhere.  p = Sigma / n (euclidean, cosine); p = (msum / n) (Sigma / n) (dot_product).
+ *   Score of the trial (m, s): euclidean sqrt(sum_e (q_e - p_e)^2) in the direct form; cosine 1 - q.p / (|q| |p|); dot_product -q.p; sums
+ *   over ascending e.  Lower = more alike.  These are oracle.n_shot_prediction's numbers for a task whose support rows are the enrolled rows.
+ *   Order of the trials of one query: (uint32 key of the fp32 score, speaker index) ascending; the key is vm_pair_score_hist's (-0.0 as
+ *   +0.0); NaN scores come after every number, among themselves by speaker index.
+ * vm_speaker_sums: sums (S, E) f64, msum (S) f64, count (S) int32 on the device.  ws >= vm_speaker_sums_workspace_bytes(N, E, S).
+ * vm_speaker_identify: query rows q (M, E), q_label (M) (the own speaker, -1 / out of range: none).  scores (M, S) fp32 may be NULL;
+ *   where (m, s) is not a trial it holds NaN.  best_idx[m] = the first speaker in the order (-1: the row has no trial), best_val[m] its
+ *   score.  rank[m] = the number of speakers before the own speaker in the order (0 = identified); -1 if the row has no own speaker or
+ *   that speaker has no model for the row.  true_score[m] = the score against the own speaker (NaN where rank is -1).
+ * vm_speaker_trial_hist: every trial binned by class (0: s == q_label[m], 1: otherwise) with exactly the window / slot / NaN-slot
+ *   conventions and limits of vm_pair_score_hist; hist (n_windows, 2, bins + 3) uint64 is ACCUMULATED (row ranges / ranks sum).  Its
+ *   scores are bit-identical to vm_speaker_identify's matrix.
+ * E <= 256; M, N, S < 2^31; q 16-byte aligned when E % 4 == 0.  ws >= the matching *_workspace_bytes(M, E, S). */
+int64_t vm_speaker_sums_workspace_bytes(int64_t N, int E, int64_t S);
+int vm_speaker_sums(const float* emb, const int32_t* label, int64_t N, int E, int64_t S, int kind, double* sums, double* msum, int32_t* count,
+                    void* ws, void* stream);
+int64_t vm_speaker_identify_workspace_bytes(int64_t M, int E, int64_t S);
+int vm_speaker_identify(const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
+                        const int32_t* count, int64_t S, int kind, int leave_one_out, float* scores, float* true_score, int32_t* rank,
+                        float* best_val, int32_t* best_idx, void* ws, void* stream);
+int64_t vm_speaker_trial_hist_workspace_bytes(int64_t M, int E, int64_t S);
+int vm_speaker_trial_hist(const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
+                          const int32_t* count, int64_t S, int kind, int leave_one_out, const int64_t* host_windows, int n_windows, int bins,
+                          uint64_t* hist, void* ws, void* stream);
 
 /* ---- a10 / f4: log-mel front-end and the 2-D CNN encoder variant (BASELINE.json config 4) -------------------
  * NOT in the reference (nothing to cite under /root/reference); the specification is DESIGN.md section 9 and the

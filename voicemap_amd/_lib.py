@@ -131,6 +131,12 @@ SIGNATURES = {
     "vm_pair_score_hist_norm": (I, [P, P, L, I, I, P, L, L, P, I, I, P, P, P, P, P]),
     "vm_cohort_stats_workspace_bytes": (L, [L, L, I]),
     "vm_cohort_topk_stats": (I, [P, L, P, L, I, I, P, L, L, P, P, P, P, P, P, P]),
+    "vm_speaker_sums_workspace_bytes": (L, [L, I, L]),
+    "vm_speaker_sums": (I, [P, P, L, I, L, I, P, P, P, P, P]),
+    "vm_speaker_identify_workspace_bytes": (L, [L, I, L]),
+    "vm_speaker_identify": (I, [P, P, L, I, P, P, P, L, I, I, P, P, P, P, P, P, P]),
+    "vm_speaker_trial_hist_workspace_bytes": (L, [L, I, L]),
+    "vm_speaker_trial_hist": (I, [P, P, L, I, P, P, P, L, I, I, P, I, I, P, P, P]),
     "vm_stft_frames": (L, [L, I, I]),
     "vm_stft_logmel": (I, [P, I, L, L, I, I, P, P, I, F, I, P, P]),
     "vm_stft_split_basis_bytes": (L, [I]),

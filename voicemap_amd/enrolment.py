@@ -1,0 +1,410 @@
+"""Speaker models over a cached embedding matrix: enrol every speaker, name the speaker of every utterance, verify utterances against models.
+
+``retrieval.evaluate_tasks`` answers the reference's sampled question (5-way, at most 20-way tasks drawn at random).  This module answers
+the exhaustive ones over a ``retrieval.EmbeddingCache``:
+
+* identification: enrol all S speakers of a corpus, score every utterance against every speaker MODEL, report the rank-1 accuracy, the
+  rank-k curve (CMC) and the mean reciprocal rank -- the reference's n-shot k-way metric with k = every speaker and n = every other file
+  of the speaker (``leave_one_out``) or a seeded choice of n files (``per_speaker``);
+* model-trial verification: a trial is (utterance, speaker model), target iff the model is the utterance's own speaker; EER, thresholds and
+  the best balanced accuracy are exact (``verification.exact_sweep`` on the histograms of ``vm_speaker_trial_hist``).
+
+Definitions (include/voicemap_hip.h states the same; the numpy twins below follow them in float64 and the tests hold the kernels to them).
+Rows ``emb (N, E)`` fp32, ``label (N)`` int32: the dense speaker index in [0, S) or -1 (the row is not enrolled); ``kind``: euclidean 0,
+cosine 1, dot_product 2.
+
+* ``|e_u| = sqrt(sum_e e^2)`` (ascending e).  Per-row contribution ``c_u``: euclidean ``e_u``; cosine ``e_u / |e_u|``; dot_product
+  ``e_u / |e_u|`` and the magnitude ``|e_u|``.
+* Speaker sums ``sum_s = sum c_u`` and ``msum_s = sum |e_u|`` over the enrolled rows of s in ascending row order, float64; ``count_s``.
+  The order is part of the contract: bit-identical from run to run and from rank to rank (no float atomics).
+* Model of speaker s as seen by query row m: ``n = count_s``, ``Sigma = sum_s``; with leave-one-out and ``q_label[m] == s``,
+  ``n = count_s - 1`` and ``Sigma = sum_s - c_m`` (``msum`` likewise).  ``n == 0``: there is no model and (m, s) is not a trial: it is
+  counted nowhere.  euclidean and cosine ``p = Sigma / n``; dot_product ``p = (msum / n) (Sigma / n)``  (the reference's prototype
+  rules, voicemap/utils.py:159-206: mean embedding / mean unit vector / mean magnitude x mean unit vector).
+* Score of the trial (m, s), float64, rounded to fp32 once: euclidean ``sqrt(sum_e (q_e - p_e)^2)`` in the direct form; cosine
+  ``1 - q.p / (|q| |p|)``; dot_product ``-q.p`` -- ``oracle.n_shot_prediction``'s numbers for a task whose support rows are the enrolled
+  rows of the speakers.  Lower = more alike, as everywhere in ``verification``.
+* Order of the trials of one query: (uint32 key of the fp32 score, speaker index) ascending, the key of ``verification.score_keys``
+  (-0.0 as +0.0); NaN scores rank after every number, among themselves by speaker index.  ``best_idx[m]`` is the first speaker in that
+  order (-1: the row has no trial) and ``best_val[m]`` its score; ``rank[m]`` the number of speakers before the row's own speaker (0 =
+  identified), -1 if ``q_label[m] < 0`` or the own speaker has no model for the row (one file under leave-one-out); ``true_score[m]`` the
+  score against the own speaker (NaN where rank is -1).
+
+Under torchrun every rank computes the sums over all rows itself (N x E reads; the models are then bit-identical everywhere), takes its
+``parallel.shard_range`` of the query rows, and the integer rank histogram / trial histograms are summed over ranks.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import parallel
+from . import verification as V
+
+KINDS = {"euclidean": 0, "cosine": 1, "dot_product": 2}
+_KEY_NAN = 0xFFFFFFFF
+
+
+def _kind(kind) -> int:
+    k = KINDS.get(kind, kind) if isinstance(kind, str) else int(kind)
+    if k not in (0, 1, 2):
+        raise ValueError("distance must be one of (euclidean, cosine, dot_product)")
+    return k
+
+
+# ---- numpy twins (float64) ---------------------------------------------------------------------------------------------------------
+def _contrib(emb, kind: int):
+    e = np.asarray(emb, dtype=np.float64)
+    mag = np.sqrt((e * e).sum(axis=1))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        c = e if kind == 0 else e / mag[:, None]
+    return c, mag
+
+
+def speaker_sums_numpy(emb, label, S: int, kind) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(sums (S, E), msum (S), count (S) int32) of the definition; rows are added in ascending row order."""
+    kind = _kind(kind)
+    c, mag = _contrib(emb, kind)
+    label = np.asarray(label)
+    sums, msum, count = np.zeros((S, c.shape[1])), np.zeros(S), np.zeros(S, dtype=np.int32)
+    for s in range(S):
+        rows = np.flatnonzero(label == s)
+        count[s] = len(rows)
+        for u in rows:
+            sums[s] += c[u]
+            msum[s] += mag[u]
+    return sums, msum, count
+
+
+def trial_scores_numpy(emb, label, q, q_label, kind, leave_one_out: bool, S: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """(scores (M, S) float64, trial (M, S) bool): the score of every query row against every speaker model of the enrolled rows
+    ``emb`` / ``label``; where ``trial`` is False there is no model (the score there is NaN and means nothing)."""
+    kind = _kind(kind)
+    label, q_label = np.asarray(label), np.asarray(q_label)
+    if S is None:
+        S = int(label.max()) + 1
+    sums, msum, count = speaker_sums_numpy(emb, label, S, kind)
+    q = np.asarray(q, dtype=np.float64)
+    M = q.shape[0]
+    cq, qmag = _contrib(q, kind)
+    out = np.full((M, S), np.nan)
+    trial = np.zeros((M, S), dtype=bool)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for m in range(M):
+            n = count.astype(np.float64).copy()
+            sg, ms = sums, msum
+            own = int(q_label[m])
+            if leave_one_out and 0 <= own < S:
+                sg, ms = sums.copy(), msum.copy()
+                n[own] -= 1
+                sg[own] -= cq[m]
+                ms[own] -= qmag[m]
+            ok = n > 0
+            trial[m] = ok
+            p = sg / n[:, None]
+            if kind == 2:
+                p = (ms / n)[:, None] * p
+            if kind == 0:
+                sc = np.sqrt(((q[m][None, :] - p) ** 2).sum(axis=1))
+            elif kind == 1:
+                sc = 1.0 - (p @ q[m]) / (qmag[m] * np.sqrt((p * p).sum(axis=1)))
+            else:
+                sc = -(p @ q[m])
+            out[m, ok] = sc[ok]
+    return out, trial
+
+
+def trial_keys(scores32) -> np.ndarray:
+    """uint64 keys of fp32 scores in the order of the definition: ``verification.score_keys``, NaN after every number."""
+    s = np.asarray(scores32, dtype=np.float32)
+    return np.where(np.isnan(s), _KEY_NAN, V.score_keys(s)).astype(np.uint64)
+
+
+def ranks_numpy(scores, trial, q_label) -> Dict[str, np.ndarray]:
+    """``rank``, ``best_idx`` (int32), ``best_val``, ``true_score`` (fp32) of the definition from an (M, S) score matrix (rounded to fp32
+    here) and its trial mask."""
+    s = np.asarray(scores).astype(np.float32)
+    trial = np.asarray(trial, dtype=bool)
+    q_label = np.asarray(q_label)
+    M, S = s.shape
+    comp = (trial_keys(s) << np.uint64(32)) | np.arange(S, dtype=np.uint64)[None, :]
+    comp = np.where(trial, comp, np.uint64(0xFFFFFFFFFFFFFFFF))
+    rows = np.arange(M)
+    bi = comp.argmin(axis=1)
+    has = trial.any(axis=1)
+    best_idx = np.where(has, bi, -1).astype(np.int32)
+    best_val = np.where(has, s[rows, bi], np.float32(np.nan)).astype(np.float32)
+    own = np.where((q_label >= 0) & (q_label < S), q_label, 0).astype(np.int64)
+    ranked = (q_label >= 0) & (q_label < S) & trial[rows, own]
+    before = ((comp < comp[rows, own][:, None]) & trial).sum(axis=1)
+    rank = np.where(ranked, before, -1).astype(np.int32)
+    true_score = np.where(ranked, s[rows, own], np.float32(np.nan)).astype(np.float32)
+    return {"rank": rank, "best_idx": best_idx, "best_val": best_val, "true_score": true_score}
+
+
+# ---- the entry points on device tensors --------------------------------------------------------------------------------------------
+def speaker_sums(emb: torch.Tensor, label: torch.Tensor, S: int, kind) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``vm_speaker_sums``: (sums (S, E) float64, msum (S) float64, count (S) int32) on the device."""
+    from . import _lib
+    lib = _lib.lib()
+    kind = _kind(kind)
+    emb = emb.contiguous()
+    label = label.to(device=emb.device, dtype=torch.int32).contiguous()
+    N, E = emb.shape
+    dev = emb.device
+    sums = torch.zeros(S, E, dtype=torch.float64, device=dev)
+    msum = torch.zeros(S, dtype=torch.float64, device=dev)
+    count = torch.zeros(S, dtype=torch.int32, device=dev)
+    if N > 0:
+        ws = torch.empty(lib.query("vm_speaker_sums_workspace_bytes", N, E, S) // 8 + 8, dtype=torch.float64, device=dev)
+        lib.call("vm_speaker_sums", emb.data_ptr(), label.data_ptr(), N, E, S, kind, sums.data_ptr(), msum.data_ptr(), count.data_ptr(),
+                 ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return sums, msum, count
+
+
+def speaker_identify(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind, leave_one_out: bool,
+                     return_scores: bool = False) -> Dict[str, torch.Tensor]:
+    """``vm_speaker_identify``: ``true_score``, ``rank``, ``best_val``, ``best_idx`` (M) and, with ``return_scores``, ``scores`` (M, S)
+    (NaN where there is no trial)."""
+    from . import _lib
+    lib = _lib.lib()
+    kind = _kind(kind)
+    q = q.contiguous()
+    dev = q.device
+    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
+    M, E = q.shape
+    S = int(count.shape[0])
+    out = {"true_score": torch.empty(M, dtype=torch.float32, device=dev), "rank": torch.empty(M, dtype=torch.int32, device=dev),
+           "best_val": torch.empty(M, dtype=torch.float32, device=dev), "best_idx": torch.empty(M, dtype=torch.int32, device=dev)}
+    if return_scores:
+        out["scores"] = torch.empty(M, S, dtype=torch.float32, device=dev)
+    if M > 0:
+        ws = torch.empty(lib.query("vm_speaker_identify_workspace_bytes", M, E, S) // 8 + 8, dtype=torch.float64, device=dev)
+        lib.call("vm_speaker_identify", q.data_ptr(), q_label.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(), S, kind,
+                 1 if leave_one_out else 0, out["scores"].data_ptr() if return_scores else None, out["true_score"].data_ptr(),
+                 out["rank"].data_ptr(), out["best_val"].data_ptr(), out["best_idx"].data_ptr(), ws.data_ptr(),
+                 torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def speaker_trial_hist(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind, leave_one_out: bool,
+                       windows: Sequence[Tuple[int, int]], bins: int, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``vm_speaker_trial_hist``: (n_windows, 2, bins + 3) int64 counts on the device (class 0 = the own speaker's model), added to
+    ``hist`` if one is given."""
+    from . import _lib
+    lib = _lib.lib()
+    kind = _kind(kind)
+    if len(windows) > V.MAX_WINDOWS or len(windows) * 2 * (bins + 3) > V.LDS_WORDS:
+        raise ValueError("at most %d windows and %d histogram words per launch" % (V.MAX_WINDOWS, V.LDS_WORDS))
+    q = q.contiguous()
+    dev = q.device
+    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
+    M, E = q.shape
+    S = int(count.shape[0])
+    if hist is None:
+        hist = torch.zeros(len(windows), 2, bins + 3, dtype=torch.int64, device=dev)
+    if M > 0:
+        win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
+        ws = torch.empty(lib.query("vm_speaker_trial_hist_workspace_bytes", M, E, S) // 8 + 8, dtype=torch.float64, device=dev)
+        lib.call("vm_speaker_trial_hist", q.data_ptr(), q_label.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(), S, kind,
+                 1 if leave_one_out else 0, win.ctypes.data, len(windows), bins, hist.data_ptr(), ws.data_ptr(),
+                 torch.cuda.current_stream(dev).cuda_stream)
+    return hist
+
+
+# ---- speaker models of an EmbeddingCache -------------------------------------------------------------------------------------------
+class SpeakerModels:
+    """The enrolled speakers of a cache: ``sums`` (S, E) / ``msum`` (S) float64 and ``count`` (S) int32 on the device, the ``distance``
+    they were summed for, ``speakers`` (dense index -> the cache's speaker code), ``label`` (N) int32 (the dense index of every enrolled
+    row of the cache, -1 for the rows left out by ``per_speaker``) and the ``cache`` itself."""
+
+    def __init__(self, sums, msum, count, distance, speakers, label, cache, per_speaker):
+        self.sums, self.msum, self.count = sums, msum, count
+        self.distance, self.speakers, self.label, self.cache, self.per_speaker = distance, speakers, label, cache, per_speaker
+
+    @property
+    def S(self) -> int:
+        return int(self.count.shape[0])
+
+    def labels_of(self, speaker_codes) -> np.ndarray:
+        """Dense indices of speaker codes (-1: the speaker is not enrolled)."""
+        codes = np.asarray(speaker_codes)
+        pos = np.clip(np.searchsorted(self.speakers, codes), 0, len(self.speakers) - 1)
+        return np.where(self.speakers[pos] == codes, pos, -1).astype(np.int32)
+
+
+def enrol(cache, distance: str = "euclidean", per_speaker: Optional[int] = None, seed: int = 0) -> SpeakerModels:
+    """Enrol the speakers of ``cache`` (dense labels from ``np.unique(cache.speaker)``).  ``per_speaker=n``: a seeded choice of n rows of
+    every speaker is enrolled (a speaker with fewer than n + 1 rows enrols all but one) and the other rows are the queries of
+    ``identify`` / ``model_trial_metrics`` -- the exhaustive n-shot S-way task.  Every rank sums all rows itself."""
+    kind = _kind(distance)
+    speakers, dense = np.unique(cache.speaker, return_inverse=True)
+    label = dense.astype(np.int32).reshape(-1)
+    if per_speaker is not None:
+        if per_speaker < 1:
+            raise ValueError("per_speaker must be >= 1 (or None: every row)")
+        rng = np.random.default_rng(seed)
+        keep = np.zeros(len(label), dtype=bool)
+        order = np.argsort(label, kind="stable")
+        bounds = np.searchsorted(label[order], np.arange(len(speakers) + 1))
+        for s in range(len(speakers)):
+            rows = order[bounds[s]:bounds[s + 1]]
+            take = min(int(per_speaker), len(rows) - 1)
+            if take > 0:
+                keep[rng.choice(rows, take, replace=False)] = True
+        label = np.where(keep, label, -1).astype(np.int32)
+    sums, msum, count = speaker_sums(cache.emb, torch.as_tensor(label), len(speakers), kind)
+    return SpeakerModels(sums, msum, count, distance, speakers, label, cache, per_speaker)
+
+
+def _queries(models: SpeakerModels, cache, leave_one_out: Optional[bool]):
+    """(query row indices of ``cache`` or None for all rows, their dense labels, leave_one_out)."""
+    same = cache is models.cache
+    if leave_one_out is None:
+        leave_one_out = same and models.per_speaker is None
+    if leave_one_out and not (same and models.per_speaker is None):
+        raise ValueError("leave_one_out needs the cache that was enrolled whole (per_speaker=None)")
+    q_label = models.labels_of(cache.speaker)
+    if same and models.per_speaker is not None:
+        idx = np.flatnonzero(models.label < 0)
+        return idx, q_label[idx], False
+    return None, q_label, bool(leave_one_out)
+
+
+def _shard(models, cache, leave_one_out, rows):
+    idx, q_label, loo = _queries(models, cache, leave_one_out)
+    n_q = len(q_label)
+    rank, world = parallel.rank_world()
+    lo, hi = rows if rows is not None else parallel.shard_range(n_q, rank, world)
+    dev = cache.emb.device
+    if idx is None:
+        q = cache.emb[lo:hi]
+    else:
+        q = cache.emb[torch.as_tensor(idx[lo:hi], dtype=torch.int64, device=dev)]
+    return q.contiguous(), torch.as_tensor(q_label[lo:hi]).to(dev), loo, (lo, hi), n_q, idx
+
+
+def _sum_ranks(t: torch.Tensor) -> np.ndarray:
+    if parallel.rank_world()[1] > 1:
+        import torch.distributed as dist
+        comm = t.to(parallel._comm_device())
+        dist.all_reduce(comm, op=dist.ReduceOp.SUM)
+        t = comm
+    return t.cpu().numpy()
+
+
+def identify(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None, rows: Optional[Tuple[int, int]] = None) -> Dict:
+    """S-way identification of the rows of ``cache`` against ``models``: ``rank1_accuracy``, ``cmc`` (float64, ``cmc[k - 1]`` = the share
+    of ranked queries with rank < k, k = 1..S), ``mean_reciprocal_rank``, ``n_queries``, ``n_unranked`` (queries without an enrolled own
+    speaker or without a model of it), and of this rank's rows (``rows`` = [lo, hi) of the queries; ``query_index``: their rows in the
+    cache) ``rank``, ``pred`` (the best speaker's code; the own code's dtype, -1 / "" where there is no trial) and ``true_score``.
+    ``leave_one_out`` defaults to "the cache is the one that was enrolled and per_speaker is None".  With ``per_speaker`` models and
+    the enrolled cache, the queries are the rows that were not enrolled."""
+    q, q_label, loo, (lo, hi), n_q, idx = _shard(models, cache, leave_one_out, rows)
+    out = speaker_identify(q, q_label, models.sums, models.msum, models.count, models.distance, loo)
+    S = models.S
+    rk = out["rank"].long()
+    hist = torch.bincount(torch.where(rk < 0, torch.full_like(rk, S), rk), minlength=S + 1)[:S + 1]
+    if rows is None:
+        hist = _sum_ranks(hist)
+    else:
+        hist = hist.cpu().numpy()
+    hist = hist.astype(np.int64)
+    n_ranked = int(hist[:S].sum())
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cmc = np.cumsum(hist[:S]).astype(np.float64) / n_ranked
+        mrr = float((hist[:S] / np.arange(1, S + 1)).sum() / n_ranked) if n_ranked else float("nan")
+    bi = out["best_idx"].cpu().numpy()
+    pred = np.where(bi >= 0, models.speakers[np.clip(bi, 0, S - 1)], "" if models.speakers.dtype.kind in "US" else -1)
+    return {"rank1_accuracy": float(cmc[0]) if n_ranked else float("nan"), "cmc": cmc, "mean_reciprocal_rank": mrr,
+            "n_queries": int(hist.sum()), "n_unranked": int(hist[S]), "rank_histogram": hist, "rows": (lo, hi),
+            "query_index": np.arange(lo, hi) if idx is None else idx[lo:hi], "rank": out["rank"].cpu().numpy(), "pred": pred,
+            "true_score": out["true_score"].cpu().numpy(), "leave_one_out": loo}
+
+
+def _prototypes(models: SpeakerModels) -> torch.Tensor:
+    """The shared models (S, E) in float64 (torch arithmetic: only the pass-1 window depends on them)."""
+    n = models.count.double().clamp_min(1.0)
+    p = models.sums / n[:, None]
+    if _kind(models.distance) == 2:
+        p = (models.msum / n)[:, None] * p
+    return p
+
+
+def _pass1(models: SpeakerModels, q: torch.Tensor, n_sample: int = 1 << 16) -> Tuple[int, int]:
+    """Pass 1's window from a seeded sample of (row, model) pairs of rank 0's rows, within cheap bounds -- it only places the window
+    (whatever falls outside lands in the under / over slots and the counts stay exact); broadcast so every rank bins alike."""
+    rank, world = parallel.rank_world()
+    kind = _kind(models.distance)
+    win = torch.zeros(2, dtype=torch.int64)
+    if rank == 0:
+        P = _prototypes(models)
+        ok = models.count > 0
+        pr = float(torch.linalg.vector_norm(P[ok], dim=1).max().item()) if bool(ok.any()) else 0.0
+        qr = float(torch.linalg.vector_norm(q.double(), dim=1).max().item()) if q.shape[0] else 0.0
+        pr, qr = (x if math.isfinite(x) else 1.0 for x in (pr, qr))
+        if kind == 1:
+            lo, hi = 0.0, 2.0
+        elif kind == 0:
+            lo, hi = 0.0, (pr + qr) * 1.001 + 1e-30
+        else:
+            lo, hi = -pr * qr * 1.001 - 1e-30, pr * qr * 1.001 + 1e-30
+        win[0], win[1] = V._pass1_window(lo, hi)
+        if q.shape[0] >= 1 and bool(ok.any()):
+            g = torch.Generator().manual_seed(0)
+            i = torch.randint(0, q.shape[0], (n_sample,), generator=g).to(q.device)
+            s = torch.randint(0, models.S, (n_sample,), generator=g).to(q.device)
+            a, b = q[i].double(), P[s]
+            if kind == 0:
+                sc = torch.linalg.vector_norm(a - b, dim=1)
+            elif kind == 1:
+                sc = 1 - (a * b).sum(1) / (torch.linalg.vector_norm(a, dim=1) * torch.linalg.vector_norm(b, dim=1))
+            else:
+                sc = -(a * b).sum(1)
+            sc = sc[torch.isfinite(sc) & ok[s]].cpu().numpy()
+            if len(sc) > 100:
+                q0, q1 = np.quantile(sc, [1e-4, 1 - 1e-4])
+                pad = 0.05 * (q1 - q0) + 1e-6 * max(abs(q0), abs(q1)) + 1e-30
+                q0, q1 = max(lo, q0 - pad), min(hi, q1 + pad)
+                if q0 < q1:
+                    win[0], win[1] = V._pass1_window(float(q0), float(q1))
+    if world > 1:
+        import torch.distributed as dist
+        comm = win.to(parallel._comm_device())
+        dist.all_reduce(comm, op=dist.ReduceOp.SUM)
+        win = comm.cpu()
+    return int(win[0]), int(win[1])
+
+
+def _hist_source(models, cache, leave_one_out):
+    q, q_label, loo, _, _, _ = _shard(models, cache, leave_one_out, None)
+
+    def hist_fn(windows, bins):
+        h = speaker_trial_hist(q, q_label, models.sums, models.msum, models.count, models.distance, loo, windows, bins)
+        return _sum_ranks(h)
+    return hist_fn, q
+
+
+def model_trial_metrics(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None) -> Dict:
+    """Exact verification metrics of the trials (row of ``cache``, speaker model): the dict of ``verification.exact_sweep`` (``eer``,
+    ``eer_threshold``, ``best_balanced_accuracy``, ``best_threshold``, FAR / FRR at both, ``auc``, ``roc``, ``n_target``,
+    ``n_nontarget``, ``n_nan``, ``passes``).  A trial is a target iff the model is the row's own speaker; queries and
+    ``leave_one_out`` as in ``identify``."""
+    hist_fn, q = _hist_source(models, cache, leave_one_out)
+    return V.exact_sweep(hist_fn, _pass1(models, q))
+
+
+def model_trial_accuracy_at_threshold(models: SpeakerModels, cache, t: float, leave_one_out: Optional[bool] = None) -> Dict:
+    """Balanced accuracy, FAR and FRR of the model trials at a fixed threshold t (accept iff score < t): one pass with key_lo = key(t),
+    whose under slot is exactly {s < t} -- a threshold found on a validation set applied to a test set."""
+    hist_fn, _ = _hist_source(models, cache, leave_one_out)
+    k = V.key_of(t) if not math.isnan(t) else V.KEY_SPACE - 1
+    h = hist_fn([(k, 31)], 1)[0]
+    nT, nN = int(h[0, :-1].sum()), int(h[1, :-1].sum())
+    far = float(h[1, 1]) / nN if nN else float("nan")
+    frr = float(nT - h[0, 1]) / nT if nT else float("nan")
+    return {"balanced_accuracy": 1.0 - (far + frr) / 2, "far": far, "frr": frr, "n_target": nT, "n_nontarget": nN,
+            "n_nan": int(h[0, -1] + h[1, -1])}
