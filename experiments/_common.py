@@ -44,6 +44,15 @@ def base_parser(description, **defaults):
                    help="under torchrun: BatchNormalization over the GLOBAL batch (one small all-reduce per BatchNorm and direction; "
                         "N ranks x B pairs then train exactly like one device with N x B pairs).  Off by default: the reference's "
                         "BatchNormalization is per process")
+    p.add_argument("--hard-fraction", type=float, default=0.0,
+                   help="share of every half batch drawn from mined hard pairs (voicemap_amd/mining.py: per training file its nearest "
+                        "other-speaker and farthest same-speaker files under the model being trained, re-mined between epochs); "
+                        "0 = off: the reference's uniform sampling, unchanged")
+    p.add_argument("--mine-k-neg", type=int, default=8, help="mined negatives kept per file (<= 64)")
+    p.add_argument("--mine-k-pos", type=int, default=4, help="mined positives kept per file (<= 64)")
+    p.add_argument("--mine-every", type=int, default=1, help="re-embed and re-mine after every this many epochs")
+    p.add_argument("--semi-hard", action="store_true",
+                   help="mined negatives must lie beyond the file's hardest positive (semi-hard mining)")
     p.add_argument("--training-set", nargs="+", default=["train-clean-100", "train-clean-360"])
     p.add_argument("--validation-set", default="dev-clean")
     return p
@@ -73,6 +82,21 @@ def device_resident(a, train):
     ds = shards.ShardedSpeechDataset(a.device_data, a.n_seconds, stochastic=True, pad=False, speaker_shard=shard)
     ds.to_device("cuda")
     return ds
+
+
+def mined_batches(a, dataset, preprocessor, device, distance="euclidean"):
+    """--hard-fraction: (the training batch generator over a HardPairSampler of ``dataset``, [the HardPairMiner callback]) -- the
+    callback goes FIRST in the list (CSVLogger records its two fields); (None, []) when mining is off: the caller keeps the dataset's
+    own generator and nothing changes.  ``device``: the --device-data path (``dataset`` is the resident ShardedSpeechDataset)."""
+    if getattr(a, "hard_fraction", 0.0) <= 0.0:
+        return None, []
+    from voicemap_amd.mining import HardPairMiner, HardPairSampler
+    from voicemap_amd import parallel
+    sampler = HardPairSampler(dataset, None, hard_fraction=a.hard_fraction, seed=parallel.rank_world()[0])
+    miner = HardPairMiner(sampler, dataset, preprocessor, every=a.mine_every, distance=distance, k_neg=a.mine_k_neg,
+                          k_pos=a.mine_k_pos, semi_hard=a.semi_hard)
+    gen = sampler.yield_verification_batches_device if device else sampler.yield_verification_batches
+    return (preprocessor(b) for b in gen(a.batchsize)), [miner]
 
 
 def apply_sync_bn(a, model):

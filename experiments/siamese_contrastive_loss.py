@@ -15,15 +15,26 @@ def main(argv=None):
     train, valid = C.datasets(a, pad=False)
     whiten_downsample = BatchPreProcessor("siamese", preprocess_instances(a.downsampling, whitening=True))
     stream = lambda ds: (whiten_downsample(b) for b in ds.yield_verification_batches(a.batchsize))
+    train_batches = stream(train)
+    workers = a.workers
+    if a.device_data:  # the windows never exist on the host: offsets into an HBM-resident int16 buffer (as in train_siamese.py)
+        resident = C.device_resident(a, train)
+        train_batches = (whiten_downsample(b) for b in resident.yield_verification_batches_device(a.batchsize))
+        workers = 0
+    # --hard-fraction: part of every batch from mined pairs (off by default: the generators above, unchanged)
+    mined, mining_cbs = C.mined_batches(a, resident if a.device_data else train, whiten_downsample, device=bool(a.device_data))
+    if mined is not None:
+        train_batches = mined
     encoder = get_baseline_convolutional_encoder(a.filters, a.embedding_dimension, dropout=a.dropout, dtype=a.dtype)
     siamese = build_siamese_net(encoder, (C.input_length(a), 1))
     siamese.compile(loss=contrastive_loss, optimizer=Adam(clipnorm=1.), metrics=["accuracy"])
     key = "val_{}-shot_acc".format(a.n_shot)
-    cbs = [NShotEvaluationCallback(a.num_evaluation_tasks, a.n_shot, a.k_way, valid, preprocessor=whiten_downsample),
-           CSVLogger(PATH + "/logs/convnet_contrastive_loss.csv"),
-           ModelCheckpoint(PATH + "/models/convnet_contrastive_loss.hdf5", monitor=key, mode="max", save_best_only=True, verbose=True)]
-    return siamese.fit_generator(generator=stream(train), steps_per_epoch=a.steps_per_epoch, validation_data=stream(valid),
-                                 validation_steps=a.validation_steps, epochs=a.epochs, workers=a.workers,
+    cbs = mining_cbs + [NShotEvaluationCallback(a.num_evaluation_tasks, a.n_shot, a.k_way, valid, preprocessor=whiten_downsample),
+                        CSVLogger(PATH + "/logs/convnet_contrastive_loss.csv"),
+                        ModelCheckpoint(PATH + "/models/convnet_contrastive_loss.hdf5", monitor=key, mode="max", save_best_only=True,
+                                        verbose=True)]
+    return siamese.fit_generator(generator=train_batches, steps_per_epoch=a.steps_per_epoch, validation_data=stream(valid),
+                                 validation_steps=a.validation_steps, epochs=a.epochs, workers=workers,
                                  use_multiprocessing=True, callbacks=cbs)
 
 

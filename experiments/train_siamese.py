@@ -25,6 +25,10 @@ def main(argv=None):
         resident = C.device_resident(a, train)
         train_batches = (pre(b) for b in resident.yield_verification_batches_device(a.batchsize))
         workers = 0
+    # --hard-fraction: part of every batch from mined pairs (off by default: the generators above, unchanged)
+    mined, mining_cbs = C.mined_batches(a, resident if a.device_data else train, pre, device=bool(a.device_data))
+    if mined is not None:
+        train_batches = mined
     build = get_spectrogram_convolutional_encoder if a.frontend == "logmel" else get_baseline_convolutional_encoder
     encoder = build(a.filters, a.embedding_dimension, dropout=a.dropout, dtype=a.dtype)
     siamese = build_siamese_net(encoder, (C.input_length(a), 1), distance_metric="uniform_euclidean")
@@ -36,7 +40,7 @@ def main(argv=None):
         name = "logmel_" + name
     return siamese.fit_generator(generator=train_batches, steps_per_epoch=a.steps_per_epoch, validation_data=batches(valid),
                                  validation_steps=a.validation_steps, epochs=a.epochs, workers=workers,
-                                 use_multiprocessing=True, callbacks=C.standard_callbacks(a, valid, pre, "siamese", name))
+                                 use_multiprocessing=True, callbacks=mining_cbs + C.standard_callbacks(a, valid, pre, "siamese", name))
 
 
 if __name__ == "__main__":

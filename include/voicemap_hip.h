@@ -664,6 +664,29 @@ int64_t vm_speaker_trial_hist_workspace_bytes(int64_t M, int E, int64_t S);
 int vm_speaker_trial_hist(const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
                           const int32_t* count, int64_t S, int kind, int leave_one_out, const int64_t* host_windows, int n_windows, int bins,
                           uint64_t* hist, void* ws, void* stream);
+/* vm_mine_pairs: hard-pair mining for siamese training (csrc/mine.hip, voicemap_amd/mining.py): per anchor row its k_neg nearest rows of
+ * another speaker and its k_pos farthest rows of its own speaker, selected on the chip -- no M x N score tile is written anywhere.
+ * Anchors and candidates.  Anchors are the rows row_lo <= i < row_hi of emb (N, E) fp32 (M = row_hi - row_lo; the row-shard form of
+ * vm_pair_score_hist); the candidates of anchor i are all rows j != i of emb.  label (N) int32: the speaker of every row.
+ * Scores.  score_kind is VM_DIST_EUCLIDEAN, VM_DIST_COSINE or VM_DIST_DOT, lower = more alike; s_ij is bit-identical to dist[i][j] of
+ * vm_pairdist_argmin(emb + row_lo * E, emb, ...).  Order key: vm_pair_score_hist's uint32 key, -0.0 taken as +0.0.
+ * Who takes part.  A candidate with label[j] < 0 or with a NaN score is never selected; an anchor with label[i] < 0 gets empty lists.
+ * Negatives.  Eligible: label[j] != label[i] and, if neg_floor is not NULL (device, M fp32, indexed by i - row_lo),
+ * key(s_ij) > key(neg_floor[i - row_lo]) -- strictly; a NaN floor means no floor for that anchor.  The list holds the k_neg eligible
+ * candidates that are smallest by (key, j) ascending, in that order.
+ * Positives.  Eligible: label[j] == label[i].  The list holds the k_pos largest by key, ties to the lower j: (key descending, j
+ * ascending), in that order.
+ * Outputs.  neg_idx (M, k_neg) int32 = j and neg_val (M, k_neg) fp32 = s_ij (its own bits: a -0.0 stays -0.0); pos_idx / pos_val
+ * (M, k_pos) likewise; unused slots hold -1 and NaN.  Either pair is optional AS A PAIR: both NULL together with its k = 0.
+ * Limits.  0 <= k_neg, k_pos <= 64, not both zero; E <= 256; N < 2^31; emb 16-byte aligned when E % 4 == 0.
+ * Determinism.  (key, j) is a total order, so the lists are a function of the inputs alone: bit-identical from run to run and however
+ * the row range is cut into calls; no float atomics, nothing depends on the order of arrival.
+ * ws >= vm_mine_pairs_workspace_bytes(...): N squared norms, the anchors in scalar-path layout (O(M E)) and the partial lists of the
+ * candidate splits, (splits, M, k_neg + k_pos) x 8 bytes. */
+int64_t vm_mine_pairs_workspace_bytes(int64_t N, int E, int64_t row_lo, int64_t row_hi, int k_neg, int k_pos);
+int vm_mine_pairs(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, int64_t row_lo, int64_t row_hi, int k_neg,
+                  int k_pos, const float* neg_floor, int32_t* neg_idx, float* neg_val, int32_t* pos_idx, float* pos_val, void* ws,
+                  void* stream);
 
 /* ---- a10 / f4: log-mel front-end and the 2-D CNN encoder variant (BASELINE.json config 4) -------------------
  * NOT in the reference (nothing to cite under /root/reference); the specification is DESIGN.md section 9 and the

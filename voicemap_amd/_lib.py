@@ -137,6 +137,8 @@ SIGNATURES = {
     "vm_speaker_identify": (I, [P, P, L, I, P, P, P, L, I, I, P, P, P, P, P, P, P]),
     "vm_speaker_trial_hist_workspace_bytes": (L, [L, I, L]),
     "vm_speaker_trial_hist": (I, [P, P, L, I, P, P, P, L, I, I, P, I, I, P, P, P]),
+    "vm_mine_pairs_workspace_bytes": (L, [L, I, L, L, I, I]),
+    "vm_mine_pairs": (I, [P, P, L, I, I, L, L, I, I, P, P, P, P, P, P, P]),
     "vm_stft_frames": (L, [L, I, I]),
     "vm_stft_logmel": (I, [P, I, L, L, I, I, P, P, I, F, I, P, P]),
     "vm_stft_split_basis_bytes": (L, [I]),
