@@ -75,13 +75,13 @@ int vm_event_destroy(void* event);
 int vm_event_record(void* event, void* stream);
 int vm_stream_wait_event(void* stream, void* event);
 /* A recorded training step made from C (round 6).  The Python side records the C-ABI calls of one step -- entry point, argument list,
- * event records / waits between its streams -- and replays that list while the configuration stays the same (voicemap_amd/engine.py
- * _Program; the reference runs the same train_on_batch 500 times an epoch, experiments/train_siamese.py:65-94).  At the reference's own
+ * event records / waits between its streams -- and replays that list while the configuration stays the same (voicemap_amd/program.py
+ * Program; the reference runs the same train_on_batch 500 times an epoch, experiments/train_siamese.py:65-94).  At the reference's own
  * batch sizes the step is bound by the host making ~70 calls, and ~1.5 us of each is the binding's argument marshalling: vm_program_run
  * takes the list as int64 words  [function id, argc, argument words ...]*  (pointers and integers as they are, floats / doubles as their
  * bits) and makes the calls itself, in order, stopping at the first non-zero return code (its word index in *fail_at).  Function ids are
  * positions in the name-sorted table of int-returning entry points whose arguments are pointers / int / int64_t / float / double
- * (csrc/program_run.hip, generated by tools/gen_program_run.py from the binding table); vm_program_table_hash() identifies that table so
+ * (csrc/program_run.hip, generated by tools/gen_program_run.py from the prototypes of this header); vm_program_table_hash() identifies that table so
  * that a binding generated from another one refuses to run. */
 int vm_program_run(const int64_t* words, int64_t n_words, int64_t* fail_at);
 int64_t vm_program_table_hash(void);

@@ -6,10 +6,54 @@ import os
 from voicemap_amd import _lib
 
 
-def test_header_and_binding_table_agree():
-    declared = _lib.header_functions()
-    assert declared, "no functions parsed from include/voicemap_hip.h"
-    assert sorted(_lib.SIGNATURES) == declared
+def test_every_declared_function_has_a_parsed_signature():
+    declared = _lib.header_functions()           # the loose regex: every `vm_name(` outside a block comment
+    assert len(declared) >= 132, "functions are missing from include/voicemap_hip.h"
+    assert sorted(_lib.SIGNATURES) == declared   # none that the prototype parser skipped, none it made up
+
+
+def test_parsed_signatures_of_the_entry_points_that_are_easy_to_get_wrong():
+    from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_void_p
+    P, I, L, F, D = c_void_p, c_int, c_int64, c_float, c_double
+    assert (_lib.P, _lib.I, _lib.L, _lib.F, _lib.D) == (P, I, L, F, D)
+    sig = _lib.SIGNATURES
+    assert sig["vm_last_error"] == (c_char_p, [])
+    assert sig["vm_event_create"] == (I, [POINTER(c_void_p)])
+    assert sig["vm_set_tuning"] == (I, [c_char_p, I])
+    assert sig["vm_program_run"] == (I, [P, L, P])
+    assert sig["vm_program_table_hash"] == (L, [])
+    assert sig["vm_adam_clip_step"] == (I, [P, P, P, P, L, F, F, F, F, F, F, P, P, I, P, P])
+    res, args = sig["vm_bn_finalize"]
+    assert res is I and len(args) == 25
+    assert [k for k, a in enumerate(args) if a is D] == [5] and [k for k, a in enumerate(args) if a is F] == [8, 9, 19]
+    assert [k for k, a in enumerate(args) if a is L] == [2] and [k for k, a in enumerate(args) if a is I] == [3, 4, 10]
+    assert sum(a is P for a in args) == 17
+    # the enum constants come from the same pass over the header
+    assert (_lib.VM_F32, _lib.VM_BF16, _lib.VM_F32S, _lib.VM_F16) == (0, 1, 2, 3)
+    assert (_lib.VM_LOSS_CONTRASTIVE, _lib.VM_LOSS_BCE, _lib.VM_HEAD_UNIFORM_EUCLIDEAN, _lib.VM_HEAD_WEIGHTED_L1) == (0, 1, 0, 1)
+    assert (_lib.VM_DIST_EUCLIDEAN, _lib.VM_DIST_COSINE, _lib.VM_DIST_DOT, _lib.VM_SCORE_WEIGHTED_L1, _lib.VM_SCORE_NEG_EUCLIDEAN) == (0, 1, 2, 3, 4)
+
+
+def test_the_header_parser_maps_the_documented_types_and_refuses_every_other():
+    import pytest
+    from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_void_p
+    sigs, enums = _lib.parse_header("""
+        /* int vm_in_a_comment(int a); */
+        #define VM_NOT_A_PROTOTYPE(x) vm_macro(x)
+        enum { VM_A = 0, VM_B = -3 };   // int vm_in_a_line_comment(void);
+        const char* vm_s(void);
+        int64_t vm_n();
+        int vm_all(const void* in, float* out, const int32_t* lens, void* const* tab, void** handle, const char* key,
+                   int i, int64_t n, float f, double d);
+    """)
+    assert enums == {"VM_A": 0, "VM_B": -3}
+    assert sigs == {"vm_s": (c_char_p, []), "vm_n": (c_int64, []),
+                    "vm_all": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), c_char_p, c_int, c_int64, c_float, c_double])}
+    for bad, named in (("int vm_u(int64_t n, unsigned count);", "unsigned count"), ("int vm_v(struct vm_dims dims);", "struct vm_dims dims"),
+                       ("int vm_w(vm_handle_t h);", "vm_handle_t h"), ("int vm_x(int32_t n);", "int32_t n"), ("void vm_y(int n);", "void"),
+                       ("uint64_t vm_z(void);", "uint64_t")):
+        with pytest.raises(TypeError, match=bad.split("(")[0].split()[-1] + ".*" + named):   # names the function and the type
+            _lib.parse_header(bad)
 
 
 def test_library_builds_loads_and_exports_every_symbol():

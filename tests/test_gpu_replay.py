@@ -30,8 +30,7 @@ def _same_state(a, b, what):
 
 
 def _programs(eng):
-    from voicemap_amd.engine import _Program
-    return [p for p in eng._programs.values() if isinstance(p, _Program)]
+    return eng._programs.recorded()
 
 
 @pytest.mark.parametrize("dtype,dropout,loss", [("f16", 0.0, "contrastive"), ("f16", 0.05, "bce"), ("bf16", 0.0, "bce"), ("f32", 0.05, "contrastive")])

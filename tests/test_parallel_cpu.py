@@ -366,7 +366,6 @@ def _gpu_worker(rank, world, port, outdir, backend="nccl"):
     res["finite"] = bool(torch.isfinite(pl["loss_acc"]).all().item())
     # round 6: a data-parallel step is recorded and replayed like a single-GPU one (the two collectives are host calls of the program,
     # engine._host_call): a replaying engine and an eager one, same seed, same batches, hold the same bits after 7 steps
-    from voicemap_amd.engine import _Program
     ea = HipEncoderEngine(blocks, 16, dropout=0.0, head="uniform_euclidean", dtype="f16", seed=9)
     eb = HipEncoderEngine(blocks, 16, dropout=0.0, head="uniform_euclidean", dtype="f16", seed=9)
     eb.replay = False
@@ -378,7 +377,7 @@ def _gpu_worker(rank, world, port, outdir, backend="nccl"):
         for e in (ea, eb):
             e.siamese_train_step(xa, xb, y, drop_masks=None)
     torch.cuda.synchronize()
-    res["replay_programs"] = sum(isinstance(p_, _Program) for p_ in ea._programs.values())
+    res["replay_programs"] = len(ea._programs.recorded())
     res["replay_same_as_eager"] = bool(all(torch.equal(getattr(ea, nm_).view(torch.int32), getattr(eb, nm_).view(torch.int32)) for nm_ in ("P", "M", "V", "G")))
     res["replay_collectives"] = (ea.grad_sync.collectives, eb.grad_sync.collectives)
     # BASELINE.json config 5 sharded: every rank embeds its rows of the corpus, the (N, E) matrix is all-gathered, tasks / query rows

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-from voicemap_amd.engine import HipEncoderEngine, _Program  # noqa: E402
+from voicemap_amd.engine import HipEncoderEngine  # noqa: E402
 
 steps = int(sys.argv[1]) if len(sys.argv) > 1 else 1500
 pairs = int(sys.argv[2]) if len(sys.argv) > 2 else 32
@@ -32,7 +32,7 @@ for run in range(2):
             worst = max(worst, l)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    progs = [p for p in eng._programs.values() if isinstance(p, _Program)]
+    progs = eng._programs.recorded()
     out.append((eng.P.clone(), eng.M.clone(), eng.V.clone(), eng.NT.clone(), float(pl["loss_acc"][0].item()), eng.loss_scale, eng.skipped_steps if hasattr(eng, "skipped_steps") else None))
     print("run %d: %d steps in %.2f s (%.3f ms per step), final loss %.6f, loss scale %g, native programs %d" % (
         run, steps, dt, dt / steps * 1e3, out[-1][4], out[-1][5], sum(p.native is not None for p in progs)))

@@ -1,4 +1,4 @@
-"""A hipGraph of the whole training step against the recorded-step replay (engine._Program): the eager step is captured through
+"""A hipGraph of the whole training step against the recorded-step replay (program.Program): the eager step is captured through
 torch.cuda.graph (three streams: the tower and side streams join the capture through the engine's own event calls) and replayed.
 Timing only -- the by-value scalars of a step (Adam's lr_t, the BatchNorm zero-debias factor) stay what they were at capture.
   python tools/probe/graph_capture_probe.py [cfgA|cfgB] [pairs]

@@ -23,7 +23,7 @@ os.environ.update(RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0
 os.environ.setdefault("MASTER_PORT", str(29600 + os.getpid() % 300))
 
 from voicemap_amd import parallel  # noqa: E402
-from voicemap_amd.engine import HipEncoderEngine, _Program  # noqa: E402
+from voicemap_amd.engine import HipEncoderEngine  # noqa: E402
 
 CFG = {"small": ([(32, 16, 4), (3, 32, 2), (3, 48, 2), (3, 64, 2)], 16, 1600),
        "cfgA": ([(32, 128, 4), (3, 256, 2), (3, 384, 2), (3, 512, 2)], 64, 12000)}
@@ -55,7 +55,7 @@ def main():
     out["same_bits"] = bool(all(torch.equal(getattr(ea, n).view(torch.int32), getattr(eb, n).view(torch.int32)) for n in ("P", "M", "V", "G")))
     out["collectives"] = ea.grad_sync.collectives
     out["collectives_per_step"] = ea.grad_sync.collectives / steps
-    out["replayed_programs"] = sum(isinstance(p_, _Program) for p_ in ea._programs.values())
+    out["replayed_programs"] = len(ea._programs.recorded())
     waits = [a.elapsed_time(b) for a, b in ea.grad_sync.wait_events]
     out["hook_ms_on_step_stream_median"] = float(np.median(waits)) if waits else None
     ea.grad_sync.time_wait = False

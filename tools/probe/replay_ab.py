@@ -1,4 +1,4 @@
-"""Interleaved A/B on one box: the training step eager vs replayed (engine._Program), ms per step (wall, GPU-synchronised blocks)."""
+"""Interleaved A/B on one box: the training step eager vs replayed (program.Program), ms per step (wall, GPU-synchronised blocks)."""
 import os
 import sys
 import time

@@ -9,8 +9,8 @@ experiments/siamese_contrastive_loss.py:67-70; experiments/train_classifier.py:1
 from __future__ import annotations
 
 import ctypes
+import functools
 import math
-import struct
 from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import VM_BF16, VM_F16, VM_F32, VM_F32S
+from .program import DynF, DynI, Program, ProgramStore
 
 # "f32s": fp32 storage, split-bf16 products in the k=3 convolution GEMMs (VM_F32S in include/voicemap_hip.h)
 # "f16": IEEE half storage -- the bf16 kernels with 11 instead of 8 significand bits per stored value, loss-scaled gradients
@@ -120,21 +121,6 @@ except AttributeError:   # older torch: the documented way
         return torch.cuda.current_stream(index).cuda_stream
 
 
-class _DynI(int):
-    """An integer C-ABI argument (a pointer, normally) that changes from step to step: recorded as a patch slot (see _Program)."""
-    def __new__(cls, value, key):
-        o = int.__new__(cls, value)
-        o.key = key
-        return o
-
-
-class _DynF(float):
-    def __new__(cls, value, key):
-        o = float.__new__(cls, value)
-        o.key = key
-        return o
-
-
 _SHARED_STREAMS: Dict[tuple, "torch.cuda.Stream"] = {}
 
 
@@ -151,20 +137,6 @@ def _shared_stream(device: torch.device, role: str) -> "torch.cuda.Stream":
     return st
 
 
-class _Program:
-    """One training step as a flat list of what the host enqueued -- [0, cfunc, args, name] C-ABI calls, [1, event, stream] records,
-    [2, stream, event] waits -- plus the (command, argument) slots whose value changes per step (input / label / mask pointers, the
-    BatchNorm zero-debias factor, the loss scale, Adam's lr_t).  The reference runs the same train_on_batch 500 times per epoch
-    (experiments/train_siamese.py:65-94); at its batch sizes (32 / 64 pairs) the step here is bound by the HOST deriving ~55 argument
-    lists and stream hand-overs through Python, not by the GPU -- replaying the recorded list costs a third of it."""
-
-    def __init__(self):
-        self.cmds, self.patches, self.events = [], [], {}
-        # the same list for the library's own runner (vm_program_run): segments -- int64 word arrays, or host calls between them -- and
-        # the (segment, word index, type) of every per-step slot; None: this program replays through the Python loop
-        self.native = None
-
-
 class HipEncoderEngine:
     """The voicemap encoder (voicemap/models.py:6-41) + optional head on one MI355X.
 
@@ -179,8 +151,6 @@ class HipEncoderEngine:
     _stream_stack = ()
     replay = False
     native_replay = True   # a recorded step is replayed by the library's own runner (vm_program_run) instead of a Python loop of ctypes calls
-    _fail_at_v = ctypes.c_int64(0)
-    _fail_at = ctypes.byref(_fail_at_v)
     fused_tail = False
     _packed_weights = False
 
@@ -331,11 +301,11 @@ class HipEncoderEngine:
         self.sync_bn_world = 1
         self._sync_bufs = {}
         self._plans: Dict[Tuple, dict] = {}
-        # recorded training steps (see _Program): on by default; a configuration is recorded on its second sighting and replayed from
+        # recorded training steps (program.py): on by default; a configuration is recorded on its second sighting and replayed from
         # the third on.  Off: data parallelism (the gradient hook runs torch.distributed calls), SyncBN, per-kernel timing (bench.py)
         self.replay = True
-        self._rec: Optional[_Program] = None
-        self._programs: Dict[Tuple, object] = {}
+        self._rec: Optional[Program] = None   # the step being recorded
+        self._programs = ProgramStore(self.lib, functools.partial(torch.cuda.synchronize, self.device))
         self._stream_stack: List[int] = []
         self._drop_bufs: Dict[int, tuple] = {}
         self.init_params(seed)
@@ -432,14 +402,8 @@ class HipEncoderEngine:
         rec = self.timed.get(as_name) if self.timed else None
         if rec is None:
             self.lib.call(name, *args)
-            prog = self._rec
-            if prog is not None:
-                a = list(args)
-                for j, v in enumerate(a):
-                    if isinstance(v, (_DynI, _DynF)):
-                        prog.patches.append((len(prog.cmds), j, v.key))
-                        a[j] = int(v) if isinstance(v, _DynI) else float(v)
-                prog.cmds.append([0, getattr(self.lib.cdll, name), a, name])
+            if self._rec is not None:
+                self._rec.call(getattr(self.lib.cdll, name), name, args)
             return
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -447,12 +411,12 @@ class HipEncoderEngine:
         e1.record()
         rec.append((e0, e1, tuple(a for k, a in enumerate(args) if k not in drop) + ((name,) if as_name != name else ())))
 
-    # ---- stream hand-overs: through these, so that a recorded step (see _Program) carries them ----------------------------------
+    # ---- stream hand-overs: through these, so that a recorded step (program.py) carries them ----------------------------------
     def _dyn(self, key, value):
         """Mark a C-ABI argument whose value changes from step to step (None stays None: its presence is part of the configuration)."""
         if self._rec is None or value is None:
             return value
-        return _DynF(value, key) if isinstance(value, float) else _DynI(value, key)
+        return DynF(value, key) if isinstance(value, float) else DynI(value, key)
 
     class _On:
         def __init__(self, eng, stream):
@@ -474,28 +438,26 @@ class HipEncoderEngine:
         """ev.record() on the current stream."""
         ev.record()
         if self._rec is not None:
-            self._rec.cmds.append([1, id(ev), self.stream()])
+            self._rec.record(id(ev), self.stream())
 
     def _wait(self, stream, ev):
         """stream.wait_event(ev)"""
         stream.wait_event(ev)
         if self._rec is not None:
-            self._rec.cmds.append([2, stream.cuda_stream, id(ev)])
+            self._rec.wait(stream.cuda_stream, id(ev))
 
     def _join(self, waiter, waited):
         """waiter.wait_stream(waited): everything enqueued on ``waited`` so far precedes what ``waiter`` gets from here on."""
         waiter.wait_stream(waited)
         if self._rec is not None:
-            key = ("join", len(self._rec.cmds))
-            self._rec.cmds.append([1, key, waited.cuda_stream])
-            self._rec.cmds.append([2, waiter.cuda_stream, key])
+            self._rec.join(waiter.cuda_stream, waited.cuda_stream)
 
     def _host_call(self, fn):
         """A step's host-side call that is not a C-ABI entry point (torch.distributed collectives): run now and, in a step being
         recorded, kept in the program at this position -- a replay calls it again between the same launches."""
         fn()
         if self._rec is not None:
-            self._rec.cmds.append([3, fn, None, "host call"])
+            self._rec.host_call(fn)
 
     def _begin_grad_tail(self, pl: dict):
         """Data parallelism: every gradient of G[conv2.kernel:] that the main stream writes is enqueued -- hand that range to the
@@ -512,138 +474,6 @@ class HipEncoderEngine:
         self._record(pl["sync_ev"])
         self._wait(self.side_stream, pl["sync_ev"])
         self._host_call(lambda: gs.ordered_begin(self))
-
-    def _finish_program(self, prog: _Program) -> _Program:
-        """Event keys -> events of the program's own (created once; a replay never touches torch's events)."""
-        for c in prog.cmds:
-            if c[0] == 0 or c[0] == 3:
-                continue
-            slot = 1 if c[0] == 1 else 2
-            h = prog.events.get(c[slot])
-            if h is None:
-                out = ctypes.c_void_p()
-                self.lib.call("vm_event_create", ctypes.byref(out))
-                h = prog.events[c[slot]] = out.value
-            c[slot] = h
-        self._ev_record, self._ev_wait = self.lib.cdll.vm_event_record, self.lib.cdll.vm_stream_wait_event
-        prog.native = self._native_program(prog)   # (used while engine.native_replay is on)
-        return prog
-
-    @staticmethod
-    def _word(v, t):
-        """One argument as the int64 word vm_program_run expects: pointers / integers as they are, floats / doubles as their bits."""
-        if t == "F":
-            return struct.unpack("<I", struct.pack("<f", float(v)))[0]
-        if t == "D":
-            return struct.unpack("<q", struct.pack("<d", float(v)))[0]
-        if v is None:
-            return 0
-        if isinstance(v, (ctypes.Array, ctypes.Structure)):   # a host-side argument block (pointer / size tables of the batched entry
-            v = ctypes.addressof(v)                           # points): its address -- the object stays alive in the program's list
-        elif isinstance(v, ctypes._SimpleCData):
-            v = v.value or 0
-        v = int(v)
-        return v - (1 << 64) if v >= (1 << 63) else v
-
-    def _native_program(self, prog: _Program):
-        """The recorded step as word arrays for vm_program_run (include/voicemap_hip.h): one array per run of C-ABI calls and event
-        records / waits, host calls (the gradient collectives of data parallelism) between them.  None where the library's table is
-        not the binding's or an argument is not a pointer / number."""
-        tab = _lib.program_table()
-        if tab is None:
-            return None
-        ids, sigs = tab
-        segs, cur, where = [], [], {}
-        try:
-            for ci, c in enumerate(prog.cmds):
-                if c[0] == 3:
-                    segs.append(cur)
-                    segs.append(c[1])
-                    cur = []
-                    continue
-                if c[0] == 0:
-                    name, args = c[3], c[2]
-                elif c[0] == 1:
-                    name, args = "vm_event_record", (c[1], c[2])
-                else:
-                    name, args = "vm_stream_wait_event", (c[1], c[2])
-                sig = sigs[name]
-                if len(sig) != len(args):
-                    return None
-                where[ci] = (len(segs), len(cur) + 2)
-                cur += [ids[name], len(args)] + [self._word(v, t) for v, t in zip(args, sig)]
-            segs.append(cur)
-            patches = []
-            for ci, ai, key in prog.patches:
-                si, w0 = where[ci]
-                patches.append((si, w0 + ai, sigs[prog.cmds[ci][3]][ai], key))
-        except (KeyError, TypeError, ValueError, struct.error):
-            return None
-        segs = [np.array(sg, dtype=np.int64) if isinstance(sg, list) else sg for sg in segs]
-        return segs, patches
-
-    def _destroy_program(self, prog):
-        if isinstance(prog, _Program):
-            for h in prog.events.values():
-                self.lib.cdll.vm_event_destroy(h)
-            prog.events = {}
-
-    def _drop_programs(self):
-        """Forget every recorded step.  Programs hold raw device pointers: whoever frees or reallocates a buffer a program may
-        reference (the fold buffers, a plan's lazily sized buffers, a stream) calls this."""
-        progs = getattr(self, "_programs", None)
-        if progs:
-            if torch.cuda.is_available():
-                torch.cuda.synchronize(self.device)   # a replayed step may still be in flight on the events about to go
-            for prog in progs.values():
-                self._destroy_program(prog)
-            progs.clear()
-
-    def __del__(self):
-        # the recorded programs' events are the only library-side objects an engine owns
-        try:
-            for prog in getattr(self, "_programs", {}).values():
-                self._destroy_program(prog)
-        except Exception:   # interpreter shutdown: the library may be gone already
-            pass
-
-    def _run_program(self, prog: _Program, dyn: dict):
-        if prog.native is not None and self.native_replay:
-            segs, patches = prog.native
-            word = self._word
-            for si, wi, t, key in patches:
-                segs[si][wi] = word(dyn[key], t)
-            run, fail = self.lib.cdll.vm_program_run, self._fail_at
-            for sg in segs:
-                if isinstance(sg, np.ndarray):
-                    if sg.size:
-                        rc = run(sg.ctypes.data, sg.size, fail)
-                        if rc != 0:
-                            msg = self.lib.cdll.vm_last_error()
-                            raise _lib.VoicemapHipError("a replayed step failed (%d) at word %d of its program: %s"
-                                                        % (rc, self._fail_at_v.value, msg.decode() if msg else ""))
-                else:
-                    sg()          # a host call of the step (the gradient collectives of data parallelism): _host_call
-            return
-        cmds = prog.cmds
-        for ci, ai, key in prog.patches:
-            cmds[ci][2][ai] = dyn[key]
-        rec, wait = self._ev_record, self._ev_wait
-        for c in cmds:
-            k = c[0]
-            if k == 0:
-                rc = c[1](*c[2])
-            elif k == 1:
-                rc = rec(c[1], c[2])
-            elif k == 2:
-                rc = wait(c[1], c[2])
-            else:
-                c[1]()          # a host call of the step (the gradient collectives of data parallelism): _host_call
-                rc = 0
-            if rc != 0:
-                msg = self.lib.cdll.vm_last_error()
-                raise _lib.VoicemapHipError("%s failed (%d) in a replayed step: %s" % (c[3] if k == 0 else "stream ordering", rc,
-                                                                                       msg.decode() if msg else ""))
 
     def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
         # (memoised per (name, buffer): a training step asks ~70 times, and at small batches the step is bound by the host)
@@ -818,7 +648,7 @@ class HipEncoderEngine:
         changed = bool(v) != getattr(self, "_packed_weights", None)
         self._packed_weights = bool(v)
         if changed and hasattr(self, "_plans"):   # (during __init__ the copies are made by init_params -> refresh_weights)
-            self._drop_programs()   # recorded steps point into the fold buffers dropped below
+            self._programs.drop_all()   # recorded steps point into the fold buffers dropped below
             self._fold = {}
             self._pack_args = None
             self._wfp_stale = True
@@ -834,7 +664,7 @@ class HipEncoderEngine:
         if int(v) == self._side_priority:
             return
         self._side_priority = int(v)
-        self._drop_programs()
+        self._programs.drop_all()
         # 0: back on the process's shared stream; anything else is a private stream of that priority (an experiment: see _shared_stream
         # for what private streams cost the later engines of a process)
         self.side_stream = _shared_stream(self.device, "tower") if int(v) == 0 else torch.cuda.Stream(device=self.device, priority=int(v))
@@ -1080,7 +910,7 @@ class HipEncoderEngine:
         if fold:
             if pl.get("fold_ready", wpt) != wpt:   # the slab split depends on the tower size
                 del pl["fold_ready"]
-                self._drop_programs()              # steps recorded for the other tower size point at the buffers re-made below
+                self._programs.drop_all()              # steps recorded for the other tower size point at the buffers re-made below
             self._fold_plan(pl)
         if training:
             self.bn_steps += 1
@@ -1616,7 +1446,7 @@ class HipEncoderEngine:
                     input_ready: bool = False):
         """preprocess (``pre`` = None | ("raw", tensor, downsampling, whitening) | ("offsets", audio, offsets, raw_len, downsampling,
         whitening)) -> forward -> head (``loss`` None: the classifier's) -> backward -> optimizer.  The SECOND time a configuration
-        is seen its enqueue sequence is recorded (_Program), from the third on it is replayed: same launches, same arguments, same
+        is seen its enqueue sequence is recorded (program.Program), from the third on it is replayed: same launches, same arguments, same
         stream ordering -- only the input / label / mask pointers and four scalars are patched in."""
         # (a gradient hook that declares itself ``replayable`` -- parallel.GradAllReduce: its two collectives are host calls kept in
         # the program, its stream ordering goes through the engine -- no longer forces the eager path; SyncBN still does)
@@ -1629,21 +1459,12 @@ class HipEncoderEngine:
                                             else (pre[0], pre[1].dtype, pre[3]) + tuple(pre[-2:]))
             masks = None if drop_masks is None else tuple(m is not None for m in drop_masks)
             key = (id(pl), wpt, loss, apply_update, self.stream(), sig, masks, bool(input_ready), self._step_flags())
-            prog = self._programs.get(key)
-            if isinstance(prog, _Program):
-                self._programs[key] = self._programs.pop(key)   # most recently used last
+            prog = self._programs.sight(key)
+            if prog is not None and prog.finished:
                 self._x0_handover(pl, prog)
                 self._replay_step(prog, pl, wpt, target, drop_masks, apply_update, pre)
                 return
-            if prog is None:
-                self._programs[key] = 1            # first sighting: run it (lazy buffers get allocated), record the next one
-                while len(self._programs) > 64:    # bounded: the least recently used configuration goes (with its events)
-                    old = next(iter(self._programs))
-                    if isinstance(self._programs[old], _Program):
-                        torch.cuda.synchronize(self.device)
-                    self._destroy_program(self._programs.pop(old))
-            else:
-                self._rec = _Program()
+            self._rec = prog   # None (first sighting: just run) or a new program (second: record)
         self._x0_handover(pl, "eager")
         try:
             if pre is not None:
@@ -1678,7 +1499,7 @@ class HipEncoderEngine:
         finally:
             rec, self._rec = self._rec, None
         if rec is not None:
-            self._programs[key] = self._finish_program(rec)
+            self._programs.finish(key, rec)
 
     def _x0_handover(self, pl: dict, who):
         """x0_free_ev is a torch event in an eager step and the program's own event in a replayed one: when the step before this one
@@ -1704,7 +1525,7 @@ class HipEncoderEngine:
                          None if raw is None else ("raw", raw, downsampling, whitening), input_ready=input_ready)
         return pl
 
-    def _replay_step(self, prog: _Program, pl: dict, wpt: int, target, drop_masks, apply_update: bool, pre):
+    def _replay_step(self, prog: Program, pl: dict, wpt: int, target, drop_masks, apply_update: bool, pre):
         dyn = {"y": target.data_ptr(), "loss_scale": float(self.loss_scale)}
         keep = [target]
         if pre is not None:
@@ -1733,7 +1554,7 @@ class HipEncoderEngine:
         if apply_update:
             t, lr_t = self._adam_scalars()
             dyn["lr_t"], dyn["gpre"] = float(lr_t), float(self.grad_prescale) / float(self.loss_scale)
-        self._run_program(prog, dyn)
+        prog.run(self.lib, dyn, self.native_replay)
         if apply_update:
             self._wfp_stale = True   # what refresh_weights() / _pack_weights() note on the eager path: the inference copies are old
             self.iterations = t
