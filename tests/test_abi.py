@@ -91,15 +91,16 @@ def test_engine_refuses_to_run_without_gpu():
 
 
 def test_tuning_table_is_small_and_rejects_unknown_keys():
-    """vm_set_tuning only selects among kernels that compute the same result (six keys, include/voicemap_hip.h); the experiment
-    switches of rounds 1-2 (ablations, ring / phase / skew variants) are gone from the shipped library.  Host-only call: no GPU."""
+    """vm_set_tuning only selects among kernels that compute the same result (thirteen keys, include/voicemap_hip.h; ten of them set
+    here); the experiment switches of rounds 1-2 (ablations, ring / phase / skew variants) and round 6's 256 x 32 wave tile of
+    conv_nt3_kernel are gone from the shipped library.  Host-only call: no GPU."""
     from voicemap_amd import _lib
     lib = _lib.lib()
-    for key, good, bad in ((b"nt_n2", 3, 4), (b"nt_glds", 1, 2), (b"tn_x", 1, 2), (b"tn_tile", 256, 64), (b"f1_blocks", 1024, 0),
-                           (b"f1_fwd_blocks", 1024, -1), (b"apply_order", 2, 3), (b"f1_products", 2, 0)):   # (good = the defaults)
+    for key, good, bad in ((b"nt_n2", 3, 4), (b"nt3", 3, 4), (b"nt3_lean", 3, 4), (b"nt_glds", 1, 2), (b"tn_x", 1, 2),
+                           (b"tn_tile", 256, 64), (b"f1_blocks", 1024, 0), (b"f1_fwd_blocks", 1024, -1), (b"apply_order", 2, 3), (b"f1_products", 2, 0)):   # (good = the defaults)
         assert lib.cdll.vm_set_tuning(key, bad) != 0, key
         assert lib.cdll.vm_set_tuning(key, good) == 0, key
-    for gone in (b"nt_ablate", b"nt_ring", b"nt_p8", b"nt_w4", b"nt_n2r", b"gemm_kb", b"no_such_knob"):
+    for gone in (b"nt_ablate", b"nt_ring", b"nt_p8", b"nt_w4", b"nt_n2r", b"gemm_kb", b"nt3_wide", b"no_such_knob"):
         assert lib.cdll.vm_set_tuning(gone, 1) != 0, gone
     assert lib.cdll.vm_set_tuning(None, 1) != 0
 

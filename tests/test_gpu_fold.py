@@ -87,7 +87,7 @@ def _conv_same(y, w):
 
 @pytest.mark.parametrize("dtype", DT16)
 @pytest.mark.parametrize("n,Lw,cin,cout,with_e", [(3, 508, 128, 256, True), (2, 254, 256, 128, False), (2, 1016, 64, 128, True),
-                                                  (1, 300, 32, 128, True)])
+                                                  (1, 300, 32, 128, True), (2, 254, 384, 128, True), (1, 254, 512, 256, False)])
 def test_conv_fwd_fold_matches_definition(dtype, n, Lw, cin, cout, with_e):
     vm, tdt = DTYPES[dtype]
     if not L().query("vm_conv_fwd_fold_supported", n, Lw, cin, cout, vm, int(with_e)):
@@ -110,15 +110,21 @@ def test_conv_fwd_fold_matches_definition(dtype, n, Lw, cin, cout, with_e):
     if L().query("vm_pack_nt_weights_supported", cout, cin, vm):
         # round 4: the same launch with the weights in fragment order (conv_nt3_kernel where the channel count has a written-out K
         # loop: L2 -> registers, no weight stage in LDS, one barrier per channel chunk) -- the same products in the same order, so
-        # every output is bit-identical to the staged kernel's
+        # every output is bit-identical to the staged kernel's, with the lean prologue (the default) and with the first form
+        # (c_in = 128, 256, 384, 512: every written-out K loop)
         wfp = torch.empty_like(wf)
         L().call("vm_pack_nt_weights", p(wf), towers, cout, cin, vm, p(wfp), stream())
-        z3, ssum3, ssq3 = torch.empty_like(z), torch.empty_like(ssum), torch.empty_like(ssq)
-        eo3 = torch.full_like(eo, 7.0) if with_e else None
-        L().call("vm_conv_fwd_fold", p(padded(e, tdt)), p(wf), p(dev(bias)), p(hb), p(dev(gamma)) if with_e else None, n, wpt, Lw, cin, cout,
-                 vm, p(z3), p(ssum3), p(ssq3), p(eo3), None, p(wfp), None, stream())
-        torch.cuda.synchronize()
-        assert torch.equal(z3, z) and torch.equal(ssum3, ssum) and torch.equal(ssq3, ssq) and (not with_e or torch.equal(eo3, eo))
+        try:
+            for lean in (3, 0):
+                L().call("vm_set_tuning", b"nt3_lean", lean)
+                z3, ssum3, ssq3 = torch.empty_like(z), torch.empty_like(ssum), torch.empty_like(ssq)
+                eo3 = torch.full_like(eo, 7.0) if with_e else None
+                L().call("vm_conv_fwd_fold", p(padded(e, tdt)), p(wf), p(dev(bias)), p(hb), p(dev(gamma)) if with_e else None, n, wpt, Lw,
+                         cin, cout, vm, p(z3), p(ssum3), p(ssq3), p(eo3), None, p(wfp), None, stream())
+                torch.cuda.synchronize()
+                assert torch.equal(z3, z) and torch.equal(ssum3, ssum) and torch.equal(ssq3, ssq) and (not with_e or torch.equal(eo3, eo)), lean
+        finally:
+            L().call("vm_set_tuning", b"nt3_lean", 3)
     # the definition, with the weights the kernel multiplies by (W * scale rounded to the storage type) and exact shift terms
     zr = np.empty((n, Lw, cout))
     for t in range(towers):

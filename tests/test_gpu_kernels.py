@@ -48,7 +48,7 @@ def _conv_ref(x, w, b):
     return O.conv1d_same_relu(x, w, b)
 
 
-GEMM_DEFAULTS = {"nt_n2": 3, "nt_glds": 1, "tn_x": 1, "tn_tile": 256, "tn9": 1, "tn9_stages": 1}   # the library's defaults (conv_gemm.hip / conv_wgrad.hip)
+GEMM_DEFAULTS = {"nt_n2": 3, "nt3": 3, "nt3_lean": 3, "nt_glds": 1, "tn_x": 1, "tn_tile": 256, "tn9": 1, "tn9_stages": 1}   # the library's defaults (conv_gemm.hip / conv_wgrad.hip)
 
 
 @pytest.fixture
@@ -917,13 +917,18 @@ def test_crop_decimate_whiten_vs_oracle(i16):
 
 
 # ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("gemm_kernels", [pytest.param({}, id=pytest.HIDDEN_PARAM), pytest.param({"nt3_lean": 0}, id="nt3-first-prologue")],
+                         indirect=True)
 @pytest.mark.parametrize("n,l,cin,cout,padded_a", [(3, 254, 128, 256, True), (2, 255, 128, 64, False), (2, 1000, 256, 384, True),
-                                                   (5, 509, 384, 512, True), (2, 2000, 128, 256, False), (1, 130, 128, 32, True)])
+                                                   (5, 509, 384, 512, True), (2, 2000, 128, 256, False), (1, 130, 128, 32, True),
+                                                   (2, 255, 128, 128, True), (1, 130, 256, 128, False)])
 @pytest.mark.parametrize("dt16", ["bf16", "f16"])
-def test_conv_dgrad_bnred(n, l, cin, cout, padded_a, dt16):
+def test_conv_dgrad_bnred(n, l, cin, cout, padded_a, dt16, gemm_kernels):
     """vm_conv_dgrad_bnred: dx bit-identical to vm_conv_dgrad, and the partial rows sum to sum_t dx and sum_t dx * A taken over
     the stored (bf16) dx in float64.  Lengths either side of the 254-row tile edge, several channel tiles, both layouts of A
-    with garbage in the halo rows (they must not be read into the sums)."""
+    with garbage in the halo rows (they must not be read into the sums); c_out = 128, 256, 384, 512: every written-out K loop of
+    conv_nt3_kernel (4, 8, 12, 16 chunks on the K side of a dgrad), with its lean prologue (the default) and with the first form --
+    the two differ by chunks > 1, > 2, > 3."""
     vm, tdt = DTYPES[dt16]
     if not L().query("vm_conv_dgrad_bnred_supported", n, l, cin, cout, vm):
         pytest.skip("shape not served by the 256 x 128 kernel under the current tuning")
