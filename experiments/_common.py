@@ -84,10 +84,11 @@ def device_resident(a, train):
     return ds
 
 
-def mined_batches(a, dataset, preprocessor, device, distance="euclidean"):
+def mined_batches(a, dataset, preprocessor, device, distance="euclidean", augment=None):
     """--hard-fraction: (the training batch generator over a HardPairSampler of ``dataset``, [the HardPairMiner callback]) -- the
     callback goes FIRST in the list (CSVLogger records its two fields); (None, []) when mining is off: the caller keeps the dataset's
-    own generator and nothing changes.  ``device``: the --device-data path (``dataset`` is the resident ShardedSpeechDataset)."""
+    own generator and nothing changes.  ``device``: the --device-data path (``dataset`` is the resident ShardedSpeechDataset);
+    ``augment``: the --augment policy of that path (voicemap_amd/augment.py), None = clean batches."""
     if getattr(a, "hard_fraction", 0.0) <= 0.0:
         return None, []
     from voicemap_amd.mining import HardPairMiner, HardPairSampler
@@ -95,6 +96,8 @@ def mined_batches(a, dataset, preprocessor, device, distance="euclidean"):
     sampler = HardPairSampler(dataset, None, hard_fraction=a.hard_fraction, seed=parallel.rank_world()[0])
     miner = HardPairMiner(sampler, dataset, preprocessor, every=a.mine_every, distance=distance, k_neg=a.mine_k_neg,
                           k_pos=a.mine_k_pos, semi_hard=a.semi_hard)
+    if device and augment is not None:
+        return (preprocessor(b) for b in sampler.yield_verification_batches_device(a.batchsize, augment)), [miner]
     gen = sampler.yield_verification_batches_device if device else sampler.yield_verification_batches
     return (preprocessor(b) for b in gen(a.batchsize)), [miner]
 

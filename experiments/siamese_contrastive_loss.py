@@ -3,6 +3,7 @@ experiments/siamese_contrastive_loss.py (filters 32, embedding 128, default drop
     python -m experiments.siamese_contrastive_loss [--synthetic] ..."""
 from config import PATH
 from experiments import _common as C
+from voicemap_amd.augment import add_augment_args, policy_from_args
 from voicemap_amd.keras_like import Adam, CSVLogger, ModelCheckpoint
 from voicemap_amd.models import build_siamese_net, get_baseline_convolutional_encoder
 from voicemap_amd.utils import BatchPreProcessor, NShotEvaluationCallback, contrastive_loss, preprocess_instances
@@ -10,7 +11,9 @@ from voicemap_amd.utils import BatchPreProcessor, NShotEvaluationCallback, contr
 
 def main(argv=None):
     p = C.base_parser(__doc__, batchsize=32, filters=32, embedding_dimension=128, dropout=0.05, epochs=25, pad=False)
+    add_augment_args(p)
     a = p.parse_args(argv)
+    augment = policy_from_args(a, a.downsampling)   # --augment (off by default; needs --device-data): training batches only
     C.setup()
     train, valid = C.datasets(a, pad=False)
     whiten_downsample = BatchPreProcessor("siamese", preprocess_instances(a.downsampling, whitening=True))
@@ -19,10 +22,11 @@ def main(argv=None):
     workers = a.workers
     if a.device_data:  # the windows never exist on the host: offsets into an HBM-resident int16 buffer (as in train_siamese.py)
         resident = C.device_resident(a, train)
-        train_batches = (whiten_downsample(b) for b in resident.yield_verification_batches_device(a.batchsize))
+        train_batches = (whiten_downsample(b) for b in resident.yield_verification_batches_device(a.batchsize, augment))
         workers = 0
     # --hard-fraction: part of every batch from mined pairs (off by default: the generators above, unchanged)
-    mined, mining_cbs = C.mined_batches(a, resident if a.device_data else train, whiten_downsample, device=bool(a.device_data))
+    mined, mining_cbs = C.mined_batches(a, resident if a.device_data else train, whiten_downsample, device=bool(a.device_data),
+                                        augment=augment)
     if mined is not None:
         train_batches = mined
     encoder = get_baseline_convolutional_encoder(a.filters, a.embedding_dimension, dropout=a.dropout, dtype=a.dtype)

@@ -2,6 +2,7 @@
 experiments/train_siamese.py (filters 128, embedding 64, dropout 0, batch 64, Adam(clipnorm=1), 500-step epochs with
 100 validation batches and 5-way 1-shot evaluation).     python -m experiments.train_siamese [--synthetic] ..."""
 from experiments import _common as C
+from voicemap_amd.augment import add_augment_args, policy_from_args
 from voicemap_amd.keras_like import Adam
 from voicemap_amd.models import build_siamese_net, get_baseline_convolutional_encoder, get_spectrogram_convolutional_encoder
 from voicemap_amd.utils import BatchPreProcessor, preprocess_instances
@@ -12,9 +13,13 @@ def main(argv=None):
     ap.add_argument("--frontend", default="waveform", choices=["waveform", "logmel"],
                     help="waveform: the reference's 1-D encoder on the decimated, whitened window; logmel: the log-mel + 2-D CNN variant "
                          "on the raw 16 kHz window (BASELINE.json config 4, not in the reference)")
+    add_augment_args(ap)
     a = ap.parse_args(argv)
     if a.frontend == "logmel":
         a.downsampling = 1   # the front-end works on the raw window: no decimation, no whitening
+    augment = policy_from_args(a, a.downsampling)   # --augment (off by default; needs --device-data): training batches only
+    if augment is not None and a.frontend == "logmel":
+        raise SystemExit("--augment is for the waveform front-end (the augmentation runs inside its preprocessing launch)")
     C.setup()
     train, valid = C.datasets(a, pad=a.pad)
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling, whitening=a.frontend != "logmel"))
@@ -23,10 +28,10 @@ def main(argv=None):
     workers = a.workers
     if a.device_data:  # same pairs, but the windows never exist on the host: offsets into an HBM-resident int16 buffer
         resident = C.device_resident(a, train)
-        train_batches = (pre(b) for b in resident.yield_verification_batches_device(a.batchsize))
+        train_batches = (pre(b) for b in resident.yield_verification_batches_device(a.batchsize, augment))
         workers = 0
     # --hard-fraction: part of every batch from mined pairs (off by default: the generators above, unchanged)
-    mined, mining_cbs = C.mined_batches(a, resident if a.device_data else train, pre, device=bool(a.device_data))
+    mined, mining_cbs = C.mined_batches(a, resident if a.device_data else train, pre, device=bool(a.device_data), augment=augment)
     if mined is not None:
         train_batches = mined
     build = get_spectrogram_convolutional_encoder if a.frontend == "logmel" else get_baseline_convolutional_encoder

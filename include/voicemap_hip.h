@@ -152,6 +152,28 @@ int vm_crop_decimate_whiten_varlen(const void* audio, int raw_is_i16, const int6
                                    int64_t n_windows, int64_t L0, int downsampling, int whitening, float rms, float* out, void* ws,
                                    void* stream);
 
+/* Waveform augmentation inside the crop (device-resident training only; voicemap_amd/augment.py augment_reference states it in
+ * float64).  Window n is the raw_len samples s[t] = audio[offsets[n] + t]; everything is defined at the decimated positions
+ * i = 0..L0-1 (t = i * downsampling), the only samples the network sees:
+ *   reverb  a_i = sum_{j=0}^{min(i ds, R-1)} r[j] s[i ds - j],  r = rirs[rir_id[n]] (R fp32 taps, causal, direct path at tap 0); zero
+ *           history before the crop start; rir_id[n] < 0: a_i = s[i ds].  A decimating FIR: L0 * R multiply-adds per window, fp32 VALU
+ *           with fp32 accumulation (the one fp32 part); windows without an RIR run none of it.
+ *   noise   v_i = sum_{k<K} noise[noise_offsets[n * K + k] + i ds] (K launch-wide; `noise` a resident buffer like `audio`, which it
+ *           may be);  g = sqrt(Pa / (Pv snr_lin[n])) with Pa, Pv the means of a_i^2, v_i^2;  g = 0 if K == 0, Pa == 0, Pv == 0 or
+ *           snr_lin[n] <= 0 (the host passes 10^(snr_dB / 10); no transcendental on the device).
+ *   gain    y_i = gain[n] (a_i + g v_i)
+ *   then the whitening of vm_decimate_whiten on y (per-window mean, one scale per tower, the 15 / 16 zero halo).
+ * Every sum, g and the whitening are fp64 in a fixed order: launches are bit-reproducible, and with K = 0, every rir_id < 0 (or
+ * n_rirs = 0) and gain = 1 the output is vm_crop_decimate_whiten's bit for bit.  No sample before audio[offsets[n]] or at / past
+ * audio[offsets[n] + raw_len] is read, and none off the decimated grid unless the window has an RIR.  snr_lin, gain: n_windows fp32;
+ * rir_id: n_windows int32; noise_offsets: (n_windows, K) int64 -- all on the device.  K == 0 permits noise = noise_offsets = NULL,
+ * n_rirs == 0 permits rirs = rir_id = NULL; R <= 8192.  ws: >= vm_crop_augment_workspace_bytes(n_windows, L0). */
+int64_t vm_crop_augment_workspace_bytes(int64_t n_windows, int64_t L0);
+int vm_crop_augment_decimate_whiten(const void* audio, int raw_is_i16, const int64_t* offsets, int64_t n_windows, int64_t raw_len,
+                                    int downsampling, int whitening, float rms, int64_t windows_per_tower, const void* noise,
+                                    int noise_is_i16, const int64_t* noise_offsets, int K, const float* snr_lin, const float* gain,
+                                    const float* rirs, int n_rirs, int R, const int32_t* rir_id, float* out, void* ws, void* stream);
+
 /* ---- a1 block 1: Conv1D(filters, 32, padding='same', activation='relu')  (voicemap/models.py:13-16) --
  * x: (n_windows, L + 31) fp32 from vm_decimate_whiten; w: (32, 1, F) fp32 Keras layout; bias (F).
  * z: (n_windows, L, F) `dtype`, = relu(conv + bias).  If stat_sum != NULL also writes per-(window, tile)

@@ -806,11 +806,14 @@ class HipEncoderEngine:
         pl["x0"][:, CONV1_HALO_L:CONV1_HALO_L + pl["l0"]].copy_(x)
 
     def preprocess(self, pl: dict, raw: torch.Tensor, downsampling: int, whitening: bool, windows_per_tower: int,
-                   rms: float = 0.038021, offsets: Optional[torch.Tensor] = None, raw_len: Optional[int] = None):
+                   rms: float = 0.038021, offsets: Optional[torch.Tensor] = None, raw_len: Optional[int] = None, aug: Optional[dict] = None):
         """voicemap/utils.py:22-34 + 88-101 on the GPU: raw (n_windows, raw_len) fp32 or int16 -> pl['x0'].
         With ``offsets`` (n_windows int64 on the device) ``raw`` is instead a resident 1-D buffer of decoded recordings
         (voicemap_amd/shards.py) and window n is the ``raw_len`` samples starting at raw[offsets[n]]: the crop of
-        voicemap/librispeech.py:103-137 happens on the device and the host only chooses offsets."""
+        voicemap/librispeech.py:103-137 happens on the device and the host only chooses offsets.
+        ``aug`` (with ``offsets`` only): the windows are augmented inside the crop (voicemap_amd/augment.py;
+        vm_crop_augment_decimate_whiten) -- device tensors ``snr`` / ``gain`` (n fp32), ``K`` with ``noise`` (a resident buffer) and
+        ``noff`` ((n, K) int64) or K = 0, ``rirs`` ((n_rirs, R) fp32) with ``rir_id`` (n int32) or None."""
         is16 = raw.dtype == torch.int16
         if offsets is not None:
             assert raw.dim() == 1 and raw.is_contiguous() and raw_len is not None
@@ -818,6 +821,27 @@ class HipEncoderEngine:
             assert (raw_len + downsampling - 1) // downsampling == pl["l0"]
             if not is16:
                 assert raw.dtype == torch.float32
+            if aug is not None:
+                n, K, noise, rirs = pl["n"], int(aug["K"]), aug.get("noise"), aug.get("rirs")
+                assert aug["snr"].dtype == aug["gain"].dtype == torch.float32 and aug["snr"].numel() == aug["gain"].numel() == n
+                if K:
+                    assert noise.dim() == 1 and noise.is_contiguous() and noise.is_cuda and noise.dtype in (torch.int16, torch.float32)
+                    assert aug["noff"].dtype == torch.int64 and aug["noff"].numel() == n * K
+                if rirs is not None:
+                    assert rirs.dim() == 2 and rirs.is_contiguous() and rirs.is_cuda and rirs.dtype == torch.float32
+                    assert aug["rir_id"].dtype == torch.int32 and aug["rir_id"].numel() == n
+                if "aug_ws" not in pl:
+                    pl["aug_ws"] = torch.empty(self.lib.query("vm_crop_augment_workspace_bytes", n, pl["l0"]) // 8 + 1, dtype=torch.float64,
+                                               device=self.device)
+                self._call("vm_crop_augment_decimate_whiten", self._dyn("raw", _p(raw)), int(is16), self._dyn("offsets", _p(offsets)), n, raw_len,
+                           downsampling, int(whitening), rms, windows_per_tower,
+                           self._dyn("aug_noise", _p(noise)) if K else None, int(K > 0 and noise.dtype == torch.int16),
+                           self._dyn("aug_noff", _p(aug["noff"])) if K else None, K, self._dyn("aug_snr", _p(aug["snr"])),
+                           self._dyn("aug_gain", _p(aug["gain"])), _p(rirs) if rirs is not None else None,
+                           int(rirs.shape[0]) if rirs is not None else 0, int(rirs.shape[1]) if rirs is not None else 0,
+                           self._dyn("aug_rir_id", _p(aug["rir_id"])) if rirs is not None else None, _p(pl["x0"]), _p(pl["aug_ws"]),
+                           self.stream())
+                return
             self._call("vm_crop_decimate_whiten", self._dyn("raw", _p(raw)), int(is16), self._dyn("offsets", _p(offsets)), pl["n"], raw_len, downsampling,
                        int(whitening), rms, windows_per_tower, _p(pl["x0"]), _p(pl["pre_ws"]), self.stream())
             return
@@ -1443,7 +1467,7 @@ class HipEncoderEngine:
                 self.grad_prescale, self.fused_infer_pool, self.center_blocks, self.pre_overlap, id(self.grad_sync), self.lib.tuning_epoch, id(self.side_stream), id(self.tower_stream), id(self.misc_stream))
 
     def _train_step(self, pl: dict, wpt: int, target: torch.Tensor, loss: Optional[str], drop_masks, apply_update: bool, pre,
-                    input_ready: bool = False):
+                    input_ready: bool = False, aug: Optional[dict] = None):
         """preprocess (``pre`` = None | ("raw", tensor, downsampling, whitening) | ("offsets", audio, offsets, raw_len, downsampling,
         whitening)) -> forward -> head (``loss`` None: the classifier's) -> backward -> optimizer.  The SECOND time a configuration
         is seen its enqueue sequence is recorded (program.Program), from the third on it is replayed: same launches, same arguments, same
@@ -1457,12 +1481,15 @@ class HipEncoderEngine:
             # (the offsets path never reads the audio buffer's length: its shape is not part of what a program depends on)
             sig = None if pre is None else ((pre[0], pre[1].dtype, tuple(pre[1].shape)) + tuple(pre[-2:]) if pre[0] == "raw"
                                             else (pre[0], pre[1].dtype, pre[3]) + tuple(pre[-2:]))
+            if aug is not None:   # what the augmented launch bakes into a program: K, the buffers' kinds, the RIR bank
+                sig = sig + ("aug", int(aug["K"]), aug["noise"].dtype if aug["K"] else None,
+                             None if aug.get("rirs") is None else (aug["rirs"].data_ptr(), tuple(aug["rirs"].shape)))
             masks = None if drop_masks is None else tuple(m is not None for m in drop_masks)
             key = (id(pl), wpt, loss, apply_update, self.stream(), sig, masks, bool(input_ready), self._step_flags())
             prog = self._programs.sight(key)
             if prog is not None and prog.finished:
                 self._x0_handover(pl, prog)
-                self._replay_step(prog, pl, wpt, target, drop_masks, apply_update, pre)
+                self._replay_step(prog, pl, wpt, target, drop_masks, apply_update, pre, aug)
                 return
             self._rec = prog   # None (first sighting: just run) or a new program (second: record)
         self._x0_handover(pl, "eager")
@@ -1481,7 +1508,7 @@ class HipEncoderEngine:
                     if pre[0] == "raw":
                         self.preprocess(pl, pre[1], pre[2], pre[3], wpt)
                     else:
-                        self.preprocess(pl, pre[1], pre[4], pre[5], wpt, offsets=pre[2], raw_len=pre[3])
+                        self.preprocess(pl, pre[1], pre[4], pre[5], wpt, offsets=pre[2], raw_len=pre[3], aug=aug)
                 finally:
                     if ahead:
                         pre_cm.__exit__(None, None, None)
@@ -1525,9 +1552,14 @@ class HipEncoderEngine:
                          None if raw is None else ("raw", raw, downsampling, whitening), input_ready=input_ready)
         return pl
 
-    def _replay_step(self, prog: Program, pl: dict, wpt: int, target, drop_masks, apply_update: bool, pre):
+    def _replay_step(self, prog: Program, pl: dict, wpt: int, target, drop_masks, apply_update: bool, pre, aug=None):
         dyn = {"y": target.data_ptr(), "loss_scale": float(self.loss_scale)}
         keep = [target]
+        if aug is not None:
+            for k, name in (("aug_noise", "noise"), ("aug_noff", "noff"), ("aug_snr", "snr"), ("aug_gain", "gain"), ("aug_rir_id", "rir_id")):
+                if aug.get(name) is not None:
+                    dyn[k] = aug[name].data_ptr()
+                    keep.append(aug[name])
         if pre is not None:
             raw = pre[1]
             if pre[0] == "raw":
@@ -1582,16 +1614,29 @@ class HipEncoderEngine:
 
     def siamese_train_step_from_offsets(self, audio: torch.Tensor, offsets_1, offsets_2, y,
                                         raw_len: int, loss: str = "contrastive", downsampling: int = 4, whitening: bool = True,
-                                        drop_masks="auto", apply_update: bool = True):
+                                        drop_masks="auto", apply_update: bool = True, aug=None):
         """``siamese_train_step`` fed from a device-resident recording buffer: ``audio`` 1-D int16/fp32 on the device,
         ``offsets_k`` (pairs,) int64 start samples of the windows of tower k (shards.ShardedSpeechDataset chooses them the way
         LibriSpeechDataset.__getitem__ / build_verification_batch do).  Host numpy offsets with host labels (what fit_generator
-        hands over) go up in one asynchronous copy (_stage_offsets_and_labels); tensors are taken as they are."""
+        hands over) go up in one asynchronous copy (_stage_offsets_and_labels); tensors are taken as they are.
+        ``aug``: (record of tower 1, record of tower 2) (augment.AugmentRecord, e.g. ``DeviceWindows.aug``): the windows are augmented
+        inside the crop; the per-window parameters travel in that same single copy (host offsets and labels required)."""
         host = isinstance(offsets_1, np.ndarray) and isinstance(offsets_2, np.ndarray)
         pairs = int(offsets_1.size) if host else int(offsets_1.numel())
         pl = self.plan(2 * pairs, (raw_len + downsampling - 1) // downsampling, True)
         staged = ready = False
-        if host and not torch.is_tensor(y):
+        augdev = None
+        if aug is not None:
+            a1, a2 = aug
+            if not (host and not torch.is_tensor(y)):
+                raise ValueError("augmented steps take host offsets and labels (they are uploaded together with the parameters)")
+            if not (len(a1) == len(a2) == pairs and a1.K == a2.K and a1.noise is a2.noise and a1.rirs is a2.rirs):
+                raise ValueError("the two towers' augmentation records must come from one draw (same K, noise buffer and RIR bank)")
+            if a1.downsampling != downsampling:
+                raise ValueError("the augmentation was drawn for downsampling %d, the step decimates by %d" % (a1.downsampling, downsampling))
+            offs, yd, ready, augdev = self._stage_offsets_and_labels(pl, offsets_1, offsets_2, y, pairs, aug=(a1, a2))
+            staged = True
+        elif host and not torch.is_tensor(y):
             offs, yd, ready = self._stage_offsets_and_labels(pl, offsets_1, offsets_2, y, pairs)
             staged = True
         else:
@@ -1600,12 +1645,12 @@ class HipEncoderEngine:
         if isinstance(drop_masks, str):
             drop_masks = self.make_drop_masks(2 * pairs)
         self._train_step(pl, pairs, yd, loss, drop_masks, apply_update, ("offsets", audio, offs, raw_len, downsampling, whitening),
-                         input_ready=ready)
+                         input_ready=ready, aug=augdev)
         if staged:
             self._staged_step_enqueued(pl)
         return pl
 
-    def _stage_offsets_and_labels(self, pl: dict, o1: "np.ndarray", o2: "np.ndarray", y, pairs: int):
+    def _stage_offsets_and_labels(self, pl: dict, o1: "np.ndarray", o2: "np.ndarray", y, pairs: int, aug=None):
         """Host arrays -> device buffers (2 * pairs int64 offsets, pairs fp32 labels) in ONE asynchronous copy from a ring of pinned
         staging buffers.  torch's ``.to(device)`` of a pageable array is a blocking copy that is ordered behind everything already
         enqueued on the stream: three of them per step made the host wait for the GPU to drain, then left the GPU idle while the host
@@ -1613,13 +1658,20 @@ class HipEncoderEngine:
         a ring as well (a step reads ITS slot, so the next step's copy needs no ordering against this step's kernels) and, with
         ``pre_overlap``, the copy goes to the tower stream in front of the preprocessing that runs there ahead of the main stream.
         A slot is reused after 32 steps; the step that last read it has its end-of-enqueue event waited for first (long done).
-        Returns (offsets, labels, input_ready)."""
-        st = pl.get("h2d")
+        Returns (offsets, labels, input_ready).  With ``aug`` (the two towers' augment.AugmentRecord) the per-window augmentation
+        parameters ride in the same copy -- [offsets | labels | snr_lin | gain | rir_id | noise offsets (2 pairs, K)], a ring of its own
+        per K -- and the device views come back as a fourth value (the ``aug`` of preprocess())."""
+        K = aug[0].K if aug is not None else 0
+        ring = "h2d" if aug is None else ("h2d_aug", K)
+        st = pl.get(ring)
         if st is None:
             nbytes = 2 * pairs * 8 + pairs * 4
-            st = pl["h2d"] = {"dev": [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(32)],
-                              "pin": [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(32)],
-                              "ev": [None] * 32, "k": 0}
+            if aug is not None:
+                nbytes += pairs * 4 + 3 * 2 * pairs * 4 + 2 * pairs * K * 8   # (the labels padded to 8 bytes per pair: int64 alignment)
+            st = pl[ring] = {"dev": [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(32)],
+                             "pin": [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(32)],
+                             "ev": [None] * 32, "k": 0}
+        pl["h2d_cur"] = st
         k = st["k"] % 32
         st["k"] += 1
         if st["ev"][k] is not None:
@@ -1627,7 +1679,14 @@ class HipEncoderEngine:
         buf = st["pin"][k].numpy()
         buf[:pairs * 8] = np.ascontiguousarray(o1, dtype=np.int64).reshape(-1).view(np.uint8)
         buf[pairs * 8:2 * pairs * 8] = np.ascontiguousarray(o2, dtype=np.int64).reshape(-1).view(np.uint8)
-        buf[2 * pairs * 8:] = np.ascontiguousarray(np.asarray(y, dtype=np.float32).reshape(pairs)).view(np.uint8)
+        buf[2 * pairs * 8:2 * pairs * 8 + pairs * 4] = np.ascontiguousarray(np.asarray(y, dtype=np.float32).reshape(pairs)).view(np.uint8)
+        if aug is not None:
+            b0 = 2 * pairs * 8 + 2 * pairs * 4   # past the labels and their padding
+            w = 2 * pairs * 4
+            for j, name in enumerate(("snr_lin", "gain", "rir_id")):
+                buf[b0 + j * w:b0 + (j + 1) * w] = np.concatenate([getattr(aug[0], name), getattr(aug[1], name)]).view(np.uint8)
+            if K:
+                buf[b0 + 3 * w:] = np.ascontiguousarray(np.concatenate([aug[0].noise_offsets, aug[1].noise_offsets])).reshape(-1).view(np.uint8)
         dev = st["dev"][k]
         ahead = bool(self.pre_overlap and not self.timed)
         if ahead:
@@ -1636,11 +1695,16 @@ class HipEncoderEngine:
         else:
             dev.copy_(st["pin"][k], non_blocking=True)
         st["cur"] = k
+        if aug is not None:
+            augdev = {"K": K, "noise": aug[0].noise, "rirs": aug[0].rirs,
+                      "snr": dev[b0:b0 + w].view(torch.float32), "gain": dev[b0 + w:b0 + 2 * w].view(torch.float32),
+                      "rir_id": dev[b0 + 2 * w:b0 + 3 * w].view(torch.int32), "noff": dev[b0 + 3 * w:].view(torch.int64) if K else None}
+            return dev[:2 * pairs * 8].view(torch.int64), dev[2 * pairs * 8:2 * pairs * 8 + pairs * 4].view(torch.float32), ahead, augdev
         return dev[:2 * pairs * 8].view(torch.int64), dev[2 * pairs * 8:].view(torch.float32), ahead
 
     def _staged_step_enqueued(self, pl: dict):
         """The step that reads the staging slot is enqueued: its slot may be refilled once everything enqueued so far has run."""
-        st = pl["h2d"]
+        st = pl["h2d_cur"]
         k = st["cur"]
         ev = st["ev"][k] = st["ev"][k] or torch.cuda.Event()
         ev.record()

@@ -240,7 +240,7 @@ class HardPairSampler:
         while True:
             yield self.build_verification_batch(batchsize)
 
-    def build_verification_batch_offsets(self, batchsize: int):
+    def build_verification_batch_offsets(self, batchsize: int, files: bool = False):
         ds = self.dataset
         half = batchsize // 2
         alike = self._pairs(0, half)
@@ -250,19 +250,27 @@ class HardPairSampler:
         l_d = ds.window_starts([i for i, _ in differing])
         r_d = ds.window_starts([j for _, j in differing])
         outputs = np.append(np.zeros(half), np.ones(half))[:, np.newaxis]
-        return np.concatenate([l_a, l_d]), np.concatenate([r_a, r_d]), outputs
+        out = (np.concatenate([l_a, l_d]), np.concatenate([r_a, r_d]), outputs)
+        if files:   # the file id every window was cut from (augment.AugmentPolicy keeps a window's own speaker out of its babble)
+            pairs = list(alike) + list(differing)
+            out += (np.array([i for i, _ in pairs], dtype=np.int64), np.array([j for _, j in pairs], dtype=np.int64))
+        return out
 
-    def build_verification_batch_device(self, batchsize: int):
-        from .shards import DeviceWindows
+    def build_verification_batch_device(self, batchsize: int, augment=None):
+        """``augment``: an ``augment.AugmentPolicy`` (its own random stream: the pairs and crops stay the ones drawn without it)."""
+        from .shards import DeviceWindows, augmented_pair
         ds = self.dataset
         assert getattr(ds, "device_audio", None) is not None, 'call to_device() first'
-        o1, o2, outputs = self.build_verification_batch_offsets(batchsize)
         T = ds.fragment_length
-        return [DeviceWindows(ds.device_audio, o1, T), DeviceWindows(ds.device_audio, o2, T)], outputs
+        if augment is None:
+            o1, o2, outputs = self.build_verification_batch_offsets(batchsize)
+            return [DeviceWindows(ds.device_audio, o1, T), DeviceWindows(ds.device_audio, o2, T)], outputs
+        o1, o2, outputs, f1, f2 = self.build_verification_batch_offsets(batchsize, files=True)
+        return augmented_pair(ds, augment, o1, o2, f1, f2), outputs
 
-    def yield_verification_batches_device(self, batchsize: int):
+    def yield_verification_batches_device(self, batchsize: int, augment=None):
         while True:
-            yield self.build_verification_batch_device(batchsize)
+            yield self.build_verification_batch_device(batchsize, augment)
 
 
 class HardPairMiner(Callback):

@@ -638,7 +638,11 @@ class SiameseNet(_TrainableModel):
             assert (x1.downsampling, x1.whitening) == (x2.downsampling, x2.whitening)
             r1, r2 = x1.raw, x2.raw
             if type(r1).__name__ == "DeviceWindows":  # windows that only exist as offsets into a device buffer (shards.py)
-                r1, r2 = r1.gather(), r2.gather()
+                if getattr(r1, "aug", None) is not None or getattr(r2, "aug", None) is not None:
+                    # augmented windows outside a training step: their host materialisation (shards.DeviceWindows.__array__)
+                    r1, r2 = np.asarray(r1, dtype=np.float32), np.asarray(r2, dtype=np.float32)
+                else:
+                    r1, r2 = r1.gather(), r2.gather()
             return fn(r1, r2, preprocessed=False, downsampling=x1.downsampling, whitening=x1.whitening, **kw)
         return fn(np.asarray(x1, dtype=np.float32), np.asarray(x2, dtype=np.float32), **kw)
 
@@ -651,9 +655,13 @@ class SiameseNet(_TrainableModel):
                 and x1.raw.audio is x2.raw.audio:
             # device data path: the crop happens inside the preprocessing kernel (vm_crop_decimate_whiten)
             assert (x1.downsampling, x1.whitening) == (x2.downsampling, x2.whitening)
+            a1, a2 = getattr(x1.raw, "aug", None), getattr(x2.raw, "aug", None)
+            if (a1 is None) != (a2 is None):
+                raise ValueError("one tower's windows are augmented and the other's are not")
             return eng.siamese_train_step_from_offsets(x1.raw.audio, x1.raw.offsets_host, x2.raw.offsets_host,
                                                        np.asarray(y, dtype=np.float32), x1.raw.length, loss=loss,
-                                                       downsampling=x1.downsampling, whitening=x1.whitening)
+                                                       downsampling=x1.downsampling, whitening=x1.whitening,
+                                                       aug=None if a1 is None else (a1, a2))
         return self._run(lambda a, b, **kw: eng.siamese_train_step(a, b, np.asarray(y, dtype=np.float32), loss=loss, **kw), x1, x2)
 
     def train_on_batch(self, x, y):

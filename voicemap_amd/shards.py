@@ -66,10 +66,17 @@ class DeviceWindows:
     """A batch of windows that exists only as start offsets into a device-resident recording buffer; quacks like the
     (n, T, 1) array the reference's generators yield (``shape``, ``ndim``, ``len``, ``np.asarray``) so that it flows through
     ``BatchPreProcessor`` / ``preprocess_instances`` / ``fit_generator`` unchanged.  The models crop + decimate + whiten it on
-    the GPU (``vm_crop_decimate_whiten``); ``np.asarray`` materialises the float windows on the host (tests, oracle)."""
+    the GPU (``vm_crop_decimate_whiten``); ``np.asarray`` materialises the float windows on the host (tests, oracle).
 
-    def __init__(self, audio, offsets, length: int):
+    ``aug`` (optional, ``augment.AugmentRecord``): the windows are augmented inside the crop (``vm_crop_augment_decimate_whiten``).
+    The augmentation is defined at the decimated positions only (augment.py), so ``np.asarray`` of an augmented batch returns the
+    clean crop with every ``aug.downsampling``-th sample replaced by the mixture y of ``augment_reference`` -- decimating and
+    whitening that on the host (``LazyWindows``) gives what the device computes; the samples in between are never seen by the
+    network and stay clean.  ``gather`` (the clean windows on the device) refuses an augmented batch."""
+
+    def __init__(self, audio, offsets, length: int, aug=None):
         self.audio = audio
+        self.aug = aug
         # the offsets stay on the HOST until somebody needs them on the device: the training step uploads both towers' offsets and
         # the labels in ONE asynchronous copy from pinned memory (engine.siamese_train_step_from_offsets); a torch ``.to(device)`` of
         # a pageable array here would block the host until the device has drained its queue -- once per tower per step
@@ -97,14 +104,34 @@ class DeviceWindows:
     def gather(self):
         """(n, T) windows on the device, in the buffer's dtype."""
         import torch
+        if self.aug is not None:
+            raise TypeError("augmented windows have no device-side gather: train on them (siamese_train_step_from_offsets) or "
+                            "materialise them on the host with np.asarray")
         idx = self.offsets[:, None] + torch.arange(self.length, device=self.audio.device)[None, :]
         return self.audio[idx]
 
     def __array__(self, dtype=None, copy=None):
         import torch
-        w = self.gather()
+        idx = self.offsets[:, None] + torch.arange(self.length, device=self.audio.device)[None, :]
+        w = self.audio[idx]
         x = (w.to(torch.float64) / INT16_SCALE if w.dtype == torch.int16 else w.to(torch.float64)).cpu().numpy()[:, :, None]
+        if self.aug is not None:
+            from .augment import augment_reference
+            a = self.aug
+            host = lambda t: t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)  # noqa: E731
+            d = augment_reference(host(self.audio), self.offsets_host, self.length, a.downsampling,
+                                  noise=host(a.noise) if a.K else None, noise_offsets=a.noise_offsets if a.K else None,
+                                  snr_lin=a.snr_lin, gain=a.gain, rirs=a.rirs_host, rir_id=a.rir_id, whitening=False, details=True)
+            x[:, ::a.downsampling, 0] = d["y"]
         return x.astype(dtype) if dtype is not None else x
+
+
+def augmented_pair(dataset, policy, o1, o2, f1, f2):
+    """[DeviceWindows, DeviceWindows] of the two towers with ONE draw of ``policy`` over both (the launch has one babble count K)."""
+    T = dataset.fragment_length
+    rec = policy.draw(dataset, np.concatenate([f1, f2]), T)
+    h = len(o1)
+    return [DeviceWindows(dataset.device_audio, o1, T, aug=rec.rows(0, h)), DeviceWindows(dataset.device_audio, o2, T, aug=rec.rows(h, 2 * h))]
 
 
 class ShardedSpeechDataset(LibriSpeechDataset):
@@ -184,9 +211,10 @@ class ShardedSpeechDataset(LibriSpeechDataset):
             start = np.zeros(len(indices), dtype=np.int64)
         return self.global_offset[indices] + start
 
-    def build_verification_batch_offsets(self, batchsize):
+    def build_verification_batch_offsets(self, batchsize, files=False):
         """(offsets_1, offsets_2, outputs): the pairs of ``build_verification_batch`` (batchsize//2 same-speaker pairs, then
-        batchsize//2 different-speaker pairs; outputs (batchsize, 1) zeros then ones) as start offsets into the device buffer."""
+        batchsize//2 different-speaker pairs; outputs (batchsize, 1) zeros then ones) as start offsets into the device buffer.
+        ``files=True`` appends (files_1, files_2), the file id every window was cut from (same draws)."""
         half = batchsize // 2
         # same np.random consumption order as build_verification_batch (reference librispeech.py:179-189)
         alike = self.get_alike_pairs(half)
@@ -196,18 +224,27 @@ class ShardedSpeechDataset(LibriSpeechDataset):
         l_d = self.window_starts([i for i, _ in differing])
         r_d = self.window_starts([j for _, j in differing])
         outputs = np.append(np.zeros(half), np.ones(half))[:, np.newaxis]
-        return np.concatenate([l_a, l_d]), np.concatenate([r_a, r_d]), outputs
+        out = (np.concatenate([l_a, l_d]), np.concatenate([r_a, r_d]), outputs)
+        if files:
+            pairs = list(alike) + list(differing)
+            out += (np.array([i for i, _ in pairs], dtype=np.int64), np.array([j for _, j in pairs], dtype=np.int64))
+        return out
 
-    def build_verification_batch_device(self, batchsize):
-        """``build_verification_batch`` with the two inputs as ``DeviceWindows`` (needs ``to_device()`` first)."""
+    def build_verification_batch_device(self, batchsize, augment=None):
+        """``build_verification_batch`` with the two inputs as ``DeviceWindows`` (needs ``to_device()`` first).  ``augment`` (an
+        ``augment.AugmentPolicy``): the windows carry the policy's draws for this batch (``DeviceWindows.aug``); the policy draws from
+        its own random stream, so the pairs and crops are the ones drawn without it."""
         assert self.device_audio is not None, 'call to_device() first'
-        o1, o2, outputs = self.build_verification_batch_offsets(batchsize)
         T = self.fragment_length
-        return [DeviceWindows(self.device_audio, o1, T), DeviceWindows(self.device_audio, o2, T)], outputs
+        if augment is None:
+            o1, o2, outputs = self.build_verification_batch_offsets(batchsize)
+            return [DeviceWindows(self.device_audio, o1, T), DeviceWindows(self.device_audio, o2, T)], outputs
+        o1, o2, outputs, f1, f2 = self.build_verification_batch_offsets(batchsize, files=True)
+        return augmented_pair(self, augment, o1, o2, f1, f2), outputs
 
-    def yield_verification_batches_device(self, batchsize):
+    def yield_verification_batches_device(self, batchsize, augment=None):
         while True:
-            yield self.build_verification_batch_device(batchsize)
+            yield self.build_verification_batch_device(batchsize, augment)
 
     def build_n_shot_task_offsets(self, k, n=1):
         """The task of ``build_n_shot_task`` (librispeech.py:204-240 of the reference) as start offsets into the device
