@@ -15,7 +15,8 @@
  *     stream.  Process-global mutable state: (a) the kernel-selection table behind vm_set_tuning, (b) a pool of zero-initialised
  *     ticket words in device memory that the fused two-stage reductions draw from (round robin per launch; every launch leaves its
  *     words zero again) -- it makes those entry points, like the table, not thread-safe across host threads.  The table
- *     (below): every selectable kernel computes the same result (each is parity-tested against the oracle), so
+ *     (below): every selectable kernel computes the same result (each is parity-tested against the oracle, and bit-exactly on
+ *     exactly representable inputs: tests/test_gpu_conv_exact.py), so
  *     the table changes speed, never values; it is read at launch time and is not thread-safe -- set it before
  *     work is enqueued from other threads, or leave the defaults (what the drop-in surface does).
  *   - returns 0 on success, <0 on error (VM_ERR_*); vm_last_error() gives a thread-local message.
@@ -291,7 +292,7 @@ int vm_pack_nt_weights_batch(int n, const void* const* bt, const int* towers, co
 /* inference-mode forward of a whole block in one launch: Conv1D + bias + ReLU, the BatchNorm affine (scale / shift per channel from
  * vm_bn_infer_affine: (c_out) floats each) and MaxPool1D(2), models.py:22-35 with learning_phase 0.  act: padded pooled output
  * (n_windows, L/2 + 2, c_out), halo rows untouched; the conv output z is never written.  Bit-identical to vm_conv_fwd followed by
- * vm_bn_drop_pool_fwd(pool = 2, drop = NULL).  Served by the 256 x 128 input-resident kernel only (bf16, even L):
+ * vm_bn_drop_pool_fwd(pool = 2, drop = NULL).  Served by the 256 x 128 input-resident kernel only (16-bit storage, even L):
  * vm_conv_fwd_pool_supported() says whether a shape is, VM_ERR_UNSUPPORTED otherwise. */
 int vm_conv_fwd_pool_supported(int64_t n_windows, int64_t L, int c_in, int c_out, int dtype);
 int vm_conv_fwd_pool(const void* in, const void* wf, const float* bias, const float* scale, const float* shift,

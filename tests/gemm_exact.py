@@ -1,0 +1,451 @@
+"""Exactly representable inputs for the conv GEMM kernels (tests/test_gpu_conv_exact.py on the device, tests/test_gemm_exact_cpu.py on
+the host): seeded operands on a power-of-two grid, small enough that every product and every partial sum of every output is an fp32
+number.  The result then does not depend on summation order, tile shape, split-K plan, MFMA shape or the hi / lo split of VM_F32S: an
+fp32 output must equal the float64 reference bit for bit, a 16-bit output its round-to-nearest-even (csrc/common.hpp: both conversions
+are RNE, like torch.Tensor.to), and one dropped, doubled or misplaced product moves an element by at least one grid unit.  Pure
+numpy / torch: nothing here touches the HIP library or a GPU."""
+import functools
+
+import numpy as np
+import torch
+
+LIMIT = 2.0 ** 24           # integers below it, and all their partial sums, are fp32 numbers
+STORE = {"f32": torch.float32, "f32s": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}
+BITS = {"f32": 24, "f32s": 24, "bf16": 8, "f16": 11}        # significand bits
+INT_VIEW = {torch.float32: torch.int32, torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float64: torch.int64}
+REGIMES = {"f32": ("small", "wide"), "f32s": ("small", "lo-x", "lo-w"), "bf16": ("small", "wide"), "f16": ("small", "wide")}
+
+# ---- the shape tables (n, L, c_in, c_out); the first two are the lists of tests/test_gpu_kernels.py (the device file asserts it) ------
+GEMM_SHAPES = [(3, 200, 16, 24), (2, 300, 128, 256), (1, 129, 8, 136), (2, 5, 24, 8), (2, 260, 32, 64), (3, 131, 96, 32),
+               (8, 140, 64, 384), (3, 520, 256, 512), (8, 300, 64, 256), (16, 1030, 256, 256)]
+RESIDENT_SHAPES = [(2, 700, 128, 256), (3, 760, 256, 256), (2, 650, 64, 512), (1, 129, 32, 128), (2, 5, 128, 128),
+                   (3, 131, 192, 320), (1, 62, 64, 64), (4, 3000, 128, 256), (4, 1500, 256, 384), (4, 750, 384, 512)]
+FALLBACK_SHAPES = [GEMM_SHAPES[i] for i in (1, 2, 3, 5, 7, 9)]                  # test_conv_fwd_dgrad_wgrad_fallback_kernels
+WGRAD_VARIANT_SHAPES = [(2, 700, 128, 256), (2, 650, 64, 512), (2, 5, 128, 128), (3, 131, 192, 320), (1, 62, 64, 64),
+                        (4, 750, 384, 512)]                                     # test_conv_wgrad_kernel_variants
+# n_windows * ceil(L / 128) > 512 = launch_nt's grid cap: the second trip of the persistent loops; 520 % 8 == 0 takes the XCD order
+PERSISTENT_SHAPES = [(520, 100, 8, 16), (515, 100, 8, 16), (520, 100, 64, 256), (515, 100, 64, 256)]
+# (n, windows per tower, L, c_in, c_out) of test_conv_wgrad_split_granularity
+SPLIT_SHAPES = [(6, 3, 190, 64, 64), (10, 5, 64, 128, 128), (3, 3, 62, 64, 128), (14, 7, 1000, 128, 128), (2, 1, 3000, 128, 256),
+                (9, 9, 129, 192, 64), (22, 11, 318, 64, 64)]
+# the fused forwards: K side 128 / 256 / 384 / 512 (every written-out K loop of conv_nt3_kernel) and 64 / 192 (none: the packed pointer
+# must fall back); lengths either side of the 254-position tile, cfg-A's block 2 with 2 windows
+FUSED_SHAPES = [(2, 508, 128, 256), (2, 254, 256, 128), (2, 1016, 64, 128), (2, 254, 384, 128), (2, 254, 512, 256), (2, 254, 192, 128),
+                (2, 3000, 128, 256)]
+BNRED_SHAPES = [(3, 254, 128, 256, True), (2, 255, 128, 64, False), (2, 1000, 256, 384, True), (3, 509, 384, 512, True),
+                (1, 130, 256, 128, False), (2, 254, 128, 192, True)]            # (n, L, c_in, c_out, red_a padded); K side = c_out
+
+
+def conv_cases(shapes, dts=("f32", "f32s", "bf16", "f16"), regimes=None):
+    """(dt, regime, n, L, c_in, c_out) for every regime the storage type has (or those of `regimes` it has)."""
+    return [(dt, reg) + tuple(s) for s in shapes for dt in dts for reg in REGIMES[dt] if regimes is None or reg in regimes]
+
+
+def case_key(dt, regime):
+    """The operand class a case is generated for: `small` and lo operands do not depend on the storage type, `wide` ones on whether it
+    is bf16 (8 significand bits) or not."""
+    return ("bf16" if dt == "bf16" else "f16") if regime == "wide" else "f32"
+
+
+# what tests/test_gpu_conv_exact.py parametrises over (tests/test_gemm_exact_cpu.py constructs every one of them on the host first)
+DT16 = ("bf16", "f16")
+DEFAULT_CASES = conv_cases(GEMM_SHAPES + RESIDENT_SHAPES)
+FALLBACK_CASES = conv_cases(FALLBACK_SHAPES, ("f32", "bf16", "f16"))
+WGRAD_VARIANT_CASES = conv_cases(WGRAD_VARIANT_SHAPES, DT16)
+PERSISTENT_CASES = conv_cases(PERSISTENT_SHAPES, ("f32", "f32s", "f16"), ("small",))
+SPLIT_CASES = [(dt, "small", n, l, cin, cout) for n, _, l, cin, cout in SPLIT_SHAPES for dt in DT16]
+FWD_E_CASES = conv_cases(FUSED_SHAPES, DT16)
+FWD_POOL_CASES = conv_cases(FUSED_SHAPES, DT16, ("small",))
+BNRED_CASES = [(dt, reg) + tuple(s) for s in BNRED_SHAPES for dt in DT16 for reg in REGIMES[dt]]   # (.., red_a padded)
+ALL_CONV_CASES = (DEFAULT_CASES + FALLBACK_CASES + WGRAD_VARIANT_CASES + PERSISTENT_CASES + SPLIT_CASES + FWD_E_CASES + FWD_POOL_CASES +
+                  [c[:6] for c in BNRED_CASES])
+
+
+# ---- number formats ------------------------------------------------------------------------------------------------------------------
+def store(a, dt):
+    """float64 -> the storage type (RNE) -> float64."""
+    return torch.as_tensor(np.asarray(a, dtype=np.float64) + 0.0).to(STORE[dt]).to(torch.float64).numpy()     # (+ 0.0: no -0.0 in a reference)
+
+
+def exact_in(a, dt):
+    return bool(np.array_equal(store(a, dt), np.asarray(a, dtype=np.float64)))
+
+
+def rounding_census(v, dt):
+    """(fraction of v that storage rounding changes, number of exact ties) from the reference alone."""
+    v = np.asarray(v, dtype=np.float64)
+    st = store(v, dt)
+    _, e = np.frexp(v)                                          # |v| = m * 2^e, m in [0.5, 1): spacing 2^(e - bits)
+    half = np.ldexp(0.5, e - BITS[dt])
+    changed = st != v
+    return float(changed.mean()), int((changed & (np.abs(st - v) == half)).sum())
+
+
+def bf16_halves(a):
+    """hi = bf16(x), lo = bf16(x - hi): the operand split of VM_F32S (csrc/conv_common.hpp split_f32x4)."""
+    t = torch.as_tensor(np.asarray(a, dtype=np.float64)).to(torch.float32)
+    hi = t.to(torch.bfloat16).to(torch.float32)
+    lo = (t - hi).to(torch.bfloat16).to(torch.float32)
+    return hi.to(torch.float64).numpy(), lo.to(torch.float64).numpy()
+
+
+def require_exact_sums(abs_sum, grid, what):
+    """THE precondition: terms that are multiples of `grid` whose absolute values sum to less than 2^24 grid units have every partial
+    sum, in any order, in fp32.  Computed from the inputs and the reference only, never from a kernel's output."""
+    m = float(np.max(abs_sum)) / grid
+    assert m < LIMIT, "%s: sum |term| = %.3g grid units >= 2^24" % (what, m)
+    return m
+
+
+def sums_exact(abs_sum, grid):
+    return float(np.max(abs_sum)) / grid < LIMIT
+
+
+# ---- float64 references: plain matmuls ---------------------------------------------------------------------------------------------------
+def pad1(a):
+    n, l, c = a.shape
+    out = np.zeros((n, l + 2, c))
+    out[:, 1:l + 1] = a
+    return out
+
+
+def conv_same(x, w):
+    """x (n, L, c_in), w (3, c_in, c_out) -> (n, L, c_out): Conv1D(3, padding='same'), out[t] = sum_k x[t + k - 1] @ w[k]."""
+    n, l, _ = x.shape
+    xp = pad1(x)
+    return sum(xp[:, k:k + l].reshape(n * l, -1) @ w[k] for k in range(3)).reshape(n, l, -1)
+
+
+def conv_dgrad(du, w):
+    """dx[t] = sum_k du[t + 1 - k] @ w[k]^T."""
+    n, l, _ = du.shape
+    dp = pad1(du)
+    return sum(dp[:, 2 - k:2 - k + l].reshape(n * l, -1) @ w[k].T for k in range(3)).reshape(n, l, -1)
+
+
+def conv_wgrad(x, du):
+    """dW[k] = sum_{n, t} x[t + k - 1]^T du[t]."""
+    n, l, _ = x.shape
+    xp = pad1(x)
+    return np.stack([xp[:, k:k + l].reshape(n * l, -1).T @ du.reshape(n * l, -1) for k in range(3)])
+
+
+def pair_extreme(z, gamma):
+    """(n, L, c) -> (n, L // 2, c): the pair maximum where gamma >= 0, else the pair minimum (what MaxPool1D(2) of the BatchNorm output
+    selects); `second`: the extreme is the pair's second element (ties: the first)."""
+    n, l, c = z.shape
+    pr = z[:, :l // 2 * 2].reshape(n, l // 2, 2, c)
+    pos = (np.asarray(gamma) >= 0)[None, None, :]
+    second = np.where(pos, pr[:, :, 1] > pr[:, :, 0], pr[:, :, 1] < pr[:, :, 0])
+    return np.where(second, pr[:, :, 1], pr[:, :, 0]), np.where(second, pr[:, :, 0], pr[:, :, 1]), second
+
+
+# ---- input generators ------------------------------------------------------------------------------------------------------------------
+def _ints(r, shape, amp, p_zero=0.0):
+    v = r.integers(-amp, amp + 1, shape).astype(np.float64)
+    if p_zero:
+        v *= r.random(shape) >= p_zero
+    return v
+
+
+def _var(a):
+    return a * (a + 1) / 3.0            # of a uniform integer in [-a, a]
+
+
+def _wide_amplitudes(dt, cin, cout):
+    """Uniform integer ranges for x, w, du whose forward / dgrad outputs have a standard deviation of about 300 (bf16: integers past 256
+    are rounded) or 2400 (f16: past 2048; fp32 storage takes the same operands)."""
+    target = 300.0 ** 2 if dt == "bf16" else 2400.0 ** 2
+    a = 1
+    while _var(-(-3 * a // 2)) * _var(a) * 3 * cin < target:
+        a += 1
+    ax, aw, ad = -(-3 * a // 2), a, 1
+    while _var(ad) * _var(aw) * 3 * cout < target:
+        ad += 1
+    return ax, aw, ad
+
+
+def _lo_operand(r, shape):
+    """a + b * 2^-9, a in {-2, -1, 1, 2} or the element is 0, |b| <= 3: 10 .. 11 significant bits, so the bf16 `lo` half carries b."""
+    a = r.choice([-2.0, -1.0, 1.0, 2.0], shape)
+    b = r.integers(-3, 4, shape).astype(np.float64)
+    v = (a + b * 2.0 ** -9) * (r.random(shape) < 0.5)
+    hi, lo = bf16_halves(v)
+    assert np.array_equal(hi + lo, v) and (lo != 0).mean() > 0.25 and exact_in(v, "f32")
+    return v
+
+
+class ConvCase:
+    """Operands and float64 references of one (shape, regime): x (n, L, c_in), w (3, c_in, c_out), b (c_out), du_d / du_w (n, L, c_out:
+    the output gradient the dgrad / the wgrad takes -- the same tensor except in the lo regimes, where each of the four cross products
+    a_hi * b_lo gets an operand pair of its own), z = relu(conv + b), dx, gw; `grid`: the unit every product is a multiple of."""
+
+    def __init__(self, shape, regime, dt):
+        n, l, cin, cout = shape
+        self.shape, self.regime = shape, regime
+        r = np.random.default_rng([n, l, cin, cout, sum(map(ord, regime))])
+        self.grid = 1.0
+        if regime == "small":
+            x, w = _ints(r, (n, l, cin), 1, 0.25), _ints(r, (3, cin, cout), 1, 0.25)       # about half zeros each
+            du = _ints(r, (n, l, cout), 1, 0.25)
+            dud, duw = du, du
+        elif regime == "wide":
+            ax, aw, ad = _wide_amplitudes(dt, cin, cout)
+            x, w, du = _ints(r, (n, l, cin), ax), _ints(r, (3, cin, cout), aw), _ints(r, (n, l, cout), ad)
+            dud, duw = du, du
+        elif regime in ("lo-x", "lo-w"):
+            self.grid = 2.0 ** -9
+            x, w, du = _ints(r, (n, l, cin), 1, 0.25), _ints(r, (3, cin, cout), 1, 0.25), _ints(r, (n, l, cout), 1, 0.25)
+            dud, duw = du, du
+            if regime == "lo-x":        # forward x_lo * w_hi, wgrad x_lo * du_hi, dgrad du_lo * w_hi
+                x, dud = _lo_operand(r, x.shape), _lo_operand(r, du.shape)
+            else:                       # forward x_hi * w_lo, dgrad du_hi * w_lo, wgrad x_hi * du_lo
+                w, duw = _lo_operand(r, w.shape), _lo_operand(r, du.shape)
+            for narrow in ((w, duw) if regime == "lo-x" else (x, dud)):
+                assert not bf16_halves(narrow)[1].any()                                     # at most 8 bits: lo == 0, so lo * lo == 0
+        else:
+            raise ValueError(regime)
+        b = _ints(r, (cout,), 3)
+        self.x, self.w, self.b, self.du_d, self.du_w = x, w, b, dud, duw
+        # the precondition, per output element: sum |product| (+ |bias|) in grid units; VM_F32S issues the hi and lo parts of an operand
+        # as separate products, so its wide operand enters as |hi| + |lo|
+        a = lambda v: np.add(*map(np.abs, bf16_halves(v))) if regime in ("lo-x", "lo-w") else np.abs(v)
+        self.head_fwd = require_exact_sums(conv_same(a(x), a(w)) + np.abs(b), self.grid, "forward")
+        self.head_dgrad = require_exact_sums(conv_dgrad(a(dud), a(w)), self.grid, "dgrad")
+        self.head_wgrad = require_exact_sums(conv_wgrad(a(x), a(duw)), self.grid, "wgrad")
+        self.z = np.maximum(conv_same(x, w) + b, 0.0)
+        self.dx = conv_dgrad(dud, w)
+        self.gw = conv_wgrad(x, duw)
+        for dt_ in (("f32", "f32s", "bf16", "f16") if regime == "small" else (dt,)):
+            assert all(exact_in(v, dt_) for v in (x, w, dud, duw)), "operands must be exact in %s" % dt_
+        if regime == "small":           # no storage rounding in any type: |values| <= 256
+            assert max(self.z.max(), np.abs(self.dx).max()) <= 256 and exact_in(self.z, "bf16") and exact_in(self.dx, "bf16")
+        if regime == "wide" and dt in ("bf16", "f16"):
+            for name, v in (("z", self.z), ("dx", self.dx)):
+                # at least 0.5 % of the outputs rounded and 100 exact ties; a tensor too small to hold 100 (about one output in ten
+                # is a tie at these amplitudes: the first rounded binade has a spacing of 2) owes one per 40 elements instead
+                frac, ties = rounding_census(v, dt)
+                assert frac >= 0.005 and ties >= min(100, v.size // 40) and np.abs(v).max() < 60000, (name, frac, ties, np.abs(v).max())
+
+    def forward(self, dt):
+        """z as stored in `dt`, the BatchNorm statistics of the stored values (n, c_out) and whether their sums meet the precondition
+        over the whole window (always in the `small` regime)."""
+        z = store(self.z, dt)
+        g = self.grid
+        ok_sum, ok_sq = sums_exact(z.sum(1), g), sums_exact((z * z).sum(1), g * g)
+        assert ok_sum and (ok_sq or self.regime != "small")     # the sum in every regime, the sum of squares at least in `small`
+        return z, z.sum(1), (z * z).sum(1), ok_sq
+
+
+@functools.lru_cache(maxsize=6)
+def _conv_case(shape, regime, klass):
+    return ConvCase(shape, regime, klass)
+
+
+def conv_case(shape, regime, dt):
+    """Cached per operand class (case_key)."""
+    return _conv_case(tuple(shape), regime, case_key(dt, regime))
+
+
+# ---- the folded-BatchNorm forms ----------------------------------------------------------------------------------------------------------
+def signs(c, seed):
+    """BatchNorm gammas of both signs, one of them zero (gamma >= 0 selects the maximum)."""
+    g = np.random.default_rng(seed).choice([-1.5, -1.0, 1.0, 2.0], c)
+    g[5 % c] = 0.0
+    return g
+
+
+def _affine(r, towers, c, scales=(0.5, 1.0, 2.0)):
+    """Per-tower BatchNorm affines that keep every product on a power-of-two grid: scale in +-{0.5, 1, 2}, integer shift."""
+    return r.choice(scales, (towers, c)) * r.choice([-1.0, 1.0], (towers, c)), _ints(r, (towers, c), 2)
+
+
+class FoldFactors:
+    """vm_conv_wgrad_fold on (x, du) of a ConvCase: dW[k][ci][co] = sum_t scale_t[ci] * G_t[k][ci][co] + shift_t[ci] * dsum[t][k][co], G_t the
+    plain weight gradient over tower t's windows, dsum[t][k] = the sum of du over the positions whose tap k lies inside the window."""
+
+    def __init__(self, shape, x, du):
+        n, wpt, l, cin, cout = shape
+        towers = n // wpt
+        r = np.random.default_rng([n, wpt, l, cin, cout])
+        self.scale, self.shift = _affine(r, towers, cin)
+        dut = du.reshape(towers, wpt, l, cout)
+        cs = dut.sum((1, 2))
+        self.dsum = np.stack([cs - dut[:, :, 0].sum(1), cs, cs - dut[:, :, -1].sum(1)], 1)
+        acs = np.abs(dut).sum((1, 2))
+        self.gw, head = 0.0, 0.0
+        for t in range(towers):
+            sl = slice(t * wpt, (t + 1) * wpt)
+            s, h = self.scale[t][None, :, None], self.shift[t][None, :, None]
+            self.gw = self.gw + s * conv_wgrad(x[sl], du[sl]) + h * self.dsum[t][:, None, :]
+            head = head + np.abs(s) * conv_wgrad(np.abs(x[sl]), np.abs(du[sl])) + np.abs(h) * acs[t][None, None, :]
+        require_exact_sums(acs, 1.0, "dsum")
+        require_exact_sums(head, 0.5, "folded wgrad")
+
+
+class FoldCase:
+    """vm_fold_bn_weights + vm_conv_fwd_fold: e (n, L, c_in) >= 0 (a pool extreme of a ReLU output), two towers with their own affines,
+    the layer's input y = scale_t * e + shift_t inside the window and 0 in the SAME padding: z = relu(conv(y) + b).  wf (towers, c_out, 3,
+    c_in) = W * scale, hb (towers, 3, c_out) = sum_ci W * shift, ctr (towers, c_out) = max(b + hb[0] + hb[1] + hb[2], 0)."""
+
+    def __init__(self, shape, dt):
+        n, l, cin, cout = shape
+        towers, wpt = 2, n // 2
+        r = np.random.default_rng([n, l, cin, cout, 7])
+        self.e = r.integers(0, 3, (n, l, cin)).astype(np.float64) * (r.random((n, l, cin)) < 0.5)
+        self.w, self.b = _ints(r, (3, cin, cout), 1, 0.25), _ints(r, (cout,), 3)
+        # (scales +-{1, 2}: with halves z^2 sits on a grid of 1/4 and the sum of squares of a 512-channel window passes 2^24 units)
+        self.scale, self.shift = _affine(r, towers, cin, (1.0, 2.0))
+        self.gamma = signs(cout, l + cout)
+        self.wf = np.stack([(self.w * self.scale[t][None, :, None]).transpose(2, 0, 1) for t in range(towers)])
+        self.hb = np.einsum("kio,ti->tko", self.w, self.shift)
+        self.ctr = np.maximum(self.b + self.hb.sum(1), 0.0)
+        z, head = np.empty((n, l, cout)), np.empty((n, l, cout))
+        for t in range(towers):
+            sl = slice(t * wpt, (t + 1) * wpt)
+            z[sl] = conv_same(self.e[sl] * self.scale[t] + self.shift[t], self.w) + self.b
+            head[sl] = conv_same(self.e[sl], np.abs(self.w) * np.abs(self.scale[t])[None, :, None]) + (
+                np.abs(self.hb[t]).sum(0) + np.abs(self.b) + self.ctr[t])
+        require_exact_sums(head, 1.0, "folded forward")
+        require_exact_sums(np.abs(self.w).sum(1) * np.abs(self.shift).max(), 1.0, "hb")
+        self.z = np.maximum(z, 0.0)
+        self.z_st = store(self.z, dt)
+        assert exact_in(self.wf, dt) and exact_in(self.ctr, dt) and exact_in(self.e, dt)
+        cw = np.repeat(self.ctr, wpt, axis=0)[:, None, :]
+        for tile in ((self.z_st, self.z - cw) if dt == "f16" else (self.z_st,)):      # f16: also the centred tile t = relu(z) - ctr
+            assert dt != "f16" or exact_in(tile, dt)                                     # (11 bits: no rounding on this grid below 1024)
+            require_exact_sums(np.abs(tile).sum(1), 1.0, "statistics: sum")
+            require_exact_sums((tile * tile).sum(1), 1.0, "statistics: sum of squares")
+
+
+@functools.lru_cache(maxsize=2)
+def fold_case(shape, dt):
+    return FoldCase(tuple(shape), dt)
+
+
+# ---- block 1: Conv1D(F, 32) on the waveform ------------------------------------------------------------------------------------------------
+CONV1_SHAPES = [(3, 700, 16), (2, 256, 128), (1, 37, 8)]                              # (n, L, F) of test_conv1_fwd
+CONV1_WGRAD_SHAPE = (3, 1500, 24)                                                     # of test_conv1_wgrad
+CONV1_FUSED_SHAPES = [(4, 700, 16), (2, 1200, 128), (2, 532, 40), (2, 300, 160)]      # ragged chunks, F tails (16, 40, 160), F > 128
+
+
+def pad_wave(x):
+    """(n, L) -> (n, L + 31): 15 zeros before, 16 after (the SAME padding of a 32-tap filter)."""
+    out = np.zeros((x.shape[0], x.shape[1] + 31))
+    out[:, 15:15 + x.shape[1]] = x
+    return out
+
+
+def conv32(x, w):
+    """x (n, L), w (32, 1, F) -> (n, L, F): out[t] = sum_k xp[t + k] * w[k]."""
+    return np.lib.stride_tricks.sliding_window_view(pad_wave(x), 32, axis=1) @ w[:, 0, :]
+
+
+def pool_extreme(z, gamma, pool):
+    n, l, c = z.shape
+    pr = z[:, :l // pool * pool].reshape(n, l // pool, pool, c)
+    return np.where((np.asarray(gamma) >= 0)[None, None, :], pr.max(2), pr.min(2))
+
+
+class Conv1Case:
+    """x (n, L) waveform, w (32, 1, F), b (F), du (n, L, F); z = relu(conv + b) UNROUNDED, gw = the filter gradient.  Regimes: small,
+    wide (as ConvCase, K = 32), lo-w: filters a + b * 2^-12, exact only as hi + lo halves (f16) or hi + lo bf16s, and lo-x: a waveform
+    a + b * 2^-9 whose bf16 lo half is non-zero (the x_lo * w_hi product of bf16 storage and of f1_products = 3) and which a half holds."""
+
+    def __init__(self, shape, regime, dt):
+        n, l, f = shape
+        self.regime = regime
+        r = np.random.default_rng([n, l, f, sum(map(ord, regime))])
+        self.grid = 1.0
+        if regime == "wide":
+            target, a = (300.0 ** 2 if dt == "bf16" else 2400.0 ** 2), 1
+            while _var(-(-3 * a // 2)) * _var(a) * 32 < target:
+                a += 1
+            x, w = _ints(r, (n, l), -(-3 * a // 2)), _ints(r, (32, 1, f), a)
+        else:
+            x, w = _ints(r, (n, l), 1, 0.25), _ints(r, (32, 1, f), 1, 0.25)
+        if regime == "lo-w":
+            self.grid = 2.0 ** -12
+            w = r.choice([-2.0, -1.0, 1.0, 2.0], w.shape) + r.integers(-3, 4, w.shape) * 2.0 ** -12
+            wh = store(w, "f16")
+            assert not exact_in(w, "f16") and exact_in(w - wh, "f16") and np.array_equal(np.add(*bf16_halves(w)), w)
+        if regime == "lo-x":
+            self.grid = 2.0 ** -9
+            x = _lo_operand(r, x.shape)
+            assert exact_in(x, "f16")
+        du = _ints(r, (n, l, f), 1, 0.25)
+        b = _ints(r, (f,), 3)
+        self.x, self.w, self.b, self.du = x, w, b, du
+        ax = np.add(*map(np.abs, bf16_halves(x)))                  # the hi and lo halves are separate products
+        require_exact_sums(conv32(ax, np.add(*map(np.abs, bf16_halves(w)))) + np.abs(b), self.grid, "conv1 forward")
+        self.z = np.maximum(conv32(x, w) + b, 0.0)
+        if regime == "lo-w":
+            self.z_hi = np.maximum(conv32(x, store(w, "f16")) + b, 0.0)     # what f1_products = 1 (x_hi * w_hi alone) computes
+        xp = pad_wave(x)
+        wg = lambda xx, dd: np.stack([np.einsum("nt,ntf->f", xx[:, k:k + l], dd) for k in range(32)])[:, None, :]
+        require_exact_sums(wg(np.abs(xp), np.abs(du)), self.grid, "conv1 wgrad")
+        self.gw = wg(xp, du)
+        assert exact_in(du, "bf16") and (regime == "lo-x" or exact_in(x, "bf16")) and (regime == "lo-w" or exact_in(w, "bf16"))
+        if regime == "lo-x":
+            self.z_xhi = np.maximum(conv32(bf16_halves(x)[0], w) + b, 0.0)     # what leaving out x_lo * w_hi would give
+        if regime == "wide" and dt in ("bf16", "f16"):
+            frac, ties = rounding_census(self.z, dt)
+            assert frac >= 0.005 and ties >= min(100, self.z.size // 40) and self.z.max() < 60000, (frac, ties)
+
+    def stats(self, z):
+        """The sums of z and z^2 per window and whether each meets the precondition: both in `small`, the sum in `wide` too."""
+        g = self.grid
+        ok_sum, ok_sq = sums_exact(z.sum(1), g), sums_exact((z * z).sum(1), g * g)
+        assert (ok_sum or self.regime in ("lo-x", "lo-w")) and (ok_sq or self.regime != "small")
+        return z.sum(1), (z * z).sum(1), ok_sum, ok_sq
+
+
+@functools.lru_cache(maxsize=4)
+def _conv1_case(shape, regime, klass):
+    return Conv1Case(shape, regime, klass)
+
+
+def conv1_case(shape, regime, dt):
+    return _conv1_case(tuple(shape), regime, case_key(dt, regime))
+
+
+# ---- the comparator ------------------------------------------------------------------------------------------------------------------
+LAYOUTS = {"nlc": ("window", "position", "channel"), "kio": ("tap", "c_in", "c_out"), "nc": ("window", "channel"),
+           "tkc": ("tower", "tap", "channel"), "c": ("channel",), "k1f": ("filter tap", "one", "filter"), "tc": ("tower", "channel"),
+           "tokc": ("tower", "c_out", "tap", "c_in")}
+
+
+def _describe(idx, layout, shape):
+    names = LAYOUTS[layout]
+    s = ", ".join("%s %d" % (nm, i) for nm, i in zip(names, idx))
+    if "position" in names:
+        pos, l = int(idx[names.index("position")]), shape[names.index("position")]
+        s += " [128-tile %d, 254-tile %d, %d from the window edge]" % (pos // 128, pos // 254, min(pos, l - 1 - pos))
+    return s
+
+
+def assert_exact(got, want, layout, neg_zero=False, what=""):
+    """Bit-pattern equality of `got` (torch tensor, any storage type) with the float64 reference `want`, which must itself be exact in
+    got's type.  neg_zero: -0.0 and +0.0 compare equal -- the one allowed difference, for outputs of a ReLU (max(-0.0, 0) may keep the
+    sign) and products with an exactly zero factor; everything else is compared as bits.  On a mismatch: the count, the first and the
+    worst element by (window, position, channel), their 128- and 254-position tile indices and the distance from the window edge."""
+    got = torch.as_tensor(got).detach().cpu().contiguous()
+    want64 = np.asarray(want, dtype=np.float64) + 0.0
+    assert tuple(got.shape) == want64.shape, (tuple(got.shape), want64.shape)
+    wt = torch.as_tensor(want64).to(got.dtype)
+    assert np.array_equal(wt.to(torch.float64).numpy(), want64), "the reference is not exact in %s" % got.dtype
+    iv = INT_VIEW[got.dtype]
+    gb, wb = got.view(iv).numpy(), wt.contiguous().view(iv).numpy()
+    bad = gb != wb
+    if neg_zero:
+        bad &= ~((got.to(torch.float64).numpy() == 0.0) & (want64 == 0.0))
+    if not bad.any():
+        return
+    g64 = got.to(torch.float64).numpy()
+    idx = np.argwhere(bad)
+    diff = np.where(bad, np.abs(np.nan_to_num(g64, nan=np.inf) - want64), -1.0)
+    worst = np.unravel_index(int(np.argmax(diff)), diff.shape)
+    first = tuple(idx[0])
+    raise AssertionError("%s: %d of %d elements differ; first at (%s): got %r, want %r; worst at (%s): got %r, want %r" % (
+        what or layout, len(idx), bad.size, _describe(first, layout, bad.shape), g64[first], want64[first],
+        _describe(worst, layout, bad.shape), g64[worst], want64[worst]))
