@@ -29,6 +29,11 @@ template <> struct Mfma<bf16> {
     __device__ static inline f32x16 run(Frag a, Frag b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
     }
+    // one 16x16x32: lane l supplies row / column l & 15 and k slots 8 (l >> 4) .. + 7 of both operands; D register e of lane l is
+    // row 4 (l >> 4) + e, column l & 15.  Same FLOPs per cycle as run; the chip holds a higher clock under it
+    __device__ static inline f32x4 run16(Frag a, Frag b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
 };
 template <> struct Mfma<f16> {
     static constexpr int KSTEP_BYTES = 32;  // one 32x32x16: 16 halves of K (same rate as the bf16 instruction)
@@ -38,6 +43,11 @@ template <> struct Mfma<f16> {
     }
     __device__ static inline f32x16 run(Frag a, Frag b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+    // one 16x16x32: lane l supplies row / column l & 15 and k slots 8 (l >> 4) .. + 7 of both operands; D register e of lane l is
+    // row 4 (l >> 4) + e, column l & 15.  Same FLOPs per cycle as run; the chip holds a higher clock under it
+    __device__ static inline f32x4 run16(Frag a, Frag b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
     }
 };
 template <> struct Mfma<float> {

@@ -462,50 +462,42 @@ constexpr int LDS_BYTES = (RING * STAGE > TM * TP) ? RING * STAGE : TM * TP;  //
 static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU");
 }  // namespace n2
 
-// accumulators start at the bias of their channel (forward) or 0 (dgrad): register 4g + e of block j <-> channel c0 + 32j + 8g + e
+// The accumulator map of the 256 x 128 kernels (v_mfma_f32_16x16x32, weights as the first operand): acc[i][j] is position block i
+// (16 rows) x channel block j (16 channels) of the wave's 128 x 64; lane l holds row 16 i + (l & 15) and, in register e, channel
+// 16 j + 4 (l >> 4) + e -- four consecutive channels of one position.
+// accumulators start at the bias of their channel (forward) or 0 (dgrad): register e of block j <-> channel c0 + 16 j + e
 template <typename T, int EPI>
-__device__ inline void n2_load_bias(const NtArgs<T>& p, f32x4 (&b4)[2][4], int c0) {
+__device__ inline void n2_load_bias(const NtArgs<T>& p, f32x4 (&b4)[4], int c0) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            b4[j][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (EPI != EPI_DGRAD) b4[j][g] = *reinterpret_cast<const f32x4*>(p.bias + c0 + 32 * j + 8 * g);
-        }
-}
-// vm_conv_fwd_fold: tile row ``row`` is the first (which = 0) or last (which = 1) position of the window -- take the constant of the
-// tap that falls into the padding off its accumulators (lane r <-> row 32 i + r of the wave's 128, registers <-> channels)
-template <typename T>
-__device__ inline void n2_fold_edge(const NtArgs<T>& p, f32x16 (&acc)[4][2], int row, int which, int wm, int r, int c0) {
-    if ((row >> 7) != wm) return;  // wave-uniform
-    const float* hb = p.fold_hb + (which ? 2 * p.N : 0) + c0;
-    f32x4 h[2][4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) h[j][g] = *reinterpret_cast<const f32x4*>(hb + 32 * j + 8 * g);
-    const int rw = row & 127;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {  // every 32-row block with a lane mask: a runtime block index would put acc into scratch
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const float m = (32 * i + r == rw) ? 1.f : 0.f;
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] -= m * h[j][g][e];
-        }
+    for (int j = 0; j < 4; ++j) {
+        b4[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (EPI != EPI_DGRAD) b4[j] = *reinterpret_cast<const f32x4*>(p.bias + c0 + 16 * j);
     }
 }
-__device__ inline void n2_fill_acc(f32x16 (&acc)[4][2], const f32x4 (&b4)[2][4]) {
+// vm_conv_fwd_fold: tile row ``row`` is the first (which = 0) or last (which = 1) position of the window -- take the constant of the
+// tap that falls into the padding off its accumulators (lane r = l & 15 <-> row 16 i + r of the wave's 128, registers <-> channels)
+template <typename T>
+__device__ inline void n2_fold_edge(const NtArgs<T>& p, f32x4 (&acc)[8][4], int row, int which, int wm, int r, int c0) {
+    if ((row >> 7) != wm) return;  // wave-uniform
+    const float* hb = p.fold_hb + (which ? 2 * p.N : 0) + c0;
+    f32x4 h[4];
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < 4; ++j) h[j] = *reinterpret_cast<const f32x4*>(hb + 16 * j);
+    const int rw = row & 127;
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
+    for (int i = 0; i < 8; ++i) {  // every 16-row block with a lane mask: a runtime block index would put acc into scratch
+        const float m = (16 * i + r == rw) ? 1.f : 0.f;
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc[i][j][4 * g + e] = b4[j][g][e];
+            for (int e = 0; e < 4; ++e) acc[i][j][e] -= m * h[j][e];
+    }
+}
+__device__ inline void n2_fill_acc(f32x4 (&acc)[8][4], const f32x4 (&b4)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i][j] = b4[j];
 }
 // Shared epilogue of the 256 x 128 kernels below.  ``trows``: valid MFMA-tile rows (256, or 254 for the input-resident kernel).
 //
@@ -548,16 +540,16 @@ struct N2DrainSync {   // the drain run by the four waves of a 256-thread workgr
 };
 
 template <typename T, int EPI>
-__device__ inline void n2_tile_write(const NtArgs<T>& p, char* lds, const f32x16 (&acc)[4][2], int t0, int n0, int trows, int lane, int wm, int wn,
-                                     const f32x4 (&negc)[2][4]) {
+__device__ inline void n2_tile_write(const NtArgs<T>& p, char* lds, const f32x4 (&acc)[8][4], int t0, int n0, int trows, int lane, int wm, int wn,
+                                     const f32x4 (&negc)[4]) {
     using namespace n2;
-    const int r = lane & 31, kh = lane >> 5;
+    const int r = lane & 15, q = lane >> 4;
     constexpr bool FWD = EPI == EPI_FWD || EPI == EPI_FWD_FOLD;
     const bool red = EPI == EPI_DGRAD && p.red_a != nullptr;
     const int valid = (p.L - t0) < trows ? (p.L - t0) : trows;  // MFMA-tile rows that are positions of the window
     // centred tile (fold_ctr): the accumulators hold z_pre - ctr (the start vector had ctr taken off), so ReLU is max(., -ctr), with
     // ONE rounding to the storage type
-    // (negc = -ctr of this lane's 32 channels, loaded by n2_epilogue in front of its first barrier)
+    // (negc = -ctr of this lane's 16 channels, loaded by n2_epilogue in front of its first barrier)
     constexpr bool CAN_CENTRE = EPI == EPI_FWD_FOLD && std::is_same<T, f16>::value;
     const bool ctrd = CAN_CENTRE && p.fold_ctr != nullptr;
     // ---- registers -> bf16 tile in LDS.  Forward: the bias is already in the accumulators (they were initialised with it) and
@@ -572,49 +564,44 @@ __device__ inline void n2_tile_write(const NtArgs<T>& p, char* lds, const f32x16
     // block instead of two selects per group -- was measured too: no faster, and the four copies of the loop cost the dgrad 1 %.)
     auto body = [&](auto ctrd_c) {
         constexpr bool CTRD = decltype(ctrd_c)::value;
-        uint32_t nc16[2][4][2];   // -ctr of the lane's channels as packed halves (exact: ctr is a half)
+        uint32_t nc16[4][2];   // -ctr of the lane's channels as packed halves (exact: ctr is a half)
         if constexpr (CTRD) {
             typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    nc16[j][g][0] = __builtin_bit_cast(uint32_t, h2{(_Float16)negc[j][g][0], (_Float16)negc[j][g][1]});
-                    nc16[j][g][1] = __builtin_bit_cast(uint32_t, h2{(_Float16)negc[j][g][2], (_Float16)negc[j][g][3]});
-                }
+            for (int j = 0; j < 4; ++j) {
+                nc16[j][0] = __builtin_bit_cast(uint32_t, h2{(_Float16)negc[j][0], (_Float16)negc[j][1]});
+                nc16[j][1] = __builtin_bit_cast(uint32_t, h2{(_Float16)negc[j][2], (_Float16)negc[j][3]});
+            }
         }
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 8; ++i) {
+            const int mb = wm * 128 + i * 16;
+            const int m = mb + r;
+            const bool partial = mb + 16 > valid;  // wave-uniform: this 16-row block has rows outside the window
+            const bool zero = (FWD || red) && partial && m >= valid;
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int mb = wm * 128 + i * 32;
-                const int m = mb + r;
-                const bool partial = mb + 32 > valid;  // wave-uniform: this 32-row block has rows outside the window
-                const bool zero = (FWD || red) && partial && m >= valid;
+            for (int j = 0; j < 4; ++j) {
+                const int nl = wn * 64 + j * 16 + 4 * q;  // first of this lane's 4 consecutive channels
+                T o[4];
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int nl = wn * 64 + j * 32 + 8 * g + 4 * kh;  // first of this lane's 4 consecutive channels
-                    T o[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[e] = Elem<T>::from_f(acc[i][j][4 * g + e]);
-                    u32x2 pk = *reinterpret_cast<const u32x2*>(o);
-                    if constexpr (CTRD) {
-                        uint32_t lo = pk[0], hi = pk[1];
-                        asm("v_pk_max_f16 %0, %1, %2" : "=v"(lo) : "v"(lo), "v"(nc16[j][g][0]));
-                        asm("v_pk_max_f16 %0, %1, %2" : "=v"(hi) : "v"(hi), "v"(nc16[j][g][1]));
-                        pk[0] = lo;
-                        pk[1] = hi;
-                    } else if constexpr (EPI != EPI_DGRAD) {
-                        uint32_t lo = pk[0], hi = pk[1];
-                        asm("v_pk_max_i16 %0, %1, 0" : "=v"(lo) : "v"(lo));
-                        asm("v_pk_max_i16 %0, %1, 0" : "=v"(hi) : "v"(hi));
-                        pk[0] = lo;
-                        pk[1] = hi;
-                    }
-                    pk[0] = zero ? 0u : pk[0];
-                    pk[1] = zero ? 0u : pk[1];
-                    *reinterpret_cast<u32x2*>(lds + m * TP + nl * 2) = pk;
+                for (int e = 0; e < 4; ++e) o[e] = Elem<T>::from_f(acc[i][j][e]);
+                u32x2 pk = *reinterpret_cast<const u32x2*>(o);
+                if constexpr (CTRD) {
+                    uint32_t lo = pk[0], hi = pk[1];
+                    asm("v_pk_max_f16 %0, %1, %2" : "=v"(lo) : "v"(lo), "v"(nc16[j][0]));
+                    asm("v_pk_max_f16 %0, %1, %2" : "=v"(hi) : "v"(hi), "v"(nc16[j][1]));
+                    pk[0] = lo;
+                    pk[1] = hi;
+                } else if constexpr (EPI != EPI_DGRAD) {
+                    uint32_t lo = pk[0], hi = pk[1];
+                    asm("v_pk_max_i16 %0, %1, 0" : "=v"(lo) : "v"(lo));
+                    asm("v_pk_max_i16 %0, %1, 0" : "=v"(hi) : "v"(hi));
+                    pk[0] = lo;
+                    pk[1] = hi;
                 }
+                pk[0] = zero ? 0u : pk[0];
+                pk[1] = zero ? 0u : pk[1];
+                *reinterpret_cast<u32x2*>(lds + m * TP + nl * 2) = pk;
             }
         }
     };
@@ -982,18 +969,16 @@ __device__ inline void n2_tile_drain(const NtArgs<T>& p, char* lds, int64_t n, i
 
 
 template <typename T, int EPI>
-__device__ inline void n2_epilogue(const NtArgs<T>& p, char* lds, const f32x16 (&acc)[4][2], int64_t n, int tl, int t0, int n0, int trows,
+__device__ inline void n2_epilogue(const NtArgs<T>& p, char* lds, const f32x4 (&acc)[8][4], int64_t n, int tl, int t0, int n0, int trows,
                                    int tid, int lane, int w, int wm, int wn) {
-    f32x4 negc[2][4];
+    f32x4 negc[4];
     if constexpr (EPI == EPI_FWD_FOLD && std::is_same<T, f16>::value) {
         if (p.fold_ctr != nullptr) {   // issued here: the barrier below hides their latency
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4 c = *reinterpret_cast<const f32x4*>(p.fold_ctr + n0 + (wn * 64 + j * 32) + 8 * g + 4 * (lane >> 5));
-                    negc[j][g] = f32x4{-c[0], -c[1], -c[2], -c[3]};
-                }
+            for (int j = 0; j < 4; ++j) {
+                const f32x4 c = *reinterpret_cast<const f32x4*>(p.fold_ctr + n0 + (wn * 64 + j * 16) + 4 * (lane >> 4));
+                negc[j] = f32x4{-c[0], -c[1], -c[2], -c[3]};
+            }
         }
     }
     VM_EPI_MARK(1);
@@ -1119,9 +1104,9 @@ __global__ __launch_bounds__(256, 2) void conv_nt2r_kernel(NtArgs<T> p, int64_t 
         if (p.fold_ctr != nullptr) p.fold_ctr += tw * p.N;
     }
     // forward: the bias loads go out first and are consumed (accumulator init) only after the prologue DMA has been issued
-    f32x4 bias4[2][4];
+    f32x4 bias4[4];
     if constexpr (EPI == EPI_FWD_FOLD) p.bias = p.fold_hb + 3 * p.N;  // row 3 of hb: bias + the three per-tap constants (vm_fold_bn_weights)
-    n2_load_bias<T, EPI>(p, bias4, n0 + wn * 64 + 4 * (lane >> 5));
+    n2_load_bias<T, EPI>(p, bias4, n0 + wn * 64 + 4 * (lane >> 4));
 
     // ---- DMA sources: one instruction = 16 rows x 64 B; A block row R <-> padded input row t0 + R (clamped to the L + 2 rows) ----
     const int lrow = lane >> 2, lchunk = lane & 3;
@@ -1150,21 +1135,21 @@ __global__ __launch_bounds__(256, 2) void conv_nt2r_kernel(NtArgs<T> p, int64_t 
         for (int i = 0; i < 2; ++i) glds16(b_src[i] + ko, base + __builtin_amdgcn_readfirstlane((w + 4 * i) * 1024));
     };
 
-    // ---- fragment geometry: A row of tap k = block row m + k.  The four 32-row blocks of a wave are 2048 bytes apart and share the
-    // swizzle key ((row >> 2) & 3 is unchanged by +32), so one address per (tap, k-step) serves them through the ds_read offset
-    // field; rows 256 / 257 (taps 1, 2 of the dropped outputs 254, 255) read whatever follows the block -- valid LDS, results unused ----
-    const int r = lane & 31, kh = lane >> 5;
-    int a_addr[3][2], b_addr[2];
+    // ---- fragment geometry: A row of tap k = block row m + k.  A K tile (32 channels) is one v_mfma_f32_16x16x32 deep: lane l reads
+    // chunk q = l >> 4 (k slots 8 q .. 8 q + 7) of row l & 15 of a 16-row block.  The eight 16-row blocks of a wave are 1024 bytes apart
+    // and share the swizzle key ((row >> 2) & 3 is unchanged by +16), so one address per tap serves them through the ds_read offset
+    // field, and any 16 consecutive rows x 4 chunks take every (row & 3, chunk ^ key) once: conflict-free.  Rows 256 / 257 (taps 1, 2
+    // of the dropped outputs 254, 255) read whatever follows the block -- valid LDS, results unused ----
+    const int r = lane & 15, q = lane >> 4;
+    int a_addr[3], b_addr;
 #pragma unroll
     for (int tap = 0; tap < 3; ++tap) {
         const int row = wm * 128 + r + tap;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_addr[tap][ks] = row * KB + (((2 * ks + kh) ^ ((row >> 2) & 3)) << 4);
+        a_addr[tap] = row * KB + ((q ^ ((row >> 2) & 3)) << 4);
     }
     {
         const int row = wn * 64 + r;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) b_addr[ks] = B0 + row * KB + (((2 * ks + kh) ^ ((row >> 2) & 3)) << 4);
+        b_addr = B0 + row * KB + ((q ^ ((row >> 2) & 3)) << 4);
     }
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -1184,7 +1169,7 @@ __global__ __launch_bounds__(256, 2) void conv_nt2r_kernel(NtArgs<T> p, int64_t 
     }
     issue_b(1, row_bytes);  // K tile 1 = (chunk 0, tap 1)
     VM_PROF(const long long pt_s3 = __builtin_amdgcn_s_memtime();)
-    f32x16 acc[4][2];
+    f32x4 acc[8][4];
     n2_fill_acc(acc, bias4);
     int n_wait = (chunks > 1 ? 4 : 0) + 2;  // pieces issued after B(0)
     int ia_prev = 0;                        // A pieces issued in the previous iteration (after its B pieces)
@@ -1218,60 +1203,31 @@ __global__ __launch_bounds__(256, 2) void conv_nt2r_kernel(NtArgs<T> p, int64_t 
             }
             n_wait = ia_prev + ib + ia;  // pieces issued after B(kt + 1): the A pieces of kt - 1, then everything of kt
             ia_prev = ia;
-            // ---- fragments: 12 x ds_read_b128 issued up front in consumption order, then COUNTED lgkmcnt waits (LDS returns in order):
-            // the first MFMAs start when 3 reads have landed, the k-step-1 reads land under the MFMAs of k-step 0.  The reads are
-            // inline asm because hipcc waits lgkmcnt(0) before the first use of any of them; every wait names the registers it
-            // releases as in/out operands, which orders the MFMAs behind it ----
-            const uint32_t aa0 = lds0 + a_blk * A_BLK + a_addr[tap][0], aa1 = lds0 + a_blk * A_BLK + a_addr[tap][1];
-            const uint32_t bb0 = lds0 + b_cur * B_STG + b_addr[0], bb1 = lds0 + b_cur * B_STG + b_addr[1];  // b_addr contains B0
+            // ---- fragments: 12 x ds_read_b128 issued up front in consumption order (the four weight blocks, then the eight position
+            // blocks), then COUNTED lgkmcnt waits (LDS returns in order): the first MFMAs start when 5 reads have landed, the others land
+            // under the MFMAs in front of them.  The reads are inline asm because hipcc waits lgkmcnt(0) before the first use of any of
+            // them; every wait names the registers it releases as in/out operands, which orders the MFMAs behind it ----
+            const uint32_t aa = lds0 + a_blk * A_BLK + a_addr[tap];
+            const uint32_t bb = lds0 + b_cur * B_STG + b_addr;  // b_addr contains B0
             b_cur = b_cur == 2 ? 0 : b_cur + 1;
-            u32x4 a0[4], b0[2], a1[4], b1[2];
-            asm volatile("ds_read_b128 %0, %1" : "=v"(b0[0]) : "v"(bb0));
-            asm volatile("ds_read_b128 %0, %1" : "=v"(a0[0]) : "v"(aa0));
-            asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(b0[1]) : "v"(bb0));
-            asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(a0[1]) : "v"(aa0));
-            asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(a0[2]) : "v"(aa0));
-            asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(a0[3]) : "v"(aa0));
-            asm volatile("ds_read_b128 %0, %1" : "=v"(b1[0]) : "v"(bb1));
-            asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(b1[1]) : "v"(bb1));
-            asm volatile("ds_read_b128 %0, %1" : "=v"(a1[0]) : "v"(aa1));
-            asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(a1[1]) : "v"(aa1));
-            asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(a1[2]) : "v"(aa1));
-            asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(a1[3]) : "v"(aa1));
-#define VM_MM(A, B, I, J) acc[I][J] = Mfma<T>::run(__builtin_bit_cast(V8, B), __builtin_bit_cast(V8, A), acc[I][J])
+            u32x4 fa[8], fb[4];
+#define VM_DSR(dst, base, I) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(base), "n"((I) * 1024))
+            VM_DSR(fb[0], bb, 0); VM_DSR(fb[1], bb, 1); VM_DSR(fb[2], bb, 2); VM_DSR(fb[3], bb, 3);
+            VM_DSR(fa[0], aa, 0); VM_DSR(fa[1], aa, 1); VM_DSR(fa[2], aa, 2); VM_DSR(fa[3], aa, 3);
+            VM_DSR(fa[4], aa, 4); VM_DSR(fa[5], aa, 5); VM_DSR(fa[6], aa, 6); VM_DSR(fa[7], aa, 7);
+#undef VM_DSR
+#define VM_MM(A, B, I, J) acc[I][J] = Mfma<T>::run16(__builtin_bit_cast(V8, B), __builtin_bit_cast(V8, A), acc[I][J])
+#define VM_ROW(I, N)                                                  \
+            asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(fa[I]));  \
+            VM_MM(fa[I], fb[0], I, 0);                                \
+            VM_MM(fa[I], fb[1], I, 1);                                \
+            VM_MM(fa[I], fb[2], I, 2);                                \
+            VM_MM(fa[I], fb[3], I, 3);                                \
             __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(9)" : "+v"(b0[0]), "+v"(a0[0]), "+v"(b0[1]));
-            VM_MM(a0[0], b0[0], 0, 0);
-            VM_MM(a0[0], b0[1], 0, 1);
             __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(a0[1]));
-            VM_MM(a0[1], b0[0], 1, 0);
-            VM_MM(a0[1], b0[1], 1, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(7)" : "+v"(a0[2]));
-            VM_MM(a0[2], b0[0], 2, 0);
-            VM_MM(a0[2], b0[1], 2, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(a0[3]));
-            VM_MM(a0[3], b0[0], 3, 0);
-            VM_MM(a0[3], b0[1], 3, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(b1[0]), "+v"(b1[1]), "+v"(a1[0]));
-            VM_MM(a1[0], b1[0], 0, 0);
-            VM_MM(a1[0], b1[1], 0, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(a1[1]));
-            VM_MM(a1[1], b1[0], 1, 0);
-            VM_MM(a1[1], b1[1], 1, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(a1[2]));
-            VM_MM(a1[2], b1[0], 2, 0);
-            VM_MM(a1[2], b1[1], 2, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a1[3]));
-            VM_MM(a1[3], b1[0], 3, 0);
-            VM_MM(a1[3], b1[1], 3, 1);
-            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(fb[0]), "+v"(fb[1]), "+v"(fb[2]), "+v"(fb[3]));
+            VM_ROW(0, 7) VM_ROW(1, 6) VM_ROW(2, 5) VM_ROW(3, 4) VM_ROW(4, 3) VM_ROW(5, 2) VM_ROW(6, 1) VM_ROW(7, 0)
+#undef VM_ROW
 #undef VM_MM
             __builtin_amdgcn_sched_barrier(0);
             VM_PROF(if (kt == 0) pt_first = __builtin_amdgcn_s_memtime();)
@@ -1280,9 +1236,9 @@ __global__ __launch_bounds__(256, 2) void conv_nt2r_kernel(NtArgs<T> p, int64_t 
     }
     VM_PROF(const long long pt_loop = __builtin_amdgcn_s_memtime();)
     if constexpr (EPI == EPI_FWD_FOLD) {
-        const int c0 = n0 + wn * 64 + 4 * (lane >> 5), rl = p.L - 1 - t0;
-        if (t0 == 0) n2_fold_edge<T>(p, acc, 0, 0, wm, lane & 31, c0);
-        if (rl >= 0 && rl < TROWS) n2_fold_edge<T>(p, acc, rl, 1, wm, lane & 31, c0);
+        const int c0 = n0 + wn * 64 + 4 * (lane >> 4), rl = p.L - 1 - t0;
+        if (t0 == 0) n2_fold_edge<T>(p, acc, 0, 0, wm, lane & 15, c0);
+        if (rl >= 0 && rl < TROWS) n2_fold_edge<T>(p, acc, rl, 1, wm, lane & 15, c0);
     }
     n2_epilogue<T, EPI>(p, lds, acc, n, tl, t0, n0, TROWS, tid, lane, w, wm, wn);
 #if defined(VM_EXPERIMENT_PROFILE)
@@ -1298,7 +1254,7 @@ __global__ __launch_bounds__(256, 2) void conv_nt2r_kernel(NtArgs<T> p, int64_t 
             q[4] = (unsigned int)(pt_s2 - pt_start);     // tile coordinates, bias loads, DMA / fragment addresses
             q[5] = (unsigned int)(pt_s3 - pt_s2);        // issue of the 10-14 prologue DMA instructions
             q[6] = (unsigned int)(pt_bar - pt_s3);       // accumulator init, first data wait, first barrier
-            q[7] = (unsigned int)(pt_first - pt_bar);    // fragment reads + 16 MFMAs of the first K tile
+            q[7] = (unsigned int)(pt_first - pt_bar);    // fragment reads + 32 MFMAs of the first K tile
         }
     }
 #endif
@@ -1312,19 +1268,20 @@ __global__ __launch_bounds__(256, 2) void conv_nt2r_kernel(NtArgs<T> p, int64_t 
 // ablation put 13 % of forward + dgrad on the in-loop weight LDS-DMA alone: a K tile costs a wave 2 weight pieces + 1.3 input pieces of
 // LDS-DMA (~250 clocks of issue each under load), 4 of its 12 fragment reads, and a workgroup barrier whose only purpose is the reuse
 // of the 8 KB weight stages.  The weights are small (0.2 .. 1.2 MB per layer), read by every workgroup and therefore L2-resident.
-// Here vm_pack_nt_weights lays them out in MFMA fragment order -- [tower][64-channel block][K tile][j][k-step][lane][8 values], so
-// that one global_load_dwordx4 of a wave IS one 32 x 16 B fragment, 1 KB contiguous, and a wave's stream is 4 KB per K tile in the
-// order the loop walks -- and the loop keeps three register sets of four fragments: K tile kt multiplies out of set kt % 3 while the
+// Here vm_pack_nt_weights lays them out in the fragment order of v_mfma_f32_32x32x16 -- [tower][64-channel block][K tile][j][k-step]
+// [lane][8 values] -- so that a wave's stream is 4 KB per K tile in the order the loop walks (the loop itself issues 16x16x32 and
+// gathers its four 16-channel fragments out of those 4 KB: see bvoff below; the layout is pinned by the tests and did not move with
+// the instruction) -- and the loop keeps three register sets of four fragments: K tile kt multiplies out of set kt % 3 while the
 // loads of K tile kt + 2 fill set (kt + 2) % 3.  What is left in LDS is the input operand: a ring of FOUR 16 KB blocks (256 rows x
 // 32 channels, the layout and swizzle of conv_nt2r_kernel; c_in = 128 -- the block-2 forward -- is resident outright), block
-// c + 3 requested during chunk c, and ONE barrier per chunk (48 MFMAs per wave) instead of one per K tile:
+// c + 3 requested during chunk c, and ONE barrier per chunk (96 MFMAs per wave) instead of one per K tile:
 //   RAW  A(c) was issued three chunks earlier, B(kt) two K tiles earlier; loads return in order, so the counted wait for B(kt) at the
 //        top of iteration kt covers both; the barrier at tap 0 makes the other waves' pieces of A(c) visible.
 //   WAR  A(c + 3) overwrites the block read during chunk c - 1; it is issued after the barrier of chunk c, which a wave passes only
 //        with its chunk c - 1 reads consumed.  Register set (kt + 2) % 3 was consumed by the MFMAs of iteration kt - 1.
 // The global loads are inline asm: beside an LDS-DMA hipcc waits vmcnt(0) before the first use of any ordinary load's result (and it
 // cannot count asm loads at all), so every wait is written by hand from the issue schedule:
-//   iteration kt:  B(kt + 2) [4 loads]  ->  s_waitcnt vmcnt(N)  ->  barrier (tap 0)  ->  A pieces [2; taps 0, 1]  ->  8 ds_read + 16 MFMA
+//   iteration kt:  B(kt + 2) [4 loads]  ->  s_waitcnt vmcnt(N)  ->  barrier (tap 0)  ->  A pieces [2; taps 0, 1]  ->  8 ds_read + 32 MFMA
 //   N = loads issued after B(kt) = A pieces of kt - 2  +  B(kt + 1)  +  A pieces of kt - 1  +  B(kt + 2)
 // The epilogue is conv_nt2r_kernel's (n2_epilogue).  Same requirements: a_c % 32 == 0, Ktot == 3 * a_c, N % 128 == 0.
 // ------------------------------------------------------------------------------------------------
@@ -1337,7 +1294,7 @@ namespace n3 {
 constexpr int NBLK = 4;
 constexpr int A_BLK = 256 * 64;
 static_assert(NBLK * A_BLK <= n2::LDS_BYTES, "the input ring fits under the epilogue tile");
-constexpr int KT_BYTES = 4096;  // one wave's weight fragments of one K tile: [j 2][k-step 2][lane 64][16 B]
+constexpr int KT_BYTES = 4096;  // one wave's weight operand of one K tile: [j 2][ks 2][lane 32 kh + r][16 B] = channel 32 j + r, chunk 2 ks + kh
 }  // namespace n3
 
 // one fragment: lane l gets the 16 bytes at sbase + imm + l * 16 (voff = l * 16); the result is valid after the counted wait that
@@ -1351,11 +1308,11 @@ __device__ inline void n3_wait_b(u32x4 (&b)[4]) {
 }
 
 // The issue schedule of conv_nt3_kernel as constexpr functions: which input (A) pieces iteration i = 3 c + tap issues under its last
-// eight MFMAs, and -- by replaying the whole schedule -- the number of vector-memory operations a wave has issued after the last
+// sixteen MFMAs, and -- by replaying the whole schedule -- the number of vector-memory operations a wave has issued after the last
 // fragment of B(kt) when it reaches the wait that opens iteration kt: the N of that iteration's s_waitcnt vmcnt(N).
 //   prologue          A(0) [4]   B(0) [4]   B(1) [4]   A(1) [4, chunks > 1]            (LEAN; the first wait needs A(0), B(0) only)
 //                     A(0) [4]   B(0) [4]   A(1) [4]   B(1) [4]   A(2) [4, chunks > 2]  (!LEAN: the first form)
-//   iteration i       WAIT   B(i + 2) [4, i + 2 < nk, under the first eight MFMAs]   A pieces [under the last eight]:
+//   iteration i       WAIT   B(i + 2) [4, i + 2 < nk, under the first sixteen MFMAs]   A pieces [under the last sixteen]:
 //                     LEAN: i = 0: all four of A(2); i = 1: all four of A(3); i = 2: none; from chunk 1 on as below
 //                     pieces 2 tap, 2 tap + 1 of A(c + 3) at taps 0, 1 while c + 3 < chunks
 // LEAN issues four LDS-DMA instructions (~250 ticks each under load) fewer before the first MFMA of a tile.
@@ -1442,21 +1399,16 @@ __global__ __launch_bounds__(256, 2) void conv_nt3_kernel(NtArgs<T> p, int64_t n
         if (p.fold_ctr != nullptr) p.fold_ctr += tw * p.N;
     }
     if constexpr (EPI == EPI_FWD_FOLD) p.bias = p.fold_hb + 3 * p.N;  // row 3 of hb: bias + the three per-tap constants (vm_fold_bn_weights)
-    // The wave's 64 bias values by SCALAR loads (the address is wave-uniform; a lane wants the 32 of its half kh).  As 8 vector loads
+    // The wave's 64 bias values by SCALAR loads (the address is wave-uniform; a lane wants the 16 of its quarter l >> 4).  As vector loads
     // per lane they cost ~3000 ticks of VMEM issue in the setup, and -- hipcc cannot see the counted waits behind the inline-asm loads
     // -- an s_waitcnt vmcnt(0) in front of the first MFMA, which drained the whole prologue (first K tile 2500 ticks against 760).
     // They must stay IN FRONT of the first inline-asm statement with a memory clobber: behind one, hipcc no longer proves the bias
     // unclobbered and falls back to vector loads (16 of them, and the vmcnt(0) again).
-    f32x4 bias_lo[2][4], bias_hi[2][4];
+    f32x4 bias_w[16];
     if constexpr (EPI != EPI_DGRAD) {
         const float* bp = p.bias + n0 + wn * 64;
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bias_lo[j][g] = *reinterpret_cast<const f32x4*>(bp + 32 * j + 8 * g);
-                bias_hi[j][g] = *reinterpret_cast<const f32x4*>(bp + 32 * j + 8 * g + 4);
-            }
+        for (int k = 0; k < 16; ++k) bias_w[k] = *reinterpret_cast<const f32x4*>(bp + 4 * k);
     }
 
     // ---- input DMA sources (as conv_nt2r_kernel): one instruction = 16 rows x 64 B ----
@@ -1485,24 +1437,27 @@ __global__ __launch_bounds__(256, 2) void conv_nt3_kernel(NtArgs<T> p, int64_t n
         const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)q), hi = __builtin_amdgcn_readfirstlane((uint32_t)(q >> 32));
         bbase = ((uint64_t)hi << 32) | lo;
     }
-    const uint32_t bvoff = lane * 16;
-    u32x4 bs[3][4];  // register sets of K tiles kt % 3 = 0, 1, 2: fragments (j, k-step) = 00, 01, 10, 11 (constant indices only)
+    // The 16-channel x 32-k fragment of channel block b is a 16-byte gather inside the K tile's 4 KB (the packed layout is that of the
+    // 32x32x16 fragments, vm_pack_nt_weights): lane l wants channel 16 b + (l & 15), chunk q = l >> 4, i.e. j = b >> 1,
+    // r = 16 (b & 1) + (l & 15), ks = q >> 1, kh = q & 1 -- per lane (q >> 1) * 1024 + (q & 1) * 512 + (l & 15) * 16, immediate
+    // (b >> 1) * 2048 + (b & 1) * 256: four 256-byte runs per load.  k slot 8 q + e = channel 8 q + e of the chunk, as in the LDS rows.
+    const int r = lane & 15, q = lane >> 4;
+    const uint32_t bvoff = (q >> 1) * 1024 + (q & 1) * 512 + r * 16;
+    u32x4 bs[3][4];  // register sets of K tiles kt % 3 = 0, 1, 2: the fragments of channel blocks 0 .. 3 (constant indices only)
 #define VM_LOAD_SET(KT)                                                           \
     {                                                                             \
         const uint64_t sb_ = bbase + (uint64_t)((KT) * n3::KT_BYTES);             \
         VM_GLOAD_FRAG(bs[(KT) % 3][0], bvoff, sb_, 0);                            \
-        VM_GLOAD_FRAG(bs[(KT) % 3][1], bvoff, sb_, 1024);                         \
+        VM_GLOAD_FRAG(bs[(KT) % 3][1], bvoff, sb_, 256);                          \
         VM_GLOAD_FRAG(bs[(KT) % 3][2], bvoff, sb_, 2048);                         \
-        VM_GLOAD_FRAG(bs[(KT) % 3][3], bvoff, sb_, 3072);                         \
+        VM_GLOAD_FRAG(bs[(KT) % 3][3], bvoff, sb_, 2304);                         \
     }
 
-    const int r = lane & 31, kh = lane >> 5;
-    int a_addr[3][2];
+    int a_addr[3];   // as conv_nt2r_kernel: one address per tap, the eight 16-row blocks through the ds_read offset field
 #pragma unroll
     for (int tap = 0; tap < 3; ++tap) {
         const int row = wm * 128 + r + tap;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) a_addr[tap][ks] = row * KB + (((2 * ks + kh) ^ ((row >> 2) & 3)) << 4);
+        a_addr[tap] = row * KB + ((q ^ ((row >> 2) & 3)) << 4);
     }
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)lds;
@@ -1528,48 +1483,47 @@ __global__ __launch_bounds__(256, 2) void conv_nt3_kernel(NtArgs<T> p, int64_t n
         }
     }
     VM_PROF(const long long pt_s3 = __builtin_amdgcn_s_memtime();)
-    f32x16 acc[4][2];
+    f32x4 acc[8][4];
     {
-        f32x4 bias4[2][4];
+        f32x4 bias4[4];
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                bias4[j][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if constexpr (EPI != EPI_DGRAD) bias4[j][g] = (lane >> 5) ? bias_hi[j][g] : bias_lo[j][g];
-            }
+        for (int j = 0; j < 4; ++j) {
+            bias4[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (EPI != EPI_DGRAD)
+                bias4[j] = q == 0 ? bias_w[4 * j] : q == 1 ? bias_w[4 * j + 1] : q == 2 ? bias_w[4 * j + 2] : bias_w[4 * j + 3];
+        }
         n2_fill_acc(acc, bias4);
     }
 #if VM_NT3_ABL & 4
 #define VM_MM(A, B, I, J) asm volatile("" : "+v"(acc[I][J]) : "v"(A), "v"(B))
 #else
-#define VM_MM(A, B, I, J) acc[I][J] = Mfma<T>::run(__builtin_bit_cast(V8, B), __builtin_bit_cast(V8, A), acc[I][J])
+#define VM_MM(A, B, I, J) acc[I][J] = Mfma<T>::run16(__builtin_bit_cast(V8, B), __builtin_bit_cast(V8, A), acc[I][J])
 #endif
     // KT is a literal in the macros below: every index, every wait count and every branch is a compile-time constant, the loop is
     // straight-line code and no register that a load is still writing ever meets a phi (the rolled form made hipcc copy them)
-    // ---- the interleaved loop.  Every memory operation of a K tile sits INSIDE its MFMA stream, one per pair of MFMAs: the
-    // k-step-1 fragments of this tile and the weight fragments of tile kt + 2 under the k-step-0 MFMAs, the k-step-0 fragments of the
-    // NEXT tile (their registers are free by then) and the input DMA pieces under the k-step-1 MFMAs.  An LDS read has eight MFMAs
-    // (256 clocks) to return, a wave never has an issue-only phase, and LDS returns in order with exactly three reads younger than
+    // ---- the interleaved loop.  A K tile is ONE MFMA deep: 8 position blocks x 4 channel blocks = 32 v_mfma_f32_16x16x32.  Every
+    // memory operation of a K tile sits INSIDE its MFMA stream, one per group of four MFMAs (one position block): the fragments of
+    // position blocks 4 .. 7 (f1) of this tile and the weight fragments of tile kt + 2 under the MFMAs of blocks 0 .. 3 (f0), blocks
+    // 0 .. 3 of the NEXT tile (their registers are free by then) and the input DMA pieces under those of blocks 4 .. 7.  An LDS read
+    // has sixteen MFMAs (256 clocks) to return, a wave never has an issue-only phase, and LDS returns in order with exactly three reads younger than
     // the one an MFMA pair needs: every wait is lgkmcnt(3) until the last tile drains.  The chunk barrier moves to the middle of
     // tap 2 (before the first read of the next block), behind lgkmcnt(0): all reads of this chunk's block have RETURNED when a wave
     // passes it, so the DMA pieces that recycle the block -- issued at least one tile later -- cannot overtake a read.
     u32x4 f0[4], f1[4];
-#define VM_FRAG_READ(dst, base, I)                                                              \
-    if constexpr ((I) == 0) asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(base));          \
-    if constexpr ((I) == 1) asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(dst) : "v"(base)); \
-    if constexpr ((I) == 2) asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(dst) : "v"(base)); \
-    if constexpr ((I) == 3) asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(dst) : "v"(base));
+    // position block B (0 .. 7) of the 128 rows whose (tap-shifted) first row `base` addresses
+#define VM_FRAG_READ(dst, base, B) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(base), "n"((B) * 1024));
 #define VM_P_STEP0(I)                                                                                                                 \
     asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(f0[I]));                                                                               \
     VM_MM(f0[I], bs[cur_][0], I, 0);                                                                                                  \
-    VM_MM(f0[I], bs[cur_][2], I, 1);                                                                                                  \
-    VM_FRAG_READ(f1[I], aa1_, I)                                                                                                      \
+    VM_MM(f0[I], bs[cur_][1], I, 1);                                                                                                  \
+    VM_MM(f0[I], bs[cur_][2], I, 2);                                                                                                  \
+    VM_MM(f0[I], bs[cur_][3], I, 3);                                                                                                  \
+    VM_FRAG_READ(f1[I], aa_, 4 + (I))                                                                                                 \
     if constexpr (kt_ + 2 < NK && !(VM_NT3_ABL & 1)) {                                                                                \
         if constexpr ((I) == 0) VM_GLOAD_FRAG(bs[nxt_][0], bvoff, sb_, 0);                                                            \
-        if constexpr ((I) == 1) VM_GLOAD_FRAG(bs[nxt_][1], bvoff, sb_, 1024);                                                         \
+        if constexpr ((I) == 1) VM_GLOAD_FRAG(bs[nxt_][1], bvoff, sb_, 256);                                                          \
         if constexpr ((I) == 2) VM_GLOAD_FRAG(bs[nxt_][2], bvoff, sb_, 2048);                                                         \
-        if constexpr ((I) == 3) VM_GLOAD_FRAG(bs[nxt_][3], bvoff, sb_, 3072);                                                         \
+        if constexpr ((I) == 3) VM_GLOAD_FRAG(bs[nxt_][3], bvoff, sb_, 2304);                                                         \
     }                                                                                                                                 \
     __builtin_amdgcn_sched_barrier(0);
 #define VM_P_STEP1(I)                                                                                                                 \
@@ -1581,9 +1535,11 @@ __global__ __launch_bounds__(256, 2) void conv_nt3_kernel(NtArgs<T> p, int64_t n
         if constexpr ((I) == 2) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(f1[I]));                                                   \
         if constexpr ((I) == 3) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f1[I]));                                                   \
     }                                                                                                                                 \
-    VM_MM(f1[I], bs[cur_][1], I, 0);                                                                                                  \
-    VM_MM(f1[I], bs[cur_][3], I, 1);                                                                                                  \
-    if constexpr (kt_ + 1 < NK) { VM_FRAG_READ(f0[I], an0_, I) }                                                                      \
+    VM_MM(f1[I], bs[cur_][0], 4 + (I), 0);                                                                                            \
+    VM_MM(f1[I], bs[cur_][1], 4 + (I), 1);                                                                                            \
+    VM_MM(f1[I], bs[cur_][2], 4 + (I), 2);                                                                                            \
+    VM_MM(f1[I], bs[cur_][3], 4 + (I), 3);                                                                                            \
+    if constexpr (kt_ + 1 < NK) { VM_FRAG_READ(f0[I], an_, I) }                                                                      \
     if constexpr ((I) < n3_pieces(kt_, CHUNKS, LEAN).count && !(VM_NT3_ABL & 2))                                                      \
         issue_a1(n3_pieces(kt_, CHUNKS, LEAN).block % 4, n3_pieces(kt_, CHUNKS, LEAN).block, n3_pieces(kt_, CHUNKS, LEAN).first + (I)); \
     __builtin_amdgcn_sched_barrier(0);
@@ -1595,11 +1551,11 @@ __global__ __launch_bounds__(256, 2) void conv_nt3_kernel(NtArgs<T> p, int64_t n
         if constexpr (kt_ == 0) {                                                                                                     \
             __builtin_amdgcn_s_barrier();                                                                                             \
             VM_PROF(pt_bar = __builtin_amdgcn_s_memtime();)                                                                           \
-            const uint32_t a00_ = lds0 + a_addr[0][0];                                                                                \
+            const uint32_t a00_ = lds0 + a_addr[0];                                                                                \
             VM_FRAG_READ(f0[0], a00_, 0) VM_FRAG_READ(f0[1], a00_, 1) VM_FRAG_READ(f0[2], a00_, 2) VM_FRAG_READ(f0[3], a00_, 3)         \
         }                                                                                                                             \
-        const uint32_t aa1_ = lds0 + ablk_ * A_BLK + a_addr[tap_][1];                                                                  \
-        const uint32_t an0_ = lds0 + (nc_ % 4) * A_BLK + a_addr[ntap_][0];                                                             \
+        const uint32_t aa_ = lds0 + ablk_ * A_BLK + a_addr[tap_];                                                                      \
+        const uint32_t an_ = lds0 + (nc_ % 4) * A_BLK + a_addr[ntap_];                                                                 \
         const uint64_t sb_ = bbase + (uint64_t)((kt_ + 2) * n3::KT_BYTES);                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                                            \
         VM_P_STEP0(0) VM_P_STEP0(1) VM_P_STEP0(2) VM_P_STEP0(3)                                                                       \
@@ -1623,13 +1579,13 @@ __global__ __launch_bounds__(256, 2) void conv_nt3_kernel(NtArgs<T> p, int64_t n
 #undef VM_MM
 #undef VM_LOAD_SET
     if constexpr (EPI == EPI_FWD_FOLD) {
-        const int c0 = n0 + wn * 64 + 4 * (lane >> 5), rl = p.L - 1 - t0;
-        if (t0 == 0) n2_fold_edge<T>(p, acc, 0, 0, wm, lane & 31, c0);
-        if (rl >= 0 && rl < n2r::TROWS) n2_fold_edge<T>(p, acc, rl, 1, wm, lane & 31, c0);
+        const int c0 = n0 + wn * 64 + 4 * q, rl = p.L - 1 - t0;
+        if (t0 == 0) n2_fold_edge<T>(p, acc, 0, 0, wm, r, c0);
+        if (rl >= 0 && rl < n2r::TROWS) n2_fold_edge<T>(p, acc, rl, 1, wm, r, c0);
     }
     VM_PROF(const long long pt_loop = __builtin_amdgcn_s_memtime();)
 #if VM_NT3_ABL & 8
-    if (acc[0][0][0] == 123.456f && acc[3][1][15] == 1.5f) n2_epilogue<T, EPI>(p, lds, acc, n, tl, t0, n0, n2r::TROWS, tid, lane, w, wm, wn);
+    if (acc[0][0][0] == 123.456f && acc[7][3][3] == 1.5f) n2_epilogue<T, EPI>(p, lds, acc, n, tl, t0, n0, n2r::TROWS, tid, lane, w, wm, wn);
 #else
     n2_epilogue<T, EPI>(p, lds, acc, n, tl, t0, n0, n2r::TROWS, tid, lane, w, wm, wn);
 #endif
@@ -1668,7 +1624,7 @@ __global__ __launch_bounds__(256, 2) void conv_nt3_kernel(NtArgs<T> p, int64_t n
             q[4] = (unsigned int)(pt_s2 - pt_start);     // tile coordinates, bias loads, DMA / fragment addresses
             q[5] = (unsigned int)(pt_s3 - pt_s2);        // issue of the prologue DMA / weight loads
             q[6] = (unsigned int)(pt_bar - pt_s3);       // accumulator init, first data wait, first barrier
-            q[7] = (unsigned int)(pt_first - pt_bar);    // fragment reads + 16 MFMAs of the first K tile
+            q[7] = (unsigned int)(pt_first - pt_bar);    // fragment reads + 32 MFMAs of the first K tile
         }
 #endif
     }
