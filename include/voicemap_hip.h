@@ -570,6 +570,25 @@ int vm_tail_param_grads(const float* gmax, const float* demb, const float* emb, 
 int vm_softmax_cce(const float* logits, const int32_t* labels, int64_t rows, int n_classes, float grad_scale, float* prob,
                    float* loss_acc, float* dlogits, float* ws, void* stream);
 
+/* ---- a9b: prototypical loss on a k-way n-shot episode (Snell et al. 2017; this project's own objective, the reference has none)
+ * emb (k*n + m, E) fp32: rows [0, k*n) the support set, class-major (class c owns rows c*n .. c*n + n - 1: the layout of
+ * vm_nshot_distances' support), rows [k*n, k*n + m) the queries; labels int32 (m) in [0, k).
+ *   p_c = mean of class c's n support rows;  logits[j][c] = -alpha * sum_t (q_j[t] - p_c[t])^2  (written, (m, k), never scaled);
+ *   loss_acc[0] = mean_j (logsumexp_c logits[j] - logits[j][y_j]) (row maximum subtracted, no clip), [1] = the share of queries whose
+ *   first maximum is y_j (alpha = 1: the argmin of vm_nshot_distances(VM_DIST_EUCLIDEAN));
+ *   demb (k*n + m, E) = grad_scale * d loss / d emb, every row written: with r = softmax - onehot a query row gets
+ *   (2 alpha / m) sum_c r[j][c] p_c, every support row of class c (2 alpha / (m n)) sum_j r[j][c] (q_j - p_c).
+ * labels NULL: predict-only (logits alone; loss_acc, demb, ws untouched).  demb NULL with labels: evaluation (loss_acc alone).
+ * A label outside [0, k) takes its query out of every sum (no loss term, no hit, no gradient; its logits are still written) while the
+ * means still divide by m.  Two launches: per query, then per class (+ the means); every sum in a fixed order (support rows in row
+ * order, the E components per lane ascending then an xor butterfly, classes ascending, queries in row order), no atomics: results
+ * are bit-identical run to run.  vm_proto_loss_supported: 2 <= k <= 128, 1 <= n <= 16, 1 <= E <= 256, k * E <= 16384 (the prototypes
+ * live in LDS), 1 <= m < 2^31; VM_ERR_UNSUPPORTED outside.  ws: vm_proto_loss_workspace_bytes (r (m, k), loss terms, hits). */
+int vm_proto_loss_supported(int k, int n, int64_t m, int E);
+int vm_proto_loss(const float* emb, const int32_t* labels, int k, int n, int64_t m, int E, float alpha, float grad_scale,
+                  float* logits, float* loss_acc, float* demb, float* ws, void* stream);
+int64_t vm_proto_loss_workspace_bytes(int k, int n, int64_t m, int E);
+
 /* ---- a5: Adam(clipnorm=1.)  (experiments/train_siamese.py:56; Keras 2.2.2 optimizers.py) -------------------
  * sqnorm: 1 fp32 on device <- sum(g^2) over the flat gradient buffer (fixed order; ws >= vm_sqnorm_workspace_bytes).  sqnorm may be
  * NULL: then only the partial sums are left in ws, for vm_adam_clip_step's sqnorm_parts (one launch less). */

@@ -1399,6 +1399,33 @@ class HipEncoderEngine:
                      self.num_classes, _p(self.view("head.kernel", G)), _p(self.view("head.bias", G)), _p(pl["demb"]), st)
         return pl["prob"]
 
+    def _proto_bufs(self, pl: dict, k: int, n: int) -> dict:
+        """Per-episode buffers of the prototypical head, per (plan, k, n): logits (m, k) and the kernel's workspace."""
+        key = ("proto", k, n)
+        b = pl.get(key)
+        if b is None:
+            m = pl["n"] - k * n
+            if k < 2 or n < 1 or m < 1:
+                raise ValueError("a %d-way %d-shot episode needs more than %d windows (got %d)" % (k, n, k * n, pl["n"]))
+            if not self.lib.query("vm_proto_loss_supported", k, n, m, self.E):
+                raise ValueError("vm_proto_loss does not serve k = %d, n = %d, m = %d, E = %d" % (k, n, m, self.E))
+            ws = self.lib.query("vm_proto_loss_workspace_bytes", k, n, m, self.E)
+            b = pl[key] = {"m": m, "logits": torch.empty(m, k, dtype=torch.float32, device=self.device),
+                           "ws": torch.empty(ws // 4, dtype=torch.float32, device=self.device)}
+        return b
+
+    def prototypical_head(self, pl: dict, labels: Optional[torch.Tensor], k: int, n: int, alpha: float = 1.0):
+        """Prototypical loss over the plan's embeddings as one k-way n-shot episode (rows [0, k n) the class-major support set, the
+        rest queries; ``labels`` int32 (m,) on the device): logits (m, k), with labels pl['loss_acc'] and -- on a training plan --
+        pl['demb'].  No head parameters: valid on an engine built with head=None."""
+        b = self._proto_bufs(pl, k, n)
+        train = labels is not None and pl["training"]
+        self._call("vm_proto_loss", _p(pl["emb"]), self._dyn("y", _p(labels)), k, n, b["m"], self.E, float(alpha),
+                   self._dyn("loss_scale", float(self.loss_scale)) if train else 1.0, _p(b["logits"]),
+                   _p(pl["loss_acc"]) if labels is not None else None, _p(pl["demb"]) if train else None,
+                   _p(b["ws"]) if labels is not None else None, self.stream())
+        return b["logits"]
+
     def _adam_scalars(self):
         """(t, lr_t) of the Adam step about to run (Keras: lr decays with the iteration count BEFORE this step)."""
         lr = self.lr
@@ -1469,7 +1496,8 @@ class HipEncoderEngine:
     def _train_step(self, pl: dict, wpt: int, target: torch.Tensor, loss: Optional[str], drop_masks, apply_update: bool, pre,
                     input_ready: bool = False, aug: Optional[dict] = None):
         """preprocess (``pre`` = None | ("raw", tensor, downsampling, whitening) | ("offsets", audio, offsets, raw_len, downsampling,
-        whitening)) -> forward -> head (``loss`` None: the classifier's) -> backward -> optimizer.  The SECOND time a configuration
+        whitening)) -> forward -> head (``loss`` None: the classifier's; ("prototypical", k, n, alpha): the prototypical loss, no head
+        parameters) -> backward -> optimizer.  The SECOND time a configuration
         is seen its enqueue sequence is recorded (program.Program), from the third on it is replayed: same launches, same arguments, same
         stream ordering -- only the input / label / mask pointers and four scalars are patched in."""
         # (a gradient hook that declares itself ``replayable`` -- parallel.GradAllReduce: its two collectives are host calls kept in
@@ -1517,6 +1545,9 @@ class HipEncoderEngine:
             if loss is None:
                 self.forward(pl, wpt, drop_masks)
                 self.classifier_head(pl, target)
+            elif isinstance(loss, tuple):   # ("prototypical", k, n, alpha): part of the replay key above
+                self.forward(pl, wpt, drop_masks)
+                self.prototypical_head(pl, target, loss[1], loss[2], loss[3])
             else:
                 self.forward(pl, wpt, drop_masks, defer_tail=True)
                 self.siamese_head(pl, target, loss)
@@ -1723,6 +1754,92 @@ class HipEncoderEngine:
             drop_masks = self.make_drop_masks(n)
         lab = torch.as_tensor(labels).reshape(n).to(self.device, torch.int32).contiguous()
         self._train_step(pl, n, lab, None, drop_masks, apply_update, None if preprocessed else ("raw", x, downsampling, whitening))
+        return pl
+
+    # ---- prototypical episodes: the whole episode is ONE encoder call (one whitening batch, one set of BatchNorm statistics) ----------
+    def prototypical_train_step(self, x, labels, k: int, n: int, alpha: float = 1.0, preprocessed: bool = True, downsampling: int = 4,
+                                whitening: bool = True, drop_masks="auto", apply_update: bool = True):
+        """One training step on a k-way n-shot episode: x (k n + m, L[, 1]) windows, rows [0, k n) the class-major support set
+        (librispeech.build_episode), the rest queries; labels (m,) the queries' classes in [0, k)."""
+        x = torch.as_tensor(x)
+        N = x.shape[0]
+        x = x.reshape(N, -1).to(self.device)
+        l0 = x.shape[1] if preprocessed else (x.shape[1] + downsampling - 1) // downsampling
+        pl = self.plan(N, l0, True)
+        m = self._proto_bufs(pl, int(k), int(n))["m"]
+        if preprocessed:
+            self.load_preprocessed(pl, x)
+        if isinstance(drop_masks, str):
+            drop_masks = self.make_drop_masks(N)
+        lab = torch.as_tensor(labels).reshape(m).to(self.device, torch.int32).contiguous()
+        self._train_step(pl, N, lab, ("prototypical", int(k), int(n), float(alpha)), drop_masks, apply_update,
+                         None if preprocessed else ("raw", x, downsampling, whitening))
+        return pl
+
+    def prototypical_train_step_from_offsets(self, audio: torch.Tensor, offsets, labels, raw_len: int, k: int, n: int, alpha: float = 1.0,
+                                             downsampling: int = 4, whitening: bool = True, drop_masks="auto", apply_update: bool = True):
+        """``prototypical_train_step`` fed from a device-resident recording buffer (shards.ShardedSpeechDataset.build_episode_device):
+        ``offsets`` (k n + m,) int64 start samples in episode order.  Host numpy offsets with host labels go up in one asynchronous
+        copy from the pinned ring, as in siamese_train_step_from_offsets; tensors are taken as they are."""
+        host = isinstance(offsets, np.ndarray) and not torch.is_tensor(labels)
+        N = int(offsets.size) if isinstance(offsets, np.ndarray) else int(offsets.numel())
+        pl = self.plan(N, (raw_len + downsampling - 1) // downsampling, True)
+        m = self._proto_bufs(pl, int(k), int(n))["m"]
+        ready = False
+        if host:
+            offs, lab, ready = self._stage_episode(pl, offsets, labels, m)
+        else:
+            offs = torch.as_tensor(offsets).reshape(-1).to(self.device, torch.int64).contiguous()
+            lab = torch.as_tensor(labels).reshape(m).to(self.device, torch.int32).contiguous()
+        if isinstance(drop_masks, str):
+            drop_masks = self.make_drop_masks(N)
+        self._train_step(pl, N, lab, ("prototypical", int(k), int(n), float(alpha)), drop_masks, apply_update,
+                         ("offsets", audio, offs, raw_len, downsampling, whitening), input_ready=ready)
+        if host:
+            self._staged_step_enqueued(pl)
+        return pl
+
+    def _stage_episode(self, pl: dict, offsets: "np.ndarray", labels, m: int):
+        """_stage_offsets_and_labels for an episode: [N int64 offsets | m int32 labels] in one asynchronous copy, a ring of its own
+        per m.  Returns (offsets, labels, input_ready)."""
+        N = pl["n"]
+        ring = ("h2d_episode", m)
+        st = pl.get(ring)
+        if st is None:
+            nbytes = N * 8 + m * 4
+            st = pl[ring] = {"dev": [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(32)],
+                             "pin": [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(32)],
+                             "ev": [None] * 32, "k": 0}
+        pl["h2d_cur"] = st
+        s = st["k"] % 32
+        st["k"] += 1
+        if st["ev"][s] is not None:
+            st["ev"][s].synchronize()
+        buf = st["pin"][s].numpy()
+        buf[:N * 8] = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1).view(np.uint8)
+        buf[N * 8:] = np.ascontiguousarray(np.asarray(labels).reshape(m).astype(np.int32)).view(np.uint8)
+        dev = st["dev"][s]
+        ahead = bool(self.pre_overlap and not self.timed)
+        if ahead:
+            with torch.cuda.stream(self.tower_stream):
+                dev.copy_(st["pin"][s], non_blocking=True)
+        else:
+            dev.copy_(st["pin"][s], non_blocking=True)
+        st["cur"] = s
+        return dev[:N * 8].view(torch.int64), dev[N * 8:].view(torch.int32), ahead
+
+    def prototypical_eval(self, x, labels, k: int, n: int, alpha: float = 1.0, preprocessed: bool = True, downsampling: int = 4,
+                          whitening: bool = True):
+        """test_on_batch of an episode: inference-mode forward (moving BatchNorm statistics) + loss / accuracy in pl['loss_acc'];
+        ``labels`` None: the logits only.  Returns the inference plan (the logits: prototypical_head's return, kept per (k, n))."""
+        x = torch.as_tensor(x)
+        N = x.shape[0]
+        self.embed(x, preprocessed, downsampling, whitening, windows_per_tower=N)
+        pl = self.plan(N, self.last_infer_l0, False)
+        lab = None
+        if labels is not None:
+            lab = torch.as_tensor(labels).reshape(N - k * n).to(self.device, torch.int32).contiguous()
+        pl["proto_logits"] = self.prototypical_head(pl, lab, int(k), int(n), alpha)
         return pl
 
     def embed(self, x, preprocessed: bool = True, downsampling: int = 4, whitening: bool = True,

@@ -171,6 +171,8 @@ def read_checkpoint(path: str) -> dict:
     if "training_config" in f.attrs:
         tc = json.loads(_text(f.attrs["training_config"]))
         training = {"loss": tc.get("loss"), "metrics": tc.get("metrics") or []}
+        if tc.get("loss_config"):   # a loss with parameters (utils.PrototypicalLoss: k_way, n_shot, alpha); files written here only
+            training["loss_config"] = tc["loss_config"]
         oc = tc.get("optimizer_config") or {}
         optimizer = {"class_name": oc.get("class_name"), "config": oc.get("config", {}), "iterations": 0, "m": None, "v": None}
         if "optimizer_weights" in f:
@@ -289,7 +291,8 @@ def write_checkpoint(path: str, kind: str, geo: dict, params: Dict[str, np.ndarr
                      training: Optional[dict] = None):
     """Inverse of ``read_checkpoint``.  ``geo`` needs filters, embedding_dimension, dropout, first_pool, input_shape
     (+ distance_metric for kind 'siamese', classifier_units for 'classifier'); ``optimizer`` = {"config": Adam config,
-    "iterations": int, "m": {...}, "v": {...}} or None; ``training`` = {"loss": str, "metrics": [...]}."""
+    "iterations": int, "m": {...}, "v": {...}} or None; ``training`` = {"loss": str, "metrics": [...]} (+ "loss_config": the parameters of
+    a loss that has some)."""
     assert kind in ("siamese", "encoder", "classifier")
     if geo.get("input_shape") is None:
         raise ValueError("input_shape is needed to write a Keras model_config")
@@ -352,6 +355,8 @@ def write_checkpoint(path: str, kind: str, geo: dict, params: Dict[str, np.ndarr
         ocfg = dict((optimizer or {}).get("config") or {})
         tc = {"optimizer_config": {"class_name": "Adam", "config": ocfg}, "loss": training.get("loss"),
               "metrics": list(training.get("metrics") or []), "sample_weight_mode": None, "loss_weights": None}
+        if training.get("loss_config"):
+            tc["loss_config"] = dict(training["loss_config"])
         root.attrs["training_config"] = json.dumps(tc).encode("utf8")
         if optimizer is not None and optimizer.get("m") is not None:
             names = trainable_names(kind != "encoder")

@@ -308,6 +308,38 @@ class LibriSpeechDataset(Sequence):
             parts.append(files[self._weighted(n, self._len[files])])
         return np.concatenate(parts)
 
+    # ---- k-way n-shot training episodes (not in the reference: utils.PrototypicalLoss) ---------------------------------
+    def _episode_files(self, k, n, q):
+        """File ids (k, n + q) of an episode: k distinct speakers drawn uniformly without replacement among the speakers with at least
+        n + q files, then n + q distinct files of each (uniformly, without replacement); the first n of a row are its support set."""
+        if k < 2 or n < 1 or q < 1:
+            raise ValueError('an episode needs k >= 2 classes, n >= 1 support and q >= 1 query windows per class')
+        eligible = np.flatnonzero(self._cnt >= n + q)
+        if len(eligible) < k:
+            raise ValueError('only {} speakers have the {} files a {}-shot episode with {} queries per class needs; k = {}'
+                             .format(len(eligible), n + q, n, q, k))
+        speakers = np.random.choice(eligible, k, replace=False)
+        return np.stack([np.random.choice(self._files[self._start[c]:self._start[c] + self._cnt[c]], n + q, replace=False)
+                         for c in speakers])
+
+    @staticmethod
+    def _episode_order(files, n):
+        """The episode's row order: the support set class-major (class c owns rows c n .. c n + n - 1, the layout of
+        build_n_shot_task), then the queries class-major."""
+        return np.concatenate([files[:, :n].reshape(-1), files[:, n:].reshape(-1)])
+
+    def build_episode(self, k, n, q):
+        """(windows, query_labels) of one k-way n-shot training episode with q queries per class: windows (k n + k q, T, 1), support set
+        first; query_labels (k q, 1), the queries' classes 0 .. k-1 (positions in the episode, not speaker ids).  One fragment per
+        file, drawn by ``__getitem__``'s rule in row order."""
+        files = self._episode_files(k, n, q)
+        windows = np.stack([self[i][0] for i in self._episode_order(files, n)])[:, :, np.newaxis]
+        return windows, np.repeat(np.arange(k), q)[:, np.newaxis]
+
+    def yield_episodes(self, k, n, q):
+        while True:
+            yield self.build_episode(k, n, q)
+
     @staticmethod
     def index_subset(subset):
         """Walk ``data/LibriSpeech/{subset}/<speaker>/<chapter>/*.flac`` and record speaker id, path and length."""

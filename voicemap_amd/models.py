@@ -140,8 +140,15 @@ class _TrainableModel:
                "v": {n: eng.view(n, eng.V).detach().cpu().numpy() for n in names}}
         if eng.clipnorm:
             opt["config"]["clipnorm"] = float(eng.clipnorm)
+        return kind, geo, eng.get_params(), opt, self._training_config()
+
+    def _training_config(self) -> dict:
+        """{"loss": its name, "metrics": [...]} (+ "loss_config" for a loss with parameters: utils.PrototypicalLoss)."""
         loss = self.loss if isinstance(self.loss, str) or self.loss is None else getattr(self.loss, "__name__", str(self.loss))
-        return kind, geo, eng.get_params(), opt, {"loss": loss, "metrics": list(self.metrics)}
+        tc = {"loss": loss, "metrics": list(self.metrics)}
+        if hasattr(self.loss, "get_config"):
+            tc["loss_config"] = self.loss.get_config()
+        return tc
 
     def save(self, filepath: str):
         """``model.save``: a Keras-2.2.2 HDF5 file for ``*.hdf5`` / ``*.h5`` names (what the reference's ModelCheckpoint
@@ -158,8 +165,7 @@ class _TrainableModel:
         eng = self._ensure_engine()
         torch.cuda.synchronize()
         cfg = dict(self.get_config())
-        loss = self.loss if isinstance(self.loss, str) or self.loss is None else getattr(self.loss, "__name__", str(self.loss))
-        cfg["training"] = {"loss": loss, "metrics": list(self.metrics),
+        cfg["training"] = {**self._training_config(),
                            "optimizer": {"lr": eng.lr, "beta_1": eng.beta_1, "beta_2": eng.beta_2, "epsilon": eng.adam_eps,
                                          "decay": eng.decay, "clipnorm": float(eng.clipnorm) if eng.clipnorm else None}}
         blob = {"P": eng.P.cpu().numpy(), "M": eng.M.cpu().numpy(), "V": eng.V.cpu().numpy(), "NT": eng.NT.cpu().numpy(),
@@ -471,8 +477,11 @@ class ConvolutionalEncoder(_TrainableModel):
     def _train_step(self, x, y):
         """One optimizer step enqueued; returns the engine's plan (``loss_acc`` on the device: reading it is the only host sync)."""
         if not self.classifier_units:
-            raise RuntimeError("the bare encoder has no loss; add Dense(num_classes, activation='softmax') or wrap it in "
-                               "build_siamese_net")
+            proto = self._proto_loss()
+            if proto is None:
+                raise RuntimeError("the bare encoder has no loss; add Dense(num_classes, activation='softmax'), wrap it in "
+                                   "build_siamese_net or compile it with utils.PrototypicalLoss")
+            return self._proto_step(x, y, proto)
         if self.loss not in ("categorical_crossentropy", None):
             raise NotImplementedError("classifier loss %r" % (self.loss,))
         eng = self._ensure_engine()
@@ -481,6 +490,26 @@ class ConvolutionalEncoder(_TrainableModel):
                                              whitening=x.whitening)
         return eng.classifier_train_step(np.asarray(x, dtype=np.float32), self._labels(y))
 
+    def _proto_loss(self):
+        """The compiled utils.PrototypicalLoss of a bare encoder, or None."""
+        from .utils import PrototypicalLoss
+        return self.loss if isinstance(self.loss, PrototypicalLoss) and not self.classifier_units else None
+
+    def _proto_step(self, x, y, proto):
+        """One optimizer step on an episode batch (x: k n + m windows, support set first; y: the m queries' classes)."""
+        eng = self._ensure_engine()
+        if not hasattr(eng, "prototypical_train_step"):
+            raise NotImplementedError("the prototypical loss is implemented for the 1-D encoder")
+        k, n, alpha = proto.k_way, proto.n_shot, proto.alpha
+        if _is_lazy(x):
+            if type(x.raw).__name__ == "DeviceWindows" and getattr(x.raw, "aug", None) is None:
+                # device data path: the crop happens inside the preprocessing kernel (vm_crop_decimate_whiten)
+                return eng.prototypical_train_step_from_offsets(x.raw.audio, x.raw.offsets_host, self._labels(y), x.raw.length, k, n, alpha,
+                                                                downsampling=x.downsampling, whitening=x.whitening)
+            return eng.prototypical_train_step(np.asarray(x.raw, dtype=np.float32), self._labels(y), k, n, alpha, preprocessed=False,
+                                               downsampling=x.downsampling, whitening=x.whitening)
+        return eng.prototypical_train_step(np.asarray(x, dtype=np.float32), self._labels(y), k, n, alpha)
+
     def train_on_batch(self, x, y):
         la = self._train_step(x, y)["loss_acc"].cpu().numpy()
         return float(la[0]), float(la[1])
@@ -488,6 +517,17 @@ class ConvolutionalEncoder(_TrainableModel):
     def test_on_batch(self, x, y):
         eng = self._ensure_engine()
         import torch
+        proto = self._proto_loss()
+        if proto is not None:
+            if _is_lazy(x):
+                raw = x.raw.gather() if type(x.raw).__name__ == "DeviceWindows" and getattr(x.raw, "aug", None) is None else \
+                    np.asarray(x.raw, dtype=np.float32)
+                pl = eng.prototypical_eval(raw, self._labels(y), proto.k_way, proto.n_shot, proto.alpha, preprocessed=False,
+                                           downsampling=x.downsampling, whitening=x.whitening)
+            else:
+                pl = eng.prototypical_eval(np.asarray(x, dtype=np.float32), self._labels(y), proto.k_way, proto.n_shot, proto.alpha)
+            la = pl["loss_acc"].cpu().numpy()
+            return float(la[0]), float(la[1])
         if _is_lazy(x):
             emb = eng.embed(x.raw, preprocessed=False, downsampling=x.downsampling, whitening=x.whitening)
         else:
@@ -735,7 +775,8 @@ def load_model(filepath: str, custom_objects=None, dtype=None):
     else:
         m = enc_from(cfg)
     tr = cfg.get("training") or {}
-    m.compile(loss=tr.get("loss"), optimizer=Adam(**tr["optimizer"]) if tr.get("optimizer") else Adam(), metrics=tr.get("metrics"))
+    m.compile(loss=loss_by_name(tr.get("loss"), tr.get("loss_config")), optimizer=Adam(**tr["optimizer"]) if tr.get("optimizer") else Adam(),
+              metrics=tr.get("metrics"))
     m._load_state(blob)
     return m
 
@@ -759,7 +800,8 @@ def _load_keras_hdf5(filepath: str, dtype=None):
         adam = Adam(lr=c.get("lr", 0.001), beta_1=c.get("beta_1", 0.9), beta_2=c.get("beta_2", 0.999), epsilon=c.get("epsilon"),
                     decay=c.get("decay", 0.0), clipnorm=c.get("clipnorm"))
         loss = tr["loss"] if tr else None
-        m.compile(loss=contrastive_loss_by_name(loss), optimizer=adam, metrics=(tr or {}).get("metrics"))
+        m.compile(loss=loss_by_name(contrastive_loss_by_name(loss), (tr or {}).get("loss_config")), optimizer=adam,
+                  metrics=(tr or {}).get("metrics"))
         if opt.get("m") is not None:
             m._pending_adam = {"iterations": opt["iterations"], "m": opt["m"], "v": opt["v"]}
     m._ensure_engine()  # like the .npz path: a loaded model is live (weights, Adam slots and counters are on the device)
@@ -769,6 +811,14 @@ def _load_keras_hdf5(filepath: str, dtype=None):
 def contrastive_loss_by_name(loss):
     """training_config stores a custom loss by its function name; the reference's only one is utils.contrastive_loss."""
     return "contrastive_loss" if loss == "contrastive_loss" else loss
+
+
+def loss_by_name(loss, loss_config=None):
+    """The compiled loss of a checkpoint: a loss saved with its parameters (utils.PrototypicalLoss) is rebuilt from them."""
+    if loss == "prototypical_loss" and loss_config:
+        from .utils import PrototypicalLoss
+        return PrototypicalLoss(**loss_config)
+    return loss
 
 
 def load_keras_checkpoint_npz(weights_npz: str, dtype="f16"):

@@ -246,6 +246,24 @@ class ShardedSpeechDataset(LibriSpeechDataset):
         while True:
             yield self.build_verification_batch_device(batchsize, augment)
 
+    def build_episode_offsets(self, k, n, q, files=False):
+        """(offsets (k n + k q,), query_labels (k q, 1)): the episode of ``build_episode`` as start offsets into the device buffer --
+        the same draws in the same order (speakers, each speaker's files, then one fragment per file in row order).  ``files=True``
+        appends the file id every window is cut from."""
+        order = self._episode_order(self._episode_files(k, n, q), n)
+        out = (self.window_starts(order), np.repeat(np.arange(k), q)[:, np.newaxis])
+        return out + (order,) if files else out
+
+    def build_episode_device(self, k, n, q):
+        """``build_episode`` with the windows as ``DeviceWindows`` (needs ``to_device()`` first)."""
+        assert self.device_audio is not None, 'call to_device() first'
+        offsets, labels = self.build_episode_offsets(k, n, q)
+        return DeviceWindows(self.device_audio, offsets, self.fragment_length), labels
+
+    def yield_episodes_device(self, k, n, q):
+        while True:
+            yield self.build_episode_device(k, n, q)
+
     def build_n_shot_task_offsets(self, k, n=1):
         """The task of ``build_n_shot_task`` (librispeech.py:204-240 of the reference) as start offsets into the device
         buffer: ((query_offset, query_label), (support_offsets (k*n,), support_labels (k*n,))), support laid out

@@ -7,6 +7,7 @@
     whiten(batch, rms=0.038021)                                                                utils.py:88
     n_shot_task_evaluation(model, dataset, preprocessor, num_tasks, n, k, network_type, distance)   utils.py:104
     NShotEvaluationCallback(num_tasks, n_shot, k_way, dataset, preprocessor, mode)             utils.py:219
+    PrototypicalLoss(k_way, n_shot, alpha=1.0)                                                 (not in the reference)
 
 What is different underneath: ``preprocess_instances`` returns a *lazy* batch (``LazyWindows``) that remembers the raw
 16 kHz windows; the HIP models decimate + whiten it on the GPU (vm_decimate_whiten) instead of in three numpy passes on
@@ -97,6 +98,35 @@ def contrastive_loss(y_true, y_pred):
     return np.mean((1 - y_true) * np.square(y_pred) + y_true * np.square(np.maximum(margin - y_pred, 0)))
 
 
+class PrototypicalLoss:
+    """Prototypical loss (Snell et al. 2017) on k-way n-shot episodes, for ``encoder.compile(loss=PrototypicalLoss(k, n))`` on the
+    bare encoder (not in the reference).  A batch is ``(x, y)``: x the episode's ``k_way * n_shot + m`` windows -- the support set
+    first, class-major, as ``LibriSpeechDataset.build_episode`` lays them out -- and y the m queries' classes in [0, k_way).
+    loss = mean_j (logsumexp_c l[j] - l[j, y_j]) with l[j, c] = -alpha |q_j - mean(support of c)|^2, evaluated with its gradient by
+    vm_proto_loss; the metric beside it is the share of queries whose nearest prototype is their own."""
+
+    __name__ = "prototypical_loss"
+
+    def __init__(self, k_way, n_shot, alpha=1.0):
+        if int(k_way) < 2 or int(n_shot) < 1 or not float(alpha) > 0:
+            raise ValueError("PrototypicalLoss needs k_way >= 2, n_shot >= 1, alpha > 0")
+        self.k_way, self.n_shot, self.alpha = int(k_way), int(n_shot), float(alpha)
+
+    def get_config(self):
+        return {"k_way": self.k_way, "n_shot": self.n_shot, "alpha": self.alpha}
+
+    def __call__(self, emb, labels):
+        """The same expression with numpy (float64) on (k n + m, E) embeddings and (m,) labels."""
+        e = np.asarray(emb, dtype=np.float64)
+        k, n = self.k_way, self.n_shot
+        y = np.asarray(labels).reshape(-1).astype(np.int64)
+        p = e[:k * n].reshape(k, n, -1).mean(axis=1)
+        lg = -self.alpha * np.square(e[k * n:, None, :] - p[None]).sum(-1)
+        mx = lg.max(axis=1, keepdims=True)
+        lse = np.log(np.exp(lg - mx).sum(axis=1)) + mx[:, 0]
+        return float(np.mean(lse - lg[np.arange(len(y)), y]))
+
+
 def get_bottleneck(classifier, samples):
     """voicemap/utils.py:9-19: activations of the layer before the classification layer (= the embedding) in
     inference mode."""
@@ -123,7 +153,8 @@ def n_shot_task_evaluation(model, dataset, preprocessor, num_tasks, n, k, networ
       verification head; each side is preprocessed (whitened) as its own batch of k (:131); correct iff
       ``argmin(pred[:, 0]) == 0`` (:135).
     * n > 1 or a classifier (:138-212): embed query and support with the encoder (``model.layers[2]`` for the siamese
-      net :141, the classifier minus its last layer :143-145), whitening the query alone and the support set as one
+      net :141, the classifier minus its last layer :143-145; ``network_type="encoder"``, not in the reference: the model is
+      the encoder itself, e.g. one trained with PrototypicalLoss), whitening the query alone and the support set as one
       batch (:153-154), class prototypes + distance (:159-206) on the GPU (vm_nshot_distances), correct iff argmin == 0.
 
     Tasks are sampled one by one with ``dataset.build_n_shot_task(k, n)`` exactly like the reference, but embedded in
@@ -147,8 +178,8 @@ def _n_shot_local(model, dataset, preprocessor, num_tasks, n, k, network_type="s
     import torch
     if n < 1:
         raise ValueError("n must be >= 1")
-    if network_type not in ("siamese", "classifier"):
-        raise ValueError("mode must be one of (siamese, classifier)")
+    if network_type not in ("siamese", "classifier", "encoder"):
+        raise ValueError("mode must be one of (siamese, classifier, encoder)")
     if not (n == 1 and network_type == "siamese") and distance not in _DIST:
         raise ValueError("Distance must be in (euclidean, cosine, dot_product)")
     inst = preprocessor.instance_preprocessor if hasattr(preprocessor, "instance_preprocessor") else None
@@ -182,6 +213,8 @@ def _n_shot_local(model, dataset, preprocessor, num_tasks, n, k, network_type="s
     if network_type == "siamese":
         encoder = model.layers[2]
         encoder.engine = model._ensure_engine()
+    elif network_type == "encoder":   # the model IS the encoder (trained on episodes: PrototypicalLoss)
+        encoder = model
     else:
         encoder = model.clone()
         encoder.set_weights(model.get_weights())
@@ -221,6 +254,8 @@ def _n_shot_device(model, dataset, preprocessor, num_tasks, n, k, network_type, 
         encoder = model.layers[2]
         encoder.engine = model._ensure_engine()
         eng = encoder._ensure_engine()
+    elif network_type == "encoder":
+        eng = model._ensure_engine()
     else:
         encoder = model.clone()
         encoder.set_weights(model.get_weights())
@@ -284,7 +319,7 @@ class NShotEvaluationCallback(Callback):
         self.k_way = k_way
         self.dataset = dataset
         self.preprocessor = preprocessor
-        assert mode in ("siamese", "classifier")
+        assert mode in ("siamese", "classifier", "encoder")
         self.mode = mode
 
     def on_epoch_end(self, epoch, logs=None):
