@@ -740,7 +740,11 @@ int vm_mine_pairs(const float* emb, const int32_t* label, int64_t N, int E, int 
  * written in `dtype` as the block-1 input of the 2-D encoder: n_clips * n_mels windows of T + 2 rows (halo rows are not
  * written: the caller zeroes the buffer once), 1 channel.  basis: (win_length, 512) fp32 = the analysis window times
  * [cos(2 pi k n / 512) for k < 256 | -sin(2 pi k n / 512) for k < 256]; melw: (256, n_mels) fp32; both built by the host side
- * (voicemap_amd/spectro.py).  n_mels in {32, 64, 96, 128}. */
+ * (voicemap_amd/spectro.py).  n_mels in {32, 64, 96, 128}.  win_length in 2 .. 512, as far as the device's LDS goes: a workgroup holds
+ * 32 frames, 32 * (win_length + 1) * 4 bytes here and 2 * 32 * (round_up(win_length, 16) + 8) * 2 bytes in the f16 entry points below --
+ * 65 664 bytes at win_length = 512 and 66 560 bytes at win_length > 496, both past 64 KiB.  Every entry point compares its need with the
+ * device's per-block limit (hipDeviceAttributeMaxSharedMemoryPerBlock; 160 KiB on an MI355X, which runs 512) and fails with an error,
+ * `out` untouched, where the limit is lower. */
 int64_t vm_stft_frames(int64_t raw_len, int win_length, int hop);
 int vm_stft_logmel(const void* raw, int is_int16, int64_t n_clips, int64_t raw_len, int win_length, int hop, const float* basis,
                    const float* melw, int n_mels, float log_floor, int dtype, void* out, void* stream);

@@ -630,7 +630,7 @@ __global__ __launch_bounds__(256) void conv2d_first_fwd_kernel(const T* __restri
         float s1[8], s2[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
-        const int t_end = pl < PPB ? min(L, (chunk + 1) * 128) : 0;   // (C = 96: 252 of the 256 threads have a position)
+        const int t_end = pl < PPB ? min(L, (chunk + 1) * 128) : 0;   // (256 % CV threads have no position: C = 96: 4, C = 24: 1)
         for (int t = chunk * 128 + pl; t < t_end; t += PPB) {
             float acc[8];
 #pragma unroll
@@ -662,8 +662,8 @@ __global__ __launch_bounds__(256) void conv2d_first_fwd_kernel(const T* __restri
         }
         if (stat_sum == nullptr) continue;
         const int64_t row = win * rows + chunk;
-        // lanes that share a channel vector: the same (tid % CV).  CV divides 64 for C = 8 .. 128 except 96 (CV = 12), whose sums go
-        // through LDS thread by thread, in a fixed order
+        // lanes that share a channel vector: the same (tid % CV).  CV divides 64 for C = 8, 16, 32, 64 and 128; every other count
+        // (C = 24, 40, 48, 56, 72, 80, 88, 96, 104, 112, 120) sums through LDS thread by thread, in a fixed order
         if (64 % CV == 0) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -747,7 +747,7 @@ __global__ __launch_bounds__(256) void conv2d_first_wgrad_kernel(const T* __rest
     }
     // sum over the threads that share a channel vector, in a fixed order: lanes (where CV divides 64), then waves
     const bool shfl = 64 % CV == 0;
-    __shared__ float all[256][9];   // the C = 96 path: one channel at a time
+    __shared__ float all[256][9];   // the path of the counts whose CV does not divide 64 (C = 24, 40, .. 96 .. 120): one channel at a time
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         if (shfl) {
@@ -1301,6 +1301,17 @@ static dim3 ew_grid(int64_t windows, int64_t vectors_per_window) { return dim3((
 
 using namespace vm;
 
+// The frame matrices of a long window pass 64 KiB (fp32 kernel: win_length = 512; f16 kernels: win_length > 496): more dynamic LDS than
+// every device grants a workgroup.  The entry points ask the current device for its per-block limit and refuse before launching.
+static size_t lds_per_block_limit() {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) {
+        (void)hipGetLastError();
+        return 64 * 1024;
+    }
+    return (size_t)v;
+}
+
 extern "C" int64_t vm_stft_frames(int64_t raw_len, int win_length, int hop) {
     if (raw_len < win_length || hop <= 0) return 0;
     return 1 + (raw_len - win_length) / hop;
@@ -1318,6 +1329,7 @@ extern "C" int vm_stft_logmel(const void* raw, int is_int16, int64_t n_clips, in
     size_t lds = (size_t)SF_FRAMES * (win_length + 1) * 4;
     const size_t red = (size_t)4 * n_mels * 32 * 4;
     if (red > lds) lds = red;
+    VM_REQUIRE(lds <= lds_per_block_limit(), "vm_stft_logmel: win_length needs more LDS than the device grants a workgroup");
 #define VM_LAUNCH_SF(TT, NMB)                                                                                                    \
     hipLaunchKernelGGL((stft_logmel_kernel<TT, NMB>), grid, dim3(256), lds, (hipStream_t)stream, raw, is_int16, raw_len, win_length, \
                        hop, n_frames, basis, melw, log_floor, (TT*)out)
@@ -1356,6 +1368,7 @@ static int stft_logmel_f16s(const char* who, const void* raw, int is_int16, int6
     size_t lds = (size_t)2 * SF_FRAMES * (Kp + 8) * 2;
     const size_t red = (size_t)4 * n_mels * 32 * 4;
     if (red > lds) lds = red;
+    VM_REQUIRE(lds <= lds_per_block_limit(), "vm_stft_logmel_f16s: win_length needs more LDS than the device grants a workgroup");
 #define VM_LAUNCH_SF16(TT, NMB)                                                                                                       \
     hipLaunchKernelGGL((stft_logmel_f16s_kernel<TT, NMB>), grid, dim3(256), lds, (hipStream_t)stream, raw, is_int16, raw_len, win_length, \
                        hop, n_frames, (const f16*)basis16, Kp, melw, log_floor, (TT*)out, (TT*)out_lo)
