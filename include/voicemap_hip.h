@@ -589,6 +589,48 @@ int vm_proto_loss(const float* emb, const int32_t* labels, int k, int n, int64_t
                   float* logits, float* loss_acc, float* demb, float* ws, void* stream);
 int64_t vm_proto_loss_workspace_bytes(int k, int n, int64_t m, int E);
 
+/* ---- a9c: triplet loss with mining inside the batch (Hermans et al. 2017 "batch hard" / "batch all", FaceNet's margin; this
+ * project's own objective, the reference has none; csrc/triplet.hip)
+ * Inputs.  emb (N, E) fp32; label (N) int32, the speaker of every row: any values, rows in any order.  A row with label < 0 takes
+ * no part: it is no anchor and no candidate, its demb row is written as zeros, and its contents are never used.
+ * Distances.  s_ij = sum_t (e_i[t] - e_j[t])^2 in fp32, the direct form (no norm expansion: all terms are non-negative), a lane's
+ * components t = lane, lane + 64, ... ascending with fmaf, then the xor butterfly;  d_ij = sqrtf(s_ij).
+ * Candidate sets.  For a participating anchor a: P_a = {j != a : label[j] == label[a]}, N_a = {j : label[j] >= 0, label[j] != label[a]}.
+ * The anchor is VALID iff both are non-empty.
+ * VM_TRIPLET_HARD.  hp(a) = the element of P_a first by (s descending, j ascending), hn(a) = the element of N_a first by (s ascending,
+ * j ascending): s is compared, never d, and the order is total, so the choice is a function of the inputs alone.
+ *   x_a = margin + d_a,hp - d_a,hn (soft == 1: the margin is ignored, x_a = d_a,hp - d_a,hn).
+ *   hinge (soft == 0): l_a = max(0, x_a), weight g_a = 1 iff x_a > 0, else 0;
+ *   soft:              l_a = max(x_a, 0) + log1p(exp(-|x_a|)), weight g_a = sigmoid(x_a).
+ *   loss_acc[0] = (1 / V) sum over valid anchors l_a, V = the number of valid anchors;  loss_acc[1] = the share of valid anchors with
+ *   x_a > 0;  V = 0: loss 0, share 0, demb all zeros.
+ * VM_TRIPLET_ALL.  Every triplet (a, p in P_a, n in N_a) counts, x = margin + d_ap - d_an (soft: d_ap - d_an); T = their number.
+ *   hinge: loss_acc[0] = sum over the triplets with x > 0 of x / max(1, A), A = their number (the "non-zero" mean); a triplet's
+ *          weight is 1 / A iff x > 0;  loss_acc[1] = A / T.
+ *   soft:  loss_acc[0] = mean over the T triplets of softplus(x); weight sigmoid(x) / T;  loss_acc[1] = the share with x > 0.
+ * hard_pos, hard_neg (N) int32 receive hp(a), hn(a) in both modes, -1 where the anchor is not valid; either may be NULL.
+ * Gradient.  demb (N, E) = grad_scale * d loss / d emb, every row written; the selections and A are constants.  A pair (a, j) whose
+ * triplets' weights sum to c (positive as a positive, negative as a negative) adds c (e_a - e_j) / d_aj to row a and its negative to
+ * row j; a pair with s_aj == 0 adds nothing: no epsilon, no division by zero, the result stays finite.
+ * demb NULL: evaluation -- loss_acc and the indices are written, demb is not touched.
+ * Non-finite input.  If a participating row holds a non-finite value, loss_acc[0] is NaN and every element of demb is NaN (an anchor
+ * that meets a non-finite s flags the call): the f16 loss-scale skip relies on it.
+ * Limits.  2 <= N <= 1024, 1 <= E <= 256 (vm_triplet_loss_supported; VM_ERR_UNSUPPORTED above, VM_ERR_ARG below); the hinge needs a
+ * finite margin >= 0; mining and soft in range; refused before any launch.
+ * Order of the sums (no float atomics; two calls are bit-identical; grad_scale times a power of two scales demb exactly).  Launch 1,
+ * one workgroup of 256 threads per anchor: candidate j belongs to thread j % 256; a selection is a thread's candidates ascending,
+ * the butterfly on (s, j), the four waves in order.  ALL: the positives ascending (the whole workgroup together), a thread's negatives
+ * ascending -- a negative's weight and the thread's loss accumulate in that order, a positive's weight is the butterfly over the lanes
+ * then the four waves in order, the anchor's loss likewise.  Launch 2: row i, component t:
+ * grad_scale * ((sum_j (W[i][j] + W[j][i]) (e_i[t] - e_j[t]), j ascending, fmaf) / norm), W[a][j] = +-c_aj / d_aj, norm = V, A or T
+ * (an integer sum); the loss: a thread's rows ascending, the butterfly, the four waves in order, one division.
+ * ws >= vm_triplet_loss_workspace_bytes(N, E, mining) = (N N + 4 N) * 4: W (N, N), the anchors' loss terms, counts and flags. */
+int vm_triplet_loss_supported(int64_t N, int E);
+int64_t vm_triplet_loss_workspace_bytes(int64_t N, int E, int mining);
+int vm_triplet_loss(const float* emb, const int32_t* label, int64_t N, int E, int mining, int soft, float margin, float grad_scale,
+                    int32_t* hard_pos, int32_t* hard_neg, float* loss_acc, float* demb, void* ws, void* stream);
+enum { VM_TRIPLET_HARD = 0, VM_TRIPLET_ALL = 1 };
+
 /* ---- a5: Adam(clipnorm=1.)  (experiments/train_siamese.py:56; Keras 2.2.2 optimizers.py) -------------------
  * sqnorm: 1 fp32 on device <- sum(g^2) over the flat gradient buffer (fixed order; ws >= vm_sqnorm_workspace_bytes).  sqnorm may be
  * NULL: then only the partial sums are left in ws, for vm_adam_clip_step's sqnorm_parts (one launch less). */

@@ -1426,6 +1426,31 @@ class HipEncoderEngine:
                    _p(b["ws"]) if labels is not None else None, self.stream())
         return b["logits"]
 
+    def _triplet_bufs(self, pl: dict) -> dict:
+        """Per-plan buffers of the triplet head: hard_pos / hard_neg (N,) int32 and the kernel's workspace (the same for both minings)."""
+        b = pl.get("triplet")
+        if b is None:
+            N = pl["n"]
+            if not self.lib.query("vm_triplet_loss_supported", N, self.E):
+                raise ValueError("vm_triplet_loss does not serve N = %d, E = %d (2 <= N <= 1024, E <= 256)" % (N, self.E))
+            ws = self.lib.query("vm_triplet_loss_workspace_bytes", N, self.E, 0)
+            b = pl["triplet"] = {"hard_pos": torch.full((N,), -1, dtype=torch.int32, device=self.device),
+                                 "hard_neg": torch.full((N,), -1, dtype=torch.int32, device=self.device),
+                                 "ws": torch.empty(ws // 4, dtype=torch.float32, device=self.device)}
+        return b
+
+    def triplet_head(self, pl: dict, labels: torch.Tensor, mining: int = 0, soft: int = 0, margin: float = 0.2):
+        """Triplet loss mined inside the batch over the plan's embeddings (``labels`` int32 (N,) on the device, the speaker of every
+        row; a negative label takes its row out; ``mining`` 0 = batch hard, 1 = batch all; ``soft`` 1 = soft margin): pl['loss_acc'],
+        the selections in pl['triplet'] and -- on a training plan -- pl['demb'].  No head parameters: valid on an engine built with
+        head=None."""
+        b = self._triplet_bufs(pl)
+        train = pl["training"]
+        self._call("vm_triplet_loss", _p(pl["emb"]), self._dyn("y", _p(labels)), pl["n"], self.E, int(mining), int(soft), float(margin),
+                   self._dyn("loss_scale", float(self.loss_scale)) if train else 1.0, _p(b["hard_pos"]), _p(b["hard_neg"]),
+                   _p(pl["loss_acc"]), _p(pl["demb"]) if train else None, _p(b["ws"]), self.stream())
+        return b
+
     def _adam_scalars(self):
         """(t, lr_t) of the Adam step about to run (Keras: lr decays with the iteration count BEFORE this step)."""
         lr = self.lr
@@ -1496,8 +1521,9 @@ class HipEncoderEngine:
     def _train_step(self, pl: dict, wpt: int, target: torch.Tensor, loss: Optional[str], drop_masks, apply_update: bool, pre,
                     input_ready: bool = False, aug: Optional[dict] = None):
         """preprocess (``pre`` = None | ("raw", tensor, downsampling, whitening) | ("offsets", audio, offsets, raw_len, downsampling,
-        whitening)) -> forward -> head (``loss`` None: the classifier's; ("prototypical", k, n, alpha): the prototypical loss, no head
-        parameters) -> backward -> optimizer.  The SECOND time a configuration
+        whitening)) -> forward -> head (``loss`` None: the classifier's; ("prototypical", k, n, alpha): the prototypical loss,
+        ("triplet", mining, soft, margin): the triplet loss mined inside the batch, neither with head parameters) -> backward ->
+        optimizer.  The SECOND time a configuration
         is seen its enqueue sequence is recorded (program.Program), from the third on it is replayed: same launches, same arguments, same
         stream ordering -- only the input / label / mask pointers and four scalars are patched in."""
         # (a gradient hook that declares itself ``replayable`` -- parallel.GradAllReduce: its two collectives are host calls kept in
@@ -1545,6 +1571,9 @@ class HipEncoderEngine:
             if loss is None:
                 self.forward(pl, wpt, drop_masks)
                 self.classifier_head(pl, target)
+            elif isinstance(loss, tuple) and loss[0] == "triplet":   # ("triplet", mining, soft, margin): part of the replay key above
+                self.forward(pl, wpt, drop_masks)
+                self.triplet_head(pl, target, loss[1], loss[2], loss[3])
             elif isinstance(loss, tuple):   # ("prototypical", k, n, alpha): part of the replay key above
                 self.forward(pl, wpt, drop_masks)
                 self.prototypical_head(pl, target, loss[1], loss[2], loss[3])
@@ -1840,6 +1869,68 @@ class HipEncoderEngine:
         if labels is not None:
             lab = torch.as_tensor(labels).reshape(N - k * n).to(self.device, torch.int32).contiguous()
         pl["proto_logits"] = self.prototypical_head(pl, lab, int(k), int(n), alpha)
+        return pl
+
+    # ---- triplet batches (P speakers x K windows): the whole batch is ONE encoder call, mined under the current weights -----------------
+    @staticmethod
+    def _triplet_loss_key(mining, soft, margin):
+        return ("triplet", int(mining), int(bool(soft)), 0.0 if soft else float(margin))
+
+    def triplet_train_step(self, x, labels, mining: int = 0, soft: int = 0, margin: float = 0.2, preprocessed: bool = True,
+                           downsampling: int = 4, whitening: bool = True, drop_masks="auto", apply_update: bool = True):
+        """One training step on a labelled batch: x (N, L[, 1]) windows, labels (N,) the speaker of every window (any values; negative:
+        the window takes no part in the loss).  Triplets are mined inside the batch by vm_triplet_loss (``mining`` 0 = batch hard,
+        1 = batch all; ``soft``: the soft margin, ``margin`` then unused)."""
+        x = torch.as_tensor(x)
+        N = x.shape[0]
+        x = x.reshape(N, -1).to(self.device)
+        l0 = x.shape[1] if preprocessed else (x.shape[1] + downsampling - 1) // downsampling
+        pl = self.plan(N, l0, True)
+        self._triplet_bufs(pl)
+        if preprocessed:
+            self.load_preprocessed(pl, x)
+        if isinstance(drop_masks, str):
+            drop_masks = self.make_drop_masks(N)
+        lab = torch.as_tensor(labels).reshape(N).to(self.device, torch.int32).contiguous()
+        self._train_step(pl, N, lab, self._triplet_loss_key(mining, soft, margin), drop_masks, apply_update,
+                         None if preprocessed else ("raw", x, downsampling, whitening))
+        return pl
+
+    def triplet_train_step_from_offsets(self, audio: torch.Tensor, offsets, labels, raw_len: int, mining: int = 0, soft: int = 0,
+                                        margin: float = 0.2, downsampling: int = 4, whitening: bool = True, drop_masks="auto",
+                                        apply_update: bool = True):
+        """``triplet_train_step`` fed from a device-resident recording buffer (shards.ShardedSpeechDataset.build_speaker_batch_device):
+        ``offsets`` (N,) int64 start samples in batch order.  Host numpy offsets with host labels go up in one asynchronous copy from
+        the pinned ring, as in prototypical_train_step_from_offsets; tensors are taken as they are."""
+        host = isinstance(offsets, np.ndarray) and not torch.is_tensor(labels)
+        N = int(offsets.size) if isinstance(offsets, np.ndarray) else int(offsets.numel())
+        pl = self.plan(N, (raw_len + downsampling - 1) // downsampling, True)
+        self._triplet_bufs(pl)
+        ready = False
+        if host:
+            offs, lab, ready = self._stage_episode(pl, offsets, labels, N)
+        else:
+            offs = torch.as_tensor(offsets).reshape(-1).to(self.device, torch.int64).contiguous()
+            lab = torch.as_tensor(labels).reshape(N).to(self.device, torch.int32).contiguous()
+        if isinstance(drop_masks, str):
+            drop_masks = self.make_drop_masks(N)
+        self._train_step(pl, N, lab, self._triplet_loss_key(mining, soft, margin), drop_masks, apply_update,
+                         ("offsets", audio, offs, raw_len, downsampling, whitening), input_ready=ready)
+        if host:
+            self._staged_step_enqueued(pl)
+        return pl
+
+    def triplet_eval(self, x, labels, mining: int = 0, soft: int = 0, margin: float = 0.2, preprocessed: bool = True, downsampling: int = 4,
+                     whitening: bool = True):
+        """test_on_batch of a labelled batch: inference-mode forward (moving BatchNorm statistics) + the loss and the share of active
+        triplets in pl['loss_acc'], the selections in pl['triplet'].  Returns the inference plan."""
+        x = torch.as_tensor(x)
+        N = x.shape[0]
+        self.embed(x, preprocessed, downsampling, whitening, windows_per_tower=N)
+        pl = self.plan(N, self.last_infer_l0, False)
+        lab = torch.as_tensor(labels).reshape(N).to(self.device, torch.int32).contiguous()
+        key = self._triplet_loss_key(mining, soft, margin)
+        self.triplet_head(pl, lab, key[1], key[2], key[3])
         return pl
 
     def embed(self, x, preprocessed: bool = True, downsampling: int = 4, whitening: bool = True,

@@ -340,6 +340,29 @@ class LibriSpeechDataset(Sequence):
         while True:
             yield self.build_episode(k, n, q)
 
+    # ---- P speakers x K utterances for triplet mining inside the batch (not in the reference: utils.TripletLoss) ----------
+    def _speaker_batch_files(self, p, k):
+        """File ids (p, k) of a batch: the draws of an episode of p classes with k files each (``_episode_files``: p distinct speakers
+        among those with at least k files, then k distinct files of each)."""
+        if p < 2 or k < 2:
+            raise ValueError('a triplet batch needs p >= 2 speakers with k >= 2 utterances each')
+        if int((self._cnt >= k).sum()) < p:
+            raise ValueError('only {} speakers have the {} files a batch of {} speakers x {} utterances needs'
+                             .format(int((self._cnt >= k).sum()), k, p, k))
+        return self._episode_files(p, 1, k - 1)
+
+    def build_speaker_batch(self, p, k):
+        """(windows, labels) of one P x K batch: windows (p k, T, 1) class-major (speaker c owns rows c k .. c k + k - 1), labels
+        (p k, 1) = 0 .. p-1 each k times (positions in the batch, not speaker ids).  One fragment per file, drawn by ``__getitem__``'s
+        rule in row order."""
+        files = self._speaker_batch_files(p, k)
+        windows = np.stack([self[i][0] for i in files.reshape(-1)])[:, :, np.newaxis]
+        return windows, np.repeat(np.arange(p), k)[:, np.newaxis]
+
+    def yield_speaker_batches(self, p, k):
+        while True:
+            yield self.build_speaker_batch(p, k)
+
     @staticmethod
     def index_subset(subset):
         """Walk ``data/LibriSpeech/{subset}/<speaker>/<chapter>/*.flac`` and record speaker id, path and length."""

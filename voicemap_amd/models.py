@@ -143,7 +143,7 @@ class _TrainableModel:
         return kind, geo, eng.get_params(), opt, self._training_config()
 
     def _training_config(self) -> dict:
-        """{"loss": its name, "metrics": [...]} (+ "loss_config" for a loss with parameters: utils.PrototypicalLoss)."""
+        """{"loss": its name, "metrics": [...]} (+ "loss_config" for a loss with parameters: utils.PrototypicalLoss, utils.TripletLoss)."""
         loss = self.loss if isinstance(self.loss, str) or self.loss is None else getattr(self.loss, "__name__", str(self.loss))
         tc = {"loss": loss, "metrics": list(self.metrics)}
         if hasattr(self.loss, "get_config"):
@@ -477,6 +477,9 @@ class ConvolutionalEncoder(_TrainableModel):
     def _train_step(self, x, y):
         """One optimizer step enqueued; returns the engine's plan (``loss_acc`` on the device: reading it is the only host sync)."""
         if not self.classifier_units:
+            trip = self._triplet_loss()
+            if trip is not None:
+                return self._triplet_step(x, y, trip)
             proto = self._proto_loss()
             if proto is None:
                 raise RuntimeError("the bare encoder has no loss; add Dense(num_classes, activation='softmax'), wrap it in "
@@ -510,6 +513,26 @@ class ConvolutionalEncoder(_TrainableModel):
                                                downsampling=x.downsampling, whitening=x.whitening)
         return eng.prototypical_train_step(np.asarray(x, dtype=np.float32), self._labels(y), k, n, alpha)
 
+    def _triplet_loss(self):
+        """The compiled utils.TripletLoss of a bare encoder, or None."""
+        from .utils import TripletLoss
+        return self.loss if isinstance(self.loss, TripletLoss) and not self.classifier_units else None
+
+    def _triplet_step(self, x, y, trip):
+        """One optimizer step on a labelled batch (x: N windows, y: their speakers), the triplets mined inside it."""
+        eng = self._ensure_engine()
+        if not hasattr(eng, "triplet_train_step"):
+            raise NotImplementedError("the triplet loss is implemented for the 1-D encoder")
+        kw = dict(mining=trip.mining_code, soft=int(trip.soft), margin=trip.margin_value)
+        if _is_lazy(x):
+            if type(x.raw).__name__ == "DeviceWindows" and getattr(x.raw, "aug", None) is None:
+                # device data path: the crop happens inside the preprocessing kernel (vm_crop_decimate_whiten)
+                return eng.triplet_train_step_from_offsets(x.raw.audio, x.raw.offsets_host, self._labels(y), x.raw.length,
+                                                           downsampling=x.downsampling, whitening=x.whitening, **kw)
+            return eng.triplet_train_step(np.asarray(x.raw, dtype=np.float32), self._labels(y), preprocessed=False,
+                                          downsampling=x.downsampling, whitening=x.whitening, **kw)
+        return eng.triplet_train_step(np.asarray(x, dtype=np.float32), self._labels(y), **kw)
+
     def train_on_batch(self, x, y):
         la = self._train_step(x, y)["loss_acc"].cpu().numpy()
         return float(la[0]), float(la[1])
@@ -517,6 +540,19 @@ class ConvolutionalEncoder(_TrainableModel):
     def test_on_batch(self, x, y):
         eng = self._ensure_engine()
         import torch
+        trip = self._triplet_loss()
+        if trip is not None:
+            if not hasattr(eng, "triplet_eval"):
+                raise NotImplementedError("the triplet loss is implemented for the 1-D encoder")
+            kw = dict(mining=trip.mining_code, soft=int(trip.soft), margin=trip.margin_value)
+            if _is_lazy(x):
+                raw = x.raw.gather() if type(x.raw).__name__ == "DeviceWindows" and getattr(x.raw, "aug", None) is None else \
+                    np.asarray(x.raw, dtype=np.float32)
+                pl = eng.triplet_eval(raw, self._labels(y), preprocessed=False, downsampling=x.downsampling, whitening=x.whitening, **kw)
+            else:
+                pl = eng.triplet_eval(np.asarray(x, dtype=np.float32), self._labels(y), **kw)
+            la = pl["loss_acc"].cpu().numpy()
+            return float(la[0]), float(la[1])
         proto = self._proto_loss()
         if proto is not None:
             if _is_lazy(x):
@@ -814,10 +850,13 @@ def contrastive_loss_by_name(loss):
 
 
 def loss_by_name(loss, loss_config=None):
-    """The compiled loss of a checkpoint: a loss saved with its parameters (utils.PrototypicalLoss) is rebuilt from them."""
+    """The compiled loss of a checkpoint: a loss saved with its parameters (utils.PrototypicalLoss, utils.TripletLoss) is rebuilt from them."""
     if loss == "prototypical_loss" and loss_config:
         from .utils import PrototypicalLoss
         return PrototypicalLoss(**loss_config)
+    if loss == "triplet_loss" and loss_config:
+        from .utils import TripletLoss
+        return TripletLoss(**loss_config)
     return loss
 
 

@@ -264,6 +264,24 @@ class ShardedSpeechDataset(LibriSpeechDataset):
         while True:
             yield self.build_episode_device(k, n, q)
 
+    def build_speaker_batch_offsets(self, p, k, files=False):
+        """(offsets (p k,), labels (p k, 1)): the batch of ``build_speaker_batch`` as start offsets into the device buffer -- the same
+        draws in the same order (speakers, each speaker's files, then one fragment per file in row order).  ``files=True`` appends the
+        file id every window is cut from."""
+        order = self._speaker_batch_files(p, k).reshape(-1)
+        out = (self.window_starts(order), np.repeat(np.arange(p), k)[:, np.newaxis])
+        return out + (order,) if files else out
+
+    def build_speaker_batch_device(self, p, k):
+        """``build_speaker_batch`` with the windows as ``DeviceWindows`` (needs ``to_device()`` first)."""
+        assert self.device_audio is not None, 'call to_device() first'
+        offsets, labels = self.build_speaker_batch_offsets(p, k)
+        return DeviceWindows(self.device_audio, offsets, self.fragment_length), labels
+
+    def yield_speaker_batches_device(self, p, k):
+        while True:
+            yield self.build_speaker_batch_device(p, k)
+
     def build_n_shot_task_offsets(self, k, n=1):
         """The task of ``build_n_shot_task`` (librispeech.py:204-240 of the reference) as start offsets into the device
         buffer: ((query_offset, query_label), (support_offsets (k*n,), support_labels (k*n,))), support laid out

@@ -556,3 +556,4 @@ class HipSpectrogramEncoderEngine(HipEncoderEngine):
         raise NotImplementedError("the spectrogram engine takes raw windows; its front-end is vm_stft_logmel")
 
     load_preprocessed = siamese_train_step_from_offsets = embed_from_offsets = classifier_train_step = preprocess
+    triplet_train_step = triplet_train_step_from_offsets = triplet_eval = preprocess   # the triplet loss is the 1-D encoder's

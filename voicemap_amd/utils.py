@@ -8,6 +8,7 @@
     n_shot_task_evaluation(model, dataset, preprocessor, num_tasks, n, k, network_type, distance)   utils.py:104
     NShotEvaluationCallback(num_tasks, n_shot, k_way, dataset, preprocessor, mode)             utils.py:219
     PrototypicalLoss(k_way, n_shot, alpha=1.0)                                                 (not in the reference)
+    TripletLoss(margin=0.2, mining="hard")                                                     (not in the reference)
 
 What is different underneath: ``preprocess_instances`` returns a *lazy* batch (``LazyWindows``) that remembers the raw
 16 kHz windows; the HIP models decimate + whiten it on the GPU (vm_decimate_whiten) instead of in three numpy passes on
@@ -125,6 +126,60 @@ class PrototypicalLoss:
         mx = lg.max(axis=1, keepdims=True)
         lse = np.log(np.exp(lg - mx).sum(axis=1)) + mx[:, 0]
         return float(np.mean(lse - lg[np.arange(len(y)), y]))
+
+
+class TripletLoss:
+    """Triplet loss with mining inside the batch (Hermans et al. 2017: "batch hard" / "batch all"; FaceNet's margin), for
+    ``encoder.compile(loss=TripletLoss(margin, mining))`` on the bare encoder (not in the reference).  A batch is ``(x, y)``: x the
+    windows of P speakers x K utterances (``LibriSpeechDataset.build_speaker_batch``), y the speaker of every window (a negative label
+    takes its window out).  ``mining="hard"``: per anchor its farthest positive and nearest negative; ``"all"``: every triplet, the
+    hinge averaged over the active ones.  ``margin="soft"``: softplus(d_ap - d_an) instead of max(0, margin + d_ap - d_an).  Evaluated
+    with its gradient by vm_triplet_loss; the metric beside it is the share of active (x > 0) anchors / triplets."""
+
+    __name__ = "triplet_loss"
+    MININGS = ("hard", "all")
+
+    def __init__(self, margin=0.2, mining="hard"):
+        if mining not in self.MININGS:
+            raise ValueError("TripletLoss mining must be one of (hard, all)")
+        self.soft = isinstance(margin, str)
+        if self.soft and margin != "soft":
+            raise ValueError('TripletLoss margin must be a number >= 0 or "soft"')
+        if not self.soft and not (0 <= float(margin) < float("inf")):
+            raise ValueError('TripletLoss margin must be a finite number >= 0 or "soft"')
+        self.margin = "soft" if self.soft else float(margin)
+        self.mining = mining
+
+    @property
+    def mining_code(self):
+        """VM_TRIPLET_HARD / VM_TRIPLET_ALL"""
+        return self.MININGS.index(self.mining)
+
+    @property
+    def margin_value(self):
+        return 0.0 if self.soft else self.margin
+
+    def get_config(self):
+        return {"margin": self.margin, "mining": self.mining}
+
+    def __call__(self, emb, labels):
+        """The same expression with numpy (float64) on (N, E) embeddings and (N,) labels."""
+        e = np.asarray(emb, dtype=np.float64)
+        y = np.asarray(labels).reshape(-1).astype(np.int64)
+        d = np.sqrt(np.square(e[:, None, :] - e[None, :, :]).sum(-1))
+        part = y >= 0
+        both = part[:, None] & part[None, :]
+        pos = both & (y[:, None] == y[None, :]) & ~np.eye(len(y), dtype=bool)
+        neg = both & (y[:, None] != y[None, :])
+        valid = pos.any(1) & neg.any(1)
+        term = (lambda x: np.maximum(x, 0) + np.log1p(np.exp(-np.abs(x)))) if self.soft else (lambda x: np.maximum(x, 0))
+        if not valid.any():
+            return 0.0
+        if self.mining == "hard":
+            x = self.margin_value + np.where(pos, d, -np.inf).max(1)[valid] - np.where(neg, d, np.inf).min(1)[valid]
+            return float(term(x).mean())
+        x = np.concatenate([(self.margin_value + d[a, pos[a]][:, None] - d[a, neg[a]][None, :]).ravel() for a in np.flatnonzero(valid)])
+        return float(term(x).sum() / (len(x) if self.soft else max(1, (x > 0).sum())))
 
 
 def get_bottleneck(classifier, samples):
