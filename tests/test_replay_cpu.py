@@ -169,3 +169,23 @@ def test_host_calls_keep_their_place_in_a_recorded_step():
     lib.log.clear()
     prog.run(lib, {})
     assert seen == [1, 1] and lib.log == [("vm_before", 1), ("vm_after", 2)]
+
+
+def test_a_step_inputs_signature_is_what_a_recorded_step_depends_on():
+    """The replay key's part for the preprocessing: kind, dtype, and the windows' shape (raw) or length (offsets) -- the resident
+    buffer's own length is never read by the offsets path, so two corpora share one program."""
+    import torch
+    from voicemap_amd.engine import HipEncoderEngine, StepInput
+    raw = lambda dt, n=4, L=64: StepInput("raw", torch.zeros(n, L, dtype=dt), None, None, 4, True)
+    offs = lambda dt, size, raw_len: StepInput("offsets", torch.zeros(size, dtype=dt), torch.zeros(4, dtype=torch.int64), raw_len, 4, True)
+    sigs = [raw(torch.float32).signature(), raw(torch.int16).signature(), raw(torch.float32, L=128).signature(),
+            offs(torch.float32, 1000, 64).signature(), offs(torch.int16, 1000, 64).signature(), offs(torch.float32, 1000, 128).signature(),
+            raw(torch.float32)._replace(downsampling=2).signature(), raw(torch.float32)._replace(whitening=False).signature()]
+    assert len(set(sigs)) == len(sigs) and all(hash(s) is not None for s in sigs)
+    assert offs(torch.int16, 1000, 64).signature() == offs(torch.int16, 77777, 64).signature()
+    assert raw(torch.float32).signature() == ("raw", torch.float32, (4, 64), 4, True)
+    assert offs(torch.int16, 9, 64).signature() == ("offsets", torch.int16, 64, 4, True)
+    # ... and the loss's part: one uniform key, the triplet key normalised so that the same step is one program
+    assert [HipEncoderEngine._loss_key(l) for l in (None, "bce", ("prototypical", 3, 2, 1.0))] == \
+        [("classifier",), ("siamese", "bce"), ("prototypical", 3, 2, 1.0)]
+    assert HipEncoderEngine._triplet_loss_key(0, True, 0.7) == HipEncoderEngine._triplet_loss_key(0, 1, 0.2) == ("triplet", 0, 1, 0.0)

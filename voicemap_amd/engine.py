@@ -12,12 +12,12 @@ import ctypes
 import functools
 import math
 from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, staging
 from ._lib import VM_BF16, VM_F16, VM_F32, VM_F32S
 from .program import DynF, DynI, Program, ProgramStore
 
@@ -135,6 +135,23 @@ def _shared_stream(device: torch.device, role: str) -> "torch.cuda.Stream":
     if st is None:
         st = _SHARED_STREAMS[(idx, role)] = torch.cuda.Stream(device=device)
     return st
+
+
+class StepInput(NamedTuple):
+    """What a training step preprocesses into its plan's input: ``kind`` "raw" -- ``tensor`` holds (n, samples) fp32 / int16 windows on
+    the device -- or "offsets" -- ``tensor`` is a resident 1-D recording buffer and window i the ``raw_len`` samples at
+    tensor[offsets[i]]."""
+    kind: str
+    tensor: torch.Tensor
+    offsets: Optional[torch.Tensor]
+    raw_len: Optional[int]
+    downsampling: int
+    whitening: bool
+
+    def signature(self) -> tuple:
+        """What a recorded step depends on.  The offsets path never reads the audio buffer's length: its shape is not part of it."""
+        shape = tuple(self.tensor.shape) if self.kind == "raw" else self.raw_len
+        return (self.kind, self.tensor.dtype, shape, self.downsampling, self.whitening)
 
 
 class HipEncoderEngine:
@@ -1518,12 +1535,11 @@ class HipEncoderEngine:
                 self.bn_zero_debias, self.bn_eps, self.bn_momentum, self.beta_1, self.beta_2, self.adam_eps, self._side_priority,
                 self.grad_prescale, self.fused_infer_pool, self.center_blocks, self.pre_overlap, id(self.grad_sync), self.lib.tuning_epoch, id(self.side_stream), id(self.tower_stream), id(self.misc_stream))
 
-    def _train_step(self, pl: dict, wpt: int, target: torch.Tensor, loss: Optional[str], drop_masks, apply_update: bool, pre,
+    def _train_step(self, pl: dict, wpt: int, target: torch.Tensor, loss: tuple, drop_masks, apply_update: bool, pre: Optional[StepInput],
                     input_ready: bool = False, aug: Optional[dict] = None):
-        """preprocess (``pre`` = None | ("raw", tensor, downsampling, whitening) | ("offsets", audio, offsets, raw_len, downsampling,
-        whitening)) -> forward -> head (``loss`` None: the classifier's; ("prototypical", k, n, alpha): the prototypical loss,
-        ("triplet", mining, soft, margin): the triplet loss mined inside the batch, neither with head parameters) -> backward ->
-        optimizer.  The SECOND time a configuration
+        """preprocess (``pre``: a StepInput, or None when the plan's input is loaded) -> forward -> head (``loss``: the key of
+        ``_loss_key`` -- ("classifier",), ("siamese", name), ("prototypical", k, n, alpha), ("triplet", mining, soft, margin); the last
+        two without head parameters) -> backward -> optimizer.  The SECOND time a configuration
         is seen its enqueue sequence is recorded (program.Program), from the third on it is replayed: same launches, same arguments, same
         stream ordering -- only the input / label / mask pointers and four scalars are patched in."""
         # (a gradient hook that declares itself ``replayable`` -- parallel.GradAllReduce: its two collectives are host calls kept in
@@ -1532,9 +1548,7 @@ class HipEncoderEngine:
                   and not self.sync_bn)
         prog = key = None
         if usable:
-            # (the offsets path never reads the audio buffer's length: its shape is not part of what a program depends on)
-            sig = None if pre is None else ((pre[0], pre[1].dtype, tuple(pre[1].shape)) + tuple(pre[-2:]) if pre[0] == "raw"
-                                            else (pre[0], pre[1].dtype, pre[3]) + tuple(pre[-2:]))
+            sig = None if pre is None else pre.signature()
             if aug is not None:   # what the augmented launch bakes into a program: K, the buffers' kinds, the RIR bank
                 sig = sig + ("aug", int(aug["K"]), aug["noise"].dtype if aug["K"] else None,
                              None if aug.get("rirs") is None else (aug["rirs"].data_ptr(), tuple(aug["rirs"].shape)))
@@ -1559,27 +1573,14 @@ class HipEncoderEngine:
                     pre_cm.__enter__()
                     self._wait(self.tower_stream, pl["x0_free_ev"])
                 try:
-                    if pre[0] == "raw":
-                        self.preprocess(pl, pre[1], pre[2], pre[3], wpt)
-                    else:
-                        self.preprocess(pl, pre[1], pre[4], pre[5], wpt, offsets=pre[2], raw_len=pre[3], aug=aug)
+                    self.preprocess(pl, pre.tensor, pre.downsampling, pre.whitening, wpt, offsets=pre.offsets, raw_len=pre.raw_len, aug=aug)
                 finally:
                     if ahead:
                         pre_cm.__exit__(None, None, None)
                 if ahead:
                     self._join(cur, self.tower_stream)
-            if loss is None:
-                self.forward(pl, wpt, drop_masks)
-                self.classifier_head(pl, target)
-            elif isinstance(loss, tuple) and loss[0] == "triplet":   # ("triplet", mining, soft, margin): part of the replay key above
-                self.forward(pl, wpt, drop_masks)
-                self.triplet_head(pl, target, loss[1], loss[2], loss[3])
-            elif isinstance(loss, tuple):   # ("prototypical", k, n, alpha): part of the replay key above
-                self.forward(pl, wpt, drop_masks)
-                self.prototypical_head(pl, target, loss[1], loss[2], loss[3])
-            else:
-                self.forward(pl, wpt, drop_masks, defer_tail=True)
-                self.siamese_head(pl, target, loss)
+            self.forward(pl, wpt, drop_masks, defer_tail=loss[0] == "siamese")
+            getattr(self, loss[0] + "_head")(pl, target, *loss[1:])   # classifier_head | siamese_head | prototypical_head | triplet_head
             self.backward(pl, sync_tail=apply_update)
             if apply_update:
                 self.optimizer_step()
@@ -1608,9 +1609,15 @@ class HipEncoderEngine:
         beside the previous step's optimizer tail (``pre_overlap``) instead of behind it."""
         if isinstance(drop_masks, str):
             drop_masks = self.make_drop_masks(pl["n"])
-        self._train_step(pl, windows_per_tower, target, loss, drop_masks, apply_update,
-                         None if raw is None else ("raw", raw, downsampling, whitening), input_ready=input_ready)
+        self._train_step(pl, windows_per_tower, target, self._loss_key(loss), drop_masks, apply_update,
+                         None if raw is None else StepInput("raw", raw, None, None, downsampling, whitening), input_ready=input_ready)
         return pl
+
+    @staticmethod
+    def _loss_key(loss) -> tuple:
+        """The uniform key of a step's loss, as _train_step dispatches on it and a recorded step is filed under it: None -> the
+        classifier's, a name -> that siamese loss, a tuple -> itself (("prototypical", k, n, alpha), ("triplet", mining, soft, margin))."""
+        return ("classifier",) if loss is None else loss if isinstance(loss, tuple) else ("siamese", loss)
 
     def _replay_step(self, prog: Program, pl: dict, wpt: int, target, drop_masks, apply_update: bool, pre, aug=None):
         dyn = {"y": target.data_ptr(), "loss_scale": float(self.loss_scale)}
@@ -1621,14 +1628,14 @@ class HipEncoderEngine:
                     dyn[k] = aug[name].data_ptr()
                     keep.append(aug[name])
         if pre is not None:
-            raw = pre[1]
-            if pre[0] == "raw":
+            raw = pre.tensor
+            if pre.kind == "raw":
                 raw = raw.reshape(pl["n"], -1).contiguous()
                 if raw.dtype != torch.int16:
                     raw = raw.to(torch.float32)
             else:
-                dyn["offsets"] = pre[2].data_ptr()
-                keep.append(pre[2])
+                dyn["offsets"] = pre.offsets.data_ptr()
+                keep.append(pre.offsets)
             dyn["raw"] = raw.data_ptr()
             keep.append(raw)
         if drop_masks is not None:
@@ -1653,24 +1660,112 @@ class HipEncoderEngine:
             if self.loss_scaled:
                 self._poll_loss_scale()
 
+    # ---- intake: host windows / resident offsets -> (plan, step input) -----------------------------------------------------------
+    def _intake(self, x, training: bool, preprocessed: bool, downsampling: int, whitening: bool, loss: Optional[tuple] = None):
+        """Host windows x (n, L[, 1]) -> (plan, StepInput): the windows go to the device in their own dtype (int16 raw windows stay
+        int16); preprocessed ones are loaded into the plan's input, and the step input is None.  ``loss``: its buffers are checked
+        first (_loss_bufs), so an unserved episode / batch raises before the plan's input is overwritten."""
+        x = torch.as_tensor(x)
+        n = x.shape[0]
+        x = x.reshape(n, -1).to(self.device)
+        l0 = x.shape[1] if preprocessed else (x.shape[1] + downsampling - 1) // downsampling
+        pl = self.plan(n, l0, training)
+        if loss is not None:
+            self._loss_bufs(pl, loss)
+        if preprocessed:
+            self.load_preprocessed(pl, x)
+            return pl, None
+        return pl, StepInput("raw", x, None, None, downsampling, whitening)
+
+    def _pair_windows(self, x1, x2):
+        """The two towers' windows (pairs, L[, 1]) as one batch (2 pairs, L), tower 1 first."""
+        x1, x2 = torch.as_tensor(x1), torch.as_tensor(x2)
+        pairs = x1.shape[0]
+        return torch.cat([x1.reshape(pairs, -1), x2.reshape(pairs, -1)], 0)
+
+    def _loss_bufs(self, pl: dict, loss: tuple):
+        """The per-plan buffers of a loss that has some; ValueError where its kernel does not serve the plan."""
+        if loss[0] == "prototypical":
+            self._proto_bufs(pl, loss[1], loss[2])
+        elif loss[0] == "triplet":
+            self._triplet_bufs(pl)
+
+    @staticmethod
+    def _step_shape(n: int, loss: tuple):
+        """(windows per tower, number of labels, their dtype) of a step of ``n`` windows: the siamese losses take two towers and fp32
+        (pairs,) labels, the others one encoder call and int32 class ids -- one per query of an episode, else one per window."""
+        if loss[0] == "siamese":
+            return n // 2, n // 2, torch.float32
+        return n, n - loss[1] * loss[2] if loss[0] == "prototypical" else n, torch.int32
+
+    def _host_step(self, x, y, loss: tuple, preprocessed: bool, downsampling: int, whitening: bool, drop_masks, apply_update: bool):
+        """One training step on host windows and host labels; returns the plan."""
+        pl, pre = self._intake(x, True, preprocessed, downsampling, whitening, loss)
+        wpt, n_lab, dt = self._step_shape(pl["n"], loss)
+        if isinstance(drop_masks, str):
+            drop_masks = self.make_drop_masks(pl["n"])
+        self._train_step(pl, wpt, self._target(y, n_lab, dt), loss, drop_masks, apply_update, pre)
+        return pl
+
+    def _target(self, y, n: int, dt) -> torch.Tensor:
+        """Labels -> (n,) device tensor: fp32 for the siamese losses (converted on the host), int32 class ids (on the device)."""
+        if dt == torch.float32:
+            return torch.as_tensor(y, dtype=dt).reshape(n).to(self.device).contiguous()
+        return torch.as_tensor(y).reshape(n).to(self.device, dt).contiguous()
+
+    def _offsets_step(self, audio: torch.Tensor, offsets: tuple, y, raw_len: int, loss: tuple, downsampling: int, whitening: bool,
+                      drop_masks, apply_update: bool, aug=None):
+        """One training step from a resident recording buffer; ``offsets``: the (n,) int64 start samples of each tower (one or two).
+        Host numpy offsets with host labels (what fit_generator hands over) go up in ONE asynchronous copy from the plan's pinned ring
+        for this layout (staging.Ring) -- with ``pre_overlap`` on the tower stream, in front of the preprocessing that runs there ahead
+        of the main stream; tensors are taken as they are.  With ``aug`` (the two towers' augment.AugmentRecord) the per-window
+        parameters ride in the same copy, a ring of its own per K, and come back as the ``aug`` of preprocess()."""
+        host = all(isinstance(o, np.ndarray) for o in offsets) and not torch.is_tensor(y)
+        n = sum(int(o.size) if isinstance(o, np.ndarray) else int(o.numel()) for o in offsets)
+        pl = self.plan(n, (raw_len + downsampling - 1) // downsampling, True)
+        self._loss_bufs(pl, loss)
+        wpt, n_lab, dt = self._step_shape(n, loss)
+        name = "h2d" if loss[0] == "siamese" else ("h2d_episode", n_lab)
+        if aug is not None:
+            a1, a2 = aug
+            if not host:
+                raise ValueError("augmented steps take host offsets and labels (they are uploaded together with the parameters)")
+            if not (len(a1) == len(a2) == wpt and a1.K == a2.K and a1.noise is a2.noise and a1.rirs is a2.rirs):
+                raise ValueError("the two towers' augmentation records must come from one draw (same K, noise buffer and RIR bank)")
+            if a1.downsampling != downsampling:
+                raise ValueError("the augmentation was drawn for downsampling %d, the step decimates by %d" % (a1.downsampling, downsampling))
+            name = ("h2d_aug", a1.K)
+        ready, augdev = False, None
+        if host:
+            segments = staging.step_segments(offsets, y, n_lab, np.float32 if dt == torch.float32 else np.int32, aug)
+            ring = pl.get(name)
+            if ring is None:
+                ring = pl[name] = staging.Ring(staging.layout(segments)[1], self.device)
+            ready = bool(self.pre_overlap and not self.timed)
+            dev, slot = ring.upload(segments, self.tower_stream if ready else None)
+            offs, target = dev["offsets"], dev["labels"]
+            if aug is not None:
+                augdev = {"K": a1.K, "noise": a1.noise, "rirs": a1.rirs, "snr": dev["snr_lin"], "gain": dev["gain"], "rir_id": dev["rir_id"],
+                          "noff": dev.get("noise_offsets")}
+        else:
+            offs = [torch.as_tensor(o).reshape(-1) for o in offsets]
+            offs = (torch.cat(offs) if len(offs) > 1 else offs[0]).to(self.device, torch.int64).contiguous()
+            target = self._target(y, n_lab, dt)
+        if isinstance(drop_masks, str):
+            drop_masks = self.make_drop_masks(n)
+        self._train_step(pl, wpt, target, loss, drop_masks, apply_update, StepInput("offsets", audio, offs, raw_len, downsampling, whitening),
+                         input_ready=ready, aug=augdev)
+        if host:
+            ring.enqueued(slot)
+        return pl
+
     def siamese_train_step(self, x1, x2, y, loss: str = "contrastive", preprocessed: bool = True, downsampling: int = 4,
                            whitening: bool = True, drop_masks="auto", apply_update: bool = True):
         """One ``train_on_batch`` of the siamese scripts.  x1/x2: (pairs, L, 1) windows (already decimated+whitened if
         ``preprocessed``, else raw fp32/int16 16 kHz windows that are decimated+whitened on the GPU, each tower
         separately like voicemap/utils.py:59-60).  y: (pairs, 1) labels, 0 = same speaker."""
-        x1 = torch.as_tensor(x1)
-        x2 = torch.as_tensor(x2)
-        pairs = x1.shape[0]
-        x = torch.cat([x1.reshape(pairs, -1), x2.reshape(pairs, -1)], 0).to(self.device)
-        l0 = x.shape[1] if preprocessed else (x.shape[1] + downsampling - 1) // downsampling
-        pl = self.plan(2 * pairs, l0, True)
-        if preprocessed:
-            self.load_preprocessed(pl, x)
-        if isinstance(drop_masks, str):
-            drop_masks = self.make_drop_masks(2 * pairs)
-        yd = torch.as_tensor(y, dtype=torch.float32).reshape(pairs).to(self.device).contiguous()
-        self._train_step(pl, pairs, yd, loss, drop_masks, apply_update, None if preprocessed else ("raw", x, downsampling, whitening))
-        return pl
+        return self._host_step(self._pair_windows(x1, x2), y, ("siamese", loss), preprocessed, downsampling, whitening, drop_masks,
+                               apply_update)
 
     def siamese_train_step_from_offsets(self, audio: torch.Tensor, offsets_1, offsets_2, y,
                                         raw_len: int, loss: str = "contrastive", downsampling: int = 4, whitening: bool = True,
@@ -1678,196 +1773,39 @@ class HipEncoderEngine:
         """``siamese_train_step`` fed from a device-resident recording buffer: ``audio`` 1-D int16/fp32 on the device,
         ``offsets_k`` (pairs,) int64 start samples of the windows of tower k (shards.ShardedSpeechDataset chooses them the way
         LibriSpeechDataset.__getitem__ / build_verification_batch do).  Host numpy offsets with host labels (what fit_generator
-        hands over) go up in one asynchronous copy (_stage_offsets_and_labels); tensors are taken as they are.
+        hands over) go up in one asynchronous copy (_offsets_step); tensors are taken as they are.
         ``aug``: (record of tower 1, record of tower 2) (augment.AugmentRecord, e.g. ``DeviceWindows.aug``): the windows are augmented
         inside the crop; the per-window parameters travel in that same single copy (host offsets and labels required)."""
-        host = isinstance(offsets_1, np.ndarray) and isinstance(offsets_2, np.ndarray)
-        pairs = int(offsets_1.size) if host else int(offsets_1.numel())
-        pl = self.plan(2 * pairs, (raw_len + downsampling - 1) // downsampling, True)
-        staged = ready = False
-        augdev = None
-        if aug is not None:
-            a1, a2 = aug
-            if not (host and not torch.is_tensor(y)):
-                raise ValueError("augmented steps take host offsets and labels (they are uploaded together with the parameters)")
-            if not (len(a1) == len(a2) == pairs and a1.K == a2.K and a1.noise is a2.noise and a1.rirs is a2.rirs):
-                raise ValueError("the two towers' augmentation records must come from one draw (same K, noise buffer and RIR bank)")
-            if a1.downsampling != downsampling:
-                raise ValueError("the augmentation was drawn for downsampling %d, the step decimates by %d" % (a1.downsampling, downsampling))
-            offs, yd, ready, augdev = self._stage_offsets_and_labels(pl, offsets_1, offsets_2, y, pairs, aug=(a1, a2))
-            staged = True
-        elif host and not torch.is_tensor(y):
-            offs, yd, ready = self._stage_offsets_and_labels(pl, offsets_1, offsets_2, y, pairs)
-            staged = True
-        else:
-            offs = torch.cat([torch.as_tensor(offsets_1).reshape(-1), torch.as_tensor(offsets_2).reshape(-1)]).to(self.device, torch.int64).contiguous()
-            yd = torch.as_tensor(y, dtype=torch.float32).reshape(pairs).to(self.device).contiguous()
-        if isinstance(drop_masks, str):
-            drop_masks = self.make_drop_masks(2 * pairs)
-        self._train_step(pl, pairs, yd, loss, drop_masks, apply_update, ("offsets", audio, offs, raw_len, downsampling, whitening),
-                         input_ready=ready, aug=augdev)
-        if staged:
-            self._staged_step_enqueued(pl)
-        return pl
-
-    def _stage_offsets_and_labels(self, pl: dict, o1: "np.ndarray", o2: "np.ndarray", y, pairs: int, aug=None):
-        """Host arrays -> device buffers (2 * pairs int64 offsets, pairs fp32 labels) in ONE asynchronous copy from a ring of pinned
-        staging buffers.  torch's ``.to(device)`` of a pageable array is a blocking copy that is ordered behind everything already
-        enqueued on the stream: three of them per step made the host wait for the GPU to drain, then left the GPU idle while the host
-        prepared the next step (fit_generator at 64 pairs: 1.67 ms per step against 1.45 ms of GPU work).  Round 6: the device side is
-        a ring as well (a step reads ITS slot, so the next step's copy needs no ordering against this step's kernels) and, with
-        ``pre_overlap``, the copy goes to the tower stream in front of the preprocessing that runs there ahead of the main stream.
-        A slot is reused after 32 steps; the step that last read it has its end-of-enqueue event waited for first (long done).
-        Returns (offsets, labels, input_ready).  With ``aug`` (the two towers' augment.AugmentRecord) the per-window augmentation
-        parameters ride in the same copy -- [offsets | labels | snr_lin | gain | rir_id | noise offsets (2 pairs, K)], a ring of its own
-        per K -- and the device views come back as a fourth value (the ``aug`` of preprocess())."""
-        K = aug[0].K if aug is not None else 0
-        ring = "h2d" if aug is None else ("h2d_aug", K)
-        st = pl.get(ring)
-        if st is None:
-            nbytes = 2 * pairs * 8 + pairs * 4
-            if aug is not None:
-                nbytes += pairs * 4 + 3 * 2 * pairs * 4 + 2 * pairs * K * 8   # (the labels padded to 8 bytes per pair: int64 alignment)
-            st = pl[ring] = {"dev": [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(32)],
-                             "pin": [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(32)],
-                             "ev": [None] * 32, "k": 0}
-        pl["h2d_cur"] = st
-        k = st["k"] % 32
-        st["k"] += 1
-        if st["ev"][k] is not None:
-            st["ev"][k].synchronize()
-        buf = st["pin"][k].numpy()
-        buf[:pairs * 8] = np.ascontiguousarray(o1, dtype=np.int64).reshape(-1).view(np.uint8)
-        buf[pairs * 8:2 * pairs * 8] = np.ascontiguousarray(o2, dtype=np.int64).reshape(-1).view(np.uint8)
-        buf[2 * pairs * 8:2 * pairs * 8 + pairs * 4] = np.ascontiguousarray(np.asarray(y, dtype=np.float32).reshape(pairs)).view(np.uint8)
-        if aug is not None:
-            b0 = 2 * pairs * 8 + 2 * pairs * 4   # past the labels and their padding
-            w = 2 * pairs * 4
-            for j, name in enumerate(("snr_lin", "gain", "rir_id")):
-                buf[b0 + j * w:b0 + (j + 1) * w] = np.concatenate([getattr(aug[0], name), getattr(aug[1], name)]).view(np.uint8)
-            if K:
-                buf[b0 + 3 * w:] = np.ascontiguousarray(np.concatenate([aug[0].noise_offsets, aug[1].noise_offsets])).reshape(-1).view(np.uint8)
-        dev = st["dev"][k]
-        ahead = bool(self.pre_overlap and not self.timed)
-        if ahead:
-            with torch.cuda.stream(self.tower_stream):
-                dev.copy_(st["pin"][k], non_blocking=True)
-        else:
-            dev.copy_(st["pin"][k], non_blocking=True)
-        st["cur"] = k
-        if aug is not None:
-            augdev = {"K": K, "noise": aug[0].noise, "rirs": aug[0].rirs,
-                      "snr": dev[b0:b0 + w].view(torch.float32), "gain": dev[b0 + w:b0 + 2 * w].view(torch.float32),
-                      "rir_id": dev[b0 + 2 * w:b0 + 3 * w].view(torch.int32), "noff": dev[b0 + 3 * w:].view(torch.int64) if K else None}
-            return dev[:2 * pairs * 8].view(torch.int64), dev[2 * pairs * 8:2 * pairs * 8 + pairs * 4].view(torch.float32), ahead, augdev
-        return dev[:2 * pairs * 8].view(torch.int64), dev[2 * pairs * 8:].view(torch.float32), ahead
-
-    def _staged_step_enqueued(self, pl: dict):
-        """The step that reads the staging slot is enqueued: its slot may be refilled once everything enqueued so far has run."""
-        st = pl["h2d_cur"]
-        k = st["cur"]
-        ev = st["ev"][k] = st["ev"][k] or torch.cuda.Event()
-        ev.record()
+        return self._offsets_step(audio, (offsets_1, offsets_2), y, raw_len, ("siamese", loss), downsampling, whitening, drop_masks,
+                                  apply_update, aug)
 
     def classifier_train_step(self, x, labels, preprocessed: bool = True, downsampling: int = 4, whitening: bool = True,
                               drop_masks="auto", apply_update: bool = True):
         """One ``train_on_batch`` of experiments/train_classifier.py (labels: int class ids)."""
-        x = torch.as_tensor(x)
-        n = x.shape[0]
-        x = x.reshape(n, -1).to(self.device)
-        l0 = x.shape[1] if preprocessed else (x.shape[1] + downsampling - 1) // downsampling
-        pl = self.plan(n, l0, True)
-        if preprocessed:
-            self.load_preprocessed(pl, x)
-        if isinstance(drop_masks, str):
-            drop_masks = self.make_drop_masks(n)
-        lab = torch.as_tensor(labels).reshape(n).to(self.device, torch.int32).contiguous()
-        self._train_step(pl, n, lab, None, drop_masks, apply_update, None if preprocessed else ("raw", x, downsampling, whitening))
-        return pl
+        return self._host_step(x, labels, ("classifier",), preprocessed, downsampling, whitening, drop_masks, apply_update)
 
     # ---- prototypical episodes: the whole episode is ONE encoder call (one whitening batch, one set of BatchNorm statistics) ----------
     def prototypical_train_step(self, x, labels, k: int, n: int, alpha: float = 1.0, preprocessed: bool = True, downsampling: int = 4,
                                 whitening: bool = True, drop_masks="auto", apply_update: bool = True):
         """One training step on a k-way n-shot episode: x (k n + m, L[, 1]) windows, rows [0, k n) the class-major support set
         (librispeech.build_episode), the rest queries; labels (m,) the queries' classes in [0, k)."""
-        x = torch.as_tensor(x)
-        N = x.shape[0]
-        x = x.reshape(N, -1).to(self.device)
-        l0 = x.shape[1] if preprocessed else (x.shape[1] + downsampling - 1) // downsampling
-        pl = self.plan(N, l0, True)
-        m = self._proto_bufs(pl, int(k), int(n))["m"]
-        if preprocessed:
-            self.load_preprocessed(pl, x)
-        if isinstance(drop_masks, str):
-            drop_masks = self.make_drop_masks(N)
-        lab = torch.as_tensor(labels).reshape(m).to(self.device, torch.int32).contiguous()
-        self._train_step(pl, N, lab, ("prototypical", int(k), int(n), float(alpha)), drop_masks, apply_update,
-                         None if preprocessed else ("raw", x, downsampling, whitening))
-        return pl
+        return self._host_step(x, labels, ("prototypical", int(k), int(n), float(alpha)), preprocessed, downsampling, whitening, drop_masks,
+                               apply_update)
 
     def prototypical_train_step_from_offsets(self, audio: torch.Tensor, offsets, labels, raw_len: int, k: int, n: int, alpha: float = 1.0,
                                              downsampling: int = 4, whitening: bool = True, drop_masks="auto", apply_update: bool = True):
         """``prototypical_train_step`` fed from a device-resident recording buffer (shards.ShardedSpeechDataset.build_episode_device):
         ``offsets`` (k n + m,) int64 start samples in episode order.  Host numpy offsets with host labels go up in one asynchronous
         copy from the pinned ring, as in siamese_train_step_from_offsets; tensors are taken as they are."""
-        host = isinstance(offsets, np.ndarray) and not torch.is_tensor(labels)
-        N = int(offsets.size) if isinstance(offsets, np.ndarray) else int(offsets.numel())
-        pl = self.plan(N, (raw_len + downsampling - 1) // downsampling, True)
-        m = self._proto_bufs(pl, int(k), int(n))["m"]
-        ready = False
-        if host:
-            offs, lab, ready = self._stage_episode(pl, offsets, labels, m)
-        else:
-            offs = torch.as_tensor(offsets).reshape(-1).to(self.device, torch.int64).contiguous()
-            lab = torch.as_tensor(labels).reshape(m).to(self.device, torch.int32).contiguous()
-        if isinstance(drop_masks, str):
-            drop_masks = self.make_drop_masks(N)
-        self._train_step(pl, N, lab, ("prototypical", int(k), int(n), float(alpha)), drop_masks, apply_update,
-                         ("offsets", audio, offs, raw_len, downsampling, whitening), input_ready=ready)
-        if host:
-            self._staged_step_enqueued(pl)
-        return pl
-
-    def _stage_episode(self, pl: dict, offsets: "np.ndarray", labels, m: int):
-        """_stage_offsets_and_labels for an episode: [N int64 offsets | m int32 labels] in one asynchronous copy, a ring of its own
-        per m.  Returns (offsets, labels, input_ready)."""
-        N = pl["n"]
-        ring = ("h2d_episode", m)
-        st = pl.get(ring)
-        if st is None:
-            nbytes = N * 8 + m * 4
-            st = pl[ring] = {"dev": [torch.empty(nbytes, dtype=torch.uint8, device=self.device) for _ in range(32)],
-                             "pin": [torch.empty(nbytes, dtype=torch.uint8).pin_memory() for _ in range(32)],
-                             "ev": [None] * 32, "k": 0}
-        pl["h2d_cur"] = st
-        s = st["k"] % 32
-        st["k"] += 1
-        if st["ev"][s] is not None:
-            st["ev"][s].synchronize()
-        buf = st["pin"][s].numpy()
-        buf[:N * 8] = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1).view(np.uint8)
-        buf[N * 8:] = np.ascontiguousarray(np.asarray(labels).reshape(m).astype(np.int32)).view(np.uint8)
-        dev = st["dev"][s]
-        ahead = bool(self.pre_overlap and not self.timed)
-        if ahead:
-            with torch.cuda.stream(self.tower_stream):
-                dev.copy_(st["pin"][s], non_blocking=True)
-        else:
-            dev.copy_(st["pin"][s], non_blocking=True)
-        st["cur"] = s
-        return dev[:N * 8].view(torch.int64), dev[N * 8:].view(torch.int32), ahead
+        return self._offsets_step(audio, (offsets,), labels, raw_len, ("prototypical", int(k), int(n), float(alpha)), downsampling,
+                                  whitening, drop_masks, apply_update)
 
     def prototypical_eval(self, x, labels, k: int, n: int, alpha: float = 1.0, preprocessed: bool = True, downsampling: int = 4,
                           whitening: bool = True):
         """test_on_batch of an episode: inference-mode forward (moving BatchNorm statistics) + loss / accuracy in pl['loss_acc'];
         ``labels`` None: the logits only.  Returns the inference plan (the logits: prototypical_head's return, kept per (k, n))."""
-        x = torch.as_tensor(x)
-        N = x.shape[0]
-        self.embed(x, preprocessed, downsampling, whitening, windows_per_tower=N)
-        pl = self.plan(N, self.last_infer_l0, False)
-        lab = None
-        if labels is not None:
-            lab = torch.as_tensor(labels).reshape(N - k * n).to(self.device, torch.int32).contiguous()
+        pl = self._infer(x, preprocessed, downsampling, whitening)
+        lab = None if labels is None else self._target(labels, pl["n"] - k * n, torch.int32)
         pl["proto_logits"] = self.prototypical_head(pl, lab, int(k), int(n), alpha)
         return pl
 
@@ -1881,20 +1819,8 @@ class HipEncoderEngine:
         """One training step on a labelled batch: x (N, L[, 1]) windows, labels (N,) the speaker of every window (any values; negative:
         the window takes no part in the loss).  Triplets are mined inside the batch by vm_triplet_loss (``mining`` 0 = batch hard,
         1 = batch all; ``soft``: the soft margin, ``margin`` then unused)."""
-        x = torch.as_tensor(x)
-        N = x.shape[0]
-        x = x.reshape(N, -1).to(self.device)
-        l0 = x.shape[1] if preprocessed else (x.shape[1] + downsampling - 1) // downsampling
-        pl = self.plan(N, l0, True)
-        self._triplet_bufs(pl)
-        if preprocessed:
-            self.load_preprocessed(pl, x)
-        if isinstance(drop_masks, str):
-            drop_masks = self.make_drop_masks(N)
-        lab = torch.as_tensor(labels).reshape(N).to(self.device, torch.int32).contiguous()
-        self._train_step(pl, N, lab, self._triplet_loss_key(mining, soft, margin), drop_masks, apply_update,
-                         None if preprocessed else ("raw", x, downsampling, whitening))
-        return pl
+        return self._host_step(x, labels, self._triplet_loss_key(mining, soft, margin), preprocessed, downsampling, whitening, drop_masks,
+                               apply_update)
 
     def triplet_train_step_from_offsets(self, audio: torch.Tensor, offsets, labels, raw_len: int, mining: int = 0, soft: int = 0,
                                         margin: float = 0.2, downsampling: int = 4, whitening: bool = True, drop_masks="auto",
@@ -1902,51 +1828,31 @@ class HipEncoderEngine:
         """``triplet_train_step`` fed from a device-resident recording buffer (shards.ShardedSpeechDataset.build_speaker_batch_device):
         ``offsets`` (N,) int64 start samples in batch order.  Host numpy offsets with host labels go up in one asynchronous copy from
         the pinned ring, as in prototypical_train_step_from_offsets; tensors are taken as they are."""
-        host = isinstance(offsets, np.ndarray) and not torch.is_tensor(labels)
-        N = int(offsets.size) if isinstance(offsets, np.ndarray) else int(offsets.numel())
-        pl = self.plan(N, (raw_len + downsampling - 1) // downsampling, True)
-        self._triplet_bufs(pl)
-        ready = False
-        if host:
-            offs, lab, ready = self._stage_episode(pl, offsets, labels, N)
-        else:
-            offs = torch.as_tensor(offsets).reshape(-1).to(self.device, torch.int64).contiguous()
-            lab = torch.as_tensor(labels).reshape(N).to(self.device, torch.int32).contiguous()
-        if isinstance(drop_masks, str):
-            drop_masks = self.make_drop_masks(N)
-        self._train_step(pl, N, lab, self._triplet_loss_key(mining, soft, margin), drop_masks, apply_update,
-                         ("offsets", audio, offs, raw_len, downsampling, whitening), input_ready=ready)
-        if host:
-            self._staged_step_enqueued(pl)
-        return pl
+        return self._offsets_step(audio, (offsets,), labels, raw_len, self._triplet_loss_key(mining, soft, margin), downsampling,
+                                  whitening, drop_masks, apply_update)
 
     def triplet_eval(self, x, labels, mining: int = 0, soft: int = 0, margin: float = 0.2, preprocessed: bool = True, downsampling: int = 4,
                      whitening: bool = True):
         """test_on_batch of a labelled batch: inference-mode forward (moving BatchNorm statistics) + the loss and the share of active
         triplets in pl['loss_acc'], the selections in pl['triplet'].  Returns the inference plan."""
-        x = torch.as_tensor(x)
-        N = x.shape[0]
-        self.embed(x, preprocessed, downsampling, whitening, windows_per_tower=N)
-        pl = self.plan(N, self.last_infer_l0, False)
-        lab = torch.as_tensor(labels).reshape(N).to(self.device, torch.int32).contiguous()
-        key = self._triplet_loss_key(mining, soft, margin)
-        self.triplet_head(pl, lab, key[1], key[2], key[3])
+        pl = self._infer(x, preprocessed, downsampling, whitening)
+        self.triplet_head(pl, self._target(labels, pl["n"], torch.int32), *self._triplet_loss_key(mining, soft, margin)[1:])
+        return pl
+
+    def _infer(self, x, preprocessed: bool, downsampling: int, whitening: bool, windows_per_tower: Optional[int] = None) -> dict:
+        """Inference-mode forward on host windows x (n, L[, 1]); returns the inference plan (the embeddings: pl['emb'])."""
+        pl, pre = self._intake(x, False, preprocessed, downsampling, whitening)
+        self.last_infer_l0 = pl["l0"]
+        if pre is not None:
+            self.preprocess(pl, pre.tensor, downsampling, whitening, windows_per_tower or pl["n"])
+        self.forward(pl, pl["n"], None)
         return pl
 
     def embed(self, x, preprocessed: bool = True, downsampling: int = 4, whitening: bool = True,
               windows_per_tower: Optional[int] = None) -> torch.Tensor:
         """Inference-mode embeddings (encoder.predict): x (n, L[, 1]) -> (n, E) fp32 device tensor."""
-        x = torch.as_tensor(x)
-        n = x.shape[0]
-        x = x.reshape(n, -1).to(self.device)
-        l0 = x.shape[1] if preprocessed else (x.shape[1] + downsampling - 1) // downsampling
-        pl = self.plan(n, l0, False)
-        self.last_infer_l0 = l0
-        if preprocessed:
-            self.load_preprocessed(pl, x)
-        else:
-            self.preprocess(pl, x, downsampling, whitening, windows_per_tower or n)
-        return self.forward(pl, n, None)
+        return self._infer(x, preprocessed, downsampling, whitening, windows_per_tower)["emb"]
+
 
     def embed_from_offsets(self, audio: torch.Tensor, offsets: torch.Tensor, raw_len: int, downsampling: int = 4,
                            whitening: bool = True, windows_per_tower: Optional[int] = None) -> torch.Tensor:
@@ -2116,13 +2022,10 @@ class HipEncoderEngine:
                      whitening: bool = True):
         """test_on_batch of the siamese model: inference-mode forward + loss / accuracy (no gradients are used; the
         head kernel writes its backward outputs into scratch)."""
-        x1 = torch.as_tensor(x1)
-        x2 = torch.as_tensor(x2)
-        pairs = x1.shape[0]
-        x = torch.cat([x1.reshape(pairs, -1), x2.reshape(pairs, -1)], 0)
-        self.embed(x, preprocessed, downsampling, whitening, windows_per_tower=pairs)
-        pl = self.plan(2 * pairs, self.last_infer_l0, False)
-        yd = torch.as_tensor(y, dtype=torch.float32).reshape(pairs).to(self.device).contiguous()
+        x = self._pair_windows(x1, x2)
+        pairs = x.shape[0] // 2
+        pl = self._infer(x, preprocessed, downsampling, whitening, pairs)
+        yd = self._target(y, pairs, torch.float32)
         if "scratch" not in pl:
             pl["scratch"] = torch.empty(2 * pairs * self.E + self.E + 8, dtype=torch.float32, device=self.device)
         sc = pl["scratch"]
@@ -2141,13 +2044,14 @@ class HipEncoderEngine:
                    None, _p(pl["cce_ws"]), self.stream())
         return pl["prob"]
 
+    def classifier_eval(self, x, labels, preprocessed: bool = True, downsampling: int = 4, whitening: bool = True):
+        """test_on_batch of the classifier: inference-mode forward + loss / accuracy in pl['loss_acc'].  Returns the inference plan."""
+        pl = self._infer(x, preprocessed, downsampling, whitening)
+        self.classifier_head_eval(pl, torch.as_tensor(labels).to(self.device, torch.int32))
+        return pl
+
     def siamese_predict(self, x1, x2, preprocessed: bool = True, downsampling: int = 4, whitening: bool = True):
         """siamese.predict([x1, x2]) -> (pairs, 1) probabilities (inference-mode BN)."""
-        x1 = torch.as_tensor(x1)
-        x2 = torch.as_tensor(x2)
-        pairs = x1.shape[0]
-        x = torch.cat([x1.reshape(pairs, -1), x2.reshape(pairs, -1)], 0)
-        self.embed(x, preprocessed, downsampling, whitening, windows_per_tower=pairs)
-        l0 = x.shape[1] if preprocessed else (x.shape[1] + downsampling - 1) // downsampling
-        pl = self.plan(2 * pairs, l0, False)
-        return self.siamese_head(pl, None).reshape(pairs, 1)
+        x = self._pair_windows(x1, x2)
+        pairs = x.shape[0] // 2
+        return self.siamese_head(self._infer(x, preprocessed, downsampling, whitening, pairs), None).reshape(pairs, 1)

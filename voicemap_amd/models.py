@@ -28,6 +28,31 @@ def _is_lazy(x):
     return isinstance(x, LazyWindows)
 
 
+def _resident(raw, augmented: bool = False) -> bool:
+    """Device-resident, un-augmented windows (shards.DeviceWindows): they exist as offsets into a device buffer, and a training step
+    crops them inside its preprocessing kernel (vm_crop_decimate_whiten).  ``augmented``: augmented ones count as well."""
+    return type(raw).__name__ == "DeviceWindows" and (augmented or getattr(raw, "aug", None) is None)
+
+
+def _windows(x, materialise: bool = False, gather: bool = True):
+    """(windows, keyword arguments) of an engine call on the batch x: a lazy batch hands over its raw windows, to be decimated and
+    whitened on the device; anything else is preprocessed float32.  ``materialise``: windows that are not an array yet become one --
+    resident ones gathered on the device (``gather``), the others (augmented ones outside a training step: DeviceWindows.__array__)
+    on the host."""
+    if not _is_lazy(x):
+        return np.asarray(x, dtype=np.float32), {}
+    raw = x.raw
+    if materialise:
+        raw = raw.gather() if gather and _resident(raw) else np.asarray(raw, dtype=np.float32)
+    return raw, dict(preprocessed=False, downsampling=x.downsampling, whitening=x.whitening)
+
+
+def _loss_acc(pl) -> tuple:
+    """(loss, accuracy) of the step or evaluation that returned the plan ``pl``: the one host read of its two numbers."""
+    la = pl["loss_acc"].cpu().numpy()
+    return float(la[0]), float(la[1])
+
+
 # =========================================================================================================
 class _TrainableModel:
     """Shared compile / fit / save plumbing of the encoder-classifier and the siamese model."""
@@ -459,10 +484,8 @@ class ConvolutionalEncoder(_TrainableModel):
     def predict(self, x, batch_size=None, verbose=0):
         """(n, L, 1) windows -> (n, E) embeddings, or (n, num_classes) probabilities for the classifier."""
         eng = self._ensure_engine()
-        if _is_lazy(x):
-            emb = eng.embed(x.raw, preprocessed=False, downsampling=x.downsampling, whitening=x.whitening)
-        else:
-            emb = eng.embed(np.asarray(x, dtype=np.float32))
+        w, kw = _windows(x)
+        emb = eng.embed(w, **kw)
         if self.classifier_units:
             pl = eng.plan(emb.shape[0], eng_last_l0(eng), False)
             return eng.classifier_head(pl, None).cpu().numpy().copy()
@@ -487,11 +510,8 @@ class ConvolutionalEncoder(_TrainableModel):
             return self._proto_step(x, y, proto)
         if self.loss not in ("categorical_crossentropy", None):
             raise NotImplementedError("classifier loss %r" % (self.loss,))
-        eng = self._ensure_engine()
-        if _is_lazy(x):
-            return eng.classifier_train_step(x.raw, self._labels(y), preprocessed=False, downsampling=x.downsampling,
-                                             whitening=x.whitening)
-        return eng.classifier_train_step(np.asarray(x, dtype=np.float32), self._labels(y))
+        w, kw = _windows(x)
+        return self._ensure_engine().classifier_train_step(w, self._labels(y), **kw)
 
     def _proto_loss(self):
         """The compiled utils.PrototypicalLoss of a bare encoder, or None."""
@@ -504,14 +524,11 @@ class ConvolutionalEncoder(_TrainableModel):
         if not hasattr(eng, "prototypical_train_step"):
             raise NotImplementedError("the prototypical loss is implemented for the 1-D encoder")
         k, n, alpha = proto.k_way, proto.n_shot, proto.alpha
-        if _is_lazy(x):
-            if type(x.raw).__name__ == "DeviceWindows" and getattr(x.raw, "aug", None) is None:
-                # device data path: the crop happens inside the preprocessing kernel (vm_crop_decimate_whiten)
-                return eng.prototypical_train_step_from_offsets(x.raw.audio, x.raw.offsets_host, self._labels(y), x.raw.length, k, n, alpha,
-                                                                downsampling=x.downsampling, whitening=x.whitening)
-            return eng.prototypical_train_step(np.asarray(x.raw, dtype=np.float32), self._labels(y), k, n, alpha, preprocessed=False,
-                                               downsampling=x.downsampling, whitening=x.whitening)
-        return eng.prototypical_train_step(np.asarray(x, dtype=np.float32), self._labels(y), k, n, alpha)
+        if _is_lazy(x) and _resident(x.raw):   # device data path
+            return eng.prototypical_train_step_from_offsets(x.raw.audio, x.raw.offsets_host, self._labels(y), x.raw.length, k, n, alpha,
+                                                            downsampling=x.downsampling, whitening=x.whitening)
+        w, kw = _windows(x, materialise=True)
+        return eng.prototypical_train_step(w, self._labels(y), k, n, alpha, **kw)
 
     def _triplet_loss(self):
         """The compiled utils.TripletLoss of a bare encoder, or None."""
@@ -524,55 +541,28 @@ class ConvolutionalEncoder(_TrainableModel):
         if not hasattr(eng, "triplet_train_step"):
             raise NotImplementedError("the triplet loss is implemented for the 1-D encoder")
         kw = dict(mining=trip.mining_code, soft=int(trip.soft), margin=trip.margin_value)
-        if _is_lazy(x):
-            if type(x.raw).__name__ == "DeviceWindows" and getattr(x.raw, "aug", None) is None:
-                # device data path: the crop happens inside the preprocessing kernel (vm_crop_decimate_whiten)
-                return eng.triplet_train_step_from_offsets(x.raw.audio, x.raw.offsets_host, self._labels(y), x.raw.length,
-                                                           downsampling=x.downsampling, whitening=x.whitening, **kw)
-            return eng.triplet_train_step(np.asarray(x.raw, dtype=np.float32), self._labels(y), preprocessed=False,
-                                          downsampling=x.downsampling, whitening=x.whitening, **kw)
-        return eng.triplet_train_step(np.asarray(x, dtype=np.float32), self._labels(y), **kw)
+        if _is_lazy(x) and _resident(x.raw):   # device data path
+            return eng.triplet_train_step_from_offsets(x.raw.audio, x.raw.offsets_host, self._labels(y), x.raw.length,
+                                                       downsampling=x.downsampling, whitening=x.whitening, **kw)
+        w, wkw = _windows(x, materialise=True)
+        return eng.triplet_train_step(w, self._labels(y), **wkw, **kw)
 
     def train_on_batch(self, x, y):
-        la = self._train_step(x, y)["loss_acc"].cpu().numpy()
-        return float(la[0]), float(la[1])
+        return _loss_acc(self._train_step(x, y))
 
     def test_on_batch(self, x, y):
         eng = self._ensure_engine()
-        import torch
-        trip = self._triplet_loss()
+        trip, proto = self._triplet_loss(), self._proto_loss()
         if trip is not None:
             if not hasattr(eng, "triplet_eval"):
                 raise NotImplementedError("the triplet loss is implemented for the 1-D encoder")
-            kw = dict(mining=trip.mining_code, soft=int(trip.soft), margin=trip.margin_value)
-            if _is_lazy(x):
-                raw = x.raw.gather() if type(x.raw).__name__ == "DeviceWindows" and getattr(x.raw, "aug", None) is None else \
-                    np.asarray(x.raw, dtype=np.float32)
-                pl = eng.triplet_eval(raw, self._labels(y), preprocessed=False, downsampling=x.downsampling, whitening=x.whitening, **kw)
-            else:
-                pl = eng.triplet_eval(np.asarray(x, dtype=np.float32), self._labels(y), **kw)
-            la = pl["loss_acc"].cpu().numpy()
-            return float(la[0]), float(la[1])
-        proto = self._proto_loss()
+            w, kw = _windows(x, materialise=True)
+            return _loss_acc(eng.triplet_eval(w, self._labels(y), mining=trip.mining_code, soft=int(trip.soft), margin=trip.margin_value, **kw))
         if proto is not None:
-            if _is_lazy(x):
-                raw = x.raw.gather() if type(x.raw).__name__ == "DeviceWindows" and getattr(x.raw, "aug", None) is None else \
-                    np.asarray(x.raw, dtype=np.float32)
-                pl = eng.prototypical_eval(raw, self._labels(y), proto.k_way, proto.n_shot, proto.alpha, preprocessed=False,
-                                           downsampling=x.downsampling, whitening=x.whitening)
-            else:
-                pl = eng.prototypical_eval(np.asarray(x, dtype=np.float32), self._labels(y), proto.k_way, proto.n_shot, proto.alpha)
-            la = pl["loss_acc"].cpu().numpy()
-            return float(la[0]), float(la[1])
-        if _is_lazy(x):
-            emb = eng.embed(x.raw, preprocessed=False, downsampling=x.downsampling, whitening=x.whitening)
-        else:
-            emb = eng.embed(np.asarray(x, dtype=np.float32))
-        pl = eng.plan(emb.shape[0], eng_last_l0(eng), False)
-        lab = torch.as_tensor(self._labels(y)).to(eng.device, torch.int32)
-        eng.classifier_head_eval(pl, lab)
-        la = pl["loss_acc"].cpu().numpy()
-        return float(la[0]), float(la[1])
+            w, kw = _windows(x, materialise=True)
+            return _loss_acc(eng.prototypical_eval(w, self._labels(y), proto.k_way, proto.n_shot, proto.alpha, **kw))
+        w, kw = _windows(x)
+        return _loss_acc(eng.classifier_eval(w, self._labels(y), **kw))
 
 
 class SpectrogramEncoder(ConvolutionalEncoder):
@@ -712,23 +702,18 @@ class SiameseNet(_TrainableModel):
             x2 = np.asarray(x2)
         if _is_lazy(x1):
             assert (x1.downsampling, x1.whitening) == (x2.downsampling, x2.whitening)
-            r1, r2 = x1.raw, x2.raw
-            if type(r1).__name__ == "DeviceWindows":  # windows that only exist as offsets into a device buffer (shards.py)
-                if getattr(r1, "aug", None) is not None or getattr(r2, "aug", None) is not None:
-                    # augmented windows outside a training step: their host materialisation (shards.DeviceWindows.__array__)
-                    r1, r2 = np.asarray(r1, dtype=np.float32), np.asarray(r2, dtype=np.float32)
-                else:
-                    r1, r2 = r1.gather(), r2.gather()
-            return fn(r1, r2, preprocessed=False, downsampling=x1.downsampling, whitening=x1.whitening, **kw)
-        return fn(np.asarray(x1, dtype=np.float32), np.asarray(x2, dtype=np.float32), **kw)
+        # windows that only exist as offsets into a device buffer (shards.py) become arrays: both towers on the device, or both on the host
+        dev = _is_lazy(x1) and _resident(x1.raw, augmented=True)
+        both = dev and _resident(x1.raw) and _resident(x2.raw)
+        (r1, wkw), (r2, _) = _windows(x1, dev, both), _windows(x2, dev, both)
+        return fn(r1, r2, **wkw, **kw)
 
     def _train_step(self, x, y):
         """One optimizer step enqueued; returns the engine's plan (``loss_acc`` on the device: reading it is the only host sync)."""
         eng = self._ensure_engine()
         x1, x2 = self._pair(x)
         loss = self._loss_name()
-        if _is_lazy(x1) and _is_lazy(x2) and type(x1.raw).__name__ == type(x2.raw).__name__ == "DeviceWindows" \
-                and x1.raw.audio is x2.raw.audio:
+        if _is_lazy(x1) and _is_lazy(x2) and _resident(x1.raw, True) and _resident(x2.raw, True) and x1.raw.audio is x2.raw.audio:
             # device data path: the crop happens inside the preprocessing kernel (vm_crop_decimate_whiten)
             assert (x1.downsampling, x1.whitening) == (x2.downsampling, x2.whitening)
             a1, a2 = getattr(x1.raw, "aug", None), getattr(x2.raw, "aug", None)
@@ -741,16 +726,13 @@ class SiameseNet(_TrainableModel):
         return self._run(lambda a, b, **kw: eng.siamese_train_step(a, b, np.asarray(y, dtype=np.float32), loss=loss, **kw), x1, x2)
 
     def train_on_batch(self, x, y):
-        la = self._train_step(x, y)["loss_acc"].cpu().numpy()
-        return float(la[0]), float(la[1])
+        return _loss_acc(self._train_step(x, y))
 
     def test_on_batch(self, x, y):
         eng = self._ensure_engine()
         x1, x2 = self._pair(x)
         loss = self._loss_name()
-        pl = self._run(lambda a, b, **kw: eng.siamese_eval(a, b, np.asarray(y, dtype=np.float32), loss=loss, **kw), x1, x2)
-        la = pl["loss_acc"].cpu().numpy()
-        return float(la[0]), float(la[1])
+        return _loss_acc(self._run(lambda a, b, **kw: eng.siamese_eval(a, b, np.asarray(y, dtype=np.float32), loss=loss, **kw), x1, x2))
 
     def predict(self, x, batch_size=None, verbose=0):
         """siamese.predict([input_1, input_2]) -> (pairs, 1) probabilities; lower = more alike."""

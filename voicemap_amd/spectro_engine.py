@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, spectro
-from .engine import HEADS, LOSSES, FlatState, HipEncoderEngine, _DT, _TORCH_DT, _align, _p, _shared_stream
+from .engine import FlatState, HipEncoderEngine, _DT, _TORCH_DT, _align, _p, _shared_stream
 
 
 class HipSpectrogramEncoderEngine(HipEncoderEngine):
@@ -522,34 +522,19 @@ class HipSpectrogramEncoderEngine(HipEncoderEngine):
             self.optimizer_step()
         return pl
 
-    def embed(self, x, preprocessed: bool = False, downsampling: int = 1, whitening: bool = False, windows_per_tower=None) -> torch.Tensor:
+    def _pair_windows(self, x1, x2):
+        return torch.cat([self._raw(x1), self._raw(x2)], 0)
+
+    def _infer(self, x, preprocessed: bool = False, downsampling: int = 1, whitening: bool = False, windows_per_tower=None) -> dict:
         x = self._raw(x)
         pl = self.plan(x.shape[0], x.shape[1], False)
         self.last_infer_l0 = x.shape[1]
         self.features(pl, x)
-        return self.forward(pl, x.shape[0], None)
-
-    def siamese_eval(self, x1, x2, y, loss: str = "contrastive", preprocessed: bool = False, downsampling: int = 1, whitening: bool = False):
-        a, b2 = self._raw(x1), self._raw(x2)
-        pairs = a.shape[0]
-        self.embed(torch.cat([a, b2], 0))
-        pl = self.plan(2 * pairs, self.last_infer_l0, False)
-        yd = torch.as_tensor(y, dtype=torch.float32).reshape(pairs).to(self.device).contiguous()
-        if "scratch" not in pl:
-            pl["scratch"] = torch.empty(2 * pairs * self.E + self.E + 8, dtype=torch.float32, device=self.device)
-        sc = pl["scratch"]
-        off = 2 * pairs * self.E
-        self._call("vm_siamese_head_loss", _p(pl["emb"]), _p(self.view("head.kernel")), _p(self.view("head.bias")), _p(yd), pairs, self.E,
-                   HEADS[self.head], LOSSES[loss], 1.0, _p(pl["pred"]), _p(pl["loss_acc"]), _p(sc), sc.data_ptr() + 4 * off,
-                   sc.data_ptr() + 4 * (off + self.E), _p(pl["head_ws"]), self.stream())
+        self.forward(pl, x.shape[0], None)
         return pl
 
-    def siamese_predict(self, x1, x2, preprocessed: bool = False, downsampling: int = 1, whitening: bool = False):
-        a, b2 = self._raw(x1), self._raw(x2)
-        pairs = a.shape[0]
-        self.embed(torch.cat([a, b2], 0))
-        pl = self.plan(2 * pairs, self.last_infer_l0, False)
-        return self.siamese_head(pl, None).reshape(pairs, 1)
+    def embed(self, x, preprocessed: bool = False, downsampling: int = 1, whitening: bool = False, windows_per_tower=None) -> torch.Tensor:
+        return self._infer(x)["emb"]
 
     # the 1-D engine's data paths that have no meaning here
     def preprocess(self, *a, **k):
