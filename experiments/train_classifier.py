@@ -1,13 +1,15 @@
 """Speaker-identification classifier on the same encoder (+ Dense(num_classes, softmax), categorical cross-entropy) --
 counterpart of the reference's experiments/train_classifier.py; its bottleneck layer is evaluated with the same
-n-shot tasks (mode='classifier').     python -m experiments.train_classifier [--synthetic] ..."""
+n-shot tasks (mode='classifier').     python -m experiments.train_classifier [--synthetic] ...
+With --margin-loss {none,cosine,angular} [--margin M] [--scale S] (not in the reference) the same head is trained for cosine scoring:
+softmax over S x the cosines to its class weights with a margin at the label (utils.MarginSoftmaxLoss)."""
 
 import numpy as np
 
 from experiments import _common as C
 from voicemap_amd.keras_like import Adam, Dense, Sequence, to_categorical
 from voicemap_amd.models import get_baseline_convolutional_encoder
-from voicemap_amd.utils import BatchPreProcessor, preprocess_instances
+from voicemap_amd.utils import BatchPreProcessor, MarginSoftmaxLoss, preprocess_instances
 
 
 class ShuffledBatches(Sequence):
@@ -31,7 +33,12 @@ class ShuffledBatches(Sequence):
 
 
 def main(argv=None):
-    a = C.base_parser(__doc__, pad=False, dropout=None).parse_args(argv)
+    parser = C.base_parser(__doc__, pad=False, dropout=None)
+    parser.add_argument("--margin-loss", choices=MarginSoftmaxLoss.KINDS, default=None,
+                        help="train the head with the margin softmax over cosines (default: the softmax classifier)")
+    parser.add_argument("--margin", type=float, default=None, help="the margin (default 0.2; implies --margin-loss angular)")
+    parser.add_argument("--scale", type=float, default=None, help="the scale of the cosines (default 30; implies --margin-loss angular)")
+    a = parser.parse_args(argv)
     C.setup()
     train, valid = C.datasets(a, pad=False)
     ids = sorted(train.df["speaker_id"].unique())
@@ -46,10 +53,15 @@ def main(argv=None):
     classifier = get_baseline_convolutional_encoder(a.filters, a.embedding_dimension, (C.input_length(a), 1), dropout=rate,
                                                     dtype=a.dtype)
     classifier.add(Dense(train.num_classes(), activation="softmax"))
-    classifier.compile(loss="categorical_crossentropy", optimizer=Adam(clipnorm=1.), metrics=["accuracy"])
+    loss = "categorical_crossentropy"
+    if a.margin_loss is not None or a.margin is not None or a.scale is not None:
+        loss = MarginSoftmaxLoss(a.margin_loss or "angular", 0.2 if a.margin is None else a.margin, 30.0 if a.scale is None else a.scale)
+    classifier.compile(loss=loss, optimizer=Adam(clipnorm=1.), metrics=["accuracy"])
     classifier.summary()
     C.apply_sync_bn(a, classifier)
     name = "classifier__filters_{}__embed_{}__drop_{}__pad={}".format(a.filters, a.embedding_dimension, a.dropout, a.pad)
+    if not isinstance(loss, str):   # the run name gains the loss only when one of the three flags is given
+        name += "__loss_{}_m{}_s{}".format(loss.kind, loss.margin, loss.scale)
     # twice the siamese step count: a siamese batch carries two windows per sample (reference comment, :126-127)
     return classifier.fit_generator(generator=ShuffledBatches(train, pre, a.batchsize), steps_per_epoch=2 * a.steps_per_epoch,
                                     epochs=a.epochs, workers=a.workers, use_multiprocessing=True,

@@ -631,6 +631,53 @@ int vm_triplet_loss(const float* emb, const int32_t* label, int64_t N, int E, in
                     int32_t* hard_pos, int32_t* hard_neg, float* loss_acc, float* demb, void* ws, void* stream);
 enum { VM_TRIPLET_HARD = 0, VM_TRIPLET_ALL = 1 };
 
+/* ---- a9d: softmax over scaled cosines with a margin at the label (NormFace; CosFace / AM-softmax; ArcFace / AAM-softmax; this
+ * project's own objective, the reference has none; csrc/margin.hip).  The head of the classifier trained for cosine scoring.
+ * Inputs.  emb (N, E) fp32; w (E, S) fp32, the Dense kernel of the classifier head: column c is class c; labels (N) int32.  The
+ * head's bias takes no part.
+ * Cosines.  ss_i = sum_t e_i[t]^2, n_i = sqrtf(ss_i); ssw_c = sum_t w[t][c]^2, m_c = sqrtf(ssw_c); d_ic = sum_t e_i[t] w[t][c];
+ *   c_ic = d_ic / (n_i * m_c) (one product, one division), then clamped to [-1, 1] by comparisons (a NaN stays a NaN); the clamp
+ *   passes the gradient through.  ss_i == 0 or ssw_c == 0 exactly: c_ic = 0, and the zero row / zero column receives a zero
+ *   gradient (no epsilon).  e_hat_i[t] = e_i[t] / n_i, w_hat_c[t] = w[t][c] / m_c (zeros for a zero row / column).
+ *   cosine (N, S) <- c_ic, prob (N, S) <- softmax_c(scale * c_ic) = expf(scale c_ic - scale cmax_i) / sum_c of the same, pred (N)
+ *   int32 <- the first maximum of row i of c (a NaN is never a maximum; a row without one: 0); never margined; each may be NULL.
+ * Target logit.  y = labels[i], c = c_iy.  VM_MARGIN_NONE: c' = c, f = 1.  VM_MARGIN_COSINE: c' = c - margin, f = 1.
+ *   VM_MARGIN_ANGULAR: cos_m, sin_m, th = -cos_m, mm = margin sin_m are computed in double from the float margin on the host and
+ *   rounded once to float; sin_t = sqrtf(max(0, fmaf(-c, c, 1))).  c > th: c' = fmaf(c, cos_m, -(sin_t sin_m)),
+ *   f = dc'/dc = fmaf(sin_m, c / max(sin_t, VM_MARGIN_SIN_FLOOR), cos_m);  otherwise c' = c - mm, f = 1.
+ *   z_ic = scale * c_ic for c != y, z_iy = scale * c'.
+ * Loss.  l_i = logf(sum_c expf(z_ic - zmax_i)) - (z_iy - zmax_i), zmax_i the row's maximum of z, no clip;
+ *   loss_acc[0] = (1 / N) sum_i l_i;  loss_acc[1] = (1 / N) #{i : pred_i == y_i} (from the un-margined cosines: what the model
+ *   predicts).  A row whose label is outside [0, S) is taken out of every sum: no loss term, no hit, a zero demb row, nothing in
+ *   grad_w; its cosine, prob and pred are still written; the means still divide by N.
+ * Gradients.  g_ic = (scale / N) * (expf(z_ic - zmax_i) / Z_i - [c == y]) (* f at c == y);  A_i = sum_c g_ic c_ic;  B_c = sum_i g_ic c_ic;
+ *   demb[i][t]   = grad_scale * ((sum_c (g_ic / m_c) w[t][c] - A_i e_hat_i[t]) / n_i)          (g_ic / m_c := 0 where m_c == 0)
+ *   grad_w[t][c] = grad_scale * ((sum_i g_ic e_hat_i[t] - B_c w_hat_c[t]) / m_c)               ((E, S), every element written)
+ *   grad_b (S) is written as zeros when not NULL: the bias stays in the parameter layout and never moves.
+ * Modes.  labels NULL: predict only -- cosine, prob, pred alone.  demb NULL with labels: evaluation -- loss_acc and those three
+ *   alone (grad_w, grad_b untouched).  demb given: labels, loss_acc and grad_w are required.  ws is always required.
+ * Non-finite input.  A non-finite component in a participating row or in any class column makes loss_acc[0] NaN and the demb of that
+ *   row (of every participating non-zero row, for a column) NaN: no clamp, max or comparison swallows a NaN.  The f16 loss-scale skip
+ *   relies on it.
+ * Limits.  1 <= N <= 4096, 2 <= S <= 16384, 1 <= E <= 256 (vm_margin_softmax_supported; VM_ERR_UNSUPPORTED above, VM_ERR_ARG
+ *   below); a finite margin with 0 <= margin < pi / 2 (every kind), a finite scale > 0, kind in range; refused before any launch.
+ * Order of the sums (three launches, no float atomics; two calls are bit-identical; grad_scale times a power of two scales demb and
+ *   grad_w exactly).  ss_i: a lane's components t = lane, lane + 64, ... ascending with fmaf, then the xor butterfly.  ssw_c and d_ic:
+ *   t ascending with fmaf.  Row i is one workgroup of 256 threads, class c belongs to thread c % 256.  The first maximum, zmax_i: a
+ *   thread's classes ascending, the butterfly on (value, c), the four waves in order.  Z_i, the prob denominator and A_i (fmaf): a
+ *   thread's classes ascending, the butterfly, the four waves in order.  demb's sum over c: a lane's classes c = lane, lane + 64, ...
+ *   ascending with fmaf, the butterfly; then fmaf(-A_i, e_hat_i[t], sum) / n_i.  grad_w's sum over i and B_c: rows ascending with
+ *   fmaf, a row with g_ic == 0 skipped; then fmaf(-B_c, w_hat_c[t], sum) / m_c.  The means: a thread's rows i = tid, tid + 256, ...
+ *   ascending, the butterfly, the four waves in order, one division by N.
+ * ws >= vm_margin_softmax_workspace_bytes(N, S, E) = (S + N E + 2 N + 2 N S) * 4: m, e_hat, the rows' loss terms and hits, g, c. */
+#define VM_MARGIN_SIN_FLOOR 0.015625f /* 2^-6: the floor of sin_t in dc'/dc; a definition, not a tolerance */
+int vm_margin_softmax_supported(int64_t N, int S, int E);
+int64_t vm_margin_softmax_workspace_bytes(int64_t N, int S, int E);
+int vm_margin_softmax(const float* emb, const float* w, const int32_t* labels, int64_t N, int S, int E, int kind, float margin,
+                      float scale, float grad_scale, float* cosine, float* prob, int32_t* pred, float* loss_acc, float* demb,
+                      float* grad_w, float* grad_b, void* ws, void* stream);
+enum { VM_MARGIN_NONE = 0, VM_MARGIN_COSINE = 1, VM_MARGIN_ANGULAR = 2 };
+
 /* ---- a5: Adam(clipnorm=1.)  (experiments/train_siamese.py:56; Keras 2.2.2 optimizers.py) -------------------
  * sqnorm: 1 fp32 on device <- sum(g^2) over the flat gradient buffer (fixed order; ws >= vm_sqnorm_workspace_bytes).  sqnorm may be
  * NULL: then only the partial sums are left in ws, for vm_adam_clip_step's sqnorm_parts (one launch less). */

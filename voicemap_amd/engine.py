@@ -1468,6 +1468,37 @@ class HipEncoderEngine:
                    _p(pl["loss_acc"]), _p(pl["demb"]) if train else None, _p(b["ws"]), self.stream())
         return b
 
+    def _margin_bufs(self, pl: dict) -> dict:
+        """Per-plan buffers of the margin head: pred (N,) int32, the kernel's workspace; the cosines go where the softmax head keeps
+        its logits."""
+        b = pl.get("margin")
+        if b is None:
+            if self.head != "classifier":
+                raise ValueError("the margin head needs an engine built with head='classifier' (its class weights are head.kernel)")
+            N, S = pl["n"], self.num_classes
+            if not self.lib.query("vm_margin_softmax_supported", N, S, self.E):
+                raise ValueError("vm_margin_softmax does not serve N = %d, S = %d, E = %d (N <= 4096, 2 <= S <= 16384, E <= 256)"
+                                 % (N, S, self.E))
+            ws = self.lib.query("vm_margin_softmax_workspace_bytes", N, S, self.E)
+            b = pl["margin"] = {"pred": torch.zeros(N, dtype=torch.int32, device=self.device), "cosine": pl["logits"],
+                                "ws": torch.empty(ws // 4, dtype=torch.float32, device=self.device)}
+        return b
+
+    def margin_head(self, pl: dict, labels: Optional[torch.Tensor], kind: int = 2, margin: float = 0.2, scale: float = 30.0):
+        """Softmax over ``scale`` x the cosines between the plan's embeddings and the columns of head.kernel, with a margin at the
+        label (``kind`` 0 = none, 1 = additive cosine, 2 = additive angular; ``labels`` int32 (N,) on the device, None: predict only):
+        the cosines, pl['prob'] (never margined), the argmax in pl['margin'], with labels pl['loss_acc'] and -- on a training plan --
+        pl['demb'] and the head gradients (head.bias: zeros).  One entry point, vm_margin_softmax."""
+        b = self._margin_bufs(pl)
+        train = labels is not None and pl["training"]
+        G = self.G
+        self._call("vm_margin_softmax", _p(pl["emb"]), _p(self.view("head.kernel")), self._dyn("y", _p(labels)), pl["n"], self.num_classes,
+                   self.E, int(kind), float(margin), float(scale), self._dyn("loss_scale", float(self.loss_scale)) if train else 1.0,
+                   _p(b["cosine"]), _p(pl["prob"]), _p(b["pred"]), _p(pl["loss_acc"]) if labels is not None else None,
+                   _p(pl["demb"]) if train else None, _p(self.view("head.kernel", G)) if train else None,
+                   _p(self.view("head.bias", G)) if train else None, _p(b["ws"]), self.stream())
+        return pl["prob"]
+
     def _adam_scalars(self):
         """(t, lr_t) of the Adam step about to run (Keras: lr decays with the iteration count BEFORE this step)."""
         lr = self.lr
@@ -1538,8 +1569,8 @@ class HipEncoderEngine:
     def _train_step(self, pl: dict, wpt: int, target: torch.Tensor, loss: tuple, drop_masks, apply_update: bool, pre: Optional[StepInput],
                     input_ready: bool = False, aug: Optional[dict] = None):
         """preprocess (``pre``: a StepInput, or None when the plan's input is loaded) -> forward -> head (``loss``: the key of
-        ``_loss_key`` -- ("classifier",), ("siamese", name), ("prototypical", k, n, alpha), ("triplet", mining, soft, margin); the last
-        two without head parameters) -> backward -> optimizer.  The SECOND time a configuration
+        ``_loss_key`` -- ("classifier",), ("siamese", name), ("prototypical", k, n, alpha), ("triplet", mining, soft, margin), both without
+        head parameters, ("margin", kind, margin, scale) on the classifier's) -> backward -> optimizer.  The SECOND time a configuration
         is seen its enqueue sequence is recorded (program.Program), from the third on it is replayed: same launches, same arguments, same
         stream ordering -- only the input / label / mask pointers and four scalars are patched in."""
         # (a gradient hook that declares itself ``replayable`` -- parallel.GradAllReduce: its two collectives are host calls kept in
@@ -1580,7 +1611,7 @@ class HipEncoderEngine:
                 if ahead:
                     self._join(cur, self.tower_stream)
             self.forward(pl, wpt, drop_masks, defer_tail=loss[0] == "siamese")
-            getattr(self, loss[0] + "_head")(pl, target, *loss[1:])   # classifier_head | siamese_head | prototypical_head | triplet_head
+            getattr(self, loss[0] + "_head")(pl, target, *loss[1:])   # classifier_head | siamese_head | prototypical_head | triplet_head | margin_head
             self.backward(pl, sync_tail=apply_update)
             if apply_update:
                 self.optimizer_step()
@@ -1616,7 +1647,8 @@ class HipEncoderEngine:
     @staticmethod
     def _loss_key(loss) -> tuple:
         """The uniform key of a step's loss, as _train_step dispatches on it and a recorded step is filed under it: None -> the
-        classifier's, a name -> that siamese loss, a tuple -> itself (("prototypical", k, n, alpha), ("triplet", mining, soft, margin))."""
+        classifier's, a name -> that siamese loss, a tuple -> itself (("prototypical", k, n, alpha), ("triplet", mining, soft, margin),
+        ("margin", kind, margin, scale))."""
         return ("classifier",) if loss is None else loss if isinstance(loss, tuple) else ("siamese", loss)
 
     def _replay_step(self, prog: Program, pl: dict, wpt: int, target, drop_masks, apply_update: bool, pre, aug=None):
@@ -1689,6 +1721,8 @@ class HipEncoderEngine:
             self._proto_bufs(pl, loss[1], loss[2])
         elif loss[0] == "triplet":
             self._triplet_bufs(pl)
+        elif loss[0] == "margin":
+            self._margin_bufs(pl)
 
     @staticmethod
     def _step_shape(n: int, loss: tuple):
@@ -1839,9 +1873,33 @@ class HipEncoderEngine:
         self.triplet_head(pl, self._target(labels, pl["n"], torch.int32), *self._triplet_loss_key(mining, soft, margin)[1:])
         return pl
 
-    def _infer(self, x, preprocessed: bool, downsampling: int, whitening: bool, windows_per_tower: Optional[int] = None) -> dict:
-        """Inference-mode forward on host windows x (n, L[, 1]); returns the inference plan (the embeddings: pl['emb'])."""
-        pl, pre = self._intake(x, False, preprocessed, downsampling, whitening)
+    # ---- margin softmax: the classifier's batches, the head replaced by one fused launch sequence over cosines ---------------------------
+    @staticmethod
+    def _margin_loss_key(kind, margin, scale):
+        return ("margin", int(kind), float(margin), float(scale))
+
+    def margin_train_step(self, x, labels, kind: int = 2, margin: float = 0.2, scale: float = 30.0, preprocessed: bool = True,
+                          downsampling: int = 4, whitening: bool = True, drop_masks="auto", apply_update: bool = True):
+        """One training step of the classifier under the margin softmax: x (N, L[, 1]) windows, labels (N,) class ids (one outside
+        [0, num_classes) takes its window out of the loss).  ``kind`` 0 = none, 1 = additive cosine, 2 = additive angular."""
+        return self._host_step(x, labels, self._margin_loss_key(kind, margin, scale), preprocessed, downsampling, whitening, drop_masks,
+                               apply_update)
+
+    def margin_eval(self, x, labels, kind: int = 2, margin: float = 0.2, scale: float = 30.0, preprocessed: bool = True,
+                    downsampling: int = 4, whitening: bool = True):
+        """test_on_batch under the margin softmax: inference-mode forward (moving BatchNorm statistics) + loss / accuracy in
+        pl['loss_acc'], the un-margined probabilities in pl['prob']; ``labels`` None: those alone.  Returns the inference plan."""
+        key = self._margin_loss_key(kind, margin, scale)
+        pl = self._infer(x, preprocessed, downsampling, whitening, loss=key)
+        lab = None if labels is None else self._target(labels, pl["n"], torch.int32)
+        self.margin_head(pl, lab, *key[1:])
+        return pl
+
+    def _infer(self, x, preprocessed: bool, downsampling: int, whitening: bool, windows_per_tower: Optional[int] = None,
+               loss: Optional[tuple] = None) -> dict:
+        """Inference-mode forward on host windows x (n, L[, 1]); returns the inference plan (the embeddings: pl['emb']).  ``loss``: as
+        in _intake."""
+        pl, pre = self._intake(x, False, preprocessed, downsampling, whitening, loss)
         self.last_infer_l0 = pl["l0"]
         if pre is not None:
             self.preprocess(pl, pre.tensor, downsampling, whitening, windows_per_tower or pl["n"])

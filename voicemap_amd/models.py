@@ -168,7 +168,8 @@ class _TrainableModel:
         return kind, geo, eng.get_params(), opt, self._training_config()
 
     def _training_config(self) -> dict:
-        """{"loss": its name, "metrics": [...]} (+ "loss_config" for a loss with parameters: utils.PrototypicalLoss, utils.TripletLoss)."""
+        """{"loss": its name, "metrics": [...]} (+ "loss_config" for a loss with parameters: utils.PrototypicalLoss, utils.TripletLoss,
+        utils.MarginSoftmaxLoss)."""
         loss = self.loss if isinstance(self.loss, str) or self.loss is None else getattr(self.loss, "__name__", str(self.loss))
         tc = {"loss": loss, "metrics": list(self.metrics)}
         if hasattr(self.loss, "get_config"):
@@ -481,13 +482,29 @@ class ConvolutionalEncoder(_TrainableModel):
         print_fn("_" * 80)
 
     # ---- inference / training ----------------------------------------------------------------------------
+    def compile(self, loss=None, optimizer=None, metrics=None, **kw):
+        from .utils import MarginSoftmaxLoss
+        if isinstance(loss, MarginSoftmaxLoss) and not self.classifier_units:
+            raise ValueError("MarginSoftmaxLoss needs the classification layer (its class weights are that layer's kernel): "
+                             "add Dense(num_classes, activation='softmax') to the encoder before compiling it")
+        super().compile(loss=loss, optimizer=optimizer, metrics=metrics, **kw)
+
+    def _margin_loss(self):
+        """The compiled utils.MarginSoftmaxLoss of a classifier, or None."""
+        from .utils import MarginSoftmaxLoss
+        return self.loss if isinstance(self.loss, MarginSoftmaxLoss) and self.classifier_units else None
+
     def predict(self, x, batch_size=None, verbose=0):
-        """(n, L, 1) windows -> (n, E) embeddings, or (n, num_classes) probabilities for the classifier."""
+        """(n, L, 1) windows -> (n, E) embeddings, or (n, num_classes) probabilities for the classifier (under MarginSoftmaxLoss: the
+        softmax of scale x cosine, never margined)."""
         eng = self._ensure_engine()
         w, kw = _windows(x)
         emb = eng.embed(w, **kw)
         if self.classifier_units:
             pl = eng.plan(emb.shape[0], eng_last_l0(eng), False)
+            mg = self._margin_loss()
+            if mg is not None:
+                return eng.margin_head(pl, None, mg.kind_code, mg.margin, mg.scale).cpu().numpy().copy()
             return eng.classifier_head(pl, None).cpu().numpy().copy()
         return emb.cpu().numpy().copy()
 
@@ -508,6 +525,10 @@ class ConvolutionalEncoder(_TrainableModel):
                 raise RuntimeError("the bare encoder has no loss; add Dense(num_classes, activation='softmax'), wrap it in "
                                    "build_siamese_net or compile it with utils.PrototypicalLoss")
             return self._proto_step(x, y, proto)
+        mg = self._margin_loss()
+        if mg is not None:
+            w, kw = _windows(x)
+            return self._ensure_engine().margin_train_step(w, self._labels(y), mg.kind_code, mg.margin, mg.scale, **kw)
         if self.loss not in ("categorical_crossentropy", None):
             raise NotImplementedError("classifier loss %r" % (self.loss,))
         w, kw = _windows(x)
@@ -562,6 +583,9 @@ class ConvolutionalEncoder(_TrainableModel):
             w, kw = _windows(x, materialise=True)
             return _loss_acc(eng.prototypical_eval(w, self._labels(y), proto.k_way, proto.n_shot, proto.alpha, **kw))
         w, kw = _windows(x)
+        mg = self._margin_loss()
+        if mg is not None:
+            return _loss_acc(eng.margin_eval(w, self._labels(y), mg.kind_code, mg.margin, mg.scale, **kw))
         return _loss_acc(eng.classifier_eval(w, self._labels(y), **kw))
 
 
@@ -589,6 +613,12 @@ class SpectrogramEncoder(ConvolutionalEncoder):
 
     def add(self, layer):
         raise NotImplementedError("the spectrogram variant is an embedding encoder only (no classification layer)")
+
+    def compile(self, loss=None, optimizer=None, metrics=None, **kw):
+        from .utils import MarginSoftmaxLoss
+        if isinstance(loss, MarginSoftmaxLoss):
+            raise NotImplementedError("the margin softmax is implemented for the 1-D classifier (the spectrogram variant has no classification layer)")
+        super().compile(loss=loss, optimizer=optimizer, metrics=metrics, **kw)
 
     def clone(self):
         return SpectrogramEncoder(self.filters, self.embedding_dimension, self.input_shape, self.dropout, self.dtype, self.n_mels)
@@ -647,6 +677,13 @@ class SiameseNet(_TrainableModel):
 
     def _make_engine(self):
         return self.encoder._make_engine(head=self.distance_metric)
+
+    def compile(self, loss=None, optimizer=None, metrics=None, **kw):
+        from .utils import MarginSoftmaxLoss
+        if isinstance(loss, MarginSoftmaxLoss):
+            raise ValueError("MarginSoftmaxLoss is a classification loss: compile it on the encoder with its "
+                             "Dense(num_classes, activation='softmax') layer, not on the siamese network")
+        super().compile(loss=loss, optimizer=optimizer, metrics=metrics, **kw)
 
     def _ensure_engine(self):
         if self.engine is None:
@@ -832,13 +869,17 @@ def contrastive_loss_by_name(loss):
 
 
 def loss_by_name(loss, loss_config=None):
-    """The compiled loss of a checkpoint: a loss saved with its parameters (utils.PrototypicalLoss, utils.TripletLoss) is rebuilt from them."""
+    """The compiled loss of a checkpoint: a loss saved with its parameters (utils.PrototypicalLoss, utils.TripletLoss, utils.MarginSoftmaxLoss) is rebuilt
+    from them."""
     if loss == "prototypical_loss" and loss_config:
         from .utils import PrototypicalLoss
         return PrototypicalLoss(**loss_config)
     if loss == "triplet_loss" and loss_config:
         from .utils import TripletLoss
         return TripletLoss(**loss_config)
+    if loss == "margin_softmax_loss" and loss_config:
+        from .utils import MarginSoftmaxLoss
+        return MarginSoftmaxLoss(**loss_config)
     return loss
 
 

@@ -542,3 +542,4 @@ class HipSpectrogramEncoderEngine(HipEncoderEngine):
 
     load_preprocessed = siamese_train_step_from_offsets = embed_from_offsets = classifier_train_step = preprocess
     triplet_train_step = triplet_train_step_from_offsets = triplet_eval = preprocess   # the triplet loss is the 1-D encoder's
+    margin_train_step = margin_eval = preprocess   # the margin softmax is the 1-D classifier's

@@ -9,6 +9,7 @@
     NShotEvaluationCallback(num_tasks, n_shot, k_way, dataset, preprocessor, mode)             utils.py:219
     PrototypicalLoss(k_way, n_shot, alpha=1.0)                                                 (not in the reference)
     TripletLoss(margin=0.2, mining="hard")                                                     (not in the reference)
+    MarginSoftmaxLoss(kind="angular", margin=0.2, scale=30.0)                                  (not in the reference)
 
 What is different underneath: ``preprocess_instances`` returns a *lazy* batch (``LazyWindows``) that remembers the raw
 16 kHz windows; the HIP models decimate + whiten it on the GPU (vm_decimate_whiten) instead of in three numpy passes on
@@ -180,6 +181,56 @@ class TripletLoss:
             return float(term(x).mean())
         x = np.concatenate([(self.margin_value + d[a, pos[a]][:, None] - d[a, neg[a]][None, :]).ravel() for a in np.flatnonzero(valid)])
         return float(term(x).sum() / (len(x) if self.soft else max(1, (x > 0).sum())))
+
+
+class MarginSoftmaxLoss:
+    """Softmax over scaled cosines with a margin at the label, for ``classifier.compile(loss=MarginSoftmaxLoss(kind, margin, scale))``
+    on the encoder WITH its ``Dense(num_classes, activation="softmax")`` head (not in the reference).  ``kind="none"``: the normalised
+    softmax (NormFace); ``"cosine"``: cos(theta) - margin at the label (AM-softmax / CosFace); ``"angular"``: cos(theta + margin)
+    (AAM-softmax / ArcFace, with the usual fallback past pi - margin).  The logits are ``scale`` times the cosines between the
+    embedding and the columns of the head's kernel; the head's bias takes no part and never moves.  A batch is the classifier's
+    ``(windows, labels)`` (one-hot or ids).  Evaluated with its gradients by vm_margin_softmax; the metric beside it is the accuracy
+    of the un-margined cosines, and ``predict()`` returns their softmax."""
+
+    __name__ = "margin_softmax_loss"
+    KINDS = ("none", "cosine", "angular")
+
+    def __init__(self, kind="angular", margin=0.2, scale=30.0):
+        if kind not in self.KINDS:
+            raise ValueError("MarginSoftmaxLoss kind must be one of (none, cosine, angular)")
+        if not (0 <= float(margin) < np.pi / 2):
+            raise ValueError("MarginSoftmaxLoss margin must be a number with 0 <= margin < pi / 2")
+        if not (0 < float(scale) < float("inf")):
+            raise ValueError("MarginSoftmaxLoss scale must be a finite number > 0")
+        self.kind, self.margin, self.scale = kind, float(margin), float(scale)
+
+    @property
+    def kind_code(self):
+        """VM_MARGIN_NONE / VM_MARGIN_COSINE / VM_MARGIN_ANGULAR"""
+        return self.KINDS.index(self.kind)
+
+    def get_config(self):
+        return {"kind": self.kind, "margin": self.margin, "scale": self.scale}
+
+    def __call__(self, cosine, labels):
+        """The same expression with numpy (float64) on the (N, S) cosines and (N,) class ids."""
+        c = np.asarray(cosine, dtype=np.float64)
+        y = np.asarray(labels).reshape(-1).astype(np.int64)
+        rows = np.flatnonzero((y >= 0) & (y < c.shape[1]))
+        cy = c[rows, y[rows]]
+        m = float(np.float32(self.margin))
+        if self.kind == "cosine":
+            cp = cy - m
+        elif self.kind == "angular":
+            cos_m, sin_m = float(np.float32(np.cos(m))), float(np.float32(np.sin(m)))
+            cp = np.where(cy > float(np.float32(-np.cos(m))), cy * cos_m - np.sqrt(np.maximum(0.0, 1.0 - cy * cy)) * sin_m,
+                          cy - float(np.float32(m * np.sin(m))))
+        else:
+            cp = cy
+        z = self.scale * c[rows]
+        z[np.arange(len(rows)), y[rows]] = self.scale * cp
+        zmax = z.max(1)
+        return float((np.log(np.exp(z - zmax[:, None]).sum(1)) - (self.scale * cp - zmax)).sum() / len(c))
 
 
 def get_bottleneck(classifier, samples):
