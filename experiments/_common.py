@@ -81,7 +81,26 @@ def device_resident(a, train):
     shard = (rank, world) if (world > 1 and getattr(a, "shard_speakers", False)) else None
     ds = shards.ShardedSpeechDataset(a.device_data, a.n_seconds, stochastic=True, pad=False, speaker_shard=shard)
     ds.to_device("cuda")
+    policy = vad_policy(a)
+    if policy is not None:   # --vad: the resident training set with its pauses trimmed out on the device (voicemap_amd/vad.py)
+        from voicemap_amd import vad
+        ds = ds.voiced(policy)
+        a.vad_summary = vad.summarise([ds.vad_counts])
+        if rank == 0:
+            print("--vad:", a.vad_summary)
     return ds
+
+
+def add_vad_args(parser):
+    """``--vad`` and its parameters for a training script (off by default; the --device-data path only: ``vad_policy`` checks)."""
+    from voicemap_amd.vad import add_vad_args as add
+    return add(parser)
+
+
+def vad_policy(a):
+    """The ``vad.VadPolicy`` of the script's ``--vad`` flags, None without them; exits when --vad comes without --device-data."""
+    from voicemap_amd.vad import policy_from_args
+    return policy_from_args(a, need_device_data=True)
 
 
 def mined_batches(a, dataset, preprocessor, device, distance="euclidean", augment=None):

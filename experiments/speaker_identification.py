@@ -4,23 +4,28 @@ and verify every utterance against every model.  Prints one JSON line: rank-1 / 
 EER and thresholds.
     python -m experiments.speaker_identification --siamese models/x.hdf5 [--enrol-set dev-clean] [--test-set test-clean]
         [--per-speaker N] [--distance euclidean|cosine|dot_product] [--whole-utterance] [--synthetic]
+        [--vad --vad-threshold-db 25 --vad-hang 10 --vad-min-run 3 --vad-frame-ms 10]
 Without --test-set (or with the same set) the enrolled set is also the test set: leave-one-out (every utterance is scored against its own
 speaker's model built from the speaker's OTHER utterances), or with --per-speaker N a seeded choice of N utterances per speaker is
 enrolled and the others are the queries.  With another --test-set its utterances are scored against the enrolled set's models (its
 speakers that were not enrolled give non-target trials only), and the best threshold of the enrolled set is applied to it.  Under
-torchrun the query rows are sharded like the other evaluation scripts."""
+torchrun the query rows are sharded like the other evaluation scripts.  With --vad the pauses are trimmed out of every file first
+(voicemap_amd/vad.py); the trimming summary is printed and joins the row."""
 import argparse
 import json
 
 from voicemap_amd import enrolment, retrieval
 from voicemap_amd.librispeech import LibriSpeechDataset, SyntheticSpeechDataset
 from voicemap_amd.utils import BatchPreProcessor, preprocess_instances
+from voicemap_amd.vad import add_vad_args, policy_from_args
 
 
-def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=None, whole_utterance=False, seed=0):
+def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=None, whole_utterance=False, seed=0, vad=None):
     """The result row: identification and model-trial figures of ``test_set`` (None: the enrolled set itself) against the models of
-    ``enrol_set``."""
+    ``enrol_set``.  ``vad`` (a ``vad.VadPolicy``): both sets are embedded with their pauses trimmed out."""
     wu = {"whole_utterance": True} if whole_utterance else {}
+    if vad is not None:
+        wu["vad"] = vad
     ce = retrieval.embed_corpus(net, enrol_set, pre, "siamese", **wu)
     models = enrolment.enrol(ce, distance, per_speaker=per_speaker, seed=seed)
     ct = ce if test_set is None else retrieval.embed_corpus(net, test_set, pre, "siamese", **wu)
@@ -38,6 +43,11 @@ def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=No
         at = enrolment.model_trial_accuracy_at_threshold(models, ct, me["best_threshold"])
         row.update(enrol_best_threshold=me["best_threshold"], test_balanced_accuracy_at_enrol_threshold=at["balanced_accuracy"],
                    test_far=at["far"], test_frr=at["frr"])
+    if vad is not None:
+        from voicemap_amd.vad import summarise
+        summary = summarise([c.vad_counts for c in ((ce,) if test_set is None else (ce, ct))])
+        print("--vad:", summary)
+        row.update({"vad_" + k: v for k, v in summary.items()})
     return row
 
 
@@ -53,12 +63,14 @@ def _parser():
     p.add_argument("--whole-utterance", action="store_true", help="embed every file whole, at its own length")
     p.add_argument("--synthetic", action="store_true", help="generated speaker sets and a freshly built model")
     p.add_argument("--seed", type=int, default=0)
+    add_vad_args(p)   # --vad ...: off by default; both sets are trimmed first
     return p
 
 
 def main(argv=None):
     p = _parser()
     a = p.parse_args(argv)
+    vad = policy_from_args(a)
     from experiments._common import setup
     rank, _ = setup()
     same = a.test_set is None or a.test_set == a.enrol_set
@@ -81,7 +93,7 @@ def main(argv=None):
         enrol_set = LibriSpeechDataset(a.enrol_set, a.n_seconds, stochastic=False)
         test_set = None if same else LibriSpeechDataset(a.test_set, a.n_seconds, stochastic=False)
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
-    row = evaluate(net, enrol_set, test_set, pre, a.distance, a.per_speaker, a.whole_utterance, a.seed)
+    row = evaluate(net, enrol_set, test_set, pre, a.distance, a.per_speaker, a.whole_utterance, a.seed, vad=vad)
     row.update(enrol_set="synthetic" if a.synthetic else a.enrol_set,
                test_set=("synthetic" if a.synthetic else a.enrol_set) if same else a.test_set)
     if rank == 0:

@@ -14,7 +14,9 @@ def main(argv=None):
                     help="waveform: the reference's 1-D encoder on the decimated, whitened window; logmel: the log-mel + 2-D CNN variant "
                          "on the raw 16 kHz window (BASELINE.json config 4, not in the reference)")
     add_augment_args(ap)
+    C.add_vad_args(ap)
     a = ap.parse_args(argv)
+    C.vad_policy(a)   # --vad (off by default; needs --device-data): C.device_resident trims the resident training set; validation stays as it is
     if a.frontend == "logmel":
         a.downsampling = 1   # the front-end works on the raw window: no decimation, no whitening
     augment = policy_from_args(a, a.downsampling)   # --augment (off by default; needs --device-data): training batches only

@@ -8,7 +8,8 @@ as-norm over the --top-k cohort rows most like each row) and the file name gains
     python -m experiments.verification_accuracy --siamese models/x.hdf5 [--score euclidean|cosine|dot_product|head] [--synthetic]
         [--score-norm none|s-norm|as-norm --cohort-set train-clean-100 --cohort-size 5000 --top-k 300] [--whole-utterance]
 With --whole-utterance every file is embedded whole, at its own length (retrieval.embed_corpus(whole_utterance=True)), and the file
-name gains _whole."""
+name gains _whole.  With --vad [--vad-threshold-db --vad-hang --vad-min-run --vad-frame-ms] the pauses are trimmed out of every file of
+every set first (voicemap_amd/vad.py), the trimming summary is printed and joins the row, and the file name gains _vad."""
 import argparse
 
 import numpy as np
@@ -18,6 +19,7 @@ from config import PATH
 from voicemap_amd import retrieval, verification
 from voicemap_amd.librispeech import LibriSpeechDataset, SyntheticSpeechDataset
 from voicemap_amd.utils import BatchPreProcessor, preprocess_instances
+from voicemap_amd.vad import add_vad_args, policy_from_args
 
 
 class CohortSubset:
@@ -43,11 +45,14 @@ def cohort_subset(dataset, size, seed=0):
     return CohortSubset(dataset, np.sort(np.random.default_rng(seed).choice(n, size, replace=False)))
 
 
-def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort=None, top_k=300, whole_utterance=False):
+def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort=None, top_k=300, whole_utterance=False, vad=None):
     """Embed both sets once, take the best-balanced-accuracy threshold of the validation trials and apply it to the test trials.
-    ``score_norm`` "s-norm" / "as-norm": both sets' scores are normalised against the embeddings of ``cohort`` (a dataset)."""
+    ``score_norm`` "s-norm" / "as-norm": both sets' scores are normalised against the embeddings of ``cohort`` (a dataset).
+    ``vad`` (a ``vad.VadPolicy``): every set, the cohort included, is embedded with its pauses trimmed out."""
     model = net if score == "head" else None
     wu = {"whole_utterance": True} if whole_utterance else {}
+    if vad is not None:
+        wu["vad"] = vad
     cv = retrieval.embed_corpus(net, valid, pre, "siamese", **wu)
     ct = retrieval.embed_corpus(net, test, pre, "siamese", **wu)
     nv = nt = None
@@ -69,6 +74,11 @@ def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort
         row["whole_utterance"] = True
     if score_norm != "none":
         row.update(score_norm=score_norm, top_k=top_k if score_norm == "as-norm" else None, cohort_size=len(cohort))
+    if vad is not None:
+        from voicemap_amd.vad import summarise
+        summary = summarise([c.vad_counts for c in (cv, ct) + ((cc,) if score_norm != "none" else ())])
+        print("--vad:", summary)
+        row.update({"vad_" + k: v for k, v in summary.items()})
     return row
 
 
@@ -80,6 +90,8 @@ def result_name(a):
         name += "_" + a.score_norm.replace("-", "") + ("_k%d" % a.top_k if a.score_norm == "as-norm" else "") + "_c%d" % a.cohort_size
     if getattr(a, "whole_utterance", False):
         name += "_whole"
+    if getattr(a, "vad", False):
+        name += "_vad"
     return name + ".csv"
 
 
@@ -101,12 +113,14 @@ def _parser():
     p.add_argument("--cohort-size", type=int, default=5000, help="files of the cohort set taken (seeded random subset)")
     p.add_argument("--top-k", type=int, default=300, help="as-norm: cohort rows per side")
     p.add_argument("--whole-utterance", action="store_true", help="embed every file whole, at its own length (not its first --n-seconds)")
+    add_vad_args(p)   # --vad ...: off by default; every set embedded, the cohort included, is trimmed first
     return p
 
 
 def main(argv=None):
     p = _parser()
     a = p.parse_args(argv)
+    vad = policy_from_args(a)
     from experiments._common import setup
     rank, _ = setup()
     if a.synthetic:
@@ -137,7 +151,7 @@ def main(argv=None):
     if cohort is not None:
         cohort = cohort_subset(cohort, a.cohort_size)
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
-    row = evaluate(net, valid, test, pre, a.score, a.score_norm, cohort, a.top_k, a.whole_utterance)
+    row = evaluate(net, valid, test, pre, a.score, a.score_norm, cohort, a.top_k, a.whole_utterance, vad=vad)
     results = pd.DataFrame([row])
     if rank == 0:
         results.to_csv(PATH + "/logs/" + result_name(a), index=False)

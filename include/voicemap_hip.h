@@ -175,6 +175,29 @@ int vm_crop_augment_decimate_whiten(const void* audio, int raw_is_i16, const int
                                     int noise_is_i16, const int64_t* noise_offsets, int K, const float* snr_lin, const float* gain,
                                     const float* rirs, int n_rirs, int R, const int32_t* rir_id, float* out, void* ws, void* stream);
 
+/* ---- voice activity detection on the resident int16 corpus (voicemap_amd/csrc/vad.hip; voicemap_amd/vad.py vad_reference is the
+ * numpy statement, matched bit for bit).  Utterance u: the lens[u] int16 samples s[0..len-1] at audio[offsets[u]], 1 <= len < 2^31,
+ * cut into F = ceil(len / frame) frames of n_f = min(frame, len - f frame) samples.  frame_base: n_utts + 1 entries, the exclusive
+ * cumulative sum of F (the host holds the lengths); energy, mask (one byte per frame) and dst are flat over all frames, utterance u's at
+ * frame_base[u]..frame_base[u + 1].
+ *   E_f = sum of s_t^2 over frame f, T = sum_f E_f (int64).  With D() = int64 -> double and * = one IEEE double multiply, frame f is active
+ *   a_f = E_f > 0  &&  D(E_f) * D(len) >= rel * (D(T) * D(n_f))  &&  D(E_f) >= floor_e * D(n_f)      (rel = 10^(-dB / 10) from the host)
+ *   p_f = some g in [f - min_run + 1, f], g >= 0, g + min_run - 1 <= F - 1, with a_g .. a_{g + min_run - 1} all set   (short bursts dropped)
+ *   v_f = some g in [max(0, f - hang), min(F - 1, f + hang)] with p_g                                                   (hangover)
+ *   V = sum_f v_f n_f;  V < min_keep: the utterance is kept whole -- every v_f = 1, V = len, fallback = 1
+ *   dst_f = sum_{g < f} v_g n_g;  mask = v, new_lens[u] = V, info (n_utts, 4) = F, sum a, sum v (after the fallback), fallback.
+ * Two launches (energies over tiles of the flat frame list; then one workgroup per utterance, in grid.x), no atomics, bit-reproducible.
+ * No sample outside [offsets[u], offsets[u] + lens[u]) is read.  1 <= frame <= 4096, 1 <= min_run <= 64, 0 <= hang <= 256 (so
+ * E_f <= 2^42, T < 2^61), else an error and no launch; n_utts == 0 returns without a launch. */
+int vm_vad_frames(const void* audio, const int64_t* offsets, const int64_t* lens, const int64_t* frame_base, int64_t n_utts,
+                  int frame, double rel, double floor_e, int min_run, int hang, int64_t min_keep,
+                  int64_t* energy, void* mask, int64_t* dst, int64_t* new_lens, int32_t* info, void* stream);
+/* The trimmed corpus of vm_vad_frames' mask / dst: out[new_offsets[u] + dst_f + t] = s[f frame + t] for every frame with v_f = 1, t < n_f
+ * (the kept frames of every utterance in order); new_offsets: the host's exclusive cumulative sum of new_lens.  One launch; 16-byte
+ * stores on the aligned body of a frame's destination, 2-byte accesses on its edges; nothing outside a kept frame is read. */
+int vm_vad_compact(const void* audio, const int64_t* offsets, const int64_t* lens, const int64_t* frame_base, const void* mask,
+                   const int64_t* dst, const int64_t* new_offsets, int64_t n_utts, int frame, void* out, void* stream);
+
 /* ---- a1 block 1: Conv1D(filters, 32, padding='same', activation='relu')  (voicemap/models.py:13-16) --
  * x: (n_windows, L + 31) fp32 from vm_decimate_whiten; w: (32, 1, F) fp32 Keras layout; bias (F).
  * z: (n_windows, L, F) `dtype`, = relu(conv + bias).  If stat_sum != NULL also writes per-(window, tile)

@@ -67,7 +67,7 @@ class EmbeddingCache:
 
 
 def embed_corpus(model, dataset, preprocessor, network_type: str = "siamese", batch: int = 256,
-                 whole_utterance: bool = False) -> EmbeddingCache:
+                 whole_utterance: bool = False, vad=None) -> EmbeddingCache:
     """Embed the first-fragment window of every file of ``dataset`` (inference mode, each window whitened alone).  With a
     device-resident corpus (``ShardedSpeechDataset.to_device``) windows are start offsets and the crop happens in the preprocessing
     kernel; otherwise windows are loaded on the host like ``dataset[i]`` with ``stochastic=False``.  Under torchrun every rank embeds
@@ -75,7 +75,12 @@ def embed_corpus(model, dataset, preprocessor, network_type: str = "siamese", ba
 
     ``whole_utterance``: every file is embedded WHOLE, at its own length, instead of its first fragment -- what the encoder computes
     on the recording alone (``HipEncoderEngine.embed_varlen``: length-masked buckets, voicemap_amd/utterances.py).  A file too short
-    for the encoder raises ``ValueError`` naming it."""
+    for the encoder raises ``ValueError`` naming it.
+
+    ``vad`` (a ``vad.VadPolicy``): the pauses are trimmed out of every file first (voicemap_amd/vad.py), then the trimmed corpus is
+    embedded exactly as above; the cache's ``vad_counts`` are what ``vad.summarise`` adds up.  None: nothing changes."""
+    if vad is not None:
+        return _embed_corpus_trimmed(model, dataset, preprocessor, network_type, batch, whole_utterance, vad)
     eng = _encoder_engine(model, network_type)
     inst = preprocessor.instance_preprocessor if hasattr(preprocessor, "instance_preprocessor") else preprocessor
     n_files = len(dataset)
@@ -122,6 +127,69 @@ def embed_corpus(model, dataset, preprocessor, network_type: str = "siamese", ba
 
 
 _WHOLE_FILES = 2048
+
+
+class _HostTrimmed:
+    """The files of a host dataset with their pauses trimmed out, as far as ``embed_corpus`` reads a dataset: file i is
+    ``vad_reference`` of ``to_int16(dataset._load(i))``."""
+
+    def __init__(self, dataset, policy):
+        self.base, self.index, self.policy = dataset, np.arange(len(dataset)), policy
+        self.fragment_length, self.pad, self._code = dataset.fragment_length, dataset.pad, dataset._code
+        self._refs, self._lens = [], []
+
+    def __len__(self):
+        return len(self.base)
+
+    def pcm(self, i) -> np.ndarray:
+        from .shards import to_int16
+        from .vad import vad_reference
+        raw = to_int16(self.base._load(int(i)))
+        ref = vad_reference(raw, self.policy)
+        self._refs.append(ref)
+        self._lens.append(len(raw))
+        return ref["pcm"]
+
+    def _load(self, i):
+        return self.pcm(i).astype(np.float64) / 32768.0
+
+    def counts(self):
+        from .vad import reference_counts
+        return reference_counts(self._refs, self._lens)
+
+
+def _embed_corpus_trimmed(model, dataset, preprocessor, network_type, batch, whole_utterance, policy) -> EmbeddingCache:
+    """``embed_corpus(vad=policy)``.  A resident corpus goes through ``ShardedSpeechDataset.voiced`` (trimmed on the device); a host
+    dataset is trimmed file by file with the numpy statement on its int16 PCM.  A policy that leaves ``min_keep`` open gets the
+    encoder's shortest input (``whole_utterance``) or the fragment length: no file becomes too short by being trimmed."""
+    from .utterances import pool_quantum
+    eng = _encoder_engine(model, network_type)
+    inst = preprocessor.instance_preprocessor if hasattr(preprocessor, "instance_preprocessor") else preprocessor
+    probe = inst(np.zeros((1, 8, 1)))
+    ds, wh = getattr(probe, "downsampling", 1), getattr(probe, "whitening", False)
+    policy = policy.with_min_keep(pool_quantum(eng.blocks) * ds if whole_utterance else dataset.fragment_length)
+    if getattr(dataset, "device_audio", None) is not None and hasattr(dataset, "voiced"):
+        trimmed = dataset.voiced(policy)
+        cache = embed_corpus(model, trimmed, preprocessor, network_type, batch, whole_utterance)
+        cache.vad_counts = trimmed.vad_counts
+        return cache
+    host = _HostTrimmed(dataset, policy)
+    if not whole_utterance:
+        cache = embed_corpus(model, host, preprocessor, network_type, batch, False)
+    else:   # the int16 files themselves reach embed_varlen (the buffer a resident corpus would hold)
+        if not hasattr(probe, "raw"):
+            raise ValueError("whole_utterance needs a preprocessor that decimates and whitens on the device (utils.preprocess_instances)")
+        n_files = len(dataset)
+        rank, world = parallel.rank_world()
+        lo, hi = parallel.shard_range(n_files, rank, world)
+        local = torch.empty(hi - lo, eng.E, dtype=torch.float32, device=eng.device)
+        for b0 in range(lo, hi, _WHOLE_FILES):
+            idx = range(b0, min(b0 + _WHOLE_FILES, hi))
+            waves = [host.pcm(i) for i in idx]
+            local[b0 - lo:b0 - lo + len(waves)].copy_(eng.embed_varlen(waves, None, None, ds, wh, names=file_names(dataset, idx.start, idx.stop)))
+        cache = EmbeddingCache(all_gather_rows(local, n_files), dataset._code)
+    cache.vad_counts = host.counts()
+    return cache
 
 
 def file_names(dataset, lo: int, hi: int):

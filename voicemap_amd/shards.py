@@ -177,9 +177,15 @@ class ShardedSpeechDataset(LibriSpeechDataset):
                 else np.zeros(0, dtype=np.int64)
         self.device_audio = None
 
+    _vad = None   # the policy of a ``voiced()`` dataset (then ``_raw_length`` holds the files' lengths in the shards)
+
     def _pcm(self, index):
         r = self.df.iloc[index]
-        return self._maps[int(r['shard'])][int(r['offset']):int(r['offset']) + int(r['length'])]
+        if self._vad is None:
+            return self._maps[int(r['shard'])][int(r['offset']):int(r['offset']) + int(r['length'])]
+        from .vad import vad_reference
+        raw = self._maps[int(r['shard'])][int(r['offset']):int(r['offset']) + int(self._raw_length[index])]
+        return vad_reference(np.asarray(raw), self._vad)["pcm"]
 
     def _load(self, index):
         return np.asarray(self._pcm(index), dtype=np.float64) / INT16_SCALE
@@ -189,13 +195,42 @@ class ShardedSpeechDataset(LibriSpeechDataset):
         """Upload all shards once (int16, back to back); returns the 1-D device tensor."""
         import torch
         if self.device_audio is None:
-            if self.speaker_shard is None:
+            if self.speaker_shard is None and self._vad is None:
                 parts = [torch.from_numpy(np.array(m, dtype=np.int16, copy=True)) for m in self._maps]
             else:
-                # only this rank's recordings, back to back in index order (the layout global_offset describes since __init__)
+                # only this rank's recordings (of a voiced() dataset: the trimmed ones), back to back in index order (the layout
+                # global_offset describes)
                 parts = [torch.from_numpy(np.array(self._pcm(i), dtype=np.int16, copy=True)) for i in range(len(self.df))]
             self.device_audio = torch.cat(parts).to(device) if parts else torch.zeros(0, dtype=torch.int16, device=device)
         return self.device_audio
+
+    def voiced(self, policy):
+        """This dataset with the pauses trimmed out of every file (voicemap_amd/vad.py): a dataset of the same class and API whose
+        ``device_audio``, ``global_offset``, ``file_length`` and ``length`` / ``seconds`` columns describe the trimmed corpus, and whose
+        ``_pcm`` / ``_load`` return the trimmed file (``vad_reference`` on the host -- bit for bit what the device keeps, so host
+        materialisation and device crops agree).  A policy that leaves ``min_keep`` open gets this dataset's ``fragment_length``: a
+        file that could give a fragment before still can.  With a resident corpus (``to_device()`` before) the trimming runs on the
+        device (``vad.trim``); without one the lengths come from the host statement and ``to_device()`` of the result uploads the
+        trimmed files.  The result's ``vad_counts`` are the counts ``vad.summarise`` adds up.  This dataset is left as it is."""
+        import copy
+        from . import vad
+        if self._vad is not None:
+            raise ValueError('this dataset is already trimmed')
+        policy = policy.with_min_keep(self.fragment_length)
+        new = copy.copy(self)
+        new._vad, new._raw_length, new._cdf_cache = policy, self.file_length.copy(), None
+        if self.device_audio is not None:
+            audio, offsets, lens, res = vad.trim(self.device_audio, self.global_offset, self.file_length, policy)
+            new.device_audio, new.vad_counts = audio, res.counts()
+        else:
+            refs = [vad.vad_reference(np.asarray(self._pcm(i)), policy) for i in range(len(self.df))]
+            lens = np.array([r["new_len"] for r in refs], dtype=np.int64)
+            offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64) if len(lens) else np.zeros(0, dtype=np.int64)
+            new.vad_counts = vad.reference_counts(refs, self.file_length)
+        new.global_offset, new.file_length = offsets, lens
+        new.df = self.df.assign(length=lens, seconds=lens * 1.0 / LIBRISPEECH_SAMPLING_RATE)
+        new._build_sampling_index()
+        return new
 
     def window_starts(self, indices) -> np.ndarray:
         """Global start sample of one fragment per file id, chosen like ``__getitem__`` (random if ``stochastic``, else the
