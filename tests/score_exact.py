@@ -1,8 +1,8 @@
 """Exact references for the embedding scorers (tests/test_gpu_score_exact.py; checked on the host by tests/test_score_exact_cpu.py).
 
 The four kernels that score cached embeddings -- pairdist_kernel (eval.hip), pair_hist_kernel (verif.hip), cohort_score_kernel
-(cohort.hip) and mine_kernel (mine.hip) -- run one hand-copied tile loop, and the rest of the suite checks three of them against the
-fourth.  This module is the anchor outside that loop: pure numpy, it imports neither the library nor torch.
+(cohort.hip) and mine_kernel (mine.hip) -- run one tile loop (score_tile_loop, csrc/score_tile.hpp; pair_hist_kernel holds a copy of it), and the
+rest of the suite checks three of them against the fourth.  This module is the anchor outside that loop: pure numpy, it imports neither the library nor torch.
 
 Method (that of gemm_exact.py / bn_exact.py / spectro_exact.py).  Embeddings are integers in [-8, 8] times one power of two per case
 (2^-3, 2^0, 2^2).  With E <= 256 every (a - b)^2, a * b and w * |a - b| (w a signed power of two) and every partial sum IN ANY ORDER
@@ -36,7 +36,7 @@ KINDS = {"euclidean": 0, "cosine": 1, "dot_product": 2, "weighted_l1": 3, "neg_e
 PAIRDIST_KINDS = ("euclidean", "cosine", "dot_product")
 LIMIT = 1 << 24                    # integers below it are fp32 numbers
 SCALES = (2.0 ** -3, 1.0, 4.0)
-PD_T, PD_RT, PD_MAX_E = 64, 128, 256   # csrc/eval.hip: queries per workgroup, references per stage, the widest embedding
+PD_T, PD_RT, PD_MAX_E = 64, 128, 256   # csrc/score_tile.hpp's ST_*: queries per workgroup, references per stage, the widest embedding
 U = 2.0 ** -24                     # fp32 unit roundoff
 
 # every side of the 4-wide vector, of the 64-component chunk and of PD_MAX_E
@@ -324,7 +324,7 @@ def shape_scores(full_q, full_r, M, N, q_row0):
 
 
 def copy_inputs(E):
-    """(emb (257, E), speaker labels, lattice weights) for the three copies of the tile loop."""
+    """(emb (257, E), speaker labels, lattice weights) for the three other kernels that run the tile loop."""
     rng = np.random.default_rng(5000 + E)
     emb = grid(rng, (COPY_N, E), SCALES[E % 3])
     return emb, rng.integers(0, 6, COPY_N).astype(np.int32), lattice_weights(rng, E)

@@ -5,7 +5,7 @@ embedding width around the 4-wide vector, the 64-component chunk and PD_MAX_E x 
 inputs: ties everywhere), planted ties of every position class on three shapes whose split plan has several tiles per split and empty
 trailing splits (the plan is read back from the workspace size), the contract's edges ((+inf, -1) rows, NaN never wins), every output
 and the workspace between guard words; vm_nshot_distances / vm_nshot_indexed with duplicated and NaN classes on both sides of the
-64-class pass; and the three copies of the tile loop (vm_pair_score_hist, vm_cohort_topk_stats, vm_mine_pairs) against the same
+64-class pass; and the three other kernels that run the tile loop (vm_pair_score_hist, vm_cohort_topk_stats, vm_mine_pairs) against the same
 reference at widths on the scalar fetch path.  A mismatch is reported by query row, reference row, lane, tile and split."""
 import numpy as np
 import pytest
@@ -232,7 +232,7 @@ def test_nshot_indexed_ties_and_nans(tasks, E, k, n, kind):
     assert np.array_equal(a, am2.fetch("argmin without pred"))
 
 
-# ---- the copies of the tile loop, against the independent reference ---------------------------------------------------------------
+# ---- the other kernels that run the tile loop, against the independent reference ------------------------------------------------------
 
 
 @pytest.mark.parametrize("E", S.COPY_E)

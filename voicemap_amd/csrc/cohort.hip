@@ -3,39 +3,23 @@
 // score with these statistics of both sides in vm_pair_score_hist_norm (verif.hip).
 //
 // Per tile of R query rows, two kernels:
-//  * cohort_score_kernel: the R x C scores into the workspace -- the structure and the arithmetic of pair_hist_kernel (verif.hip): 8
-//    waves, wave w owns 8 WAVE-UNIFORM queries (scalar path), lane l the cohort rows l and l + 64 of a 128-row LDS stage, the same
-//    ascending-component fmaf chain -- so every score is bit-identical to vm_pair_score_hist's (and to dist[m][c] of vm_pairdist_argmin).
-//    The excluded self pair is written as NaN: the selection skips it with the NaN scores.
-//  * cohort_select_kernel: one 1024-thread workgroup per row.  The row's C order-preserving uint32 keys (verif.hip's key; NaN -> 2^32 - 1,
+//  * cohort_score_kernel: the R x C scores into the workspace, from score_tile_loop (score_tile.hpp) -- so every score is bit-identical
+//    to vm_pair_score_hist's (and to dist[m][c] of vm_pairdist_argmin).  The excluded self pair is written as NaN: the selection skips
+//    it with the NaN scores.
+//  * cohort_select_kernel: one 1024-thread workgroup per row.  The row's C order-preserving uint32 keys (score_key_nan_last; NaN -> 2^32 - 1,
 //    above every other key) go into LDS (C <= 32 768) or are re-read from the tile in every round (larger cohorts).  A 4 x 8-bit MSB-first
 //    radix select finds the K'-th smallest key T (per-wave 256-bin sub-histograms, wave-aggregated adds for the common digit, one wave
 //    scans); the ties at T are cut in index order by a ballot / popcount prefix count.  The selected scores are reduced in float64 in a
 //    fixed order (per-thread ascending index, a shuffle tree, then the waves in order): no float atomics, bit-identical from run to run.
-#include "common.hpp"
+#include "score_tile.hpp"
 
 namespace vm {
 
-constexpr int CS_T = 64, CS_RT = 128, CS_EC = 64, CS_MAX_E = 256;
 constexpr int CS_SEL_THREADS = 1024, CS_SEL_WAVES = CS_SEL_THREADS / 64;
 constexpr int CS_CAP_SMALL = 4096, CS_CAP_LARGE = 32768;   // keys held in LDS: 16 KiB / 128 KiB (+ 16 KiB of sub-histograms)
 constexpr int CS_LOAD_BATCH = 16;                          // score loads per thread in flight while the keys are staged
 constexpr int64_t CS_TILE_FLOATS = 48LL << 20;             // the score tile: 192 MiB
 constexpr uint32_t CS_KEY_NAN = 0xffffffffu;
-
-__device__ inline uint32_t cs_key(float s) {
-    if (s != s) return CS_KEY_NAN;
-    uint32_t u = __float_as_uint(s);
-    if (u == 0x80000000u) u = 0u;   // -0.0 == +0.0: one key
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ inline float cs_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-__global__ __launch_bounds__(256) void cs_pad_weights_kernel(const float* __restrict__ w, int E, float* __restrict__ wpad) {
-    const int e = threadIdx.x;
-    if (e < CS_MAX_E) wpad[e] = (w != nullptr && e < E) ? w[e] : 0.f;
-}
 
 // grid (query blocks of 64 of the tile's R rows, splits of the cohort tiles); 512 threads.  out (R, C) fp32.
 template <int KIND>
@@ -43,12 +27,12 @@ __global__ __launch_bounds__(512) void cohort_score_kernel(const float* __restri
                                                            int E, int64_t self_col0, const float* __restrict__ qsq,
                                                            const float* __restrict__ rsq, const float* __restrict__ wpad, int tiles_per_split,
                                                            float* __restrict__ out) {
-    constexpr int RT = CS_RT, RP = CS_EC + 4;
-    __shared__ __attribute__((aligned(16))) float rs[RT * RP];
+    constexpr int RT = ST_RT;
+    __shared__ __attribute__((aligned(16))) float rs[ST_RT * ST_RP];
     const int EP = ((E + 3) / 4) * 4, E4 = EP / 4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t m0 = (int64_t)blockIdx.x * CS_T + 8 * w;   // this wave's first query (row of the tile)
+    const int64_t m0 = (int64_t)blockIdx.x * ST_T + 8 * w;   // this wave's first query (row of the tile)
     const int64_t last_group = (R - 1) >> 3;                  // a wave past the last query computes on the last group and stores nothing
     const float* qg = qT + ((m0 >> 3) < last_group ? (m0 >> 3) : last_group) * (int64_t)E4 * 32;
     float qn[8];
@@ -57,78 +41,7 @@ __global__ __launch_bounds__(512) void cohort_score_kernel(const float* __restri
     const int n_tiles = (int)((C + RT - 1) / RT);
     const int t_lo = blockIdx.y * tiles_per_split;
     const int t_hi = min(n_tiles, t_lo + tiles_per_split);
-    const int nchunk = (EP + CS_EC - 1) / CS_EC;
-    const int n_stage = (t_hi - t_lo) * nchunk;
-    const bool vec = (E & 3) == 0;
-    auto fetch = [&](int s, f32x4 (&v)[4]) {
-        const int64_t n0 = (int64_t)(t_lo + s / nchunk) * RT;
-        const int ec = (s % nchunk) * CS_EC;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int piece = tid + 512 * k, r = piece >> 4, c = (piece & 15) * 4;
-            const int64_t row = n0 + r;
-            const int col = ec + c;
-            if (vec) {
-                const bool ok = row < C && col < E;
-                const f32x4 x = *reinterpret_cast<const f32x4*>(cohort + (ok ? row * E + col : 0));
-                v[k] = ok ? x : f32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[k][u] = (row < C && col + u < E) ? cohort[row * E + col + u] : 0.f;
-            }
-        }
-    };
-    auto stash = [&](const f32x4 (&v)[4]) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int piece = tid + 512 * k, r = piece >> 4, c = (piece & 15) * 4;
-            *reinterpret_cast<f32x4*>(rs + r * RP + c) = v[k];
-        }
-    };
-    f32x4 nxt[4];
-    if (n_stage > 0) fetch(0, nxt);
-    float acc[8][2];
-    for (int s = 0; s < n_stage; ++s) {
-        const int t = t_lo + s / nchunk, ck = s % nchunk;
-        const int ec = ck * CS_EC;
-        const int ew4 = min(CS_EC, EP - ec) / 4;
-        const int64_t n0 = (int64_t)t * RT;
-        __syncthreads();   // the previous stage's readers are done
-        stash(nxt);
-        if (s + 1 < n_stage) fetch(s + 1, nxt);
-        __syncthreads();
-        if (ck == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[i][0] = acc[i][1] = 0.f;
-        }
-        const float* qe = qg + (ec / 4) * 32;
-        const float* we = wpad + ec;
-#pragma unroll 2
-        for (int e4 = 0; e4 < ew4; ++e4) {
-            const f32x4 r0 = *reinterpret_cast<const f32x4*>(rs + lane * RP + e4 * 4);
-            const f32x4 r1 = *reinterpret_cast<const f32x4*>(rs + (lane + 64) * RP + e4 * 4);
-            f32x4 wv = {0.f, 0.f, 0.f, 0.f};
-            if (KIND == VM_SCORE_WEIGHTED_L1) wv = *reinterpret_cast<const f32x4*>(we + e4 * 4);   // uniform: a scalar load
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const f32x4 qv = *reinterpret_cast<const f32x4*>(qe + e4 * 32 + i * 4);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (KIND == VM_DIST_EUCLIDEAN || KIND == VM_SCORE_NEG_EUCLIDEAN) {
-                        const float d0 = qv[c] - r0[c], d1 = qv[c] - r1[c];
-                        acc[i][0] = fmaf(d0, d0, acc[i][0]);
-                        acc[i][1] = fmaf(d1, d1, acc[i][1]);
-                    } else if (KIND == VM_SCORE_WEIGHTED_L1) {
-                        acc[i][0] = fmaf(wv[c], fabsf(qv[c] - r0[c]), acc[i][0]);
-                        acc[i][1] = fmaf(wv[c], fabsf(qv[c] - r1[c]), acc[i][1]);
-                    } else {
-                        acc[i][0] = fmaf(qv[c], r0[c], acc[i][0]);
-                        acc[i][1] = fmaf(qv[c], r1[c], acc[i][1]);
-                    }
-                }
-            }
-        }
-        if (ck != nchunk - 1) continue;
+    score_tile_loop<KIND>(rs, qg, cohort, C, E, wpad, t_lo, t_hi, [&](int64_t n0, const float (&acc)[8][2]) {
         float rn[2] = {1.f, 1.f};
         if (KIND == VM_DIST_COSINE) {
 #pragma unroll
@@ -156,7 +69,7 @@ __global__ __launch_bounds__(512) void cohort_score_kernel(const float* __restri
                 if (m < R && nn < C) out[m * C + nn] = d;   // a wave = 256 contiguous bytes of a row
             }
         }
-    }
+    });
 }
 
 // One workgroup per row r of the score tile sc (rows, C).  CAP > 0: the keys are staged in LDS (C <= CAP); CAP == 0: every pass re-reads
@@ -178,7 +91,7 @@ __global__ __launch_bounds__(CS_SEL_THREADS) void cohort_select_kernel(const flo
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     auto key_at = [&](int64_t c) -> uint32_t {
         if constexpr (CAP > 0) return keys[c];
-        else return cs_key(row[c]);
+        else return score_key_nan_last(row[c]);
     };
     // workgroup sums in a fixed order: a shuffle tree per wave, then the waves in order
     auto block_sum_u = [&](uint32_t x) -> uint32_t {
@@ -216,7 +129,7 @@ __global__ __launch_bounds__(CS_SEL_THREADS) void cohort_select_kernel(const flo
         for (int u = 0; u < CS_LOAD_BATCH; ++u) {
             const int64_t c = c0 + (int64_t)u * CS_SEL_THREADS + tid;
             if (c < C) {
-                const uint32_t k = cs_key(v[u]);
+                const uint32_t k = score_key_nan_last(v[u]);
                 if constexpr (CAP > 0) keys[c] = k;
                 nnan += k == CS_KEY_NAN;
             }
@@ -333,14 +246,14 @@ __global__ __launch_bounds__(CS_SEL_THREADS) void cohort_select_kernel(const flo
     double s = 0.0;
     for (int64_t c = tid; c < C; c += CS_SEL_THREADS) {
         const uint32_t key = key_at(c);
-        if (selected(c, key)) s += (double)cs_value(key);
+        if (selected(c, key)) s += (double)score_value(key);
     }
     const double mean = block_sum_d(s) / (double)kk;
     double ss = 0.0;
     for (int64_t c = tid; c < C; c += CS_SEL_THREADS) {
         const uint32_t key = key_at(c);
         if (selected(c, key)) {
-            const double dv = (double)cs_value(key) - mean;
+            const double dv = (double)score_value(key) - mean;
             ss += dv * dv;
         }
     }
@@ -391,17 +304,9 @@ __global__ __launch_bounds__(CS_SEL_THREADS) void cohort_select_kernel(const flo
 
 // rows of one score tile: the tile stays within CS_TILE_FLOATS
 static int64_t cs_tile_rows(int64_t M, int64_t C) {
-    int64_t R = (CS_TILE_FLOATS / C) / CS_T * CS_T;
-    if (R < CS_T) R = CS_T;
+    int64_t R = (CS_TILE_FLOATS / C) / ST_T * ST_T;
+    if (R < ST_T) R = ST_T;
     return R < M ? R : M;
-}
-
-static int cs_splits(int64_t R, int64_t C) {
-    const int64_t qb = (R + CS_T - 1) / CS_T, nt = (C + CS_RT - 1) / CS_RT;
-    int64_t s = (2048 + qb - 1) / qb;   // >= 2048 workgroups (8 per CU)
-    if (s > nt) s = nt;
-    if (s < 1) s = 1;
-    return (int)s;
 }
 
 }  // namespace vm
@@ -411,7 +316,7 @@ extern "C" int64_t vm_cohort_stats_workspace_bytes(int64_t M, int64_t C, int E) 
     const int64_t R = vm::cs_tile_rows(M, C), EP = ((E + 3) / 4) * 4;
     // query and cohort squared norms, the padded weights, the scalar-path copy of a tile's queries, the score tile (+ one row: with
     // topk_idx, half the rows per tile and the other half holds the index lists)
-    return M * 4 + 256 + C * 4 + 256 + vm::CS_MAX_E * 4 + 256 + ((R + 7) / 8) * 8 * EP * 4 + 256 + (R + 1) * C * 4 + 256;
+    return M * 4 + 256 + C * 4 + 256 + vm::ST_MAX_E * 4 + 256 + ((R + 7) / 8) * 8 * EP * 4 + 256 + (R + 1) * C * 4 + 256;
 }
 
 extern "C" int vm_cohort_topk_stats(const float* q, int64_t M, const float* cohort, int64_t C, int E, int score_kind, const float* weights,
@@ -419,8 +324,8 @@ extern "C" int vm_cohort_topk_stats(const float* q, int64_t M, const float* coho
                                     void* ws, void* stream) {
     using namespace vm;
     VM_REQUIRE(q && cohort && mu && sigma && rsig && count && ws, "vm_cohort_topk_stats: null pointer");
-    VM_REQUIRE(M > 0 && M < (1LL << 31) && C > 0 && C < (1LL << 31) && E > 0 && E <= CS_MAX_E,
-               "vm_cohort_topk_stats: bad sizes (M, C < 2^31, E <= %d)", CS_MAX_E);
+    VM_REQUIRE(M > 0 && M < (1LL << 31) && C > 0 && C < (1LL << 31) && E > 0 && E <= ST_MAX_E,
+               "vm_cohort_topk_stats: bad sizes (M, C < 2^31, E <= %d)", ST_MAX_E);
     VM_REQUIRE(K >= 1 && K < (1LL << 31), "vm_cohort_topk_stats: K must be in [1, 2^31)");
     VM_REQUIRE(score_kind >= VM_DIST_EUCLIDEAN && score_kind <= VM_SCORE_NEG_EUCLIDEAN, "vm_cohort_topk_stats: unknown score_kind %d",
                score_kind);
@@ -432,7 +337,7 @@ extern "C" int vm_cohort_topk_stats(const float* q, int64_t M, const float* coho
     float* qsq = (float*)ws;
     float* rsq = (float*)(((uintptr_t)(qsq + M) + 255) & ~(uintptr_t)255);
     float* wpad = (float*)(((uintptr_t)(rsq + C) + 255) & ~(uintptr_t)255);
-    float* qT = (float*)(((uintptr_t)(wpad + CS_MAX_E) + 255) & ~(uintptr_t)255);
+    float* qT = (float*)(((uintptr_t)(wpad + ST_MAX_E) + 255) & ~(uintptr_t)255);
     const int64_t EP = ((E + 3) / 4) * 4;
     float* tile = (float*)(((uintptr_t)(qT + ((R + 7) / 8) * 8 * EP) + 255) & ~(uintptr_t)255);
     int32_t* list = (int32_t*)(tile + RT * C);   // with topk_idx: RT rows of C indices behind the RT score rows, within (R + 1) * C
@@ -440,14 +345,14 @@ extern "C" int vm_cohort_topk_stats(const float* q, int64_t M, const float* coho
         launch_rowsq(q, M, E, qsq, st);
         launch_rowsq(cohort, C, E, rsq, st);
     }
-    hipLaunchKernelGGL(cs_pad_weights_kernel, dim3(1), dim3(256), 0, st, score_kind == VM_SCORE_WEIGHTED_L1 ? weights : nullptr, E, wpad);
-    const int splits = cs_splits(RT, C);
-    const int tps = (int)(((C + CS_RT - 1) / CS_RT + splits - 1) / splits);
+    launch_pad_weights(score_kind == VM_SCORE_WEIGHTED_L1 ? weights : nullptr, E, wpad, st);
+    const int splits = score_splits(RT, C, 2048);
+    const int tps = (int)(((C + ST_RT - 1) / ST_RT + splits - 1) / splits);
     for (int64_t row0 = 0; row0 < M; row0 += RT) {
         const int64_t rows = RT < M - row0 ? RT : M - row0;
         launch_pairdist_qt(q + row0 * E, rows, E, qT, st);
         const int64_t self_col0 = self_row0 >= 0 ? self_row0 + row0 : -1;
-        const dim3 grid((unsigned)((rows + CS_T - 1) / CS_T), (unsigned)splits);
+        const dim3 grid((unsigned)((rows + ST_T - 1) / ST_T), (unsigned)splits);
 #define VM_CS(KD) hipLaunchKernelGGL(cohort_score_kernel<KD>, grid, dim3(512), 0, st, qT, cohort, rows, C, E, self_col0, qsq + row0, rsq, wpad, \
                                      tps, tile)
         switch (score_kind) {

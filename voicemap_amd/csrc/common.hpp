@@ -108,9 +108,6 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 int f1_set_blocks(int v);  // conv1_fused.hip tuning
 int f1_set_fwd_blocks(int v);
-// eval.hip: row squared norms (fmaf, ascending component per lane, wave sum) and the scalar-path query layout of pairdist_kernel
-void launch_rowsq(const float* x, int64_t rows, int E, float* out, hipStream_t st);
-void launch_pairdist_qt(const float* q, int64_t M, int E, float* qT, hipStream_t st);
 
 // 16-bit storage types only (bf16 / f16): the LDS-DMA kernels and the fused block-1 kernels
 #define VM_DISPATCH_16(dtype, ...)                                  \

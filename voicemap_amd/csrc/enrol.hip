@@ -26,7 +26,7 @@
 // row at the end.  HIST = true: the counts by class, exactly as pair_hist_kernel (verif.hip) keeps them: u32 LDS bins, per-lane
 // under / over / NaN counts, one flush of 64-bit integer atomics per workgroup.  One template, one en_acc / en_finish: the two entry
 // points score bit-identically.
-#include "common.hpp"
+#include "score_tile.hpp"
 
 namespace vm {
 
@@ -38,13 +38,6 @@ struct EnWindows {
     uint32_t lo[EN_MAX_WIN];
     uint32_t shift[EN_MAX_WIN];
 };
-
-__device__ inline uint32_t en_key(float s) {
-    if (s != s) return 0xffffffffu;
-    uint32_t u = __float_as_uint(s);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // ---- the one scoring function of both entry points --------------------------------------------------------------------------------
 template <int KIND>
@@ -229,7 +222,7 @@ __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ 
         own_ok[i] = l >= 0 && count[l] - (loo ? 1 : 0) > 0;
         qnv[i] = (KIND == VM_DIST_COSINE && okm[i]) ? qn[m] : 1.0;
         ownv[i] = okm[i] ? own[m] : nanf_;
-        okey[i] = en_key(ownv[i]);
+        okey[i] = score_key_nan_last(ownv[i]);
     }
     uint32_t before[4] = {0u, 0u, 0u, 0u};
     unsigned long long best[4] = {~0ull, ~0ull, ~0ull, ~0ull};
@@ -327,7 +320,7 @@ __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ 
                 if (!HIST) {
                     if (scores != nullptr && okm[i] && oks) scores[m * S + s] = trial ? d : nanf_;
                     if (trial) {
-                        const uint32_t k = en_key(d);
+                        const uint32_t k = score_key_nan_last(d);
                         const unsigned long long cand = ((unsigned long long)k << 32) | (uint32_t)s;
                         if (cand < best[i]) {
                             best[i] = cand;
@@ -341,7 +334,7 @@ __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ 
                         nanc[cls] += 1u;
                         continue;
                     }
-                    const uint32_t k = en_key(d);
+                    const uint32_t k = score_key_nan_last(d);
 #pragma unroll
                     for (int v = 0; v < EN_MAX_WIN; ++v) {
                         if (v >= n_win) break;

@@ -1,7 +1,7 @@
 // n-shot k-way evaluation distances (voicemap/utils.py:159-206): per task, k class prototypes from n support
 // embeddings each, distance to the query embedding, argmin.  The reference does this per task in float64 numpy
 // after two predict() calls; here all tasks of an evaluation run go through one launch (fp64 accumulation).
-#include "common.hpp"
+#include "score_tile.hpp"
 
 namespace vm {
 
@@ -192,15 +192,8 @@ __global__ __launch_bounds__(256) void nshot_indexed_kernel(const float* __restr
 }
 
 // vm_pairdist_argmin: the (M, N) distance matrix between a block of query rows and the whole reference matrix, fp32, with the
-// nearest reference row per query (first minimum; the query's own row can be excluded).  The euclidean distance is the direct form
-// sqrt(sum (a - b)^2) -- no ||a||^2 + ||b||^2 - 2ab cancellation -- 2 VALU instructions per component pair: the kernel's bound is
-// fp32 VALU issue (2 x M x N x E / 64 wave instructions; v_pk_* do not issue faster on gfx950).  Round 6, on the 13 002 x 104 014 x 64
-// shard of BASELINE.json config 5 (profiles/r06_pairdist.txt): the round-5 kernel (16 x 16 threads, 4 x 4 register tiles, both operands
-// from LDS) ran 8.9 ms -- it was LDS-bound: a thread's four ADJACENT reference rows put lanes tx, tx + 4, tx + 8, tx + 12 on the same
-// banks (4-way conflicts on every reference read).  Rows 16 apart + register prefetch of the next stage: 5.5 ms, and the dot product
-// at 3.5 ms showed the LDS still level with the VALU (8 reads per 64 component pairs).  Now the QUERIES are wave-uniform and come through
-// the scalar path (pairdist_qt_kernel lays them out for it), lanes are references: one LDS read per 32 component pairs.
-constexpr int PD_T = 64, PD_RT = 128, PD_EC = 64, PD_MAX_E = 256;   // queries per workgroup, references per stage, components per stage
+// nearest reference row per query (first minimum; the query's own row can be excluded).  The scores are score_tile_loop's
+// (score_tile.hpp); the epilogue here is the distance store and the argmin.
 
 __global__ __launch_bounds__(256) void rowsq_kernel(const float* __restrict__ x, int64_t rows, int E, float* __restrict__ out) {
     const int lane = threadIdx.x & 63;
@@ -227,20 +220,22 @@ __global__ __launch_bounds__(256) void pairdist_qt_kernel(const float* __restric
     qT[i] = (m < M && e < E) ? q[m * E + e] : 0.f;
 }
 
-// Workgroup = 8 waves; wave w owns the 8 queries m0 + 8 w .. + 7 -- WAVE-UNIFORM, so their components arrive through scalar loads
-// (SGPR operands of the subtract / FMA: no LDS read, no vector register) -- and lane l the references n0 + l and n0 + l + 64 of a
-// 128-reference stage, whose 64 components per stage it reads from LDS 16 bytes at a time: ONE LDS read per 32 component pairs.
+__global__ __launch_bounds__(256) void pad_weights_kernel(const float* __restrict__ w, int E, float* __restrict__ wpad) {
+    const int e = threadIdx.x;
+    if (e < ST_MAX_E) wpad[e] = (w != nullptr && e < E) ? w[e] : 0.f;
+}
+
+// grid (query blocks of 64 rows, splits of the reference tiles); 512 threads; wave w owns the queries m0 + 8 w .. + 7.
 template <int DIST>
 __global__ __launch_bounds__(512) void pairdist_kernel(const float* __restrict__ qT, const float* __restrict__ ref, int64_t M, int64_t N,
                                                        int E, int64_t q_row0, const float* __restrict__ qsq,
                                                        const float* __restrict__ rsq, int tiles_per_split, float* __restrict__ dist,
                                                        float* __restrict__ part_val, int32_t* __restrict__ part_idx) {
-    constexpr int RT = PD_RT, RP = PD_EC + 4;   // 128 references per stage; row pitch 68 floats = 17 bank quads
-    __shared__ __attribute__((aligned(16))) float rs[RT * RP];
+    __shared__ __attribute__((aligned(16))) float rs[ST_RT * ST_RP];
     const int EP = ((E + 3) / 4) * 4, E4 = EP / 4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t m0 = (int64_t)blockIdx.x * PD_T + 8 * w;          // this wave's first query
+    const int64_t m0 = (int64_t)blockIdx.x * ST_T + 8 * w;          // this wave's first query
     // its group's rows of qT (wave-uniform).  A wave past the last query (M not a multiple of 64) computes on the LAST group's rows --
     // qT holds ceil(M / 8) groups and nothing behind them -- and stores nothing (every use below is guarded by m < M).
     const int64_t last_group = (M - 1) >> 3;
@@ -253,76 +248,10 @@ __global__ __launch_bounds__(512) void pairdist_kernel(const float* __restrict__
         bestv[i] = INFINITY;
         besti[i] = 0x7fffffff;
     }
-    const int n_tiles = (int)((N + RT - 1) / RT);
+    const int n_tiles = (int)((N + ST_RT - 1) / ST_RT);
     const int t_lo = blockIdx.y * tiles_per_split;
     const int t_hi = min(n_tiles, t_lo + tiles_per_split);
-    const int nchunk = (EP + PD_EC - 1) / PD_EC;
-    const int n_stage = (t_hi - t_lo) * nchunk;
-    const bool vec = (E & 3) == 0;
-    // stage s = (tile t_lo + s / nchunk, components (s % nchunk) * 64 ..): this thread's four 16-byte pieces, piece = tid + 512 k
-    auto fetch = [&](int s, f32x4 (&v)[4]) {
-        const int64_t n0 = (int64_t)(t_lo + s / nchunk) * RT;
-        const int ec = (s % nchunk) * PD_EC;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int piece = tid + 512 * k, r = piece >> 4, c = (piece & 15) * 4;
-            const int64_t row = n0 + r;
-            const int col = ec + c;
-            if (vec) {
-                const bool ok = row < N && col < E;
-                const f32x4 x = *reinterpret_cast<const f32x4*>(ref + (ok ? row * E + col : 0));
-                v[k] = ok ? x : f32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[k][u] = (row < N && col + u < E) ? ref[row * E + col + u] : 0.f;
-            }
-        }
-    };
-    auto stash = [&](const f32x4 (&v)[4]) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int piece = tid + 512 * k, r = piece >> 4, c = (piece & 15) * 4;
-            *reinterpret_cast<f32x4*>(rs + r * RP + c) = v[k];
-        }
-    };
-    f32x4 nxt[4];
-    if (n_stage > 0) fetch(0, nxt);
-    float acc[8][2];
-    for (int s = 0; s < n_stage; ++s) {
-        const int t = t_lo + s / nchunk, ck = s % nchunk;
-        const int ec = ck * PD_EC;
-        const int ew4 = min(PD_EC, EP - ec) / 4;
-        const int64_t n0 = (int64_t)t * RT;
-        __syncthreads();  // the previous stage's readers are done
-        stash(nxt);
-        if (s + 1 < n_stage) fetch(s + 1, nxt);   // in flight while this stage is consumed
-        __syncthreads();
-        if (ck == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[i][0] = acc[i][1] = 0.f;
-        }
-        const float* qe = qg + (ec / 4) * 32;
-#pragma unroll 2
-        for (int e4 = 0; e4 < ew4; ++e4) {
-            const f32x4 r0 = *reinterpret_cast<const f32x4*>(rs + lane * RP + e4 * 4);
-            const f32x4 r1 = *reinterpret_cast<const f32x4*>(rs + (lane + 64) * RP + e4 * 4);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const f32x4 qv = *reinterpret_cast<const f32x4*>(qe + e4 * 32 + i * 4);   // uniform address: a scalar load
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (DIST == VM_DIST_EUCLIDEAN) {
-                        const float d0 = qv[c] - r0[c], d1 = qv[c] - r1[c];
-                        acc[i][0] = fmaf(d0, d0, acc[i][0]);
-                        acc[i][1] = fmaf(d1, d1, acc[i][1]);
-                    } else {
-                        acc[i][0] = fmaf(qv[c], r0[c], acc[i][0]);
-                        acc[i][1] = fmaf(qv[c], r1[c], acc[i][1]);
-                    }
-                }
-            }
-        }
-        if (ck != nchunk - 1) continue;
+    score_tile_loop<DIST>(rs, qg, ref, N, E, nullptr, t_lo, t_hi, [&](int64_t n0, const float (&acc)[8][2]) {
         float rn[2] = {1.f, 1.f};
         if (DIST == VM_DIST_COSINE) {
 #pragma unroll
@@ -349,7 +278,7 @@ __global__ __launch_bounds__(512) void pairdist_kernel(const float* __restrict__
                 }
             }
         }
-    }
+    });
     // a lane's minimum is the first in ITS references; across lanes the smaller index wins a tie
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -389,7 +318,7 @@ __global__ __launch_bounds__(256) void pairdist_final_kernel(const float* __rest
     best_idx[m] = bi == 0x7fffffff ? -1 : bi;
 }
 
-// launchers of the two preparation kernels above for verif.hip (the pair-score histogram stages its queries the same way)
+// launchers of the preparation kernels for the other scorers (declared in score_tile.hpp)
 void launch_rowsq(const float* x, int64_t rows, int E, float* out, hipStream_t st) {
     hipLaunchKernelGGL(rowsq_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, rows, E, out);
 }
@@ -399,12 +328,8 @@ void launch_pairdist_qt(const float* q, int64_t M, int E, float* qT, hipStream_t
     hipLaunchKernelGGL(pairdist_qt_kernel, dim3((unsigned)((qt_n + 255) / 256)), dim3(256), 0, st, q, M, E, EP, qT);
 }
 
-static int pd_splits(int64_t M, int64_t N) {
-    const int64_t mt = (M + PD_T - 1) / PD_T, nt = (N + PD_RT - 1) / PD_RT;
-    int64_t s = (2048 + mt - 1) / mt;  // aim for >= 2048 workgroups (8 per CU)
-    if (s > nt) s = nt;
-    if (s < 1) s = 1;
-    return (int)s;
+void launch_pad_weights(const float* w, int E, float* wpad, hipStream_t st) {
+    hipLaunchKernelGGL(pad_weights_kernel, dim3(1), dim3(256), 0, st, w, E, wpad);
 }
 
 }  // namespace vm
@@ -424,19 +349,19 @@ extern "C" int vm_nshot_indexed(const float* emb, int64_t n_rows, const int32_t*
 
 extern "C" int64_t vm_pairdist_workspace_bytes(int64_t M, int64_t N) {
     if (M <= 0 || N <= 0) return 0;
-    // partial minima per split, the two squared-norm vectors, and the scalar-path copy of the queries (8-row groups x up to PD_MAX_E)
-    return (int64_t)vm::pd_splits(M, N) * M * 8 + (M + N) * 4 + 256 + ((M + 7) / 8) * 8 * (int64_t)vm::PD_MAX_E * 4 + 256;
+    // partial minima per split, the two squared-norm vectors, and the scalar-path copy of the queries (8-row groups x up to ST_MAX_E)
+    return (int64_t)vm::score_splits(M, N, 2048) * M * 8 + (M + N) * 4 + 256 + ((M + 7) / 8) * 8 * (int64_t)vm::ST_MAX_E * 4 + 256;
 }
 
 extern "C" int vm_pairdist_argmin(const float* q, const float* ref, int64_t M, int64_t N, int E, int dist_kind, int64_t q_row0,
                                   float* dist, float* best_val, int32_t* best_idx, void* ws, void* stream) {
     using namespace vm;
     VM_REQUIRE(q && ref && best_val && best_idx && ws, "vm_pairdist_argmin: null pointer");
-    VM_REQUIRE(M > 0 && N > 0 && E > 0 && E <= PD_MAX_E, "vm_pairdist_argmin: bad sizes (E <= %d)", PD_MAX_E);
-    VM_REQUIRE(N < (1LL << 31) && (M + PD_T - 1) / PD_T < (1LL << 31), "vm_pairdist_argmin: matrix too large for one launch");
+    VM_REQUIRE(M > 0 && N > 0 && E > 0 && E <= ST_MAX_E, "vm_pairdist_argmin: bad sizes (E <= %d)", ST_MAX_E);
+    VM_REQUIRE(N < (1LL << 31) && (M + ST_T - 1) / ST_T < (1LL << 31), "vm_pairdist_argmin: matrix too large for one launch");
     VM_REQUIRE(dist_kind >= VM_DIST_EUCLIDEAN && dist_kind <= VM_DIST_DOT,
                "vm_pairdist_argmin: Distance must be in (euclidean, cosine, dot_product)");
-    const int splits = pd_splits(M, N);
+    const int splits = score_splits(M, N, 2048);
     float* part_val = (float*)ws;
     int32_t* part_idx = (int32_t*)(part_val + (int64_t)splits * M);
     float* qsq = (float*)(part_idx + (int64_t)splits * M);
@@ -451,10 +376,10 @@ extern "C" int vm_pairdist_argmin(const float* q, const float* ref, int64_t M, i
     float* qT = (float*)(((uintptr_t)(rsq + N) + 255) & ~(uintptr_t)255);
     const int64_t qt_n = ((M + 7) / 8) * 8 * (int64_t)EP;
     hipLaunchKernelGGL(pairdist_qt_kernel, dim3((unsigned)((qt_n + 255) / 256)), dim3(256), 0, st, q, M, E, EP, qT);
-    const int n_tiles = (int)((N + PD_RT - 1) / PD_RT);
+    const int n_tiles = (int)((N + ST_RT - 1) / ST_RT);
     const int tps = (n_tiles + splits - 1) / splits;
     VM_REQUIRE((E & 3) != 0 || (((uintptr_t)ref) & 15) == 0, "vm_pairdist_argmin: ref must be 16-byte aligned when E %% 4 == 0");
-    const dim3 grid((unsigned)((M + PD_T - 1) / PD_T), (unsigned)splits);
+    const dim3 grid((unsigned)((M + ST_T - 1) / ST_T), (unsigned)splits);
 #define VM_PD(D) hipLaunchKernelGGL(pairdist_kernel<D>, grid, dim3(512), 0, st, qT, ref, M, N, E, q_row0, qsq, rsq, tps, dist, part_val, part_idx)
     if (dist_kind == VM_DIST_EUCLIDEAN) VM_PD(VM_DIST_EUCLIDEAN);
     else if (dist_kind == VM_DIST_COSINE) VM_PD(VM_DIST_COSINE);

@@ -2,12 +2,11 @@
 // rows of another speaker and its k_pos FARTHEST rows of its own speaker under the training distance -- the pairs a siamese step still
 // learns from once uniformly drawn negatives lie beyond the margin.  Only the (M, K) lists leave the chip: no M x N score tile exists.
 //
-// mine_kernel = the tile loop of pair_hist_kernel (verif.hip) / pairdist_kernel (eval.hip): 8 waves, wave w owns 8 WAVE-UNIFORM anchors
-// that arrive through the scalar path, lane l the candidate rows l and l + 64 of a 128-row LDS stage, the same ascending-component fmaf
-// chain -- every score is bit-identical to dist[i][j] of vm_pairdist_argmin.  What differs is the epilogue: a small-K selection.
+// mine_kernel's scores come from score_tile_loop (score_tile.hpp): every one is bit-identical to dist[i][j] of vm_pairdist_argmin.  Its
+// own part is the epilogue: a small-K selection.
 //
-// An entry is ONE uint64: (order key << 32) | (j << 1) | (the score was -0.0).  The order key is verif.hip's uint32 key for the negatives
-// and its complement for the positives, so "the K smallest entries, ascending" is the contract's (key, j) order for the first and (key
+// An entry is ONE uint64: (order key << 32) | (j << 1) | (the score was -0.0).  The order key is score_key (score_tile.hpp) for the
+// negatives and its complement for the positives, so "the K smallest entries, ascending" is the contract's (key, j) order for the first and (key
 // descending, j ascending) for the second; the low bit only carries the sign of a zero back to the value output (j is unique per
 // anchor, so it never decides an order).  Entries are totally ordered: the K smallest of a set do not depend on the order of arrival.
 //
@@ -20,18 +19,12 @@
 //
 // The candidate range is split over blockIdx.y so the grid fills the chip; each split leaves its partial lists (splits, M, K) in the
 // workspace and mine_merge_kernel (one wave per anchor) folds them with the same insertion and decodes index and score.
-#include "common.hpp"
+#include "score_tile.hpp"
 
 namespace vm {
 
-constexpr int MN_T = 64, MN_RT = 128, MN_EC = 64, MN_MAX_E = 256, MN_MAX_K = 64;
+constexpr int MN_MAX_K = 64;
 constexpr unsigned long long MN_EMPTY = ~0ull;
-
-__device__ inline uint32_t mn_key(float s) {
-    uint32_t u = __float_as_uint(s);
-    if (u == 0x80000000u) u = 0u;   // -0.0 == +0.0: one key
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __device__ inline unsigned long long mn_readlane(unsigned long long v, int src) {   // src wave-uniform
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
@@ -66,12 +59,12 @@ __global__ __launch_bounds__(512, 4) void mine_kernel(const float* __restrict__ 
                                                    const float* __restrict__ rsq, const float* __restrict__ neg_floor, int k_neg, int k_pos,
                                                    int tiles_per_split, unsigned long long* __restrict__ part_neg,
                                                    unsigned long long* __restrict__ part_pos) {
-    constexpr int RT = MN_RT, RP = MN_EC + 4;
-    __shared__ __attribute__((aligned(16))) float rs[RT * RP];
+    constexpr int RT = ST_RT;
+    __shared__ __attribute__((aligned(16))) float rs[ST_RT * ST_RP];
     const int EP = ((E + 3) / 4) * 4, E4 = EP / 4;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t m0 = row_lo + (int64_t)blockIdx.x * MN_T + 8 * w;   // this wave's first anchor (global row)
+    const int64_t m0 = row_lo + (int64_t)blockIdx.x * ST_T + 8 * w;   // this wave's first anchor (global row)
     const int64_t ml0 = m0 - row_lo;                                   // ... as a row of qT
     const int64_t last_group = (M - 1) >> 3;   // a wave past the last anchor computes on the last group and keeps nothing
     const float* qg = qT + ((ml0 >> 3) < last_group ? (ml0 >> 3) : last_group) * (int64_t)E4 * 32;
@@ -89,79 +82,14 @@ __global__ __launch_bounds__(512, 4) void mine_kernel(const float* __restrict__ 
         ql[i] = ok ? label[m0 + i] : -1;
         aok[i] = ok && ql[i] >= 0;
         const float fl = (ok && neg_floor != nullptr) ? neg_floor[m0 + i - row_lo] : __uint_as_float(0x7fc00000u);
-        fkey[i] = fl != fl ? 0u : mn_key(fl) + 1u;   // key(+inf) + 1 still fits
+        fkey[i] = fl != fl ? 0u : score_key(fl) + 1u;   // key(+inf) + 1 still fits
         nl[i] = pl[i] = MN_EMPTY;
         nthr[i] = pthr[i] = 0xffffffffu;
     }
     const int n_tiles = (int)((N + RT - 1) / RT);
     const int t_lo = blockIdx.y * tiles_per_split;
     const int t_hi = min(n_tiles, t_lo + tiles_per_split);
-    const int nchunk = (EP + MN_EC - 1) / MN_EC;
-    const int n_stage = max(t_hi - t_lo, 0) * nchunk;
-    const bool vec = (E & 3) == 0;
-    auto fetch = [&](int s, f32x4 (&v)[4]) {
-        const int64_t n0 = (int64_t)(t_lo + s / nchunk) * RT;
-        const int ec = (s % nchunk) * MN_EC;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int piece = tid + 512 * k, r = piece >> 4, c = (piece & 15) * 4;
-            const int64_t row = n0 + r;
-            const int col = ec + c;
-            if (vec) {
-                const bool ok = row < N && col < E;
-                const f32x4 x = *reinterpret_cast<const f32x4*>(ref + (ok ? row * E + col : 0));
-                v[k] = ok ? x : f32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) v[k][u] = (row < N && col + u < E) ? ref[row * E + col + u] : 0.f;
-            }
-        }
-    };
-    auto stash = [&](const f32x4 (&v)[4]) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int piece = tid + 512 * k, r = piece >> 4, c = (piece & 15) * 4;
-            *reinterpret_cast<f32x4*>(rs + r * RP + c) = v[k];
-        }
-    };
-    f32x4 nxt[4];
-    if (n_stage > 0) fetch(0, nxt);
-    float acc[8][2];
-    for (int s = 0; s < n_stage; ++s) {
-        const int t = t_lo + s / nchunk, ck = s % nchunk;
-        const int ec = ck * MN_EC;
-        const int ew4 = min(MN_EC, EP - ec) / 4;
-        const int64_t n0 = (int64_t)t * RT;
-        __syncthreads();   // the previous stage's readers are done
-        stash(nxt);
-        if (s + 1 < n_stage) fetch(s + 1, nxt);
-        __syncthreads();
-        if (ck == 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) acc[i][0] = acc[i][1] = 0.f;
-        }
-        const float* qe = qg + (ec / 4) * 32;
-#pragma unroll 2
-        for (int e4 = 0; e4 < ew4; ++e4) {
-            const f32x4 r0 = *reinterpret_cast<const f32x4*>(rs + lane * RP + e4 * 4);
-            const f32x4 r1 = *reinterpret_cast<const f32x4*>(rs + (lane + 64) * RP + e4 * 4);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const f32x4 qv = *reinterpret_cast<const f32x4*>(qe + e4 * 32 + i * 4);   // uniform address: a scalar load
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    if (KIND == VM_DIST_EUCLIDEAN) {
-                        const float d0 = qv[c] - r0[c], d1 = qv[c] - r1[c];
-                        acc[i][0] = fmaf(d0, d0, acc[i][0]);
-                        acc[i][1] = fmaf(d1, d1, acc[i][1]);
-                    } else {
-                        acc[i][0] = fmaf(qv[c], r0[c], acc[i][0]);
-                        acc[i][1] = fmaf(qv[c], r1[c], acc[i][1]);
-                    }
-                }
-            }
-        }
-        if (ck != nchunk - 1) continue;
+    score_tile_loop<KIND>(rs, qg, ref, N, E, nullptr, t_lo, t_hi, [&](int64_t n0, const float (&acc)[8][2]) {
         float rn[2] = {1.f, 1.f};
         int32_t rl[2];
 #pragma unroll
@@ -183,7 +111,7 @@ __global__ __launch_bounds__(512, 4) void mine_kernel(const float* __restrict__ 
                 } else {
                     d = -acc[i][j];
                 }
-                const uint32_t key = mn_key(d);
+                const uint32_t key = score_key(d);
                 const bool cand = aok[i] && rl[j] >= 0 && d == d && nn != m0 + i;
                 const bool same = rl[j] == ql[i];
                 const uint32_t low = ((uint32_t)nn << 1) | (__float_as_uint(d) == 0x80000000u ? 1u : 0u);
@@ -192,7 +120,7 @@ __global__ __launch_bounds__(512, 4) void mine_kernel(const float* __restrict__ 
                 mn_insert(pl[i], pthr[i], ((unsigned long long)(~key) << 32) | low, cand && same, k_pos, lane);
             }
         }
-    }
+    });
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         if (m0 + i >= row_hi) break;   // wave-uniform
@@ -228,14 +156,6 @@ __global__ __launch_bounds__(256) void mine_merge_kernel(const unsigned long lon
     val[row * K + lane] = __uint_as_float(bits);
 }
 
-static int mn_splits(int64_t M, int64_t N) {
-    const int64_t qb = (M + MN_T - 1) / MN_T, nt = (N + MN_RT - 1) / MN_RT;
-    int64_t s = (2048 + qb - 1) / qb;   // >= 2048 workgroups (8 per CU), like vm_pairdist_argmin
-    if (s > nt) s = nt;
-    if (s < 1) s = 1;
-    return (int)s;
-}
-
 static inline int64_t mn_pad(int64_t bytes) { return (bytes + 255) & ~(int64_t)255; }
 
 }  // namespace vm
@@ -244,7 +164,7 @@ extern "C" int64_t vm_mine_pairs_workspace_bytes(int64_t N, int E, int64_t row_l
     if (N <= 0 || E <= 0 || row_lo < 0 || row_hi <= row_lo || k_neg < 0 || k_pos < 0) return 0;
     const int64_t M = row_hi - row_lo, EP = ((E + 3) / 4) * 4;
     // squared row norms, the scalar-path copy of the anchors, the partial lists of every split
-    return 256 + vm::mn_pad(N * 4) + vm::mn_pad(((M + 7) / 8) * 8 * EP * 4) + (int64_t)vm::mn_splits(M, N) * M * (k_neg + k_pos) * 8;
+    return 256 + vm::mn_pad(N * 4) + vm::mn_pad(((M + 7) / 8) * 8 * EP * 4) + (int64_t)vm::score_splits(M, N, 2048) * M * (k_neg + k_pos) * 8;
 }
 
 extern "C" int vm_mine_pairs(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, int64_t row_lo, int64_t row_hi,
@@ -258,7 +178,7 @@ extern "C" int vm_mine_pairs(const float* emb, const int32_t* label, int64_t N, 
                "vm_mine_pairs: neg_idx and neg_val go with k_neg > 0 (both) or k_neg == 0 (both NULL)");
     VM_REQUIRE((k_pos > 0) == (pos_idx != nullptr) && (k_pos > 0) == (pos_val != nullptr),
                "vm_mine_pairs: pos_idx and pos_val go with k_pos > 0 (both) or k_pos == 0 (both NULL)");
-    VM_REQUIRE(N > 0 && N < (1LL << 31) && E > 0 && E <= MN_MAX_E, "vm_mine_pairs: bad sizes (N < 2^31, E <= %d)", MN_MAX_E);
+    VM_REQUIRE(N > 0 && N < (1LL << 31) && E > 0 && E <= ST_MAX_E, "vm_mine_pairs: bad sizes (N < 2^31, E <= %d)", ST_MAX_E);
     VM_REQUIRE(score_kind >= VM_DIST_EUCLIDEAN && score_kind <= VM_DIST_DOT,
                "vm_mine_pairs: score_kind must be in (euclidean, cosine, dot_product)");
     VM_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= N, "vm_mine_pairs: bad row range");
@@ -272,14 +192,14 @@ extern "C" int vm_mine_pairs(const float* emb, const int32_t* label, int64_t N, 
     p += mn_pad(N * 4);
     float* qT = (float*)p;
     p += mn_pad(((M + 7) / 8) * 8 * EP * 4);
-    const int splits = mn_splits(M, N);
+    const int splits = score_splits(M, N, 2048);
     unsigned long long* part_neg = (unsigned long long*)p;
     unsigned long long* part_pos = part_neg + (int64_t)splits * M * k_neg;
     if (score_kind == VM_DIST_COSINE) launch_rowsq(emb, N, E, rsq, st);
     launch_pairdist_qt(emb + row_lo * (int64_t)E, M, E, qT, st);
-    const int n_tiles = (int)((N + MN_RT - 1) / MN_RT);
+    const int n_tiles = (int)((N + ST_RT - 1) / ST_RT);
     const int tps = (n_tiles + splits - 1) / splits;
-    const dim3 grid((unsigned)((M + MN_T - 1) / MN_T), (unsigned)splits);
+    const dim3 grid((unsigned)((M + ST_T - 1) / ST_T), (unsigned)splits);
 #define VM_MN(KD) hipLaunchKernelGGL(mine_kernel<KD>, grid, dim3(512), 0, st, qT, emb, label, N, E, row_lo, M, rsq, neg_floor, k_neg, k_pos, tps, \
                                      part_neg, part_pos)
     if (score_kind == VM_DIST_EUCLIDEAN) VM_MN(VM_DIST_EUCLIDEAN);

@@ -8,20 +8,19 @@
 // (key_lo, shift) puts key k in bin (k - key_lo) >> shift when k >= key_lo and that is < bins; three extra slots per window and class
 // count keys below key_lo (under), the rest (over) and NaN scores.
 //
-// Structure = pairdist_kernel (eval.hip): 8 waves, wave w owns 8 WAVE-UNIFORM queries that arrive through the scalar path, lane l the
-// references l and l + 64 of a 128-row stage staged in LDS, the same ascending-component fmaf chain -- so every score is bit-identical
-// to dist[i][j] of vm_pairdist_argmin.  Only reference tiles that hold some j > i are visited and the pairs j <= i are masked.  Counts go
+// The tile loop is score_tile_loop's (score_tile.hpp), kept here as a copy (see pair_hist_kernel): every score is bit-identical to
+// dist[i][j] of vm_pairdist_argmin.  Only reference tiles that hold some j > i are visited and the pairs j <= i are masked.  Counts go
 // into per-workgroup u32 LDS histograms (ds_add_u32: integer adds, order-independent) and each workgroup flushes its non-zero bins once
 // with 64-bit agent-scope atomic adds into the u64 global counts: results are bit-identical from run to run.
 //
 // vm_pair_score_hist_norm (NORM): the same pass on cohort-normalised scores (cohort.hip computes the per-row statistics): the pair
 // {i, j} is binned on 0.5 (a rsig[i] + b rsig[j]), a = s - mu[i], b = s - mu[j], each operation rounded on its own (no fma contraction,
 // so numpy's fp32 reproduces it).  The query side's mu / rsig are wave-uniform registers, the reference side's are read beside its labels.
-#include "common.hpp"
+#include "score_tile.hpp"
 
 namespace vm {
 
-constexpr int VH_T = 64, VH_RT = 128, VH_EC = 64, VH_MAX_E = 256, VH_MAX_WIN = 4;
+constexpr int VH_MAX_WIN = 4;
 // LDS histogram words per workgroup: 4 windows x 1024 bins or 1 x 4096, two classes, three extra slots.  With the 34 KiB reference
 // stage that is 67 KiB per workgroup: two workgroups (16 waves) per CU.
 constexpr int VH_LDS_HIST_WORDS = 2 * 4 * (1024 + 3);
@@ -30,12 +29,6 @@ struct VhWindows {
     uint32_t lo[VH_MAX_WIN];
     uint32_t shift[VH_MAX_WIN];
 };
-
-__device__ inline uint32_t vh_key(float s) {
-    uint32_t u = __float_as_uint(s);
-    if (u == 0x80000000u) u = 0u;   // -0.0 == +0.0: one key
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // the normalised score: fp32, every operation rounded on its own
 __device__ inline float vh_norm(float s, float mi, float ri, float mj, float rj) {
@@ -47,11 +40,6 @@ __device__ inline float vh_norm(float s, float mi, float ri, float mj, float rj)
     return 0.5f * (x + y);
 }
 
-__global__ __launch_bounds__(256) void vh_pad_weights_kernel(const float* __restrict__ w, int E, float* __restrict__ wpad) {
-    const int e = threadIdx.x;
-    if (e < VH_MAX_E) wpad[e] = (w != nullptr && e < E) ? w[e] : 0.f;
-}
-
 // grid (query blocks of 64 rows of [row_lo, row_lo + M), splits of the block's reference tiles); 512 threads; the first
 // n_win * 2 * (bins + 3) words of the LDS histogram are used.  ghist (n_win, 2, bins + 3) u64, accumulated.  NORM: the score is
 // normalised with mu / rsig (N) first (the plain pass, NORM = false, never reads them).
@@ -61,14 +49,14 @@ __global__ __launch_bounds__(512) void pair_hist_kernel(const float* __restrict_
                                                         const float* __restrict__ rsq, const float* __restrict__ wpad, VhWindows win,
                                                         int n_win, int bins, int splits, unsigned long long* __restrict__ ghist,
                                                         const float* __restrict__ mu, const float* __restrict__ rsig) {
-    constexpr int RT = VH_RT, RP = VH_EC + 4;
+    constexpr int RT = ST_RT, RP = ST_RP;
     __shared__ __attribute__((aligned(16))) float rs[RT * RP];
     __shared__ uint32_t hist[VH_LDS_HIST_WORDS];
     const int slots = bins + 3;
     const int n_words = n_win * 2 * slots;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int64_t mb = row_lo + (int64_t)blockIdx.x * VH_T;   // the block's first query row (global index)
+    const int64_t mb = row_lo + (int64_t)blockIdx.x * ST_T;   // the block's first query row (global index)
     const int n_tiles = (int)((N + RT - 1) / RT);
     // reference tiles holding some j > i for a query of this block: from the tile of row mb + 1 on, split over blockIdx.y
     const int t_first = (int)((mb + 1) / RT);
@@ -102,12 +90,13 @@ __global__ __launch_bounds__(512) void pair_hist_kernel(const float* __restrict_
             qrs[i] = ok ? rsig[m0 + i] : 0.f;
         }
     }
-    const int nchunk = (EP + VH_EC - 1) / VH_EC;
+    // its own copy of score_tile_loop (score_tile.hpp): through the shared one pass 1 took 20.50 instead of 20.19 ms, normalised 21.21 / 20.22
+    const int nchunk = (EP + ST_EC - 1) / ST_EC;
     const int n_stage = (t_hi - t_lo) * nchunk;
     const bool vec = (E & 3) == 0;
     auto fetch = [&](int s, f32x4 (&v)[4]) {
         const int64_t n0 = (int64_t)(t_lo + s / nchunk) * RT;
-        const int ec = (s % nchunk) * VH_EC;
+        const int ec = (s % nchunk) * ST_EC;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int piece = tid + 512 * k, r = piece >> 4, c = (piece & 15) * 4;
@@ -140,8 +129,8 @@ __global__ __launch_bounds__(512) void pair_hist_kernel(const float* __restrict_
     float acc[8][2];
     for (int s = 0; s < n_stage; ++s) {
         const int t = t_lo + s / nchunk, ck = s % nchunk;
-        const int ec = ck * VH_EC;
-        const int ew4 = min(VH_EC, EP - ec) / 4;
+        const int ec = ck * ST_EC;
+        const int ew4 = min(ST_EC, EP - ec) / 4;
         const int64_t n0 = (int64_t)t * RT;
         __syncthreads();   // the previous stage's readers are done (and, at s = 0, the histogram is zero)
         stash(nxt);
@@ -223,7 +212,7 @@ __global__ __launch_bounds__(512) void pair_hist_kernel(const float* __restrict_
                         nanc[1] += !tgt;
                         continue;
                     }
-                    const uint32_t k = vh_key(d);
+                    const uint32_t k = score_key(d);
 #pragma unroll
                     for (int v = 0; v < VH_MAX_WIN; ++v) {
                         if (v >= n_win) break;
@@ -265,14 +254,10 @@ __global__ __launch_bounds__(512) void pair_hist_kernel(const float* __restrict_
 }
 
 static int vh_splits(int64_t M, int64_t N) {
-    const int64_t qb = (M + VH_T - 1) / VH_T, nt = (N + VH_RT - 1) / VH_RT;
-    int64_t s = (4096 + qb - 1) / qb;   // >= 4096 workgroups before the triangle empties the late blocks' ranges
+    const int s = score_splits(M, N, 4096);   // >= 4096 workgroups before the triangle empties the late blocks' ranges
     // a workgroup counts at most 64 x 128 x tiles pairs in its u32 LDS bins
-    const int64_t s_min = (nt + (1 << 19) - 2) / ((1 << 19) - 1);
-    if (s < s_min) s = s_min;
-    if (s > nt) s = nt;
-    if (s < 1) s = 1;
-    return (int)s;
+    const int s_min = (int)cdiv(cdiv(N, ST_RT), (1 << 19) - 1);
+    return s < s_min ? s_min : s;
 }
 
 }  // namespace vm
@@ -281,7 +266,7 @@ extern "C" int64_t vm_pair_score_hist_workspace_bytes(int64_t N, int E) {
     if (N <= 0 || E <= 0) return 0;
     const int64_t EP = ((E + 3) / 4) * 4;
     // squared row norms, the zero-padded weights, the scalar-path copy of (up to) all rows as queries
-    return N * 4 + 256 + vm::VH_MAX_E * 4 + 256 + ((N + 7) / 8) * 8 * EP * 4 + 256;
+    return N * 4 + 256 + vm::ST_MAX_E * 4 + 256 + ((N + 7) / 8) * 8 * EP * 4 + 256;
 }
 
 namespace vm {
@@ -290,7 +275,7 @@ static int vh_run(const char* what, const float* emb, const int32_t* label, int6
                   int64_t row_lo, int64_t row_hi, const int64_t* host_windows, int n_windows, int bins, uint64_t* hist, const float* mu,
                   const float* rsig, void* ws, void* stream) {
     VM_REQUIRE(emb && label && host_windows && hist && ws, "%s: null pointer", what);
-    VM_REQUIRE(N > 0 && N < (1LL << 31) && E > 0 && E <= VH_MAX_E, "%s: bad sizes (N < 2^31, E <= %d)", what, VH_MAX_E);
+    VM_REQUIRE(N > 0 && N < (1LL << 31) && E > 0 && E <= ST_MAX_E, "%s: bad sizes (N < 2^31, E <= %d)", what, ST_MAX_E);
     VM_REQUIRE(score_kind >= VM_DIST_EUCLIDEAN && score_kind <= VM_SCORE_NEG_EUCLIDEAN, "%s: unknown score_kind %d", what, score_kind);
     VM_REQUIRE(score_kind != VM_SCORE_WEIGHTED_L1 || weights, "%s: weighted_l1 needs weights", what);
     VM_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= N, "%s: bad row range", what);
@@ -310,12 +295,12 @@ static int vh_run(const char* what, const float* emb, const int32_t* label, int6
     hipStream_t st = (hipStream_t)stream;
     float* rsq = (float*)ws;
     float* wpad = (float*)(((uintptr_t)(rsq + N) + 255) & ~(uintptr_t)255);
-    float* qT = (float*)(((uintptr_t)(wpad + VH_MAX_E) + 255) & ~(uintptr_t)255);
+    float* qT = (float*)(((uintptr_t)(wpad + ST_MAX_E) + 255) & ~(uintptr_t)255);
     if (score_kind == VM_DIST_COSINE) launch_rowsq(emb, N, E, rsq, st);
-    hipLaunchKernelGGL(vh_pad_weights_kernel, dim3(1), dim3(256), 0, st, score_kind == VM_SCORE_WEIGHTED_L1 ? weights : nullptr, E, wpad);
+    launch_pad_weights(score_kind == VM_SCORE_WEIGHTED_L1 ? weights : nullptr, E, wpad, st);
     launch_pairdist_qt(emb + row_lo * (int64_t)E, M, E, qT, st);
     const int splits = vh_splits(M, N);
-    const dim3 grid((unsigned)((M + VH_T - 1) / VH_T), (unsigned)splits);
+    const dim3 grid((unsigned)((M + ST_T - 1) / ST_T), (unsigned)splits);
     unsigned long long* gh = (unsigned long long*)hist;
 #define VM_VH(K, NM) hipLaunchKernelGGL((pair_hist_kernel<K, NM>), grid, dim3(512), 0, st, qT, emb, label, N, E, row_lo, M, rsq, wpad, win, \
                                         n_windows, bins, splits, gh, mu, rsig)
