@@ -259,8 +259,7 @@ class HipEncoderEngine:
         # on one box -- the weight-gradient GEMM then starts as soon as du exists and the step's tail (block-1 backward, slab sums,
         # optimizer) no longer waits for the last of them
         self.wgrad_after_dgrad = False
-        self.defer_wgrad_tail = 0   # experiment (backward()): where the tap sums / per-tower slab folds behind every weight-gradient GEMM go
-        self.misc_stream = _shared_stream(self.device, "misc")
+        self.misc_stream = _shared_stream(self.device, "misc")   # no launch of a step goes here (the process's third shared stream)
         # training option (bf16): vm_conv_fwd_e -- the conv epilogue also writes the pool-window extreme, the pool pass reads that
         # pooled-size tensor (same bits) and the fused BatchNorm-backward sums are taken against the exact extreme.  Off by default:
         # the passes get 0.07 ms shorter and the two epilogues 0.04 ms longer, the step does not move
@@ -268,7 +267,7 @@ class HipEncoderEngine:
         # training without the BatchNorm / pool pass between blocks (dropout rate 0, 16-bit storage, one tower per launch): block i+1
         # reads block i's pool extreme e with block i's BatchNorm affine folded into its weights (vm_fold_bn_weights + vm_conv_fwd_fold,
         # weight gradient vm_conv_wgrad_fold) -- the pooled BatchNorm output is never written or read, and it is no longer rounded to
-        # the storage type either.  Falls back to the pass wherever a kernel does not serve a shape (_fold_ok)
+        # the storage type either.  Falls back to the pass wherever a kernel does not serve a shape (_decide_step)
         self.fold_affine = self.is16
         # ... and the folded convs leave (extreme, other element + position flag) instead of (z, extreme): same bytes as a plain
         # forward epilogue, the BatchNorm-backward apply pass reads the pair form (vm_bn_pool_bwd_apply_pairs)
@@ -282,12 +281,6 @@ class HipEncoderEngine:
             self.center_blocks = tuple(int(v) for v in _os.environ["VOICEMAP_CENTER_BLOCKS"].split(",") if v.strip())
         self._fold = {}
         self.fused_infer_pool = self.is16  # inference: vm_conv_fwd_pool where the kernel serves the shape
-        # round 6, measured and left OFF: the last block's forward leaves (e, o) pairs, GlobalMaxPool1D reads e alone (half of z's bytes
-        # on the forward -> backward turn-around) and the sparse backward takes the pair form.  Bit-identical (tests/test_gpu_fold.py), and
-        # an even trade: cfg-A 128 pairs 2.554 -> 2.555, 2.566 -> 2.571 ms -- what the pass over z saves, the pair arithmetic of the
-        # forward epilogue costs (profiles/r06_wgrad_tail.txt)
-        self.last_pairs = False
-        self.tower_swap = False  # experiment (forward()): the first tower on the tower stream, the second on the current one
         self.tower_stagger = 0  # experiment: tower 2's forward starts after tower 1's block-1 conv (1) / whole block 1 (2)
         # (round 6, last session) the weight-gradient chain rides the TOWER stream: that stream is idle during the backward, the side
         # stream was idle during the forward, and one stream beside the main one beats two at every size -- interleaved on one box
@@ -869,27 +862,51 @@ class HipEncoderEngine:
         self._call("vm_decimate_whiten", self._dyn("raw", _p(raw)), int(is16), pl["n"], raw.shape[1], downsampling, int(whitening), rms,
                       windows_per_tower, _p(pl["x0"]), _p(pl["pre_ws"]), self.stream())
 
-    def _fold_ok(self, pl: dict, wpt: int, drop_masks) -> bool:
-        """Can this training forward run blocks 2.. on the pool extremes with the BatchNorm affines folded into the weights?  Asked per
-        call (the answer follows the dropout masks and vm_set_tuning)."""
-        if not (self.fold_affine and pl["training"] and self.is16 and self.fuse_block1 and self.fused_bn_reduce
-                and self.fused_sums_finalize and self.nb >= 2 and self.wt):
-            return False
-        if self.sync_bn:
-            return False   # SyncBN goes through the two plain finalize funnels (vm_bn_finalize, vm_bn_bwd_finalize): the unfolded path
-        if drop_masks is not None and any(m is not None for m in drop_masks):
-            return False   # SpatialDropout1D scales per (window, channel): not a per-channel affine
-        n, dt = pl["n"], self.dtype
-        for i in range(1, self.nb):
-            cin, c, L = self.blocks[i - 1][1], self.blocks[i][1], pl["L"][i]
-            with_e = i < self.nb - 1
-            if with_e and self.blocks[i][2] != 2:
-                return False
-            if not self.lib.query("vm_conv_fwd_fold_supported", n, L, cin, c, dt, int(with_e)):
-                return False
-            if not self.lib.query("vm_conv_dgrad_bnred_supported", n, L, cin, c, dt):
-                return False
-        return True
+    def _decide_step(self, pl: dict, wpt: int, drop_masks, defer_tail: bool):
+        """The form of the forward about to be enqueued and of the backward behind it, decided per call (the answer follows the switches,
+        the dropout masks and vm_set_tuning) from the engine's switches, the plan's sizes and the library's host-side *_supported
+        queries, each asked once.  The ONLY writer of these keys -- _forward_range, the heads and backward() read them; allocates nothing:
+          pl['fold_now']      blocks 2.. run on the pool extremes with the BatchNorm affines folded into their weights
+          pl['tail_pending']  global max finish .. loss and their backward are one launch in siamese_head (which clears it)
+          pl['tail_parts']    ... and the last block's pass leaves it segment partials of the global max
+          pl[i]['conv']       block i's convolution: 'fused1' (vm_conv1_fused_fwd) | 'plain' | 'pool' (inference: vm_conv_fwd_pool) |
+                              'e' (vm_conv_fwd_e) | 'fold' (vm_fold_bn_weights + vm_conv_fwd_fold)
+          pl[i]['e_now']      it leaves its pool extreme; ['pairs_now']: as (extreme, other element) instead of z; ['ctr_now']: centred
+          pl[i]['bnred_now']  its two BatchNorm-backward sums come out of block i+1's dgrad GEMM (vm_conv_dgrad_bnred)"""
+        n, ls, dt, nb, training, q = pl["n"], pl["L"], self.dtype, self.nb, pl["training"], self.lib.query
+        two = training and n // wpt == 2
+        nw = wpt if two and self.split_towers else n   # windows per _forward_range call
+        geo = {i: (ls[i], self.blocks[i - 1][1], self.blocks[i][1]) for i in range(1, nb)}   # (L, c_in, c_out) of the k=3 blocks
+        bnred = {i: bool(training and self.fused_bn_reduce and q("vm_conv_dgrad_bnred_supported", n, *g, dt)) for i, g in geo.items()}
+        # not folded: SyncBN (it goes through the two plain finalize funnels, vm_bn_finalize / vm_bn_bwd_finalize) and SpatialDropout1D
+        # masks (they scale per (window, channel): not a per-channel affine)
+        fold = bool(training and self.fold_affine and self.is16 and self.fuse_block1 and self.fused_bn_reduce and self.fused_sums_finalize
+                    and nb >= 2 and self.wt and not self.sync_bn and not (drop_masks is not None and any(m is not None for m in drop_masks))
+                    and all(self.blocks[i][2] == 2 for i in range(1, nb - 1)) and all(bnred.values())
+                    and all(q("vm_conv_fwd_fold_supported", n, *g, dt, int(i < nb - 1)) for i, g in geo.items()))
+        tail = bool(defer_tail and two and self.fused_tail and self.head in HEADS
+                    and q("vm_tail_fwd_bwd_supported", self.blocks[-1][1], self.E))
+        pl["fold_now"], pl["tail_pending"] = fold, tail
+        pl["tail_parts"] = tail and not (nb == 1 and self.fuse_block1)   # (a fused block 1 that is also the last: vm_global_maxpool_fwd)
+        for i, (_, _, pool) in enumerate(self.blocks):
+            b, inner = pl[i], 0 < i < nb - 1
+            if i == 0:
+                conv = "fused1" if self.fuse_block1 else "plain"
+            elif not training:
+                conv = "pool" if self.fused_infer_pool and pool == 2 and q("vm_conv_fwd_pool_supported", nw, *geo[i], dt) else "plain"
+            elif fold:
+                conv = "fold"
+            elif self.fused_pool_extreme and pool == 2 and inner and q("vm_conv_fwd_e_supported", nw, *geo[i], dt):
+                conv = "e"
+            else:
+                conv = "plain"
+            b["conv"] = conv
+            b["e_now"] = conv == "e" or (fold and inner)
+            b["pairs_now"] = bool(fold and inner and self.fold_pairs)
+            b["ctr_now"] = b["pairs_now"] and dt == VM_F16 and i in self.center_blocks   # f16: the tile centred on its pedestal (round 5)
+            # the sums are taken against the extreme itself (block 1's, or e) or else against the pooled output
+            b["bnred_now"] = bool(i < nb - 1 and bnred[i + 1] and ((i == 0 and self.fuse_block1) or b["e_now"]
+                                                                   or (self.pooled_reduce and ls[i] % pool == 0)))
 
     def _fold_bufs(self, i: int):
         """Per tower: the folded forward weights of block i (0-based) and the per-tap constants hb (3, c_out)."""
@@ -906,7 +923,7 @@ class HipEncoderEngine:
         if "fold_ready" in pl:
             return
         n, ls, wpt = pl["n"], pl["L"], pl["wpt"]
-        for i in range(self.nb - 1 if not (self.last_pairs and self.nb > 1) else self.nb):
+        for i in range(self.nb - 1):
             c = self.blocks[i][1]
             pl[i]["ep"] = torch.zeros(n, ls[i + 1] + 2, c, dtype=self.tdt, device=self.device)
             if i > 0:
@@ -923,11 +940,11 @@ class HipEncoderEngine:
         """x0 -> embeddings (pl['emb']).  Training plans use batch statistics per tower and update the moving
         statistics; inference plans use the moving statistics (Keras learning phase 0).
 
-        ``split_towers`` (training, two towers): the two encoder calls of the siamese model (voicemap/models.py:52-53) are
         ``defer_tail`` (the siamese training steps): the caller goes on to ``siamese_head(pl, y)`` and ``backward(pl)``; the finish of the
         global max, the dense layer, the head, the loss and their backward then run as one launch there (vm_tail_fwd_bwd) and
         pl['gmax'] / pl['emb'] are not valid before it.
 
+        ``split_towers`` (training, two towers): the two encoder calls of the siamese model (voicemap/models.py:52-53) are
         independent until the head, so tower 2's kernel sequence is enqueued on a second stream over the second half of the
         same buffers: a GEMM of one tower then runs next to a streaming BatchNorm pass of the other (8.6 % off the forward at
         cfg-A forward alone, 1.5 % off the step, tools/tower_pipeline_probe.py).  Every launch computes what its half of the
@@ -941,14 +958,8 @@ class HipEncoderEngine:
         wpt = windows_per_tower if training else n
         pl["wpt"], pl["drop"] = wpt, drop_masks
         split = training and n_towers == 2 and self.split_towers
-        fold = training and self._fold_ok(pl, wpt, drop_masks)
-        pl["fold_now"] = fold
-        cl = self.blocks[-1][1]
-        tail = bool(defer_tail and training and n_towers == 2 and self.fused_tail and self.head in HEADS
-                    and self.lib.query("vm_tail_fwd_bwd_supported", cl, self.E))
-        pl["tail_pending"] = tail
-        pl["tail_parts"] = tail   # the last block leaves segment partials (cleared by _forward_range where it runs vm_global_maxpool_fwd)
-        if fold:
+        self._decide_step(pl, wpt, drop_masks, defer_tail)   # before the first launch: everything below reads the step's form from pl
+        if pl["fold_now"]:
             if pl.get("fold_ready", wpt) != wpt:   # the slab split depends on the tower size
                 del pl["fold_ready"]
                 self._programs.drop_all()              # steps recorded for the other tower size point at the buffers re-made below
@@ -966,32 +977,31 @@ class HipEncoderEngine:
                 pl["tower_ev"] = [torch.cuda.Event() for _ in self.blocks]
             cur = torch.cuda.current_stream(self.device)
             self._join(self.tower_stream, cur)   # the pre-processed windows are ready
-            pl["t2_stream"] = cur if self.tower_swap else self.tower_stream   # the stream the second tower's chain is on
-            if self.tower_swap:
-                # (round 6) the chain that is enqueued SECOND finishes last, and what follows the forward (tail, backward) is on the
-                # current stream: with the first tower on the tower stream and the second on the current one, the hand-over at the
-                # end of the forward waits for a chain that finished long ago instead of crossing queues behind the last kernel
-                with self._on(self.tower_stream):
-                    self._forward_range(pl, 0, wpt, 0, 1, wpt, drop_masks, pl["cr_ws"], pl["gmax_ws"], first_of_two=True, fold=fold)
-                self._forward_range(pl, wpt, wpt, 1, 1, wpt, drop_masks, pl["cr_ws_t2"], pl["gmax_ws_t2"], second_of_two=True, fold=fold)
-            else:
-                self._forward_range(pl, 0, wpt, 0, 1, wpt, drop_masks, pl["cr_ws"], pl["gmax_ws"], first_of_two=True, fold=fold)
-                if self.tower_stagger and "stagger_ev" in pl:
-                    self._wait(self.tower_stream, pl["stagger_ev"])
-                with self._on(self.tower_stream):
-                    self._forward_range(pl, wpt, wpt, 1, 1, wpt, drop_masks, pl["cr_ws_t2"], pl["gmax_ws_t2"], second_of_two=True, fold=fold)
+            self._forward_range(pl, 0, wpt, 0, 1, wpt, drop_masks, pl["cr_ws"], pl["gmax_ws"], first_of_two=True)
+            if self.tower_stagger and "stagger_ev" in pl:
+                self._wait(self.tower_stream, pl["stagger_ev"])
+            with self._on(self.tower_stream):
+                self._forward_range(pl, wpt, wpt, 1, 1, wpt, drop_masks, pl["cr_ws_t2"], pl["gmax_ws_t2"], second_of_two=True)
             self._join(cur, self.tower_stream)
         else:
-            self._forward_range(pl, 0, n, 0, n_towers, wpt, drop_masks, pl["cr_ws"], pl["gmax_ws"], fold=fold)
-        if not tail:
-            self._call("vm_dense_fwd", _p(pl["gmax"]), _p(self.view("dense.kernel")), _p(self.view("dense.bias")), n, cl, self.E,
-                       _p(pl["emb"]), self.stream())
+            self._forward_range(pl, 0, n, 0, n_towers, wpt, drop_masks, pl["cr_ws"], pl["gmax_ws"])
+        if not pl["tail_pending"]:
+            self._call("vm_dense_fwd", _p(pl["gmax"]), _p(self.view("dense.kernel")), _p(self.view("dense.bias")), n, self.blocks[-1][1],
+                       self.E, _p(pl["emb"]), self.stream())
         return pl["emb"]
 
+    def _stagger(self, pl: dict, first_of_two: bool, at: int):
+        """tower_stagger == ``at``: the first tower's chain marks the point the second tower's chain starts behind."""
+        if first_of_two and self.tower_stagger == at:
+            if "stagger_ev" not in pl:
+                pl["stagger_ev"] = torch.cuda.Event()
+            self._record(pl["stagger_ev"])
+
     def _forward_range(self, pl: dict, w0: int, nw: int, tw0: int, ntw: int, wpt: int, drop_masks, cr_ws, gmax_ws,
-                       first_of_two: bool = False, second_of_two: bool = False, fold: bool = False):
-        """The encoder blocks for windows [w0, w0 + nw) = towers [tw0, tw0 + ntw) on the current stream."""
-        st, dt, training = self.stream(), self.dtype, pl["training"]
+                       first_of_two: bool = False, second_of_two: bool = False):
+        """The encoder blocks for windows [w0, w0 + nw) = towers [tw0, tw0 + ntw) on the current stream, in the form _decide_step left
+        in the plan."""
+        st, dt, training, fold = self.stream(), self.dtype, pl["training"], pl["fold_now"]
 
         def W(t, per_window=1):   # rows of a per-window tensor that belong to this range
             return t[w0 * per_window:(w0 + nw) * per_window].data_ptr()
@@ -999,9 +1009,10 @@ class HipEncoderEngine:
         def T(t):                 # rows of a per-tower (2, C) tensor
             return t[tw0:].data_ptr()
 
-        fused_tail = False
+        gmax_done = False   # the last block's pass took the global max too
         for i, (k, c, pool) in enumerate(self.blocks):
-            b, L = pl[i], pl["L"][i]
+            b, L, conv = pl[i], pl["L"][i], pl[i]["conv"]
+            cin = self.blocks[i - 1][1] if i else 1
             rows = b["stat_rows"]
             ssum = W(b["ssum"], rows) if training else None
             ssq = W(b["ssq"], rows) if training else None
@@ -1020,13 +1031,13 @@ class HipEncoderEngine:
                         m_ = pl["mov_scratch"].data_ptr()   # updates its accumulators
                         v_ = m_ + 4 * c
                 elif second_of_two:         # plain average: the two updates are sequential -- after tower 1's
-                    self._wait(pl.get("t2_stream", self.tower_stream), pl["tower_ev"][i])
+                    self._wait(self.tower_stream, pl["tower_ev"][i])
                 centred = i == 0 and fold and self.fuse_block1   # block 1's extreme is stored as e - max(bias, 0): the offset's constants
                 s_sum, s_sq, s_rows, s_cnt = ssum, ssq, wpt * rows, float(wpt * L)
                 if self.sync_bn:
                     s_sum, s_sq = self._sync_rows(("fwd", i, tw0), ssum, ssq, wpt * rows, ntw, c, 1, _p(cr_ws), st)
                     s_rows, s_cnt = 1, float(wpt * L) * self.sync_bn_world
-                tile_ctr = bool(b.get("ctr_now")) and i > 0   # this block's tile (statistics and stored extreme) is centred: vm_conv_fwd_fold e_center
+                tile_ctr = b["ctr_now"]   # this block's tile (statistics and stored extreme) is centred: vm_conv_fwd_fold e_center
                 adj = centred or tile_ctr
                 self._call("vm_bn_finalize", s_sum, s_sq, s_rows, ntw, c, s_cnt, gam, bet, self.bn_eps, self.bn_momentum,
                            int(self.unbiased), m_, v_, T(b["mean"]), T(b["invstd"]), T(b["scale"]), T(b["shift"]), _p(cr_ws), zd, zc,
@@ -1035,91 +1046,66 @@ class HipEncoderEngine:
                 if zd is None and first_of_two:
                     self._record(pl["tower_ev"][i])
 
-            if i == 0 and self.fuse_block1:
+            if conv == "fused1":
                 w1 = _p(self.view("conv1.kernel"))
                 if training:
                     # fold: the extreme goes out as a padded activation tensor (mode 2) and block 2 reads it as it is
                     self._call("vm_conv1_fused_fwd", W(pl["x0"]), w1, bias, gam, None, nw, L, c, pool, 2 if fold else 0, dt,
                                W(b["ep"] if fold else b["e"]), ssum, ssq, st)
-                    if first_of_two and self.tower_stagger == 1:
-                        if "stagger_ev" not in pl:
-                            pl["stagger_ev"] = torch.cuda.Event()
-                        self._record(pl["stagger_ev"])
+                    self._stagger(pl, first_of_two, 1)
                     finalize()
                     if not fold:
                         self._call("vm_bn_drop_pool_fwd", W(b["e"]), T(b["scale"]), T(b["shift"]), dm, nw, wpt, pl["L"][1], c, 1, dt,
                                    W(b["act"]), st)
-                    if first_of_two and self.tower_stagger == 2:
-                        if "stagger_ev" not in pl:
-                            pl["stagger_ev"] = torch.cuda.Event()
-                        self._record(pl["stagger_ev"])
+                    self._stagger(pl, first_of_two, 2)
                 else:
                     self._call("vm_bn_infer_affine", gam, bet, mm, mv, self.bn_eps, c, _p(b["scale"]), _p(b["shift"]), st)
                     self._call("vm_conv1_fused_fwd", W(pl["x0"]), w1, bias, _p(b["scale"]), _p(b["shift"]), nw, L, c, pool, 1, dt,
                                W(b["act"]), None, None, st)
                 continue
-            if i == 0:
+            if conv == "pool":
+                # inference: conv + ReLU + BatchNorm affine + max-pool in one launch, z is never written (bit-identical to the
+                # two-kernel path below); the last block's GlobalMaxPool1D then runs on its pooled tensor
+                self._call("vm_bn_infer_affine", gam, bet, mm, mv, self.bn_eps, c, _p(b["scale"]), _p(b["shift"]), st)
+                self._call("vm_conv_fwd_pool", W(pl[i - 1]["act"]), _p(self.wf[i]), bias, _p(b["scale"]), _p(b["shift"]), nw, L, cin,
+                           c, dt, W(b["act"]), _p(self.wfp.get(i)) if self.packed_weights else None, st)
+                continue
+            if conv == "fold":
+                # the BatchNorm affine of the block below (this tower's) goes into this block's weights, the conv reads that
+                # block's pool extreme and leaves its own; no pass in between
+                lo = pl[i - 1]
+                wfo, hbo, wfp = self._fold_bufs(i)
+                with_e, pairs = b["e_now"], b["pairs_now"]   # (the last block leaves z: its pass takes the global max)
+                use_packed = wfp is not None and self.packed_weights
+                # (a block whose input extreme is stored CENTRED -- block 1's always, a centred tile's below -- folds the shift over
+                # the stored value)
+                lo_c = i == 1 or lo["ctr_now"]
+                # f16: this block's own tile centred on the pedestal its accumulators start from (round 5)
+                ctr = T(b["ctr"]) if b["ctr_now"] else None
+                self._call("vm_fold_bn_weights", _p(self.wt[i]), T(lo["scale"]), T(lo["shift_c" if lo_c else "shift"]),
+                           bias, ntw, cin, c, dt,
+                           wfo[tw0].data_ptr(), wfp[tw0].data_ptr() if use_packed else None, hbo[tw0].data_ptr(), ctr, st)
+                self._call("vm_conv_fwd_fold", W(lo["ep"]), wfo[tw0].data_ptr(), bias, hbo[tw0].data_ptr(), gam if with_e else None,
+                           nw, wpt, L, cin, c, dt, None if pairs else W(b["z"]), ssum, ssq, W(b["ep"]) if with_e else None,
+                           W(b["o"]) if pairs else None, wfp[tw0].data_ptr() if use_packed else None, ctr, st)
+                if with_e:
+                    finalize()
+                    continue
+            elif conv == "e":
+                # the conv epilogue also leaves the pool-window extreme of z (chosen by sign(gamma)): the BatchNorm / pool pass
+                # then reads that pooled-size tensor instead of z -- same bits -- and the backward sums are taken against it
+                if "e" not in b:
+                    b["e"] = torch.empty(pl["n"], L // 2, c, dtype=self.tdt, device=self.device)
+                self._call("vm_conv_fwd_e", W(pl[i - 1]["act"]), _p(self.wf[i]), bias, gam, nw, L, cin, c, dt, W(b["z"]), ssum, ssq,
+                           W(b["e"]), st)
+                finalize()
+                self._call("vm_bn_drop_pool_fwd", W(b["e"]), T(b["scale"]), T(b["shift"]), dm, nw, wpt, L // 2, c, 1, dt,
+                           W(b["act"]), st)
+                continue
+            elif i == 0:
                 self._call("vm_conv1_fwd", W(pl["x0"]), _p(self.view("conv1.kernel")), bias, nw, L, c, dt, W(b["z"]), ssum, ssq, st)
             else:
-                cin = self.blocks[i - 1][1]
-                if (not training and self.fused_infer_pool and pool == 2
-                        and self.lib.query("vm_conv_fwd_pool_supported", nw, L, cin, c, dt)):
-                    # inference: conv + ReLU + BatchNorm affine + max-pool in one launch, z is never written (bit-identical to the
-                    # two-kernel path below); the last block's GlobalMaxPool1D then runs on its pooled tensor
-                    self._call("vm_bn_infer_affine", gam, bet, mm, mv, self.bn_eps, c, _p(b["scale"]), _p(b["shift"]), st)
-                    self._call("vm_conv_fwd_pool", W(pl[i - 1]["act"]), _p(self.wf[i]), bias, _p(b["scale"]), _p(b["shift"]), nw, L, cin,
-                               c, dt, W(b["act"]), _p(self.wfp.get(i)) if self.packed_weights else None, st)
-                    continue
-                b["e_now"] = b["pairs_now"] = b["ctr_now"] = False
-                if fold:
-                    # the BatchNorm affine of the block below (this tower's) goes into this block's weights, the conv reads that
-                    # block's pool extreme and leaves its own; no pass in between
-                    lo = pl[i - 1]
-                    wfo, hbo, wfp = self._fold_bufs(i)
-                    # (round 6) the LAST block in pair form too: its (e, o) feed the GlobalMaxPool1D pass (e alone: half of z's bytes on
-                    # the forward -> backward turn-around) and the backward's sparse sums / apply pass
-                    last_pairs = (i == self.nb - 1 and self.last_pairs and self.fold_pairs and pool == 2 and L % 2 == 0 and c % 8 == 0
-                                  and bool(pl.get("tail_parts")) and self.fused_sums_finalize and not self.sync_bn and "o" in b)
-                    with_e = i < self.nb - 1 or last_pairs
-                    use_packed = wfp is not None and self.packed_weights
-                    # (a block whose input extreme is stored CENTRED -- block 1's always, a centred tile's below -- folds the shift over
-                    # the stored value)
-                    lo_c = (i == 1 and self.fuse_block1) or bool(lo.get("ctr_now"))
-                    pairs = with_e and self.fold_pairs
-                    # f16: this block's own tile centred on the pedestal its accumulators start from (round 5)
-                    ctr = T(b["ctr"]) if (pairs and dt == VM_F16 and i in self.center_blocks) else None
-                    self._call("vm_fold_bn_weights", _p(self.wt[i]), T(lo["scale"]), T(lo["shift_c" if lo_c else "shift"]),
-                               bias, ntw, cin, c, dt,
-                               wfo[tw0].data_ptr(), wfp[tw0].data_ptr() if use_packed else None, hbo[tw0].data_ptr(), ctr, st)
-                    self._call("vm_conv_fwd_fold", W(lo["ep"]), wfo[tw0].data_ptr(), bias, hbo[tw0].data_ptr(), gam if with_e else None,
-                               nw, wpt, L, cin, c, dt, None if pairs else W(b["z"]), ssum, ssq, W(b["ep"]) if with_e else None,
-                               W(b["o"]) if pairs else None, wfp[tw0].data_ptr() if use_packed else None, ctr, st)
-                    b["e_now"], b["pairs_now"], b["ctr_now"] = with_e, pairs, ctr is not None
-                    if last_pairs:
-                        finalize()
-                        parts, seg = pl["gmax_ws"], self._seg_rows
-                        self._call("vm_bn_drop_pool_gmax_partials_e", W(b["ep"]), T(b["scale"]), T(b["shift"]), dm, nw, wpt, L // 2, c, dt,
-                                   parts.data_ptr() + w0 * seg * c * 4, parts.data_ptr() + (pl["n"] + w0) * seg * c * 4, st)
-                        fused_tail = True
-                        continue
-                    if with_e:
-                        finalize()
-                        continue
-                elif (training and self.fused_pool_extreme and pool == 2 and i < self.nb - 1
-                        and self.lib.query("vm_conv_fwd_e_supported", nw, L, cin, c, dt)):
-                    # the conv epilogue also leaves the pool-window extreme of z (chosen by sign(gamma)): the BatchNorm / pool pass
-                    # then reads that pooled-size tensor instead of z -- same bits -- and the backward sums are taken against it
-                    if "e" not in b:
-                        b["e"] = torch.empty(pl["n"], L // 2, c, dtype=self.tdt, device=self.device)
-                    self._call("vm_conv_fwd_e", W(pl[i - 1]["act"]), _p(self.wf[i]), bias, gam, nw, L, cin, c, dt, W(b["z"]), ssum, ssq,
-                               W(b["e"]), st)
-                    finalize()
-                    self._call("vm_bn_drop_pool_fwd", W(b["e"]), T(b["scale"]), T(b["shift"]), dm, nw, wpt, L // 2, c, 1, dt,
-                               W(b["act"]), st)
-                    b["e_now"] = True
-                    continue
-                else:
-                    self._call("vm_conv_fwd", W(pl[i - 1]["act"]), _p(self.wf[i]), bias, nw, L, cin, c, dt, W(b["z"]), ssum, ssq, st)
+                self._call("vm_conv_fwd", W(pl[i - 1]["act"]), _p(self.wf[i]), bias, nw, L, cin, c, dt, W(b["z"]), ssum, ssq, st)
             if training:
                 finalize()
             else:
@@ -1128,7 +1114,7 @@ class HipEncoderEngine:
             if i == self.nb - 1:
                 # last block: BN apply + dropout + max-pool + GlobalMaxPool1D in one pass; its pooled tensor has no other
                 # consumer and is never written
-                if pl.get("tail_parts"):
+                if pl["tail_parts"]:
                     # the fused tail finishes the segment partials inside its own launch: every range (tower) writes the rows of its
                     # windows into the one pair of arrays (value rows, then position rows)
                     parts, seg = pl["gmax_ws"], self._seg_rows
@@ -1137,11 +1123,10 @@ class HipEncoderEngine:
                 else:
                     self._call("vm_bn_drop_pool_gmax_fwd", W(b["z"]), sc, sh, dm, nw, wpt, L, c, pool, dt, W(pl["gmax"]), W(pl["gidx"]),
                                _p(gmax_ws), st)
-                fused_tail = True
+                gmax_done = True
                 continue
             self._call("vm_bn_drop_pool_fwd", W(b["z"]), sc, sh, dm, nw, wpt, L, c, pool, dt, W(b["act"]), st)
-        if not fused_tail:
-            pl["tail_parts"] = False   # (both ranges of a split forward take this branch or neither)
+        if not gmax_done:   # the last block went through a fused kernel that writes its pooled output ('fused1', 'pool')
             cl, Ll = self.blocks[-1][1], pl["L"][-1]
             self._call("vm_global_maxpool_fwd", W(pl[self.nb - 1]["act"]), nw, Ll, cl, dt, W(pl["gmax"]), W(pl["gidx"]), st)
 
@@ -1154,7 +1139,7 @@ class HipEncoderEngine:
         sync_tail = sync_tail and self.grad_sync is not None and hasattr(self.grad_sync, "begin_tail")
         lib, st, n, dt, wpt = self.lib, self.stream(), pl["n"], self.dtype, pl["wpt"]
         drop = pl["drop"]
-        fold = bool(pl.get("fold_now"))   # the forward ran blocks 2.. on pool extremes with folded BatchNorm affines
+        fold = pl["fold_now"]   # the forward ran blocks 2.. on pool extremes with folded BatchNorm affines
         cl, Ll = self.blocks[-1][1], pl["L"][-1]
         G = self.G
         dense = (_p(pl["gmax"]), _p(self.view("dense.kernel")), _p(pl["demb"]), n, cl, self.E)
@@ -1197,20 +1182,19 @@ class HipEncoderEngine:
             self._call("vm_dense_bwd", *dense, _p(self.view("dense.kernel", G)), _p(self.view("dense.bias", G)), _p(pl["dgmax"]), st)
         # GlobalMaxPool1D backward stays sparse (dgmax, gidx): the last block's BN-backward passes consume that form
         last = self.nb - 1
-        wgrad_tails = []   # side stream: the small launches behind every weight-gradient GEMM, deferred behind the last one
         for i in range(self.nb - 1, -1, -1):
             k, c, pool = self.blocks[i]
             b, L = pl[i], pl["L"][i]
             dm = self._dyn(("dropb", i), _p(drop[i])) if drop is not None and drop[i] is not None else None
             if i == 0 and self.fuse_block1:
                 Lq = pl["L"][1]
-                if b.get("bnred_now") and self.fused_sums_finalize and not self.sync_bn:
+                if b["bnred_now"] and self.fused_sums_finalize and not self.sync_bn:
                     # the sums of the dgrad epilogue straight into the column reduction: two small launches instead of three
                     self._call("vm_bn_bwd_from_sums_finalize", _p(b["rs0"]), _p(b["rs1"]), b["rs_rows"], None, _p(b["dp"]), _p(b["scale"]),
                                _p(b["shift"]), _p(b["mean_c" if fold else "mean"]), _p(b["invstd"]), dm, n, wpt, Lq, c, 1, dt, 0, float(wpt * L), _p(b["c1"]),
                                _p(b["c2"]), _p(self.view("bn1.gamma", G)), _p(self.view("bn1.beta", G)), _p(pl["cr_ws"]), st)
                 else:
-                    if b.get("bnred_now"):
+                    if b["bnred_now"]:
                         self._call("vm_bn_bwd_from_sums", _p(b["rs0"]), _p(b["rs1"]), b["rs_rows"], None, _p(b["dp"]), _p(b["scale"]),
                                    _p(b["shift"]), _p(b["mean_c" if fold else "mean"]), _p(b["invstd"]), dm, n, wpt, Lq, c, 1, dt, 0, _p(b["pa"]),
                                    _p(b["pb"]), st)
@@ -1232,12 +1216,7 @@ class HipEncoderEngine:
             else:
                 common = (_p(b["z"]), _p(b["dp"]), _p(b["scale"]), _p(b["shift"]), _p(b["mean"]), _p(b["invstd"]), dm)
             fused_fin = False
-            if sparse and b.get("pairs_now"):
-                # the last block left (e, o): the sparse sums gather e, the apply pass takes the pair form
-                self._call("vm_bn_bwd_gmax_finalize_e", _p(b["ep"]), *common[1:], n, wpt, L // 2, c, dt, float(wpt * L), _p(b["c1"]), _p(b["c2"]),
-                           _p(self.view(f"bn{i+1}.gamma", G)), _p(self.view(f"bn{i+1}.beta", G)), st)
-                fused_fin = True
-            elif sparse and self.fused_sums_finalize and not self.sync_bn and c % 8 == 0:
+            if sparse and self.fused_sums_finalize and not self.sync_bn and c % 8 == 0:
                 # the gather of the sparse sums and their finalize in one launch (three dependent small launches of the forward ->
                 # backward turn-around otherwise)
                 self._call("vm_bn_bwd_gmax_finalize", *common, n, wpt, L, c, pool, dt, float(wpt * L), _p(b["c1"]), _p(b["c2"]),
@@ -1245,16 +1224,16 @@ class HipEncoderEngine:
                 fused_fin = True
             elif sparse:
                 self._call("vm_bn_pool_bwd_reduce_gmax", *common, n, wpt, L, c, pool, dt, _p(b["pa"]), _p(b["pb"]), st)
-            elif b.get("bnred_now") and self.fused_sums_finalize and not self.sync_bn:
-                self._call("vm_bn_bwd_from_sums_finalize", _p(b["rs0"]), _p(b["rs1"]), b["rs_rows"], None if b.get("pairs_now") else _p(b["z"]),
+            elif b["bnred_now"] and self.fused_sums_finalize and not self.sync_bn:
+                self._call("vm_bn_bwd_from_sums_finalize", _p(b["rs0"]), _p(b["rs1"]), b["rs_rows"], None if b["pairs_now"] else _p(b["z"]),
                            _p(b["dp"]), _p(b["scale"]),
-                           _p(b["shift"]), _p(b["mean_c" if b.get("ctr_now") else "mean"]), _p(b["invstd"]), dm, n, wpt, L, c, pool, dt, 0 if b.get("e_now") else 1,
+                           _p(b["shift"]), _p(b["mean_c" if b["ctr_now"] else "mean"]), _p(b["invstd"]), dm, n, wpt, L, c, pool, dt, 0 if b["e_now"] else 1,
                            float(wpt * L), _p(b["c1"]), _p(b["c2"]), _p(self.view(f"bn{i+1}.gamma", G)), _p(self.view(f"bn{i+1}.beta", G)),
                            _p(pl["cr_ws"]), st)
                 fused_fin = True
-            elif b.get("bnred_now"):
+            elif b["bnred_now"]:
                 self._call("vm_bn_bwd_from_sums", _p(b["rs0"]), _p(b["rs1"]), b["rs_rows"], _p(b["z"]), _p(b["dp"]), _p(b["scale"]),
-                           _p(b["shift"]), _p(b["mean_c" if b.get("ctr_now") else "mean"]), _p(b["invstd"]), dm, n, wpt, L, c, pool, dt, 0 if b.get("e_now") else 1,
+                           _p(b["shift"]), _p(b["mean_c" if b["ctr_now"] else "mean"]), _p(b["invstd"]), dm, n, wpt, L, c, pool, dt, 0 if b["e_now"] else 1,
                            _p(b["pa"]), _p(b["pb"]), st)
             elif self.pooled_reduce and L % pool == 0:
                 # throughput mode: the pool-window extreme comes from this block's pooled output (= the next block's input),
@@ -1266,45 +1245,27 @@ class HipEncoderEngine:
             if not fused_fin:
                 self._bn_bwd_finalize(("bwd", i), _p(b["pa"]), _p(b["pb"]), n, wpt, c, float(wpt * L), _p(b["c1"]), _p(b["c2"]),
                                       _p(self.view(f"bn{i+1}.gamma", G)), _p(self.view(f"bn{i+1}.beta", G)), _p(pl["cr_ws"]), st)
-            if b.get("pairs_now") and sparse:
-                self._call("vm_bn_pool_bwd_apply_pairs_gmax", _p(b["ep"]), _p(b["o"]), *common[1:], _p(b["c1"]), _p(b["c2"]), n, wpt, L, c, dt,
-                           _p(b["du"]), _p(b["pdu"]), st)
-            elif b.get("pairs_now") and not sparse:
+            if b["pairs_now"]:   # (never the sparse last block)
                 self._call("vm_bn_pool_bwd_apply_pairs", _p(b["ep"]), _p(b["o"]), *common[1:], _p(b["c1"]), _p(b["c2"]), n, wpt, L, c, dt,
-                           _p(b["du"]), _p(b["pdu"]), _p(b["ctr"]) if b.get("ctr_now") else None, st)
+                           _p(b["du"]), _p(b["pdu"]), _p(b["ctr"]) if b["ctr_now"] else None, st)
             else:
                 self._call("vm_bn_pool_bwd_apply_gmax" if sparse else "vm_bn_pool_bwd_apply", *common, _p(b["c1"]), _p(b["c2"]), n,
                            wpt, L, c, pool, dt, _p(b["du"]), _p(b["pdu"]), st)
-            side = self.overlap_wgrad and i > 0
             gb = _p(self.view(f"conv{i+1}.bias", G))
             gw = _p(self.view(f"conv{i+1}.kernel", G))
 
-            def wgrad(stream, cr_ws, i=i, b=b, L=L, c=c, gb=gb, gw=gw):
+            def wgrad(stream, cr_ws):
                 # the conv bias gradient = column sums of du (from the apply pass's partials), then the weight gradient
                 cin = self.blocks[i - 1][1]
                 if fold:
                     lo = pl[i - 1]
                     # the GEMM first (it needs e and du only), the tap sums behind it, then the per-tower slab sums with their factors
+                    # (moving the two small launches elsewhere was tried and left: profiles/r06_wgrad_tail.txt)
                     self._call("vm_conv_wgrad_fold", _p(lo["ep"]), _p(b["du"]), n, wpt, L, cin, c, dt, None, None, None,
                                _p(b["wgrad_ws_fold"]), None, stream)
-
-                    def finish(st_):
-                        self._call("vm_du_tower_sums", _p(b["pdu"]), _p(b["du"]), n, wpt, L, c, dt, gb, _p(b["dsum"]), _p(cr_ws), st_)
-                        self._call("vm_conv_wgrad_fold_finish", _p(b["wgrad_ws_fold"]), n, wpt, L, cin, c, _p(lo["scale"]),
-                                   _p(lo["shift_c" if ((i == 1 and self.fuse_block1) or lo.get("ctr_now")) else "shift"]), _p(b["dsum"]), gw, st_)
-                    # (round 6 experiments, profiles/r06_wgrad_tail.txt) on the side stream these small launches sit BETWEEN two
-                    # weight-gradient GEMMs; beside the memory-bound apply pass of the main stream their 1024-thread workgroups find
-                    # no compute unit until that pass has drained (85-130 us for a 5 us reduction).  defer_wgrad_tail 1: all of them
-                    # behind the LAST weight-gradient GEMM; 2: on a stream of their own behind their GEMM.
-                    on_side = stream == self.side_stream.cuda_stream
-                    if self.defer_wgrad_tail == 1 and on_side:
-                        wgrad_tails.append(lambda: finish(stream))
-                    elif self.defer_wgrad_tail == 2 and on_side:
-                        self._join(self.misc_stream, self.side_stream)
-                        with self._on(self.misc_stream):
-                            finish(self.stream())
-                    else:
-                        finish(stream)
+                    self._call("vm_du_tower_sums", _p(b["pdu"]), _p(b["du"]), n, wpt, L, c, dt, gb, _p(b["dsum"]), _p(cr_ws), stream)
+                    self._call("vm_conv_wgrad_fold_finish", _p(b["wgrad_ws_fold"]), n, wpt, L, cin, c, _p(lo["scale"]),
+                               _p(lo["shift_c" if (i == 1 or lo["ctr_now"]) else "shift"]), _p(b["dsum"]), gw, stream)
                 else:
                     self._call("vm_conv_wgrad", _p(pl[i - 1]["act"]), _p(b["du"]), n, L, cin, c, dt, _p(b["wgrad_ws"]), gw, stream)
                     self._call("vm_colsum", _p(b["pdu"]), b["pdu"].shape[0], c, gb, _p(cr_ws), stream)
@@ -1323,12 +1284,6 @@ class HipEncoderEngine:
                         self._wait(self.side_stream, b["ev"])
                         # (the bias gradient is nobody's input until the optimizer: off the main stream, with its own workspace)
                         wgrad(self.stream(), pl["cr_ws_side"])
-                        if i == 1:   # the last weight-gradient GEMM of the step is enqueued: now the deferred sums / slab folds
-                            for fin in wgrad_tails:
-                                fin()
-                            del wgrad_tails[:]
-                            if self.defer_wgrad_tail == 2:   # what waits for the side stream from here on waits for the small launches too
-                                self._join(self.side_stream, self.misc_stream)
                     if i == 1 and sync_tail:
                         self._begin_grad_tail(pl)
 
@@ -1340,9 +1295,9 @@ class HipEncoderEngine:
                     if i == 1 and sync_tail:
                         self._begin_grad_tail(pl)
                 lo = pl[i - 1]
-                lo["bnred_now"] = self._bnred_plan(pl, i)
                 if lo["bnred_now"]:
-                    use_e = (i == 1 and self.fuse_block1) or bool(lo.get("e_now"))   # the extreme itself, else the pooled output
+                    self._bnred_bufs(pl, i)
+                    use_e = (i == 1 and self.fuse_block1) or lo["e_now"]   # the extreme itself, else the pooled output
                     red_a, padded = (lo["ep"], 1) if fold else ((lo["e"], 0) if use_e else (lo["act"], 1))
                     self._call("vm_conv_dgrad_bnred", _p(b["du"]), _p(self.wd[i]), n, L, cin, c, dt, _p(lo["dp"]), _p(red_a), padded,
                                _p(lo["rs0"]), _p(lo["rs1"]), _p(self.wdp.get(i)) if self.packed_weights else None, st)
@@ -1353,23 +1308,13 @@ class HipEncoderEngine:
         if self.overlap_wgrad:
             self._join(torch.cuda.current_stream(self.device), self.side_stream)
 
-    def _bnred_plan(self, pl: dict, i: int) -> bool:
-        """Does block i's dgrad also reduce block i-1's BatchNorm-backward sums?  Asked per call (the answer follows
-        vm_set_tuning); allocates the partial rows on first use."""
-        if not self.fused_bn_reduce or i < 1:
-            return False
-        lo, n, L = pl[i - 1], pl["n"], pl["L"][i]
-        cin, c = self.blocks[i - 1][1], self.blocks[i][1]
-        if not (i == 1 and self.fuse_block1) and not lo.get("e_now"):
-            if not (self.pooled_reduce and pl["L"][i - 1] % self.blocks[i - 1][2] == 0):
-                return False
-        if not self.lib.query("vm_conv_dgrad_bnred_supported", n, L, cin, c, self.dtype):
-            return False
+    def _bnred_bufs(self, pl: dict, i: int):
+        """The partial rows block i's dgrad leaves of block i-1's BatchNorm-backward sums (vm_conv_dgrad_bnred), on first use."""
+        lo = pl[i - 1]
         if "rs0" not in lo:
-            lo["rs_rows"] = self.lib.query("vm_conv_dgrad_bnred_rows", L)
+            lo["rs_rows"] = self.lib.query("vm_conv_dgrad_bnred_rows", pl["L"][i])
             for nm in ("rs0", "rs1"):
-                lo[nm] = torch.empty(n * lo["rs_rows"], cin, dtype=torch.float32, device=self.device)
-        return True
+                lo[nm] = torch.empty(pl["n"] * lo["rs_rows"], self.blocks[i - 1][1], dtype=torch.float32, device=self.device)
 
     # ------------------------------------------------------------------------------------------------
     def siamese_head(self, pl: dict, y: Optional[torch.Tensor], loss: str = "contrastive"):
@@ -1560,11 +1505,11 @@ class HipEncoderEngine:
 
     # ---- one training step, eager or replayed -----------------------------------------------------------------------------------
     def _step_flags(self):
-        return (self.fold_affine, self.fuse_block1, self.fused_bn_reduce, self.fused_sums_finalize, self.split_towers, self.tower_stagger, self.tower_swap, self.last_pairs,
-                self.overlap_wgrad, self.wgrad_after_dgrad, self.defer_wgrad_tail, self.fused_pool_extreme, self.fold_pairs, self.pooled_reduce,
+        return (self.fold_affine, self.fuse_block1, self.fused_bn_reduce, self.fused_sums_finalize, self.split_towers, self.tower_stagger,
+                self.overlap_wgrad, self.wgrad_after_dgrad, self.fused_pool_extreme, self.fold_pairs, self.pooled_reduce,
                 self.packed_weights, self.fused_tail, self.defer_head_reduce, self.unbiased, self.clipnorm, self.loss_scaled,
                 self.bn_zero_debias, self.bn_eps, self.bn_momentum, self.beta_1, self.beta_2, self.adam_eps, self._side_priority,
-                self.grad_prescale, self.fused_infer_pool, self.center_blocks, self.pre_overlap, id(self.grad_sync), self.lib.tuning_epoch, id(self.side_stream), id(self.tower_stream), id(self.misc_stream))
+                self.grad_prescale, self.fused_infer_pool, self.center_blocks, self.pre_overlap, id(self.grad_sync), self.lib.tuning_epoch, id(self.side_stream), id(self.tower_stream))
 
     def _train_step(self, pl: dict, wpt: int, target: torch.Tensor, loss: tuple, drop_masks, apply_update: bool, pre: Optional[StepInput],
                     input_ready: bool = False, aug: Optional[dict] = None):
