@@ -9,7 +9,11 @@ as-norm over the --top-k cohort rows most like each row) and the file name gains
         [--score-norm none|s-norm|as-norm --cohort-set train-clean-100 --cohort-size 5000 --top-k 300] [--whole-utterance]
 With --whole-utterance every file is embedded whole, at its own length (retrieval.embed_corpus(whole_utterance=True)), and the file
 name gains _whole.  With --vad [--vad-threshold-db --vad-hang --vad-min-run --vad-frame-ms] the pauses are trimmed out of every file of
-every set first (voicemap_amd/vad.py), the trimming summary is printed and joins the row, and the file name gains _vad."""
+every set first (voicemap_amd/vad.py), the trimming summary is printed and joins the row, and the file name gains _vad.
+--dcf P[,CMISS,CFA] (repeatable) adds the test set's exact minimum detection cost at each operating point (columns
+test_min_dcf_<point>, with its threshold), and the file name gains _dcf.  --calibrate [--calib-prior P] fits llr = a s + b on the
+validation trials (voicemap_amd/calibration.py) and adds Cllr of both sets and, per --dcf point (without one: (P, 1, 1) at the
+calibration prior), the test set's actDCF at the Bayes threshold beside its minDCF; the file name gains _calib."""
 import argparse
 
 import numpy as np
@@ -45,10 +49,30 @@ def cohort_subset(dataset, size, seed=0):
     return CohortSubset(dataset, np.sort(np.random.default_rng(seed).choice(n, size, replace=False)))
 
 
-def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort=None, top_k=300, whole_utterance=False, vad=None):
+def point_name(pt):
+    """Column suffix of a detection-cost point: p0.01, or p0.05_cm10_cf1 with costs other than 1."""
+    return "p%g" % pt[0] + ("" if (pt[1], pt[2]) == (1.0, 1.0) else "_cm%g_cf%g" % (pt[1], pt[2]))
+
+
+def parse_dcf(text):
+    """P or P,CMISS,CFA -> (P, C_miss, C_fa)."""
+    try:
+        v = [float(x) for x in text.split(",")]
+        return verification.as_dcf_points([v[0] if len(v) == 1 else tuple(v)])[0]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort=None, top_k=300, whole_utterance=False, vad=None,
+             dcf=(), calibrate=False, calib_prior=0.5):
     """Embed both sets once, take the best-balanced-accuracy threshold of the validation trials and apply it to the test trials.
     ``score_norm`` "s-norm" / "as-norm": both sets' scores are normalised against the embeddings of ``cohort`` (a dataset).
-    ``vad`` (a ``vad.VadPolicy``): every set, the cohort included, is embedded with its pauses trimmed out."""
+    ``vad`` (a ``vad.VadPolicy``): every set, the cohort included, is embedded with its pauses trimmed out.
+    ``dcf``: detection-cost points for the test set; ``calibrate``: fit llr = a s + b on the validation trials at ``calib_prior`` and
+    report Cllr and, per point, actDCF on the test set (module docstring)."""
+    dcf = verification.as_dcf_points(dcf)
+    if calibrate and not dcf:
+        dcf = [(float(calib_prior), 1.0, 1.0)]
     model = net if score == "head" else None
     wu = {"whole_utterance": True} if whole_utterance else {}
     if vad is not None:
@@ -62,7 +86,7 @@ def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort
         nv = verification.score_norm(cv, cc, score, top_k=k, model=model)
         nt = verification.score_norm(ct, cc, score, top_k=k, model=model)
     mv = verification.verification_metrics(cv, score, model=model, norm=nv)
-    mt = verification.verification_metrics(ct, score, model=model, norm=nt)
+    mt = verification.verification_metrics(ct, score, model=model, norm=nt, dcf_points=dcf)
     at = verification.accuracy_at_threshold(ct, mv["best_threshold"], score, model=model, norm=nt)
     row = {"score": score, "threshold": mv["best_threshold"], "valid_balanced_accuracy": mv["best_balanced_accuracy"],
            "valid_eer": mv["eer"], "valid_eer_threshold": mv["eer_threshold"], "test_balanced_accuracy": at["balanced_accuracy"],
@@ -70,6 +94,22 @@ def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort
            "valid_pairs": mv["n_target"] + mv["n_nontarget"], "test_pairs": mt["n_target"] + mt["n_nontarget"]}
     if "best_threshold_p" in mv:
         row["threshold_p"] = mv["best_threshold_p"]
+    costs = mt.get("dcf", [])
+    if calibrate:
+        from voicemap_amd import calibration
+        cal = calibration.fit_calibration(cv, prior=calib_prior, score=score, model=model, norm=nv)
+        row.update(calib_a=cal.a, calib_b=cal.b, calib_prior=cal.prior, calib_converged=cal.converged, calib_iterations=cal.iterations,
+                   calib_passes=cal.passes, valid_cllr=cal.cllr_train, test_cllr=calibration.cllr(ct, cal, model=model, norm=nt))
+        try:
+            costs = verification.detection_costs(ct, cal, dcf, model=model, norm=nt, metrics=mt)
+        except ValueError as e:   # a >= 0: there is no Bayes threshold in score units; the minimum costs stand alone
+            print("--calibrate: no actDCF:", e)
+    for d in costs:
+        name = point_name((d["p_target"], d["c_miss"], d["c_fa"]))
+        row["test_min_dcf_" + name], row["test_min_dcf_threshold_" + name] = d["min_dcf"], d["min_dcf_threshold"]
+        if calibrate:
+            row["test_act_dcf_" + name] = d.get("act_dcf", float("nan"))
+            row["test_act_threshold_" + name] = d.get("act_threshold", float("nan"))
     if whole_utterance:
         row["whole_utterance"] = True
     if score_norm != "none":
@@ -92,6 +132,10 @@ def result_name(a):
         name += "_whole"
     if getattr(a, "vad", False):
         name += "_vad"
+    if getattr(a, "dcf", None):
+        name += "_dcf"
+    if getattr(a, "calibrate", False):
+        name += "_calib"
     return name + ".csv"
 
 
@@ -113,6 +157,10 @@ def _parser():
     p.add_argument("--cohort-size", type=int, default=5000, help="files of the cohort set taken (seeded random subset)")
     p.add_argument("--top-k", type=int, default=300, help="as-norm: cohort rows per side")
     p.add_argument("--whole-utterance", action="store_true", help="embed every file whole, at its own length (not its first --n-seconds)")
+    p.add_argument("--dcf", action="append", default=[], type=parse_dcf, metavar="P[,CMISS,CFA]",
+                   help="a detection-cost operating point for the test set's minDCF (repeatable)")
+    p.add_argument("--calibrate", action="store_true", help="fit llr = a s + b on the validation set; Cllr and actDCF on the test set")
+    p.add_argument("--calib-prior", type=float, default=0.5, help="the target prior of the calibration fit")
     add_vad_args(p)   # --vad ...: off by default; every set embedded, the cohort included, is trimmed first
     return p
 
@@ -151,7 +199,8 @@ def main(argv=None):
     if cohort is not None:
         cohort = cohort_subset(cohort, a.cohort_size)
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
-    row = evaluate(net, valid, test, pre, a.score, a.score_norm, cohort, a.top_k, a.whole_utterance, vad=vad)
+    row = evaluate(net, valid, test, pre, a.score, a.score_norm, cohort, a.top_k, a.whole_utterance, vad=vad, dcf=a.dcf,
+                   calibrate=a.calibrate, calib_prior=a.calib_prior)
     results = pd.DataFrame([row])
     if rank == 0:
         results.to_csv(PATH + "/logs/" + result_name(a), index=False)

@@ -783,6 +783,28 @@ int vm_cohort_topk_stats(const float* q, int64_t M, const float* cohort, int64_t
 int vm_pair_score_hist_norm(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, const float* weights, int64_t row_lo,
                             int64_t row_hi, const int64_t* host_windows, int n_windows, int bins, const float* mu, const float* rsig,
                             uint64_t* hist, void* ws, void* stream);
+/* vm_pair_calib_sums: the sums of score calibration (csrc/calib.hip, voicemap_amd/calibration.py) -- prior-weighted logistic regression
+ * llr = a s + b over the trials of vm_pair_score_hist, Cllr, and the Bayes-threshold detection costs -- reduced on the chip.
+ * Trials.  Exactly vm_pair_score_hist's: unordered pairs {i, j}, row_lo <= i < row_hi, i < j < N; class 0 (target) iff label[i] ==
+ * label[j], class 1 otherwise.  s is the fp32 score of score_kind (same bits as vm_pair_score_hist's); with mu / rsig (both or neither)
+ * it is replaced by vm_pair_score_hist_norm's normalised score, in exactly that fp32 order.  A trial whose s is NaN or infinite is
+ * skipped and counted in n_skipped.
+ * Per-trial terms, in float64, every operation rounded on its own (no contraction into fma):
+ *   z = a * s + b + tau;  t = -z for a target, +z for a non-target;  e = exp(-|t|);  loss = max(t, 0) + log1p(e);
+ *   p = 1 / (1 + e) if t >= 0, else e / (1 + e);  w = e / ((1 + e) * (1 + e)).
+ * sums (2, 8) float64 on the device, OVERWRITTEN: per class  n, n_skipped, L = sum loss, P0 = sum p, P1 = sum p * s, W0 = sum w,
+ * W1 = sum w * s, W2 = sum (w * s) * s.  The counts are exact.
+ * Determinism.  Per-lane accumulators, a fixed-order wave / workgroup reduction, per-workgroup partials in ws and a fixed-order final
+ * sum in a second launch; no floating-point atomics.  Bit-identical from run to run for the same arguments; a row range cut into
+ * several calls sums in another order (within rounding).
+ * vm_pair_calib_sums_splits(M, N): the splits of the reference tiles of a call with M = row_hi - row_lo rows (the grid is
+ * ceil(M / 64) x splits workgroups; query block k visits the 128-row tiles from that of row row_lo + 64 k + 1 on).
+ * a, b, tau finite; sums 8-byte aligned; the other limits are vm_pair_score_hist's.  ws >= vm_pair_calib_sums_workspace_bytes(N, E). */
+int64_t vm_pair_calib_sums_workspace_bytes(int64_t N, int E);
+int64_t vm_pair_calib_sums_splits(int64_t M, int64_t N);
+int vm_pair_calib_sums(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, const float* weights, int64_t row_lo,
+                       int64_t row_hi, const float* mu, const float* rsig, double a, double b, double tau, double* sums, void* ws,
+                       void* stream);
 /* Speaker models: enrolment, S-way identification and model-trial verification (csrc/enrol.hip, voicemap_amd/enrolment.py) -- the
  * exhaustive limit of the reference's n-shot k-way metric (voicemap/utils.py:159-206 with k = every speaker, n = every (other) file).
  * Rows emb (N, E) fp32, label (N) int32: the dense speaker index in [0, S), anything else (-1) = the row is not enrolled.  kind is

@@ -1,7 +1,8 @@
 // The tile loop of everything that scores cached embeddings -- pairdist_kernel (eval.hip), cohort_score_kernel (cohort.hip), mine_kernel
-// (mine.hip) call it; pair_hist_kernel (verif.hip) keeps a copy, because it measured slower through the call -- and the small helpers
-// around it.  Every score of the four is bit-identical to dist[i][j] of vm_pairdist_argmin because they run THIS text; what a kernel does
-// with a finished tile (argmin, histogram, score tile, selection lists) is its own epilogue in its own file.
+// (mine.hip), pair_calib_kernel (calib.hip) call it; pair_hist_kernel (verif.hip) keeps a copy, because it measured slower through the
+// call -- and the small helpers around it.  Every score of theirs is bit-identical to dist[i][j] of vm_pairdist_argmin because they run
+// THIS text; what a kernel does with a finished tile (argmin, histogram, score tile, selection lists, calibration sums) is its own
+// epilogue in its own file.
 #pragma once
 #include "common.hpp"
 
@@ -21,6 +22,16 @@ __device__ inline uint32_t score_key(float s) {
 __device__ inline uint32_t score_key_nan_last(float s) { return s != s ? 0xffffffffu : score_key(s); }
 // the score of a key (the +0.0 of a zero)
 __device__ inline float score_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// the cohort-normalised score of vm_pair_score_hist_norm and vm_pair_calib_sums: fp32, every operation rounded on its own
+__device__ inline float vh_norm(float s, float mi, float ri, float mj, float rj) {
+#pragma clang fp contract(off)
+    const float a = s - mi;
+    const float b = s - mj;
+    const float x = a * ri;
+    const float y = b * rj;
+    return 0.5f * (x + y);
+}
 
 // ---- preparation launches (defined in eval.hip) --------------------------------------------------------------------------------------
 // row squared norms (fmaf, ascending component per lane, wave sum) and the scalar-path query layout qT of the tile loop

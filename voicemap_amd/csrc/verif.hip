@@ -30,16 +30,6 @@ struct VhWindows {
     uint32_t shift[VH_MAX_WIN];
 };
 
-// the normalised score: fp32, every operation rounded on its own
-__device__ inline float vh_norm(float s, float mi, float ri, float mj, float rj) {
-#pragma clang fp contract(off)
-    const float a = s - mi;
-    const float b = s - mj;
-    const float x = a * ri;
-    const float y = b * rj;
-    return 0.5f * (x + y);
-}
-
 // grid (query blocks of 64 rows of [row_lo, row_lo + M), splits of the block's reference tiles); 512 threads; the first
 // n_win * 2 * (bins + 3) words of the LDS histogram are used.  ghist (n_win, 2, bins + 3) u64, accumulated.  NORM: the score is
 // normalised with mu / rsig (N) first (the plain pass, NORM = false, never reads them).

@@ -388,13 +388,14 @@ def _hist_source(models, cache, leave_one_out):
     return hist_fn, q
 
 
-def model_trial_metrics(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None) -> Dict:
+def model_trial_metrics(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None, dcf_points=()) -> Dict:
     """Exact verification metrics of the trials (row of ``cache``, speaker model): the dict of ``verification.exact_sweep`` (``eer``,
     ``eer_threshold``, ``best_balanced_accuracy``, ``best_threshold``, FAR / FRR at both, ``auc``, ``roc``, ``n_target``,
     ``n_nontarget``, ``n_nan``, ``passes``).  A trial is a target iff the model is the row's own speaker; queries and
-    ``leave_one_out`` as in ``identify``."""
+    ``leave_one_out`` as in ``identify``.  ``dcf_points``: detection-cost points (P_target, C_miss, C_fa), adding ``dcf`` as in
+    ``verification.exact_sweep``."""
     hist_fn, q = _hist_source(models, cache, leave_one_out)
-    return V.exact_sweep(hist_fn, _pass1(models, q))
+    return V.exact_sweep(hist_fn, _pass1(models, q), dcf_points=dcf_points)
 
 
 def model_trial_accuracy_at_threshold(models: SpeakerModels, cache, t: float, leave_one_out: Optional[bool] = None) -> Dict:

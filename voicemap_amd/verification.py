@@ -332,9 +332,41 @@ def _finite_part(lo, hi):
     return max(lo, KEY_FIN_LO) < min(hi, KEY_POS_INF)
 
 
-def _plan(cum: _Cumulative, nT: int, nN: int):
+def _dcf_weights(point) -> Tuple[int, int]:
+    """Integers (wa, wb) in the exact ratio C_miss P : C_fa (1 - P) of a point (P, C_miss, C_fa) (the floats as the rationals they
+    are): DCF(t) is then (wa FRR(t) + wb FAR(t)) / min(wa, wb), and every comparison of costs one of integers."""
+    from fractions import Fraction
+    pt, cm, cf = (Fraction(float(x)) for x in point)
+    if not (0 < pt < 1 and cm > 0 and cf > 0):
+        raise ValueError("a detection-cost point is (P_target in (0, 1), C_miss > 0, C_fa > 0), not %r" % (tuple(point),))
+    A, B = cm * pt, cf * (1 - pt)
+    den = A.denominator * B.denominator // math.gcd(A.denominator, B.denominator)
+    return int(A * den), int(B * den)
+
+
+def as_dcf_points(points) -> List[Tuple[float, float, float]]:
+    """Detection-cost points as (P_target, C_miss, C_fa) triples: a bare P, or (P,), stands for (P, 1, 1)."""
+    out = []
+    for pt in points:
+        pt = (pt,) if np.isscalar(pt) else tuple(pt)
+        if len(pt) not in (1, 3):
+            raise ValueError("a detection-cost point is P_target or (P_target, C_miss, C_fa)")
+        pt = tuple(float(x) for x in (pt if len(pt) == 3 else (pt[0], 1.0, 1.0)))
+        _dcf_weights(pt)
+        out.append(pt)
+    return out
+
+
+def dcf_value(point, far: float, frr: float) -> float:
+    """DCF = (C_miss P FRR + C_fa (1 - P) FAR) / min(C_miss P, C_fa (1 - P)) in float64, from the rates as floats."""
+    pt, cm, cf = point
+    return (cm * pt * frr + cf * (1.0 - pt) * far) / min(cm * pt, cf * (1.0 - pt))
+
+
+def _plan(cum: _Cumulative, nT: int, nN: int, dcf_w: Sequence[Tuple[int, int]] = ()):
     """One step of the zoom: (result or None, segments [lo, hi) to refine).  Items in key order: known candidates (a single-key
-    finite segment that holds scores, and +inf) and 'open' segments (several keys, holding scores, some of them finite)."""
+    finite segment that holds scores, and +inf) and 'open' segments (several keys, holding scores, some of them finite).  ``dcf_w``:
+    the integer weights of the detection-cost points, each treated as the balanced accuracy is."""
     items = []   # (kind, lo, hi, c_lo, c_hi): kind 'c' = candidate at key lo, 'o' = open segment
     pinf = None
     refine = []
@@ -356,18 +388,24 @@ def _plan(cum: _Cumulative, nT: int, nN: int):
     items.append(("c", KEY_POS_INF, KEY_SPACE, pinf, pinf))
     g = lambda c: c[0] * nN - c[1] * nT                     # (1 - (FAR + FRR) / 2 - 1/2) x 2 nT nN: balanced accuracy
     d = lambda c: c[1] * nT + c[0] * nN - nT * nN          # (FAR - FRR) x nT nN: strictly increasing over the candidates
-    # best balanced accuracy
+    # best balanced accuracy, and the minimum of each detection cost: maximise ga c_T nN - gb c_N nT over the candidates (ga = gb = 1:
+    # balanced accuracy; a cost point: minus its cost x nT nN up to a constant), the smallest threshold on ties.
     # the best value known to be reached: at a candidate, or at the first score of an open segment (its lower edge) when that score
     # is finite -- the segment then holds that candidate, key unknown; best_at = the first item known to reach it
-    best, best_at = None, None
-    for it in items:
-        if (it[0] == "c" or it[1] >= KEY_FIN_LO) and (best is None or g(it[3]) > best):
-            best, best_at = g(it[3]), it
-    for it in items:
-        if it[0] == "o":
-            ub = it[4][0] * nN - it[3][1] * nT           # every target of the segment below t, none of its non-targets
-            if ub > best or (ub == best and it[1] <= best_at[1]):
-                refine.append((it[1], it[2]))
+    def best_of(ga, gb):
+        gv = lambda c: ga * c[0] * nN - gb * c[1] * nT
+        best, best_at = None, None
+        for it in items:
+            if (it[0] == "c" or it[1] >= KEY_FIN_LO) and (best is None or gv(it[3]) > best):
+                best, best_at = gv(it[3]), it
+        for it in items:
+            if it[0] == "o":
+                ub = ga * it[4][0] * nN - gb * it[3][1] * nT           # every target of the segment below t, none of its non-targets
+                if ub > best or (ub == best and it[1] <= best_at[1]):
+                    refine.append((it[1], it[2]))
+        return best_at
+    best_at = best_of(1, 1)
+    dcf_at = [best_of(wa, wb) for wa, wb in dcf_w]
     # EER: the first item that holds (or may hold) a candidate with d >= 0, and the item before it
     # (+inf's d is negative when +inf scores exist: then no candidate reaches d >= 0 and t* is the last one)
     first = next((i for i, it in enumerate(items) if (d(it[3]) >= 0 if it[0] == "c" else d(it[4]) >= 0)), len(items))
@@ -387,7 +425,7 @@ def _plan(cum: _Cumulative, nT: int, nN: int):
     tb = items[first] if first < len(items) else None
     ta = items[first - 1] if first > 0 else None
     eer_it = ta if ta is not None and (tb is None or -d(ta[3]) <= d(tb[3])) else tb
-    return (eer_it, best_at), []
+    return (eer_it, best_at, dcf_at), []
 
 
 def _windows_for(refine, bins=1024, gain=16):
@@ -404,9 +442,14 @@ def _windows_for(refine, bins=1024, gain=16):
     return [(lo, hi) for lo, hi, _ in out]
 
 
-def exact_sweep(hist_fn: Callable, pass1: Tuple[int, int], max_passes: int = 10000) -> Dict:
+def exact_sweep(hist_fn: Callable, pass1: Tuple[int, int], max_passes: int = 10000, dcf_points: Sequence = ()) -> Dict:
     """The zoom loop on any histogram source ``hist_fn(windows, bins) -> (n_windows, 2, bins + 3) int64`` (the device histogram, or
-    ``bin_scores`` on a score array in the CPU tests).  Returns the metrics dict of ``verification_metrics`` (without the model part)."""
+    ``bin_scores`` on a score array in the CPU tests).  Returns the metrics dict of ``verification_metrics`` (without the model part).
+    ``dcf_points``: detection-cost points (P_target, C_miss, C_fa); the dict then has ``dcf``, one entry per point in their order:
+    ``min_dcf`` (the minimum over the candidate thresholds, exact like the other metrics), ``min_dcf_threshold`` (the smallest that
+    reaches it) and ``far_at_min_dcf`` / ``frr_at_min_dcf``.  Without points neither the keys nor the passes change."""
+    points = as_dcf_points(dcf_points)
+    dcf_w = [_dcf_weights(pt) for pt in points]
     h1 = hist_fn([pass1], PASS1_BINS)
     n_nan = int(h1[0, 0, -1] + h1[0, 1, -1])
     nT, nN = int(h1[0, 0, :-1].sum()), int(h1[0, 1, :-1].sum())
@@ -425,9 +468,12 @@ def exact_sweep(hist_fn: Callable, pass1: Tuple[int, int], max_passes: int = 100
         nan = float("nan")
         out.update(eer=nan, eer_threshold=nan, best_balanced_accuracy=nan, best_threshold=nan, far_at_eer=nan, frr_at_eer=nan,
                    far_at_best=nan, frr_at_best=nan, auc=nan, auc_bound=nan, passes=passes)
+        if points:
+            out["dcf"] = [{"p_target": pt[0], "c_miss": pt[1], "c_fa": pt[2], "min_dcf": nan, "min_dcf_threshold": nan,
+                           "far_at_min_dcf": nan, "frr_at_min_dcf": nan} for pt in points]
         return out
     while True:
-        res, refine = _plan(cum, nT, nN)
+        res, refine = _plan(cum, nT, nN, dcf_w)
         if res is not None:
             break
         wins = _windows_for(refine)
@@ -441,7 +487,7 @@ def exact_sweep(hist_fn: Callable, pass1: Tuple[int, int], max_passes: int = 100
             for v, (lo, sh) in enumerate(chunk):
                 cum.add_window(h[v], lo, sh, bins)
             passes += 1
-    (eer_it, best_it) = res
+    (eer_it, best_it, dcf_its) = res
     rate = lambda c: (c[1] / nN, (nT - c[0]) / nT)
     far_e, frr_e = rate(eer_it[3])
     far_b, frr_b = rate(best_it[3])
@@ -456,6 +502,40 @@ def exact_sweep(hist_fn: Callable, pass1: Tuple[int, int], max_passes: int = 100
     out.update(eer=(far_e + frr_e) / 2, eer_threshold=thr(eer_it), far_at_eer=far_e, frr_at_eer=frr_e,
                best_balanced_accuracy=1.0 - (far_b + frr_b) / 2, best_threshold=thr(best_it), far_at_best=far_b, frr_at_best=frr_b,
                auc=auc2 / (2 * nT * nN), auc_bound=bound2 / (2 * nT * nN), passes=passes)
+    if points:
+        out["dcf"] = []
+        for pt, it in zip(points, dcf_its):
+            far_d, frr_d = rate(it[3])
+            out["dcf"].append({"p_target": pt[0], "c_miss": pt[1], "c_fa": pt[2], "min_dcf": dcf_value(pt, far_d, frr_d),
+                               "min_dcf_threshold": thr(it), "far_at_min_dcf": far_d, "frr_at_min_dcf": frr_d})
+    return out
+
+
+def sorted_dcf(scores, target, points) -> List[Dict]:
+    """The definition of the minimum detection cost, by a full sort (tests and small sets): per point (P_target, C_miss, C_fa) the
+    entry of ``exact_sweep``'s ``dcf``.  The thresholds are the distinct finite scores and +inf, a pair is accepted iff s < t, NaN
+    scores are left out, the costs are compared as exact rationals and the smallest threshold wins a tie."""
+    s = np.asarray(scores, dtype=np.float32).ravel()
+    tg = np.asarray(target, dtype=bool).ravel()
+    ok = ~np.isnan(s)
+    st, sn = np.sort(s[ok & tg]), np.sort(s[ok & ~tg])
+    nT, nN = len(st), len(sn)
+    cand = np.concatenate([np.unique(s[ok & np.isfinite(s)]), np.array([np.inf], np.float32)])
+    cT = [int(c) for c in np.searchsorted(st, cand, side="left")]
+    cN = [int(c) for c in np.searchsorted(sn, cand, side="left")]
+    out = []
+    nan = float("nan")
+    for pt in as_dcf_points(points):
+        if nT == 0 or nN == 0:
+            out.append({"p_target": pt[0], "c_miss": pt[1], "c_fa": pt[2], "min_dcf": nan, "min_dcf_threshold": nan,
+                        "far_at_min_dcf": nan, "frr_at_min_dcf": nan})
+            continue
+        wa, wb = _dcf_weights(pt)
+        cost = [wa * (nT - a) * nN + wb * b * nT for a, b in zip(cT, cN)]   # DCF x nT nN min(wa, wb)
+        i = min(range(len(cand)), key=lambda k: (cost[k], k))
+        far, frr = cN[i] / nN, (nT - cT[i]) / nT
+        out.append({"p_target": pt[0], "c_miss": pt[1], "c_fa": pt[2], "min_dcf": dcf_value(pt, far, frr),
+                    "min_dcf_threshold": float(cand[i]), "far_at_min_dcf": far, "frr_at_min_dcf": frr})
     return out
 
 
@@ -564,12 +644,14 @@ def _norm_bounds(norm: ScoreNorm, lo: float, hi: float) -> Tuple[float, float]:
     return max(lo2, -big), min(hi2, big)
 
 
-def verification_metrics(cache, score: str = "euclidean", model=None, bins: int = PASS1_BINS, norm: Optional[ScoreNorm] = None) -> Dict:
+def verification_metrics(cache, score: str = "euclidean", model=None, bins: int = PASS1_BINS, norm: Optional[ScoreNorm] = None,
+                         dcf_points: Sequence = ()) -> Dict:
     """All-pairs verification metrics of ``cache`` (module docstring): ``eer``, ``eer_threshold``, ``best_balanced_accuracy``,
     ``best_threshold``, FAR / FRR at both, ``auc`` and ``auc_bound`` (the true AUC lies within it), ``roc`` (pass-1 edges as float
     thresholds with FAR and FRR), ``n_target``, ``n_nontarget``, ``n_nan`` and ``passes``.  score="head": the siamese model's own head
     (a uniform_euclidean head is monotone in the distance; the thresholds are then also reported as head outputs p, ``*_p``).
-    ``norm``: the metrics of the cohort-normalised scores (``score_norm``); the thresholds are then in normalised units."""
+    ``norm``: the metrics of the cohort-normalised scores (``score_norm``); the thresholds are then in normalised units.
+    ``dcf_points``: detection-cost points (P_target, C_miss, C_fa) -- adds ``dcf`` with the exact minimum cost of each (``exact_sweep``)."""
     if bins != PASS1_BINS:
         raise ValueError("pass 1 takes %d bins" % PASS1_BINS)
     kind, weights, head = _score_kind(cache, score, model)
@@ -583,9 +665,10 @@ def verification_metrics(cache, score: str = "euclidean", model=None, bins: int 
     if norm is not None:
         lo, hi = _norm_bounds(norm, lo, hi)
         out = exact_sweep(lambda wins, b: _histogram(cache, kind, weights, wins, b, norm=norm),
-                          _sampled_window(cache, kind, weights, lo, hi, norm=norm))
+                          _sampled_window(cache, kind, weights, lo, hi, norm=norm), dcf_points=dcf_points)
         return out
-    out = exact_sweep(lambda wins, b: _histogram(cache, kind, weights, wins, b), _sampled_window(cache, kind, weights, lo, hi))
+    out = exact_sweep(lambda wins, b: _histogram(cache, kind, weights, wins, b), _sampled_window(cache, kind, weights, lo, hi),
+                      dcf_points=dcf_points)
     if head is not None:
         w, b = head
         out["eer_threshold_p"] = _head_p(out["eer_threshold"], w, b)
@@ -613,3 +696,36 @@ def accuracy_at_threshold(cache, t: float, score: str = "euclidean", model=None,
     frr = float(nT - h[0, 1]) / nT if nT else float("nan")
     return {"balanced_accuracy": 1.0 - (far + frr) / 2, "far": far, "frr": frr, "n_target": nT, "n_nontarget": nN,
             "n_nan": int(h[0, -1] + h[1, -1])}
+
+
+def bayes_threshold(calibration, point) -> float:
+    """The Bayes decision threshold of calibrated scores llr = a s + b at a point (P, C_miss, C_fa), moved into score units: accept iff
+    llr > -logit(P~), P~ = P C_miss / (P C_miss + (1 - P) C_fa), which for a < 0 is s < t_s = fp32((-logit(P~) - b) / a).  A fit with
+    a >= 0 (scores that do not separate the classes the right way round) has no such threshold and raises."""
+    if not calibration.a < 0:
+        raise ValueError("the calibration's slope a = %r is not negative: the scores do not separate targets from non-targets" % calibration.a)
+    pt, cm, cf = as_dcf_points([point])[0]
+    theta = -(math.log(pt * cm) - math.log((1.0 - pt) * cf))
+    with np.errstate(over="ignore"):
+        return float(np.float32((theta - calibration.b) / calibration.a))
+
+
+def detection_costs(cache, calibration, points, model=None, norm: Optional[ScoreNorm] = None, metrics: Optional[Dict] = None) -> List[Dict]:
+    """Per point (P_target, C_miss, C_fa): the entry of ``verification_metrics``'s ``dcf`` (``min_dcf`` and where it is reached) plus
+    ``act_dcf``, the cost at the calibration's Bayes threshold ``act_threshold`` (``bayes_threshold``, in score units) counted by
+    ``accuracy_at_threshold``, with ``far_at_act`` / ``frr_at_act``.  ``calibration``: a ``calibration.Calibration`` fitted (on other
+    data) for the same score; with ``norm`` it must have been fitted on normalised scores.  ``metrics``: the result of
+    ``verification_metrics(cache, ..., dcf_points=points)`` where it has been computed already (the sweep is then not repeated)."""
+    if (norm is not None) != bool(calibration.normalised):
+        raise ValueError("the calibration was fitted on %s scores" % ("normalised" if calibration.normalised else "raw"))
+    points = as_dcf_points(points)
+    ts = [bayes_threshold(calibration, pt) for pt in points]   # raises before any pass
+    if metrics is None:
+        metrics = verification_metrics(cache, calibration.score, model=model, norm=norm, dcf_points=points)
+    out = [dict(d) for d in metrics["dcf"]]
+    if [(d["p_target"], d["c_miss"], d["c_fa"]) for d in out] != points:
+        raise ValueError("``metrics`` was computed for other detection-cost points")
+    for d, pt, t in zip(out, points, ts):
+        at = accuracy_at_threshold(cache, t, calibration.score, model=model, norm=norm)
+        d.update(act_dcf=dcf_value(pt, at["far"], at["frr"]), act_threshold=t, far_at_act=at["far"], frr_at_act=at["frr"])
+    return out
