@@ -124,7 +124,7 @@ def test_sorted_dcf_equals_a_brute_force_loop_over_thresholds():
 
 
 def _sweep(s, tg, lo, hi, points=POINTS):
-    return V.exact_sweep(lambda wins, bins: V.bin_scores(s, tg, wins, bins), V._pass1_window(lo, hi), dcf_points=points)
+    return V.exact_sweep(lambda wins, bins: V.bin_scores(s, tg, wins, bins), V.pass1_window(lo, hi), dcf_points=points)
 
 
 def _check_dcf(s, tg, lo, hi):
@@ -181,18 +181,18 @@ def test_without_points_the_sweep_is_what_it_was():
     def hist(wins, bins):
         calls.append((tuple(wins), bins))
         return V.bin_scores(s, tg, wins, bins)
-    old = V.exact_sweep(hist, V._pass1_window(0.0, 3.0))   # the old call signature
+    old = V.exact_sweep(hist, V.pass1_window(0.0, 3.0))   # the old call signature
     old_calls, calls = calls, []
-    new = V.exact_sweep(hist, V._pass1_window(0.0, 3.0), dcf_points=())
+    new = V.exact_sweep(hist, V.pass1_window(0.0, 3.0), dcf_points=())
     assert list(old) == list(new) and "dcf" not in new and old["passes"] == new["passes"] and calls == old_calls
     for k in old:
         if k != "roc":
             assert old[k] == new[k]
-    with_pts = V.exact_sweep(hist, V._pass1_window(0.0, 3.0), dcf_points=[0.01])   # a bare P is (P, 1, 1)
+    with_pts = V.exact_sweep(hist, V.pass1_window(0.0, 3.0), dcf_points=[0.01])   # a bare P is (P, 1, 1)
     assert list(with_pts) == list(old) + ["dcf"] and with_pts["dcf"][0]["c_miss"] == 1.0
     for bad in ([(0.0, 1, 1)], [(1.0, 1, 1)], [(0.5, 0, 1)], [(0.5, 1)]):
         with pytest.raises(ValueError):
-            V.exact_sweep(hist, V._pass1_window(0.0, 3.0), dcf_points=bad)
+            V.exact_sweep(hist, V.pass1_window(0.0, 3.0), dcf_points=bad)
 
 
 def test_bayes_threshold_and_its_refusal():

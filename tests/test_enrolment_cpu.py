@@ -109,7 +109,7 @@ def test_exact_sweep_on_model_trials_equals_the_sorted_definition(distance):
     assert tg.sum() == len(label) - 1 and (~tg).sum() == len(label) * 11
     ref = V.sorted_metrics(s32, tg)
     lo, hi = float(s32.min()), float(s32.max())
-    got = V.exact_sweep(lambda wins, bins: V.bin_scores(s32, tg, wins, bins), V._pass1_window(lo, hi))
+    got = V.exact_sweep(lambda wins, bins: V.bin_scores(s32, tg, wins, bins), V.pass1_window(lo, hi))
     for k in ("eer", "eer_threshold", "far_at_eer", "frr_at_eer", "best_balanced_accuracy", "best_threshold", "n_target", "n_nontarget",
               "n_nan"):
         assert got[k] == ref[k], k

@@ -230,7 +230,7 @@ def test_trial_histogram_equals_numpy_binning_of_the_device_score_matrix(kind, l
         sv, tv = s[trial], target[trial]
         f = sv[np.isfinite(sv)]
         lo, hi = float(f.min()), float(f.max())
-        one = [V._pass1_window(lo, 0.5 * (lo + hi))]
+        one = [V.pass1_window(lo, 0.5 * (lo + hi))]
         h = EN.speaker_trial_hist(q, ql, sums, msum, count, kind, loo, one, 4096).cpu().numpy()
         assert np.array_equal(h, V.bin_scores(sv, tv, one, 4096)), (E, "one window")
         assert h.sum() == trial.sum() and h[0, :, -1].sum() == (S if kind == "cosine" else 0)
@@ -346,7 +346,7 @@ def test_two_runs_give_identical_bytes():
         runs = []
         for _ in range(2):
             got, (sums, msum, count), (q, ql) = _device(emb, label, emb, label, kind, True, 40)
-            h = EN.speaker_trial_hist(q, ql, sums, msum, count, kind, True, [V._pass1_window(0.0, 2.0)], 4096).cpu().numpy()
+            h = EN.speaker_trial_hist(q, ql, sums, msum, count, kind, True, [V.pass1_window(0.0, 2.0)], 4096).cpu().numpy()
             runs.append([got[k].tobytes() for k in sorted(got)] + [sums.cpu().numpy().tobytes(), msum.cpu().numpy().tobytes(),
                                                                     count.cpu().numpy().tobytes(), h.tobytes()])
         assert runs[0] == runs[1], kind

@@ -250,12 +250,12 @@ def test_pair_score_hist_bins_the_reference_scores(E):
         f = s[np.isfinite(s)]
         a, b = float(f.min()), float(f.max())
         wt = w_t if kind == "weighted_l1" else None
-        coarse = [V._pass1_window(a, 0.5 * (a + b))]           # the top half of the scores lands in the over slot
-        got = V._histogram(cache, S.KINDS[kind], wt, coarse, 4096, rows=(lo, hi))
+        coarse = [V.pass1_window(a, 0.5 * (a + b))]           # the top half of the scores lands in the over slot
+        got = V.histogram(cache, S.KINDS[kind], wt, coarse, 4096, rows=(lo, hi))
         assert got.sum() == len(s) and np.array_equal(got, V.bin_scores(s, tg, coarse, 4096)), (E, kind)
         u = np.unique(f)
         single = [(V.key_of(float(v)), 0) for v in u[sorted({0, len(u) // 2, len(u) - 1})]]      # single-key windows
-        got = V._histogram(cache, S.KINDS[kind], wt, single, 1024, rows=(lo, hi))
+        got = V.histogram(cache, S.KINDS[kind], wt, single, 1024, rows=(lo, hi))
         assert np.array_equal(got, V.bin_scores(s, tg, single, 1024)), (E, kind)
 
 

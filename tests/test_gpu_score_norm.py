@@ -147,7 +147,7 @@ def test_normalised_histogram_equals_numpy_binning(dist):
     sn, tg = _norm_scores(emb, spk, dist, norm)
     f = sn[np.isfinite(sn)]
     lo, hi = float(f.min()), float(f.max())
-    coarse = [V._pass1_window(lo, 0.5 * (lo + hi))]
+    coarse = [V.pass1_window(lo, 0.5 * (lo + hi))]
     got = V.score_histogram(cache, dist, coarse, 4096, norm=norm)
     assert np.array_equal(got, V.bin_scores(sn, tg, coarse, 4096))
     b = int(np.argmax(got[0, 0, :4096] + got[0, 1, :4096]))

@@ -56,7 +56,7 @@ def test_histogram_counts_equal_numpy_binning_of_pairdist_scores(N, dist):
             s, tg = np.zeros(0, np.float32), np.zeros(0, bool)
         f = s[np.isfinite(s)]
         lo, hi = (float(f.min()), float(f.max())) if len(f) else (0.0, 1.0)
-        coarse = [V._pass1_window(lo, 0.5 * (lo + hi))]   # the top half of the scores lands in the over slot
+        coarse = [V.pass1_window(lo, 0.5 * (lo + hi))]   # the top half of the scores lands in the over slot
         got = V.score_histogram(cache, dist, coarse, 4096)
         assert np.array_equal(got, V.bin_scores(s, tg, coarse, 4096)), (N, E)
         if N > 1:
@@ -105,11 +105,11 @@ def test_weighted_l1_on_a_lattice_is_exact():
     s = (np.abs(emb[iu[0]].astype(np.float64) - emb[iu[1]]) * w).sum(1).astype(np.float32)   # every partial sum exact in fp32
     tg = spk[iu[0]] == spk[iu[1]]
     cache = _cache(emb, spk)
-    wins = [V._pass1_window(float(s.min()), float(s.max()))]
-    got = V._histogram(cache, V.SCORES["weighted_l1"], torch.as_tensor(w).cuda(), wins, 4096)
+    wins = [V.pass1_window(float(s.min()), float(s.max()))]
+    got = V.histogram(cache, V.SCORES["weighted_l1"], torch.as_tensor(w).cuda(), wins, 4096)
     assert np.array_equal(got, V.bin_scores(s, tg, wins, 4096))
     wins = [(V.key_of(float(v)), 0) for v in np.unique(s)[:4]]
-    got = V._histogram(cache, V.SCORES["weighted_l1"], torch.as_tensor(w).cuda(), wins, 1024)
+    got = V.histogram(cache, V.SCORES["weighted_l1"], torch.as_tensor(w).cuda(), wins, 1024)
     assert np.array_equal(got, V.bin_scores(s, tg, wins, 1024))
 
 
@@ -160,7 +160,7 @@ def test_head_score_ranks_pairs_like_the_siamese_head(head):
         rank_s[np.argsort(sc, kind="stable")] = np.arange(pairs)
         assert np.corrcoef(rank_p, rank_s)[0, 1] > 0.99
         # the kernel's histogram of the head score is numpy's binning of it, up to the last-bit difference of the fp32 sum order
-        h = V.score_histogram(cache, "head", [V._pass1_window(float(sc.min()), float(sc.max()))], 4096, model=net)
+        h = V.score_histogram(cache, "head", [V.pass1_window(float(sc.min()), float(sc.max()))], 4096, model=net)
         assert h.sum() == pairs
 
 
@@ -168,7 +168,7 @@ def test_head_score_ranks_pairs_like_the_siamese_head(head):
 def test_triangle_shards_sum_to_the_single_call(dist):
     emb, spk = _emb(1111, 64, 21)
     cache = _cache(emb, spk)
-    wins = [V._pass1_window(0.0, 2.0 if dist == "cosine" else 30.0)]
+    wins = [V.pass1_window(0.0, 2.0 if dist == "cosine" else 30.0)]
     one = V.score_histogram(cache, dist, wins, 4096)
     for world in range(1, 9):
         tot = sum(V.score_histogram(cache, dist, wins, 4096, rows=r) for r in V.triangle_shards(cache.n, world))
@@ -214,7 +214,7 @@ def test_nan_row_lands_only_in_the_nan_slots():
     emb[37] = np.nan
     s, iu = _pair_scores(emb, "euclidean")
     tg = spk[iu[0]] == spk[iu[1]]
-    wins = [V._pass1_window(0.0, 40.0)]
+    wins = [V.pass1_window(0.0, 40.0)]
     got = V.score_histogram(_cache(emb, spk), "euclidean", wins, 4096)
     assert got[0, :, -1].sum() == 499
     clean = (iu[0] != 37) & (iu[1] != 37)

@@ -116,6 +116,13 @@ def _batches(rank, pairs, length):
         yield [x1, x2], y
 
 
+def _window_cache(rank):
+    """A cache whose scores, and so whose own pass-1 window, depend on the rank."""
+    from voicemap_amd.retrieval import EmbeddingCache
+    emb = torch.randn(200, 8, generator=torch.Generator().manual_seed(11)) * (1.0 + 3.0 * rank)
+    return EmbeddingCache(emb, np.repeat(np.arange(20), 10))
+
+
 def _worker(rank, world, port, outdir):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     torch.set_num_threads(1)
@@ -191,10 +198,27 @@ def _worker(rank, world, port, outdir):
     res["max"] = parallel.max_over_ranks(1.0 + rank)
     res["sum"] = parallel.sum_over_ranks(1.0 + rank)
     # ---- 4. the row all-gather of the cached-embedding evaluation (retrieval.embed_corpus): unequal shards, rank order ----------
-    from voicemap_amd import retrieval
     full = torch.arange(5 * 3, dtype=torch.float32).reshape(5, 3)
     lo, hi = parallel.shard_range(5, rank, world)
-    res["gather_rows"] = bool(torch.equal(retrieval.all_gather_rows(full[lo:hi].clone(), 5), full))
+    res["gather_rows"] = bool(torch.equal(parallel.all_gather_rows(full[lo:hi].clone(), 5), full))
+    # ---- 5. the trial evaluators' host driver (verification.py): the rank sum, rank 0's window everywhere, the sharded triangle ----
+    from voicemap_amd import verification as V
+    res["sum_ranks"] = parallel.sum_ranks(torch.arange(4, dtype=torch.int64) * (rank + 1)).tolist()
+    cache = _window_cache(rank)
+    res["window"] = V.sampled_window(cache, 0, None, *V.bounds(cache, 0))
+    N = 37
+    g = np.random.default_rng(9)                          # the same matrix on both ranks
+    scores, spk = g.normal(0, 1, (N, N)).astype(np.float32), g.integers(0, 5, N)
+    wins = [V.pass1_window(-4.0, 4.0), (V.key_of(0.5), 31)]
+
+    def device_fn(rows):   # a stand-in for a scorer: the counts of the pairs {i, j}, j > i, with i in rows
+        i, j = np.triu_indices(N, 1)
+        mine = (i >= rows[0]) & (i < rows[1])
+        i, j = i[mine], j[mine]
+        return torch.from_numpy(V.bin_scores(scores[i, j], spk[i] == spk[j], wins, 64))
+    whole = V.triangle_sum(device_fn, N, rows=(0, N))
+    res["triangle_same"] = bool(np.array_equal(V.triangle_sum(device_fn, N), whole)) and int(whole[0].sum()) == N * (N - 1) // 2
+    res["triangle_local"] = int(device_fn(V.triangle_shards(N, world)[rank])[0].sum())
     torch.save(res, os.path.join(outdir, "res%d.pt" % rank))
     parallel.barrier()
     dist.destroy_process_group()
@@ -211,6 +235,12 @@ def test_two_rank_data_parallel_gloo(tmp_path):
         assert r["lr_final"] == pytest.approx(1e-3 * 0.5 * 0.5)   # patience 1: reductions after epochs 2 and 3 -- on BOTH ranks
         assert r["nshot_total"] == 9 and r["max"] == 2.0 and r["sum"] == 3.0 and r["gather_rows"]
     assert (r0["nshot_local"], r1["nshot_local"]) == (6, 5)
+    from voicemap_amd import verification as V
+    alone = [V.sampled_window(c, 0, None, *V.bounds(c, 0)) for c in (_window_cache(0), _window_cache(1))]   # no process group here
+    assert alone[0] != alone[1]
+    for r in (r0, r1):
+        assert r["sum_ranks"] == [0, 3, 6, 9] and r["window"] == alone[0] and r["triangle_same"]
+    assert r0["triangle_local"] + r1["triangle_local"] == 37 * 36 // 2 and min(r0["triangle_local"], r1["triangle_local"]) > 0
     files = sorted(os.listdir(str(tmp_path)))
     assert [f for f in files if f.startswith("marker_")] == ["marker_rank0_epoch%d" % e for e in range(3)]   # rank-0-only callback
     rows = open(str(tmp_path / "log.csv")).read().strip().splitlines()

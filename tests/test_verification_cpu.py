@@ -12,7 +12,7 @@ EXACT = ("eer", "eer_threshold", "far_at_eer", "frr_at_eer", "best_balanced_accu
 
 
 def _sweep(s, tg, lo, hi):
-    return V.exact_sweep(lambda wins, bins: V.bin_scores(s, tg, wins, bins), V._pass1_window(lo, hi))
+    return V.exact_sweep(lambda wins, bins: V.bin_scores(s, tg, wins, bins), V.pass1_window(lo, hi))
 
 
 def _check(s, tg, lo, hi):
@@ -111,7 +111,7 @@ def test_triangle_shards_cover_every_pair_once_and_balance(N):
         sh = V.triangle_shards(N, world)
         assert len(sh) == world and sh[0][0] == 0 and sh[-1][1] == N
         assert all(a[1] == b[0] for a, b in zip(sh[:-1], sh[1:])) and all(lo <= hi for lo, hi in sh)
-        counts = [V._pairs_before(hi, N) - V._pairs_before(lo, N) for lo, hi in sh]
+        counts = [V.pairs_before(hi, N) - V.pairs_before(lo, N) for lo, hi in sh]
         assert sum(counts) == total
         assert max(counts) - min(counts) <= N, (world, counts)
         if N < 100:   # brute force: every pair {i < j} in exactly one shard

@@ -48,17 +48,17 @@ def main(argv=None):
     kind = V.SCORES["euclidean"]
     st = torch.cuda.current_stream(dev).cuda_stream
     M = min(a.shard_rows, N)
-    pairs = lambda rows: V._pairs_before(rows, N)
+    pairs = lambda rows: V.pairs_before(rows, N)
 
     sums = torch.zeros(2, 8, dtype=torch.float64, device=dev)
-    wsc = torch.empty(lib.query("vm_pair_calib_sums_workspace_bytes", N, E) // 4 + 64, device=dev)
+    wsc = lib.workspace("vm_pair_calib_sums_workspace_bytes", N, E, device=dev)
     abt = (-0.5, 7.0, -2.0)   # z within a few units of 0 for these scores: no term is trivial
     calib = lambda hi: lib.call("vm_pair_calib_sums", emb.data_ptr(), cache.speaker_dev.data_ptr(), N, E, kind, None, 0, hi, None, None,
                                 abt[0], abt[1], abt[2], sums.data_ptr(), wsc.data_ptr(), st)
-    lo, hi = V._bounds(cache, kind)
-    w1 = V._sampled_window(cache, kind, None, lo, hi)
+    lo, hi = V.bounds(cache, kind)
+    w1 = V.sampled_window(cache, kind, None, lo, hi)
     hist = torch.zeros(1, 2, V.PASS1_BINS + 3, dtype=torch.int64, device=dev)
-    wsh = torch.empty(lib.query("vm_pair_score_hist_workspace_bytes", N, E) // 4 + 64, device=dev)
+    wsh = lib.workspace("vm_pair_score_hist_workspace_bytes", N, E, device=dev)
     win = np.array([w1], dtype=np.int64)
     hist1 = lambda hi: lib.call("vm_pair_score_hist", emb.data_ptr(), cache.speaker_dev.data_ptr(), N, E, kind, None, 0, hi, win.ctypes.data,
                                 1, V.PASS1_BINS, hist.data_ptr(), wsh.data_ptr(), st)

@@ -52,7 +52,7 @@ def main():
     lab = torch.as_tensor(label).cuda()
     t_sums = timed(lambda: EN.speaker_sums(emb, lab, S, 0), 3, 1)
     sums, msum, count = EN.speaker_sums(emb, lab, S, 0)
-    win = [V._pass1_window(0.0, 24.0)]
+    win = [V.pass1_window(0.0, 24.0)]
     keep = {}
 
     def ours_identify():

@@ -57,13 +57,13 @@ def main(argv=None):
     lib = _lib.lib()
     st = torch.cuda.current_stream(dev).cuda_stream
     lo, hi = 0, M
-    ws = torch.empty(lib.query("vm_mine_pairs_workspace_bytes", N, E, lo, hi, a.k_neg, a.k_pos) // 4 + 64, device=dev)
+    ws = lib.workspace("vm_mine_pairs_workspace_bytes", N, E, lo, hi, a.k_neg, a.k_pos, device=dev)
     ni, pi = (torch.empty(M, k, dtype=torch.int32, device=dev) for k in (a.k_neg, a.k_pos))
     nv, pv = (torch.empty(M, k, device=dev) for k in (a.k_neg, a.k_pos))
     ptr = lambda t, k: t.data_ptr() if k else None
     mine = lambda: lib.call("vm_mine_pairs", emb.data_ptr(), label.data_ptr(), N, E, 0, lo, hi, a.k_neg, a.k_pos, None, ptr(ni, a.k_neg),
                             ptr(nv, a.k_neg), ptr(pi, a.k_pos), ptr(pv, a.k_pos), ws.data_ptr(), st)
-    ws2 = torch.empty(lib.query("vm_pairdist_workspace_bytes", M, N) // 4 + 16, device=dev)
+    ws2 = lib.workspace("vm_pairdist_workspace_bytes", M, N, device=dev)
     bv, bi = torch.empty(M, device=dev), torch.empty(M, dtype=torch.int32, device=dev)
     argmin = lambda: lib.call("vm_pairdist_argmin", emb.data_ptr(), emb.data_ptr(), M, N, E, 0, 0, None, bv.data_ptr(), bi.data_ptr(),
                               ws2.data_ptr(), st)
@@ -89,7 +89,7 @@ def main(argv=None):
         "ratio_mine_over_argmin": sm["median_ms"] / sa["median_ms"],
         "gpairs_per_s_mine": M * N / (sm["median_ms"] * 1e-3) / 1e9,
         "valu_bound_ms": 2.0 * M * N * E / 64 / (peak * 1e9) * 1e3,
-        "workspace_mb": ws.numel() * 4 / 2 ** 20,
+        "workspace_mb": ws.numel() / 2 ** 20,
         "nearest_negative_not_nearer_than_nearest_row": bool((nv[:, 0] >= bv).all().item()) if a.k_neg else None,
         "anchors_with_a_positive": float((pi[:, 0] >= 0).float().mean().item()) if a.k_pos else None,
         "device": torch.cuda.get_device_name(dev),

@@ -55,7 +55,7 @@ def main(argv=None):
     # cohort statistics, whole entry point
     mu, sig, rsig = (torch.empty(N, device=dev) for _ in range(3))
     cnt = torch.empty(N, dtype=torch.int32, device=dev)
-    ws = torch.empty(lib.query("vm_cohort_stats_workspace_bytes", N, C, E) // 4 + 64, device=dev)
+    ws = lib.workspace("vm_cohort_stats_workspace_bytes", N, C, E, device=dev)
     stats = blocks(lambda: lib.call("vm_cohort_topk_stats", emb.data_ptr(), N, cohort.data_ptr(), C, E, kind, None, -1, K, mu.data_ptr(),
                                     sig.data_ptr(), rsig.data_ptr(), cnt.data_ptr(), None, ws.data_ptr(), st), a.reps, a.blocks)
     # one tile's rows (both kernels once): the split between scoring and selection comes from the kernel trace of this tool
@@ -66,12 +66,12 @@ def main(argv=None):
     norm = V.score_norm(cache, cohort, "euclidean", top_k=K)
 
     # pass 1, plain and normalised
-    lo, hi = V._bounds(cache, kind)
-    w1 = V._sampled_window(cache, kind, None, lo, hi)
-    nlo, nhi = V._norm_bounds(norm, lo, hi)
-    w1n = V._sampled_window(cache, kind, None, nlo, nhi, norm=norm)
+    lo, hi = V.bounds(cache, kind)
+    w1 = V.sampled_window(cache, kind, None, lo, hi)
+    nlo, nhi = V.norm_bounds(norm, lo, hi)
+    w1n = V.sampled_window(cache, kind, None, nlo, nhi, norm=norm)
     hist = torch.zeros(1, 2, V.PASS1_BINS + 3, dtype=torch.int64, device=dev)
-    wsh = torch.empty(lib.query("vm_pair_score_hist_workspace_bytes", N, E) // 4 + 64, device=dev)
+    wsh = lib.workspace("vm_pair_score_hist_workspace_bytes", N, E, device=dev)
     win, winn = np.array([w1], dtype=np.int64), np.array([w1n], dtype=np.int64)
     plain = blocks(lambda: lib.call("vm_pair_score_hist", emb.data_ptr(), cache.speaker_dev.data_ptr(), N, E, kind, None, 0, N, win.ctypes.data,
                                     1, V.PASS1_BINS, hist.data_ptr(), wsh.data_ptr(), st), a.reps, a.blocks)
@@ -81,7 +81,7 @@ def main(argv=None):
 
     # vm_pairdist_argmin over one row shard: the per-pair yardstick
     M = min(a.shard_rows, N)
-    ws2 = torch.empty(lib.query("vm_pairdist_workspace_bytes", M, N) // 4 + 16, device=dev)
+    ws2 = lib.workspace("vm_pairdist_workspace_bytes", M, N, device=dev)
     bv, bi = torch.empty(M, device=dev), torch.empty(M, dtype=torch.int32, device=dev)
     pd = blocks(lambda: lib.call("vm_pairdist_argmin", emb.data_ptr(), emb.data_ptr(), M, N, E, 0, 0, None, bv.data_ptr(), bi.data_ptr(),
                                  ws2.data_ptr(), st), a.reps, a.blocks)

@@ -63,8 +63,8 @@ def main(argv=None):
     pairs = N * (N - 1) // 2
     lib = _lib.lib()
     kind = V.SCORES["euclidean"]
-    lo, hi = V._bounds(cache, kind)
-    w1 = V._sampled_window(cache, kind, None, lo, hi)
+    lo, hi = V.bounds(cache, kind)
+    w1 = V.sampled_window(cache, kind, None, lo, hi)
 
     # the whole call, with its zoom passes recorded
     passes = []
@@ -72,7 +72,7 @@ def main(argv=None):
     def hist_fn(wins, bins):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        h = V._histogram(cache, kind, None, wins, bins)
+        h = V.histogram(cache, kind, None, wins, bins)
         e1.record()
         e1.synchronize()
         passes.append({"windows": len(wins), "bins": bins, "ms": e0.elapsed_time(e1)})
@@ -92,7 +92,7 @@ def main(argv=None):
 
     # pass 1 alone, device-timed
     hist = torch.zeros(1, 2, V.PASS1_BINS + 3, dtype=torch.int64, device=dev)
-    ws = torch.empty(lib.query("vm_pair_score_hist_workspace_bytes", N, E) // 4 + 64, device=dev)
+    ws = lib.workspace("vm_pair_score_hist_workspace_bytes", N, E, device=dev)
     win = np.array([w1], dtype=np.int64)
     st = torch.cuda.current_stream(dev).cuda_stream
     p1 = blocks(lambda: lib.call("vm_pair_score_hist", emb.data_ptr(), cache.speaker_dev.data_ptr(), N, E, kind, None, 0, N, win.ctypes.data, 1,
@@ -100,7 +100,7 @@ def main(argv=None):
 
     # vm_pairdist_argmin, argmin only, over one 1/8 row shard: bench.py --full's config-5 figure
     M = min(a.shard_rows, N)
-    ws2 = torch.empty(lib.query("vm_pairdist_workspace_bytes", M, N) // 4 + 16, device=dev)
+    ws2 = lib.workspace("vm_pairdist_workspace_bytes", M, N, device=dev)
     bv, bi = torch.empty(M, device=dev), torch.empty(M, dtype=torch.int32, device=dev)
     pd = blocks(lambda: lib.call("vm_pairdist_argmin", emb.data_ptr(), emb.data_ptr(), M, N, E, 0, 0, None, bv.data_ptr(), bi.data_ptr(),
                                  ws2.data_ptr(), st), a.reps, a.blocks)

@@ -63,6 +63,7 @@ VM_LOSS_CONTRASTIVE, VM_LOSS_BCE = _ENUMS["VM_LOSS_CONTRASTIVE"], _ENUMS["VM_LOS
 VM_HEAD_UNIFORM_EUCLIDEAN, VM_HEAD_WEIGHTED_L1 = _ENUMS["VM_HEAD_UNIFORM_EUCLIDEAN"], _ENUMS["VM_HEAD_WEIGHTED_L1"]
 VM_DIST_EUCLIDEAN, VM_DIST_COSINE, VM_DIST_DOT = (_ENUMS[k] for k in ("VM_DIST_EUCLIDEAN", "VM_DIST_COSINE", "VM_DIST_DOT"))
 VM_SCORE_WEIGHTED_L1, VM_SCORE_NEG_EUCLIDEAN = _ENUMS["VM_SCORE_WEIGHTED_L1"], _ENUMS["VM_SCORE_NEG_EUCLIDEAN"]
+DIST = {"euclidean": VM_DIST_EUCLIDEAN, "cosine": VM_DIST_COSINE, "dot_product": VM_DIST_DOT}   # the one distance-name table
 
 
 def header_functions(path=HEADER_PATH):
@@ -108,6 +109,10 @@ class _Lib:
 
     def query(self, name, *args):
         return getattr(self.cdll, name)(*args)
+
+    def workspace(self, name, *args, device):
+        """A byte tensor on ``device`` of the size the ``..._workspace_bytes`` query ``name`` gives for ``args``, plus 256 bytes of slack."""
+        return torch.empty(self.query(name, *args) + 256, dtype=torch.uint8, device=device)
 
     def program_table(self):
         """(name -> function id, name -> "PILFD" argument types) of vm_program_run, or None when the loaded library was generated from

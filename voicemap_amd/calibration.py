@@ -31,7 +31,7 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 import torch
 
-from . import parallel
+from . import _lib
 from . import verification as V
 
 SUM_NAMES = ("n", "n_skipped", "L", "P0", "P1", "W0", "W1", "W2")
@@ -70,7 +70,6 @@ def calib_sums_numpy(scores, target, a: float, b: float, tau: float) -> np.ndarr
 def plan_splits(n: int, rows: Tuple[int, int]) -> Tuple[int, int, int]:
     """(query blocks, splits, most reference tiles in one split) of the grid ``vm_pair_calib_sums`` launches for the rows [lo, hi) of
     an n-row cache: block k's tiles run from that of row lo + 64 k + 1 to the last, cut into ``splits`` equal runs."""
-    from . import _lib
     lo, hi = rows
     blocks = -(-(hi - lo) // 64)
     splits = int(_lib.lib().query("vm_pair_calib_sums_splits", hi - lo, n))
@@ -80,13 +79,12 @@ def plan_splits(n: int, rows: Tuple[int, int]) -> Tuple[int, int, int]:
 
 
 def _device_sums(cache, kind: int, weights, a: float, b: float, tau: float, rows: Tuple[int, int], norm=None) -> torch.Tensor:
-    from . import _lib
     lib = _lib.lib()
     dev = cache.emb.device
     sums = torch.zeros(2, 8, dtype=torch.float64, device=dev)
     if cache.n > 0:
         emb = cache.emb.contiguous()
-        ws = torch.empty(lib.query("vm_pair_calib_sums_workspace_bytes", cache.n, cache.E) // 4 + 64, dtype=torch.float32, device=dev)
+        ws = lib.workspace("vm_pair_calib_sums_workspace_bytes", cache.n, cache.E, device=dev)
         lib.call("vm_pair_calib_sums", emb.data_ptr(), cache.speaker_dev.data_ptr(), cache.n, cache.E, kind,
                  None if weights is None else weights.data_ptr(), rows[0], rows[1], None if norm is None else norm.mu.data_ptr(),
                  None if norm is None else norm.rsig.data_ptr(), float(a), float(b), float(tau), sums.data_ptr(), ws.data_ptr(),
@@ -95,16 +93,7 @@ def _device_sums(cache, kind: int, weights, a: float, b: float, tau: float, rows
 
 
 def _sums(cache, kind, weights, a, b, tau, rows=None, norm=None) -> np.ndarray:
-    if rows is not None:
-        return _device_sums(cache, kind, weights, a, b, tau, rows, norm).cpu().numpy()
-    rank, world = parallel.rank_world()
-    s = _device_sums(cache, kind, weights, a, b, tau, V.triangle_shards(cache.n, world)[rank], norm)
-    if world > 1:
-        import torch.distributed as dist
-        comm = s.to(parallel._comm_device())
-        dist.all_reduce(comm, op=dist.ReduceOp.SUM)
-        s = comm
-    return s.cpu().numpy()
+    return V.triangle_sum(lambda r: _device_sums(cache, kind, weights, a, b, tau, r, norm), cache.n, rows)
 
 
 def calib_sums(cache, a: float, b: float, tau: float, score: str = "euclidean", model=None, norm=None,
@@ -112,8 +101,8 @@ def calib_sums(cache, a: float, b: float, tau: float, score: str = "euclidean", 
     """The (2, 8) float64 sums (``SUM_NAMES``; class 0 = target) of all pair trials of ``cache`` at (a, b, tau): one pass of
     ``vm_pair_calib_sums``.  ``rows``: only the pairs with i in [lo, hi); by default this rank's ``triangle_shards`` range, and under
     torchrun the sums of all ranks are added.  ``norm``: on the cohort-normalised scores (``verification.score_norm``)."""
-    kind, weights, _ = V._score_kind(cache, score, model)
-    V._check_norm(cache, score, norm)
+    kind, weights, _ = V.score_kind(cache, score, model)
+    V.check_norm(cache, score, norm)
     return _sums(cache, kind, weights, a, b, tau, rows, norm)
 
 
@@ -229,8 +218,8 @@ def fit_calibration(cache, prior: float = 0.5, score: str = "euclidean", model=N
     at most ``NEWTON_STOP``^2 C(a, b) (``NEWTON_STOP`` = 1e-9; since C <= ln 2 the decrement itself is then below ``NEWTON_STOP``),
     returned as ``stop``.  Perfectly separable trials have no minimiser (C -> 0 as a -> -inf): the fit then returns ``converged=False``
     after ``max_iter`` steps, or earlier when the Hessian underflows."""
-    kind, weights, _ = V._score_kind(cache, score, model)
-    V._check_norm(cache, score, norm)
+    kind, weights, _ = V.score_kind(cache, score, model)
+    V.check_norm(cache, score, norm)
     return _fit(lambda a, b, tau: _sums(cache, kind, weights, a, b, tau, None, norm), prior, score, norm is not None, max_iter)
 
 

@@ -41,10 +41,10 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import parallel
+from . import _lib, parallel
 from . import verification as V
 
-KINDS = {"euclidean": 0, "cosine": 1, "dot_product": 2}
+KINDS = _lib.DIST
 _KEY_NAN = 0xFFFFFFFF
 
 
@@ -148,7 +148,6 @@ def ranks_numpy(scores, trial, q_label) -> Dict[str, np.ndarray]:
 # ---- the entry points on device tensors --------------------------------------------------------------------------------------------
 def speaker_sums(emb: torch.Tensor, label: torch.Tensor, S: int, kind) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``vm_speaker_sums``: (sums (S, E) float64, msum (S) float64, count (S) int32) on the device."""
-    from . import _lib
     lib = _lib.lib()
     kind = _kind(kind)
     emb = emb.contiguous()
@@ -159,7 +158,7 @@ def speaker_sums(emb: torch.Tensor, label: torch.Tensor, S: int, kind) -> Tuple[
     msum = torch.zeros(S, dtype=torch.float64, device=dev)
     count = torch.zeros(S, dtype=torch.int32, device=dev)
     if N > 0:
-        ws = torch.empty(lib.query("vm_speaker_sums_workspace_bytes", N, E, S) // 8 + 8, dtype=torch.float64, device=dev)
+        ws = lib.workspace("vm_speaker_sums_workspace_bytes", N, E, S, device=dev)
         lib.call("vm_speaker_sums", emb.data_ptr(), label.data_ptr(), N, E, S, kind, sums.data_ptr(), msum.data_ptr(), count.data_ptr(),
                  ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     return sums, msum, count
@@ -169,7 +168,6 @@ def speaker_identify(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, 
                      return_scores: bool = False) -> Dict[str, torch.Tensor]:
     """``vm_speaker_identify``: ``true_score``, ``rank``, ``best_val``, ``best_idx`` (M) and, with ``return_scores``, ``scores`` (M, S)
     (NaN where there is no trial)."""
-    from . import _lib
     lib = _lib.lib()
     kind = _kind(kind)
     q = q.contiguous()
@@ -182,7 +180,7 @@ def speaker_identify(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, 
     if return_scores:
         out["scores"] = torch.empty(M, S, dtype=torch.float32, device=dev)
     if M > 0:
-        ws = torch.empty(lib.query("vm_speaker_identify_workspace_bytes", M, E, S) // 8 + 8, dtype=torch.float64, device=dev)
+        ws = lib.workspace("vm_speaker_identify_workspace_bytes", M, E, S, device=dev)
         lib.call("vm_speaker_identify", q.data_ptr(), q_label.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(), S, kind,
                  1 if leave_one_out else 0, out["scores"].data_ptr() if return_scores else None, out["true_score"].data_ptr(),
                  out["rank"].data_ptr(), out["best_val"].data_ptr(), out["best_idx"].data_ptr(), ws.data_ptr(),
@@ -194,11 +192,9 @@ def speaker_trial_hist(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count
                        windows: Sequence[Tuple[int, int]], bins: int, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``vm_speaker_trial_hist``: (n_windows, 2, bins + 3) int64 counts on the device (class 0 = the own speaker's model), added to
     ``hist`` if one is given."""
-    from . import _lib
     lib = _lib.lib()
     kind = _kind(kind)
-    if len(windows) > V.MAX_WINDOWS or len(windows) * 2 * (bins + 3) > V.LDS_WORDS:
-        raise ValueError("at most %d windows and %d histogram words per launch" % (V.MAX_WINDOWS, V.LDS_WORDS))
+    V.check_windows(windows, bins)
     q = q.contiguous()
     dev = q.device
     q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
@@ -208,7 +204,7 @@ def speaker_trial_hist(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count
         hist = torch.zeros(len(windows), 2, bins + 3, dtype=torch.int64, device=dev)
     if M > 0:
         win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
-        ws = torch.empty(lib.query("vm_speaker_trial_hist_workspace_bytes", M, E, S) // 8 + 8, dtype=torch.float64, device=dev)
+        ws = lib.workspace("vm_speaker_trial_hist_workspace_bytes", M, E, S, device=dev)
         lib.call("vm_speaker_trial_hist", q.data_ptr(), q_label.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(), S, kind,
                  1 if leave_one_out else 0, win.ctypes.data, len(windows), bins, hist.data_ptr(), ws.data_ptr(),
                  torch.cuda.current_stream(dev).cuda_stream)
@@ -287,15 +283,6 @@ def _shard(models, cache, leave_one_out, rows):
     return q.contiguous(), torch.as_tensor(q_label[lo:hi]).to(dev), loo, (lo, hi), n_q, idx
 
 
-def _sum_ranks(t: torch.Tensor) -> np.ndarray:
-    if parallel.rank_world()[1] > 1:
-        import torch.distributed as dist
-        comm = t.to(parallel._comm_device())
-        dist.all_reduce(comm, op=dist.ReduceOp.SUM)
-        t = comm
-    return t.cpu().numpy()
-
-
 def identify(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None, rows: Optional[Tuple[int, int]] = None) -> Dict:
     """S-way identification of the rows of ``cache`` against ``models``: ``rank1_accuracy``, ``cmc`` (float64, ``cmc[k - 1]`` = the share
     of ranked queries with rank < k, k = 1..S), ``mean_reciprocal_rank``, ``n_queries``, ``n_unranked`` (queries without an enrolled own
@@ -308,11 +295,7 @@ def identify(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None,
     S = models.S
     rk = out["rank"].long()
     hist = torch.bincount(torch.where(rk < 0, torch.full_like(rk, S), rk), minlength=S + 1)[:S + 1]
-    if rows is None:
-        hist = _sum_ranks(hist)
-    else:
-        hist = hist.cpu().numpy()
-    hist = hist.astype(np.int64)
+    hist = (parallel.sum_ranks(hist) if rows is None else hist).cpu().numpy().astype(np.int64)
     n_ranked = int(hist[:S].sum())
     with np.errstate(invalid="ignore", divide="ignore"):
         cmc = np.cumsum(hist[:S]).astype(np.float64) / n_ranked
@@ -335,12 +318,11 @@ def _prototypes(models: SpeakerModels) -> torch.Tensor:
 
 
 def _pass1(models: SpeakerModels, q: torch.Tensor, n_sample: int = 1 << 16) -> Tuple[int, int]:
-    """Pass 1's window from a seeded sample of (row, model) pairs of rank 0's rows, within cheap bounds -- it only places the window
-    (whatever falls outside lands in the under / over slots and the counts stay exact); broadcast so every rank bins alike."""
-    rank, world = parallel.rank_world()
+    """``verification.place_window`` for the model trials of rank 0's rows ``q``: bounds from the largest row and model norms, and a
+    seeded sample of (row, model) pairs, those of a speaker without a model left out."""
     kind = _kind(models.distance)
-    win = torch.zeros(2, dtype=torch.int64)
-    if rank == 0:
+
+    def sample():
         P = _prototypes(models)
         ok = models.count > 0
         pr = float(torch.linalg.vector_norm(P[ok], dim=1).max().item()) if bool(ok.any()) else 0.0
@@ -352,31 +334,13 @@ def _pass1(models: SpeakerModels, q: torch.Tensor, n_sample: int = 1 << 16) -> T
             lo, hi = 0.0, (pr + qr) * 1.001 + 1e-30
         else:
             lo, hi = -pr * qr * 1.001 - 1e-30, pr * qr * 1.001 + 1e-30
-        win[0], win[1] = V._pass1_window(lo, hi)
-        if q.shape[0] >= 1 and bool(ok.any()):
-            g = torch.Generator().manual_seed(0)
-            i = torch.randint(0, q.shape[0], (n_sample,), generator=g).to(q.device)
-            s = torch.randint(0, models.S, (n_sample,), generator=g).to(q.device)
-            a, b = q[i].double(), P[s]
-            if kind == 0:
-                sc = torch.linalg.vector_norm(a - b, dim=1)
-            elif kind == 1:
-                sc = 1 - (a * b).sum(1) / (torch.linalg.vector_norm(a, dim=1) * torch.linalg.vector_norm(b, dim=1))
-            else:
-                sc = -(a * b).sum(1)
-            sc = sc[torch.isfinite(sc) & ok[s]].cpu().numpy()
-            if len(sc) > 100:
-                q0, q1 = np.quantile(sc, [1e-4, 1 - 1e-4])
-                pad = 0.05 * (q1 - q0) + 1e-6 * max(abs(q0), abs(q1)) + 1e-30
-                q0, q1 = max(lo, q0 - pad), min(hi, q1 + pad)
-                if q0 < q1:
-                    win[0], win[1] = V._pass1_window(float(q0), float(q1))
-    if world > 1:
-        import torch.distributed as dist
-        comm = win.to(parallel._comm_device())
-        dist.all_reduce(comm, op=dist.ReduceOp.SUM)
-        win = comm.cpu()
-    return int(win[0]), int(win[1])
+        if q.shape[0] < 1 or not bool(ok.any()):
+            return lo, hi, None
+        g = torch.Generator().manual_seed(0)
+        i = torch.randint(0, q.shape[0], (n_sample,), generator=g).to(q.device)
+        s = torch.randint(0, models.S, (n_sample,), generator=g).to(q.device)
+        return lo, hi, V.sample_scores(q[i], P[s], kind).masked_fill(~ok[s], float("nan"))   # no model: no trial, dropped as not finite
+    return V.place_window(sample)
 
 
 def _hist_source(models, cache, leave_one_out):
@@ -384,7 +348,7 @@ def _hist_source(models, cache, leave_one_out):
 
     def hist_fn(windows, bins):
         h = speaker_trial_hist(q, q_label, models.sums, models.msum, models.count, models.distance, loo, windows, bins)
-        return _sum_ranks(h)
+        return parallel.sum_ranks(h).cpu().numpy()
     return hist_fn, q
 
 
@@ -402,10 +366,4 @@ def model_trial_accuracy_at_threshold(models: SpeakerModels, cache, t: float, le
     """Balanced accuracy, FAR and FRR of the model trials at a fixed threshold t (accept iff score < t): one pass with key_lo = key(t),
     whose under slot is exactly {s < t} -- a threshold found on a validation set applied to a test set."""
     hist_fn, _ = _hist_source(models, cache, leave_one_out)
-    k = V.key_of(t) if not math.isnan(t) else V.KEY_SPACE - 1
-    h = hist_fn([(k, 31)], 1)[0]
-    nT, nN = int(h[0, :-1].sum()), int(h[1, :-1].sum())
-    far = float(h[1, 1]) / nN if nN else float("nan")
-    frr = float(nT - h[0, 1]) / nT if nT else float("nan")
-    return {"balanced_accuracy": 1.0 - (far + frr) / 2, "far": far, "frr": frr, "n_target": nT, "n_nontarget": nN,
-            "n_nan": int(h[0, -1] + h[1, -1])}
+    return V.counts_at_threshold(hist_fn, t)

@@ -16,11 +16,11 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import parallel
+from . import _lib, parallel
 from .keras_like import Callback
 from .verification import score_keys
 
-_DIST = {"euclidean": 0, "cosine": 1, "dot_product": 2}
+_DIST = _lib.DIST
 MAX_K = 64   # csrc/mine.hip MN_MAX_K: a list is one entry per lane of a wave
 _NONE = np.uint64(0xFFFFFFFFFFFFFFFF)
 
@@ -76,7 +76,6 @@ def mine_rows(emb: torch.Tensor, label: torch.Tensor, kind: int, rows: Tuple[int
               neg_floor: Optional[torch.Tensor] = None):
     """``vm_mine_pairs`` on device tensors: emb (N, E) fp32, label (N) int32, anchors ``rows = (lo, hi)``, neg_floor (hi - lo) fp32 or
     None -> (neg_idx, neg_val, pos_idx, pos_val) on the device ((hi - lo, 0) tensors for a list that was not asked for)."""
-    from . import _lib
     lib = _lib.lib()
     dev = emb.device
     emb = emb.contiguous()
@@ -92,8 +91,7 @@ def mine_rows(emb: torch.Tensor, label: torch.Tensor, kind: int, rows: Tuple[int
         neg_floor = neg_floor.to(device=dev, dtype=torch.float32).contiguous()
         if neg_floor.numel() != M:
             raise ValueError("neg_floor must hold one value per anchor row")
-    nbytes = lib.query("vm_mine_pairs_workspace_bytes", N, E, lo, hi, k_neg, k_pos)
-    ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device=dev)
+    ws = lib.workspace("vm_mine_pairs_workspace_bytes", N, E, lo, hi, k_neg, k_pos, device=dev)
     ptr = lambda t, k: t.data_ptr() if k > 0 else None
     lib.call("vm_mine_pairs", emb.data_ptr(), label.data_ptr(), N, E, kind, lo, hi, k_neg, k_pos,
              None if neg_floor is None else neg_floor.data_ptr(), ptr(neg_idx, k_neg), ptr(neg_val, k_neg), ptr(pos_idx, k_pos),
@@ -147,7 +145,6 @@ def mine_pairs(cache, distance: str = "euclidean", k_neg: int = 8, k_pos: int = 
         raise ValueError("k_neg and k_pos must be in [0, %d] and not both zero" % MAX_K)
     if semi_hard and (k_pos < 1 or k_neg < 1):
         raise ValueError("semi_hard needs k_pos >= 1 (the floor is the hardest positive) and k_neg >= 1")
-    from .retrieval import all_gather_rows
     kind = _DIST[distance]
     label = torch.as_tensor(dense_labels(cache.speaker)).to(cache.emb.device)
     rank, world = parallel.rank_world()
@@ -158,7 +155,7 @@ def mine_pairs(cache, distance: str = "euclidean", k_neg: int = 8, k_pos: int = 
     else:
         ni, nv, pi, pv = mine_rows(cache.emb, label, kind, (lo, hi), k_neg, k_pos)
     if rows is None and world > 1:
-        ni, nv, pi, pv = (all_gather_rows(t, cache.n) if t.shape[1] else torch.empty(cache.n, 0, dtype=t.dtype, device=t.device)
+        ni, nv, pi, pv = (parallel.all_gather_rows(t, cache.n) if t.shape[1] else torch.empty(cache.n, 0, dtype=t.dtype, device=t.device)
                           for t in (ni, nv, pi, pv))
         lo, hi = 0, cache.n
     return MinedPairs(ni.cpu().numpy(), nv.cpu().numpy(), pi.cpu().numpy(), pv.cpu().numpy(), distance, (lo, hi), semi_hard)

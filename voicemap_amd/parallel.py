@@ -196,6 +196,30 @@ def broadcast_state(engine, src: int = 0):
         engine.refresh_weights()
 
 
+def sum_ranks(t: torch.Tensor, device=None) -> torch.Tensor:
+    """The element-wise sum of ``t`` over ranks, on the communication device (``device``, or the backend's own); with one rank ``t``
+    itself.  A tensor of zeros on every rank but one is that rank's broadcast."""
+    if rank_world()[1] > 1:
+        t = t.to(_comm_device(device))
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t
+
+
+def all_gather_rows(local: torch.Tensor, n_total: int) -> torch.Tensor:
+    """Concatenate the ranks' row blocks (``shard_range`` sizes, which differ by at most one row) in rank order."""
+    rank, world = rank_world()
+    if world == 1:
+        return local
+    sizes = [shard_range(n_total, r, world) for r in range(world)]
+    most = max(h - l for l, h in sizes)
+    pad = torch.zeros(most, local.shape[1], dtype=local.dtype, device=local.device)
+    pad[:local.shape[0]].copy_(local)
+    comm = pad if dist.get_backend() != "gloo" else pad.cpu()
+    parts = [torch.empty_like(comm) for _ in range(world)]
+    dist.all_gather(parts, comm)
+    return torch.cat([p[:h - l] for p, (l, h) in zip(parts, sizes)]).to(local.device)
+
+
 def max_over_ranks(value: float, device=None) -> float:
     if not (dist.is_initialized() and dist.get_world_size() > 1):
         return value
@@ -206,11 +230,9 @@ def max_over_ranks(value: float, device=None) -> float:
 
 def sum_over_ranks(value: float, device=None) -> float:
     """Sum of one number over ranks (n_correct of the sharded k-way evaluation)."""
-    if not (dist.is_initialized() and dist.get_world_size() > 1):
+    if rank_world()[1] == 1:
         return value
-    t = torch.tensor([value], dtype=torch.float64, device=_comm_device(device))
-    dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    return float(t.item())
+    return float(sum_ranks(torch.tensor([value], dtype=torch.float64), device).item())
 
 
 def weighted_mean_logs(sums: Dict[str, float], weight: float, device=None) -> Dict[str, float]:
@@ -218,11 +240,7 @@ def weighted_mean_logs(sums: Dict[str, float], weight: float, device=None) -> Di
     rank's sample count; returns the global sample-weighted means -- the SAME numbers on every rank, so callbacks that act on
     them (ReduceLROnPlateau, ModelCheckpoint's best-so-far) decide identically everywhere."""
     keys = sorted(sums)
-    vals = [float(sums[k]) for k in keys] + [float(weight)]
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        t = torch.tensor(vals, dtype=torch.float64, device=_comm_device(device))
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        vals = t.tolist()
+    vals = sum_ranks(torch.tensor([float(sums[k]) for k in keys] + [float(weight)], dtype=torch.float64), device).tolist()
     w = max(vals[-1], 1.0)
     return {k: v / w for k, v in zip(keys, vals[:-1])}
 

@@ -28,9 +28,9 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import parallel
+from . import _lib, parallel
 
-_DIST = {"euclidean": 0, "cosine": 1, "dot_product": 2}
+_DIST = _lib.DIST
 
 
 def _encoder_engine(model, network_type: str):
@@ -105,7 +105,7 @@ def embed_corpus(model, dataset, preprocessor, network_type: str = "siamese", ba
                 waves = [np.asarray(dataset._load(int(i)), dtype=np.float32) for i in idx]
                 local[b0 - lo:b0 - lo + len(waves)].copy_(eng.embed_varlen(waves, None, None, ds, wh,
                                                                            names=file_names(dataset, idx.start, idx.stop)))
-        return EmbeddingCache(all_gather_rows(local, n_files), dataset._code)
+        return EmbeddingCache(parallel.all_gather_rows(local, n_files), dataset._code)
     for b0 in range(lo, hi, batch):
         idx = np.arange(b0, min(b0 + batch, hi))
         if dev_audio is not None and lazy_ok:
@@ -122,7 +122,7 @@ def embed_corpus(model, dataset, preprocessor, network_type: str = "siamese", ba
             else:   # a preprocessor that already returned numbers: whiten-alone semantics are the caller's business
                 e = eng.embed(np.asarray(lazy, dtype=np.float32))
         local[b0 - lo:b0 - lo + len(idx)].copy_(e)
-    emb = all_gather_rows(local, n_files)
+    emb = parallel.all_gather_rows(local, n_files)
     return EmbeddingCache(emb, dataset._code)
 
 
@@ -187,7 +187,7 @@ def _embed_corpus_trimmed(model, dataset, preprocessor, network_type, batch, who
             idx = range(b0, min(b0 + _WHOLE_FILES, hi))
             waves = [host.pcm(i) for i in idx]
             local[b0 - lo:b0 - lo + len(waves)].copy_(eng.embed_varlen(waves, None, None, ds, wh, names=file_names(dataset, idx.start, idx.stop)))
-        cache = EmbeddingCache(all_gather_rows(local, n_files), dataset._code)
+        cache = EmbeddingCache(parallel.all_gather_rows(local, n_files), dataset._code)
     cache.vad_counts = host.counts()
     return cache
 
@@ -216,22 +216,6 @@ def _first_fragment(dataset, index: int) -> np.ndarray:
             raise ValueError("file %d is shorter than the fragment length and the dataset does not pad" % index)
         x = np.pad(x, (0, dataset.fragment_length - len(x)), "constant")   # stochastic=False pads at the end (:123-127)
     return x
-
-
-def all_gather_rows(local: torch.Tensor, n_total: int) -> torch.Tensor:
-    """Concatenate the ranks' row blocks (``parallel.shard_range`` sizes, which differ by at most one row) in rank order."""
-    rank, world = parallel.rank_world()
-    if world == 1:
-        return local
-    import torch.distributed as dist
-    sizes = [parallel.shard_range(n_total, r, world) for r in range(world)]
-    most = max(h - l for l, h in sizes)
-    pad = torch.zeros(most, local.shape[1], dtype=local.dtype, device=local.device)
-    pad[:local.shape[0]].copy_(local)
-    comm = pad if dist.get_backend() != "gloo" else pad.cpu()
-    parts = [torch.empty_like(comm) for _ in range(world)]
-    dist.all_gather(parts, comm)
-    return torch.cat([p[:h - l] for p, (l, h) in zip(parts, sizes)]).to(local.device)
 
 
 # ---- tasks as indices -----------------------------------------------------------------------------------------------------------
@@ -318,7 +302,6 @@ def evaluate_tasks(cache: EmbeddingCache, query_idx, support_idx, k: int, n: int
                    return_pred: bool = False):
     """n_correct (and optionally the (tasks, k) distances) of tasks given as row indices -- correct iff argmin == 0, the support set
     being laid out with the query's speaker first (voicemap/utils.py:208-210)."""
-    from . import _lib
     if distance not in _DIST:
         raise ValueError("Distance must be in (euclidean, cosine, dot_product)")
     dev = cache.emb.device
@@ -412,7 +395,6 @@ def pairwise_retrieval(cache: EmbeddingCache, distance: str = "euclidean", retur
     (lo, hi)): nearest OTHER utterance per query row with ``vm_pairdist_argmin`` and the retrieval form of verification accuracy --
     the share of utterances whose nearest neighbour is the same speaker -- summed over ranks.  Returns a dict with ``n_correct``,
     ``n_rows`` (global), ``accuracy``, this rank's ``best_idx`` / ``best_val`` and, on request, its (rows, N) block of the matrix."""
-    from . import _lib
     if distance not in _DIST:
         raise ValueError("Distance must be in (euclidean, cosine, dot_product)")
     rank, world = parallel.rank_world()
@@ -422,7 +404,7 @@ def pairwise_retrieval(cache: EmbeddingCache, distance: str = "euclidean", retur
     out = {"rows": (lo, hi)}
     if M > 0:
         lib = _lib.lib()
-        ws = torch.empty(lib.query("vm_pairdist_workspace_bytes", M, N) // 4 + 16, dtype=torch.float32, device=dev)
+        ws = lib.workspace("vm_pairdist_workspace_bytes", M, N, device=dev)
         bv = torch.empty(M, dtype=torch.float32, device=dev)
         bi = torch.empty(M, dtype=torch.int32, device=dev)
         dist = torch.empty(M, N, dtype=torch.float32, device=dev) if return_matrix else None

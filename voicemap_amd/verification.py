@@ -33,10 +33,10 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import parallel
+from . import _lib, parallel
+from ._lib import VM_SCORE_NEG_EUCLIDEAN
 
-SCORES = {"euclidean": 0, "cosine": 1, "dot_product": 2, "weighted_l1": 3}
-VM_SCORE_NEG_EUCLIDEAN = 4
+SCORES = {**_lib.DIST, "weighted_l1": _lib.VM_SCORE_WEIGHTED_L1}
 KEY_SPACE = 1 << 32
 KEY_NEG_INF = 0x007FFFFF        # key(-inf)
 KEY_FIN_LO = 0x00800000         # key(-FLT_MAX): the smallest finite key
@@ -151,7 +151,6 @@ class ScoreNorm:
 def cohort_topk_stats(q: torch.Tensor, cohort: torch.Tensor, kind: int, weights, top_k: int, self_row0: int = -1,
                       return_topk: bool = False):
     """``vm_cohort_topk_stats`` on device tensors: (mu, sigma, rsig, count[, topk_idx])."""
-    from . import _lib
     lib = _lib.lib()
     dev = q.device
     M, E = q.shape
@@ -161,7 +160,7 @@ def cohort_topk_stats(q: torch.Tensor, cohort: torch.Tensor, kind: int, weights,
     cnt = torch.empty(M, dtype=torch.int32, device=dev)
     topk = torch.empty(M, top_k, dtype=torch.int32, device=dev) if return_topk else None
     if M > 0:
-        ws = torch.empty(lib.query("vm_cohort_stats_workspace_bytes", M, C, E) // 4 + 64, dtype=torch.float32, device=dev)
+        ws = lib.workspace("vm_cohort_stats_workspace_bytes", M, C, E, device=dev)
         lib.call("vm_cohort_topk_stats", q.data_ptr(), M, cohort.data_ptr(), C, E, kind, None if weights is None else weights.data_ptr(),
                  self_row0, top_k, mu.data_ptr(), sig.data_ptr(), rsig.data_ptr(), cnt.data_ptr(),
                  None if topk is None else topk.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
@@ -173,8 +172,7 @@ def score_norm(cache, cohort, score: str = "euclidean", top_k: Optional[int] = 3
     like the row).  ``cohort``: an ``EmbeddingCache`` or a (C, E) tensor; ``cohort is cache`` excludes each row from its own cohort.
     score="head" takes the siamese model's head score like ``verification_metrics``.  Under torchrun every rank computes its
     ``parallel.shard_range`` rows and the rows are all-gathered: every rank holds all N."""
-    from .retrieval import all_gather_rows
-    kind, weights, _ = _score_kind(cache, score, model)
+    kind, weights, _ = score_kind(cache, score, model)
     self_ex = cohort is cache
     ce = cohort.emb if hasattr(cohort, "emb") else torch.as_tensor(cohort)
     ce = ce.to(device=cache.emb.device, dtype=torch.float32).contiguous()
@@ -189,13 +187,13 @@ def score_norm(cache, cohort, score: str = "euclidean", top_k: Optional[int] = 3
     mu, sig, rsig, cnt = cohort_topk_stats(cache.emb[lo:hi], ce, kind, weights, K, lo if self_ex else -1)
     if world > 1:
         loc = torch.stack([mu.double(), sig.double(), rsig.double(), cnt.double()], 1)
-        allr = all_gather_rows(loc, cache.n)
+        allr = parallel.all_gather_rows(loc, cache.n)
         mu, sig, rsig = (allr[:, k].float().contiguous() for k in range(3))
         cnt = allr[:, 3].to(torch.int32).contiguous()
     return ScoreNorm(mu, sig, rsig, cnt, score, top_k, C)
 
 
-def _check_norm(cache, score, norm):
+def check_norm(cache, score, norm):
     if norm is None:
         return
     if norm.score != score:
@@ -205,7 +203,7 @@ def _check_norm(cache, score, norm):
 
 
 # ---- rows of the triangle --------------------------------------------------------------------------------------------------------
-def _pairs_before(i, N):
+def pairs_before(i, N):
     """Pairs {i', j}, i' < i, j > i'."""
     return i * (N - 1) - i * (i - 1) // 2
 
@@ -213,27 +211,37 @@ def _pairs_before(i, N):
 def triangle_shards(N: int, world: int) -> List[Tuple[int, int]]:
     """Contiguous row ranges [lo, hi) of the triangle {i < j < N} with near-equal PAIR counts (the early rows hold the most pairs): each
     boundary is the row whose pair prefix is nearest to an even split of the pairs left to the remaining shards."""
-    total = _pairs_before(N, N)
-    bounds = [0]
+    total = pairs_before(N, N)
+    cuts = [0]
     for k in range(1, world):
-        done = _pairs_before(bounds[-1], N)
+        done = pairs_before(cuts[-1], N)
         goal = done + (total - done) / (world - k + 1)
-        lo, hi = bounds[-1], N
+        lo, hi = cuts[-1], N
         while lo < hi:   # first row i with prefix >= goal
             mid = (lo + hi) // 2
-            if _pairs_before(mid, N) >= goal:
+            if pairs_before(mid, N) >= goal:
                 hi = mid
             else:
                 lo = mid + 1
-        if lo > bounds[-1] and goal - _pairs_before(lo - 1, N) < _pairs_before(lo, N) - goal:
+        if lo > cuts[-1] and goal - pairs_before(lo - 1, N) < pairs_before(lo, N) - goal:
             lo -= 1
-        bounds.append(lo)
-    bounds.append(N)
-    return list(zip(bounds[:-1], bounds[1:]))
+        cuts.append(lo)
+    cuts.append(N)
+    return list(zip(cuts[:-1], cuts[1:]))
+
+
+def triangle_sum(device_fn: Callable, n: int, rows: Optional[Tuple[int, int]] = None) -> np.ndarray:
+    """The pass of an all-pairs evaluator over the triangle of an n-row cache.  ``device_fn((lo, hi))`` returns a device tensor of
+    integer counts or float64 sums over the pairs with i in [lo, hi).  ``rows`` given: that range alone, no communication.  Otherwise
+    this rank's ``triangle_shards`` range, summed over the ranks (every rank then holds the same array)."""
+    if rows is not None:
+        return device_fn(rows).cpu().numpy()
+    rank, world = parallel.rank_world()
+    return parallel.sum_ranks(device_fn(triangle_shards(n, world)[rank])).cpu().numpy()
 
 
 # ---- the device histogram --------------------------------------------------------------------------------------------------------
-def _score_kind(cache, score: str, model) -> Tuple[int, Optional[torch.Tensor], Optional[Tuple[float, float]]]:
+def score_kind(cache, score: str, model) -> Tuple[int, Optional[torch.Tensor], Optional[Tuple[float, float]]]:
     """(kernel score kind, weights, (w, b) of a uniform_euclidean head)."""
     if score in ("euclidean", "cosine", "dot_product"):
         return SCORES[score], None, None
@@ -254,14 +262,13 @@ def _score_kind(cache, score: str, model) -> Tuple[int, Optional[torch.Tensor], 
 
 
 def _device_hist(cache, kind: int, weights, windows, bins: int, rows: Tuple[int, int], norm=None) -> np.ndarray:
-    from . import _lib
     lib = _lib.lib()
     dev = cache.emb.device
     hist = torch.zeros(len(windows), 2, bins + 3, dtype=torch.int64, device=dev)
     lo, hi = rows
     if hi > lo:
         emb = cache.emb.contiguous()
-        ws = torch.empty(lib.query("vm_pair_score_hist_workspace_bytes", cache.n, cache.E) // 4 + 64, dtype=torch.float32, device=dev)
+        ws = lib.workspace("vm_pair_score_hist_workspace_bytes", cache.n, cache.E, device=dev)
         win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
         if norm is None:
             lib.call("vm_pair_score_hist", emb.data_ptr(), cache.speaker_dev.data_ptr(), cache.n, cache.E, kind,
@@ -279,24 +286,33 @@ def score_histogram(cache, score: str, windows: Sequence[Tuple[int, int]], bins:
     """(n_windows, 2, bins + 3) int64 counts of all pair scores of ``cache`` (class 0 = target) in windows (key_lo, shift).  ``rows``:
     only the pairs with i in [lo, hi); by default this rank's ``triangle_shards`` range, and under torchrun the histograms of all ranks
     are summed.  ``norm``: the counts of the normalised scores (``score_norm``)."""
-    kind, weights, _ = _score_kind(cache, score, model)
-    _check_norm(cache, score, norm)
-    return _histogram(cache, kind, weights, windows, bins, rows, norm)
+    kind, weights, _ = score_kind(cache, score, model)
+    check_norm(cache, score, norm)
+    return histogram(cache, kind, weights, windows, bins, rows, norm)
 
 
-def _histogram(cache, kind, weights, windows, bins, rows=None, norm=None) -> np.ndarray:
+def check_windows(windows, bins: int):
+    """What one histogram launch can hold (csrc/verif.hip: the windows' counters live in LDS)."""
     if len(windows) > MAX_WINDOWS or len(windows) * 2 * (bins + 3) > LDS_WORDS:
         raise ValueError("at most %d windows and %d histogram words per launch" % (MAX_WINDOWS, LDS_WORDS))
-    rank, world = parallel.rank_world()
-    if rows is not None:
-        return _device_hist(cache, kind, weights, windows, bins, rows, norm).cpu().numpy()
-    h = _device_hist(cache, kind, weights, windows, bins, triangle_shards(cache.n, world)[rank], norm)
-    if world > 1:
-        import torch.distributed as dist
-        comm = h.to(parallel._comm_device())
-        dist.all_reduce(comm, op=dist.ReduceOp.SUM)
-        h = comm
-    return h.cpu().numpy()
+
+
+def histogram(cache, kind, weights, windows, bins, rows=None, norm=None) -> np.ndarray:
+    """``score_histogram`` for a kernel score kind and its weights (``score_kind``)."""
+    check_windows(windows, bins)
+    return triangle_sum(lambda r: _device_hist(cache, kind, weights, windows, bins, r, norm), cache.n, rows)
+
+
+def counts_at_threshold(hist_fn: Callable, t: float) -> Dict:
+    """Balanced accuracy, FAR, FRR and the trial counts at a fixed threshold t from any histogram source (``exact_sweep``): one
+    1-bin window with key_lo = key(t), whose under slot is exactly {s < t}.  A NaN t takes the last key: every number is below it."""
+    k = key_of(t) if not math.isnan(t) else KEY_SPACE - 1
+    h = hist_fn([(k, 31)], 1)[0]
+    nT, nN = int(h[0, :-1].sum()), int(h[1, :-1].sum())
+    far = float(h[1, 1]) / nN if nN else float("nan")
+    frr = float(nT - h[0, 1]) / nT if nT else float("nan")
+    return {"balanced_accuracy": 1.0 - (far + frr) / 2, "far": far, "frr": frr, "n_target": nT, "n_nontarget": nN,
+            "n_nan": int(h[0, -1] + h[1, -1])}
 
 
 # ---- exact metrics from cumulative counts ----------------------------------------------------------------------------------------
@@ -563,7 +579,7 @@ def sorted_metrics(scores, target) -> Dict:
 
 
 # ---- pass-1 bounds ---------------------------------------------------------------------------------------------------------------
-def _pass1_window(lo_val: float, hi_val: float, bins: int = PASS1_BINS) -> Tuple[int, int]:
+def pass1_window(lo_val: float, hi_val: float, bins: int = PASS1_BINS) -> Tuple[int, int]:
     """A window whose bins cover [lo_val, hi_val] (keys), aligned to its bin width."""
     klo, khi = key_of(lo_val), key_of(hi_val)
     sh = min(31, _ceil_log2(-(-(khi - klo + 1) // bins)))
@@ -574,7 +590,8 @@ def _pass1_window(lo_val: float, hi_val: float, bins: int = PASS1_BINS) -> Tuple
         sh += 1
 
 
-def _bounds(cache, kind) -> Tuple[float, float]:
+def bounds(cache, kind) -> Tuple[float, float]:
+    """Cheap bounds of every pair score of ``cache`` under an embedding score kind, from the largest row norm."""
     if kind == SCORES["cosine"]:
         return 0.0, 2.0
     norms = torch.linalg.vector_norm(cache.emb.double(), dim=1)
@@ -587,49 +604,57 @@ def _bounds(cache, kind) -> Tuple[float, float]:
     return -r * r, r * r   # dot product (and weighted_l1 below)
 
 
-def _sampled_window(cache, kind, weights, lo: float, hi: float, n_sample: int = 1 << 16, norm=None) -> Tuple[int, int]:
-    """Pass 1's window: the 1e-4 .. 1 - 1e-4 quantiles of the scores of a seeded sample of pairs (torch arithmetic: it only places the
-    window -- whatever falls outside lands in the under / over slots and the counts stay exact), clipped to the cheap bounds [lo, hi].
-    The bins then cover the bulk of the scores, not the key range of the bounds, and one zoom pass usually reaches single keys.  Under
-    torchrun rank 0's window is broadcast: every rank bins into the same window."""
-    rank, world = parallel.rank_world()
+def sample_scores(a: torch.Tensor, b: torch.Tensor, kind: int, weights=None) -> torch.Tensor:
+    """float64 scores of the sampled rows (a, b) under a kernel score kind (torch arithmetic: only a window's place depends on them)."""
+    a, b = a.double(), b.double()
+    if kind in (SCORES["euclidean"], VM_SCORE_NEG_EUCLIDEAN):
+        return torch.linalg.vector_norm(a - b, dim=1) * (1 if kind == SCORES["euclidean"] else -1)
+    if kind == SCORES["cosine"]:
+        return 1 - (a * b).sum(1) / (torch.linalg.vector_norm(a, dim=1) * torch.linalg.vector_norm(b, dim=1))
+    if kind == SCORES["dot_product"]:
+        return -(a * b).sum(1)
+    return ((a - b).abs() * weights.double()).sum(1)
+
+
+def place_window(sample_fn: Callable) -> Tuple[int, int]:
+    """Pass 1's window of any evaluator.  ``sample_fn()`` runs on rank 0 only and returns (lo, hi, sample): cheap bounds of every score,
+    and a float64 tensor of the scores of a seeded sample of trials (or None).  The window spans the 1e-4 .. 1 - 1e-4 quantiles of the
+    finite sampled scores, padded by 5 % and clipped to [lo, hi]; with 100 such scores or fewer, or nothing left after the clip, it
+    spans the bounds.  It only places the bins over the bulk of the scores, so that one zoom pass usually reaches single keys: whatever
+    falls outside lands in the under / over slots and the counts stay exact.  Under torchrun rank 0's window is broadcast."""
     win = torch.zeros(2, dtype=torch.int64)
-    if rank == 0:
-        win[0], win[1] = _pass1_window(lo, hi)
-        if cache.n >= 2:
-            g = torch.Generator().manual_seed(0)
-            i = torch.randint(0, cache.n, (n_sample,), generator=g)
-            j = (i + torch.randint(1, cache.n, (n_sample,), generator=g)) % cache.n
-            a = cache.emb[i.to(cache.emb.device)].double()
-            b = cache.emb[j.to(cache.emb.device)].double()
-            if kind in (SCORES["euclidean"], VM_SCORE_NEG_EUCLIDEAN):
-                sc = torch.linalg.vector_norm(a - b, dim=1) * (1 if kind == SCORES["euclidean"] else -1)
-            elif kind == SCORES["cosine"]:
-                sc = 1 - (a * b).sum(1) / (torch.linalg.vector_norm(a, dim=1) * torch.linalg.vector_norm(b, dim=1))
-            elif kind == SCORES["dot_product"]:
-                sc = -(a * b).sum(1)
-            else:
-                sc = ((a - b).abs() * weights.double()).sum(1)
-            if norm is not None:   # the sample's normalised scores (float64: only the window depends on them)
-                ii, jj = i.to(norm.mu.device), j.to(norm.mu.device)
-                mu, rs = norm.mu.double(), norm.rsig.double()
-                sc = 0.5 * ((sc - mu[ii]) * rs[ii] + (sc - mu[jj]) * rs[jj])
-            sc = sc[torch.isfinite(sc)].cpu().numpy()
-            if len(sc) > 100:
-                q0, q1 = np.quantile(sc, [1e-4, 1 - 1e-4])
-                pad = 0.05 * (q1 - q0) + 1e-6 * max(abs(q0), abs(q1)) + 1e-30
-                q0, q1 = max(lo, q0 - pad), min(hi, q1 + pad)
-                if q0 < q1:
-                    win[0], win[1] = _pass1_window(float(q0), float(q1))
-    if world > 1:
-        import torch.distributed as dist
-        comm = win.to(parallel._comm_device())
-        dist.all_reduce(comm, op=dist.ReduceOp.SUM)
-        win = comm.cpu()
+    if parallel.rank_world()[0] == 0:
+        lo, hi, sc = sample_fn()
+        win[0], win[1] = pass1_window(lo, hi)
+        sc = sc[torch.isfinite(sc)].cpu().numpy() if sc is not None else ()
+        if len(sc) > 100:
+            q0, q1 = np.quantile(sc, [1e-4, 1 - 1e-4])
+            pad = 0.05 * (q1 - q0) + 1e-6 * max(abs(q0), abs(q1)) + 1e-30
+            q0, q1 = max(lo, q0 - pad), min(hi, q1 + pad)
+            if q0 < q1:
+                win[0], win[1] = pass1_window(float(q0), float(q1))
+    win = parallel.sum_ranks(win).cpu()
     return int(win[0]), int(win[1])
 
 
-def _norm_bounds(norm: ScoreNorm, lo: float, hi: float) -> Tuple[float, float]:
+def sampled_window(cache, kind, weights, lo: float, hi: float, n_sample: int = 1 << 16, norm=None) -> Tuple[int, int]:
+    """``place_window`` for the pair trials of ``cache`` within the bounds [lo, hi]: a seeded sample of pairs, normalised with ``norm``."""
+    def sample():
+        if cache.n < 2:
+            return lo, hi, None
+        g = torch.Generator().manual_seed(0)
+        i = torch.randint(0, cache.n, (n_sample,), generator=g)
+        j = (i + torch.randint(1, cache.n, (n_sample,), generator=g)) % cache.n
+        sc = sample_scores(cache.emb[i.to(cache.emb.device)], cache.emb[j.to(cache.emb.device)], kind, weights)
+        if norm is not None:
+            ii, jj = i.to(norm.mu.device), j.to(norm.mu.device)
+            mu, rs = norm.mu.double(), norm.rsig.double()
+            sc = 0.5 * ((sc - mu[ii]) * rs[ii] + (sc - mu[jj]) * rs[jj])
+        return lo, hi, sc
+    return place_window(sample)
+
+
+def norm_bounds(norm: ScoreNorm, lo: float, hi: float) -> Tuple[float, float]:
     """Bounds of the normalised scores of raw scores in [lo, hi]: each half (s - mu_i) rsig_i lies in [(lo - mu_i) rsig_i, (hi - mu_i)
     rsig_i] (rsig >= 0); rows whose statistics are not finite are left out (their scores are NaN or infinite: the NaN / over slots)."""
     mu, rs = norm.mu.double(), norm.rsig.double()
@@ -654,22 +679,19 @@ def verification_metrics(cache, score: str = "euclidean", model=None, bins: int 
     ``dcf_points``: detection-cost points (P_target, C_miss, C_fa) -- adds ``dcf`` with the exact minimum cost of each (``exact_sweep``)."""
     if bins != PASS1_BINS:
         raise ValueError("pass 1 takes %d bins" % PASS1_BINS)
-    kind, weights, head = _score_kind(cache, score, model)
-    _check_norm(cache, score, norm)
+    kind, weights, head = score_kind(cache, score, model)
+    check_norm(cache, score, norm)
     if kind == SCORES["weighted_l1"]:
         wsum = float(weights.abs().double().sum().item())
         amax = float(cache.emb.abs().max().item()) if cache.n else 0.0
         lo, hi = -2 * amax * wsum * 1.001 - 1e-30, 2 * amax * wsum * 1.001 + 1e-30
     else:
-        lo, hi = _bounds(cache, kind)
+        lo, hi = bounds(cache, kind)
     if norm is not None:
-        lo, hi = _norm_bounds(norm, lo, hi)
-        out = exact_sweep(lambda wins, b: _histogram(cache, kind, weights, wins, b, norm=norm),
-                          _sampled_window(cache, kind, weights, lo, hi, norm=norm), dcf_points=dcf_points)
-        return out
-    out = exact_sweep(lambda wins, b: _histogram(cache, kind, weights, wins, b), _sampled_window(cache, kind, weights, lo, hi),
-                      dcf_points=dcf_points)
-    if head is not None:
+        lo, hi = norm_bounds(norm, lo, hi)
+    out = exact_sweep(lambda wins, b: histogram(cache, kind, weights, wins, b, norm=norm),
+                      sampled_window(cache, kind, weights, lo, hi, norm=norm), dcf_points=dcf_points)
+    if head is not None and norm is None:
         w, b = head
         out["eer_threshold_p"] = _head_p(out["eer_threshold"], w, b)
         out["best_threshold_p"] = _head_p(out["best_threshold"], w, b)
@@ -687,15 +709,9 @@ def _head_p(t: float, w: float, b: float) -> float:
 def accuracy_at_threshold(cache, t: float, score: str = "euclidean", model=None, norm: Optional[ScoreNorm] = None) -> Dict:
     """Balanced accuracy, FAR and FRR at a fixed threshold t (in score units; with ``norm``, in normalised units): one pass with key_lo =
     key(t), whose under slot is then exactly {s < t}."""
-    kind, weights, _ = _score_kind(cache, score, model)
-    _check_norm(cache, score, norm)
-    k = key_of(t) if not math.isnan(t) else KEY_SPACE - 1
-    h = _histogram(cache, kind, weights, [(k, 31)], 1, norm=norm)[0]
-    nT, nN = int(h[0, :-1].sum()), int(h[1, :-1].sum())
-    far = float(h[1, 1]) / nN if nN else float("nan")
-    frr = float(nT - h[0, 1]) / nT if nT else float("nan")
-    return {"balanced_accuracy": 1.0 - (far + frr) / 2, "far": far, "frr": frr, "n_target": nT, "n_nontarget": nN,
-            "n_nan": int(h[0, -1] + h[1, -1])}
+    kind, weights, _ = score_kind(cache, score, model)
+    check_norm(cache, score, norm)
+    return counts_at_threshold(lambda wins, b: histogram(cache, kind, weights, wins, b, norm=norm), t)
 
 
 def bayes_threshold(calibration, point) -> float:
