@@ -533,3 +533,34 @@ def test_spectrogram_encoder_api_and_full_size():
         assert np.array_equal(again.predict([x1, x2]), pr)
         with pytest.raises(NotImplementedError):
             nets["bf16"].save(os.path.join(d, "x.hdf5"))
+
+
+@pytest.mark.parametrize("dt", ["f16", "f32"])
+def test_spectrogram_model_calls_are_the_engines_bit_for_bit(dt):
+    """train_on_batch / test_on_batch / predict of a siamese net over the variant give exactly the loss, accuracy and predictions of
+    siamese_train_step / siamese_eval / siamese_predict on an engine built directly with the same seed: the model adds nothing to the
+    arithmetic, and the shared siamese evaluation, prediction, label and optimizer code serves the 2-D engine as it does the 1-D one."""
+    from voicemap_amd.keras_like import Adam
+    from voicemap_amd.models import build_siamese_net, get_spectrogram_convolutional_encoder
+    from voicemap_amd.spectro_engine import HipSpectrogramEncoderEngine
+    from voicemap_amd.utils import contrastive_loss
+    _, raw_len, F_, E = SMALL
+    pairs = 2
+    x1, x2 = _clips(pairs, raw_len, 31)[:, :, None], _clips(pairs, raw_len, 32)[:, :, None]
+    y = np.array([[0.0], [1.0]])
+    torch.manual_seed(3)
+    seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())   # what an engine built without a seed draws first
+    torch.manual_seed(3)
+    net = build_siamese_net(get_spectrogram_convolutional_encoder(F_, E, (raw_len, 1), dropout=0.0, dtype=dt), (raw_len, 1))
+    net.compile(loss=contrastive_loss, optimizer=Adam(clipnorm=1.0), metrics=["accuracy"])
+    eng = HipSpectrogramEncoderEngine(F_, E, dropout=0.0, head="uniform_euclidean", dtype=dt, seed=seed)
+    Adam(clipnorm=1.0).apply_to(eng)
+    for _ in range(2):
+        got = net.train_on_batch([x1, x2], y)
+        la = eng.siamese_train_step(x1, x2, y, loss="contrastive")["loss_acc"].cpu().numpy()
+        assert net.engine.seed == seed and got == (float(la[0]), float(la[1])) and np.isfinite(got[0])
+    la = eng.siamese_eval(x1, x2, y, loss="contrastive")["loss_acc"].cpu().numpy()
+    assert net.test_on_batch([x1, x2], y) == (float(la[0]), float(la[1]))
+    pred = net.predict([x1, x2])
+    assert pred.shape == (pairs, 1) and np.array_equal(pred, eng.siamese_predict(x1, x2).cpu().numpy())
+    assert all(np.array_equal(a, b) for a, b in zip(net.engine.get_params().values(), eng.get_params().values()))

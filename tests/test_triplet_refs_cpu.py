@@ -222,8 +222,22 @@ def test_triplet_loss_compile_and_config_round_trip():
 
 
 def test_the_2d_variant_refuses_the_loss():
-    """As for the prototypical loss: the spectrogram engine has no triplet step (its data paths are the raw-window ones)."""
+    """As for the prototypical loss: the spectrogram engine has no triplet step (its data paths are the raw-window ones).  It does
+    not carry the 1-D engine's other entry points either -- it says what it serves -- and the model refuses the two losses before an
+    engine is built, when training and when evaluating."""
+    from voicemap_amd import models, utils
+    from voicemap_amd.keras_like import Adam
     from voicemap_amd.spectro_engine import HipSpectrogramEncoderEngine as S
-    for name in ("triplet_train_step", "triplet_train_step_from_offsets", "triplet_eval"):
-        with pytest.raises(NotImplementedError):
-            getattr(S, name)(None, np.zeros((4, 100, 1)), np.zeros(4))
+    for name in ("triplet_train_step", "triplet_train_step_from_offsets", "triplet_eval",
+                 "prototypical_train_step", "prototypical_train_step_from_offsets", "prototypical_eval",
+                 "margin_train_step", "margin_eval", "classifier_train_step",
+                 "embed_from_offsets", "embed_varlen", "load_preprocessed", "preprocess", "_train_step", "_offsets_step"):
+        assert not hasattr(S, name), name
+    assert S.losses == {"siamese"}
+    for loss in (utils.TripletLoss(), utils.PrototypicalLoss(2, 1)):
+        enc = models.get_spectrogram_convolutional_encoder(8, 16)
+        enc.compile(loss=loss, optimizer=Adam())
+        for call in (enc.train_on_batch, enc.test_on_batch):
+            with pytest.raises(NotImplementedError, match="implemented for the 1-D encoder"):
+                call(np.zeros((4, 100, 1), np.float32), np.zeros(4))
+        assert enc.engine is None

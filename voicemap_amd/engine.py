@@ -10,131 +10,18 @@ from __future__ import annotations
 
 import ctypes
 import functools
-import math
-from collections import OrderedDict
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, staging
-from ._lib import VM_BF16, VM_F16, VM_F32, VM_F32S
-from .program import DynF, DynI, Program, ProgramStore
+from . import staging
+from ._lib import VM_F16
+from .engine_core import (DEFAULT_DTYPE, DEFAULT_F16_LOSS_SCALE, HEADS, LOSSES, EngineCore, FlatState, _DT, _TIMED_AS, _TORCH_DT,  # noqa: F401
+                          _align, _p, _raw_stream, _shared_stream, flat_layout)   # (the names this module has always exported)
+from .program import Program, ProgramStore
 
-# "f32s": fp32 storage, split-bf16 products in the k=3 convolution GEMMs (VM_F32S in include/voicemap_hip.h)
-# "f16": IEEE half storage -- the bf16 kernels with 11 instead of 8 significand bits per stored value, loss-scaled gradients
-_DT = {"f32": VM_F32, "fp32": VM_F32, "float32": VM_F32, "bf16": VM_BF16, "bfloat16": VM_BF16, "f32s": VM_F32S,
-       "f16": VM_F16, "fp16": VM_F16, "float16": VM_F16}
-_TORCH_DT = {VM_F32: torch.float32, VM_BF16: torch.bfloat16, VM_F32S: torch.float32, VM_F16: torch.float16}
-DEFAULT_F16_LOSS_SCALE = 4096.0
-# the drop-in surface's default storage mode: the 16-bit one whose embeddings stay within 1e-3 of the reference arithmetic (DESIGN.md
-# 4.6b); "bf16" -- BASELINE.json's word for config 2 -- is the same kernels with 8 significand bits (2 % faster, 6e-3)
-DEFAULT_DTYPE = "f16"
-HEADS = {"uniform_euclidean": _lib.VM_HEAD_UNIFORM_EUCLIDEAN, "weighted_l1": _lib.VM_HEAD_WEIGHTED_L1}
-LOSSES = {"contrastive": _lib.VM_LOSS_CONTRASTIVE, "contrastive_loss": _lib.VM_LOSS_CONTRASTIVE,
-          "bce": _lib.VM_LOSS_BCE, "binary_crossentropy": _lib.VM_LOSS_BCE}
 CONV1_HALO_L, CONV1_HALO = 15, 31  # TF SAME padding of the k=32 first conv: 15 left / 16 right
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _align(n: int, a: int = 64) -> int:
-    return (n + a - 1) // a * a
-
-
-def flat_layout(blocks: Sequence[Tuple[int, int, int]], embedding_dimension: int, head: Optional[str], num_classes: int = 0):
-    """Layout of the flat fp32 buffers (parameters / gradients / Adam slots share it): tensors in Keras ``trainable_weights``
-    order, each starting on a 64-element boundary, and the non-trainable BatchNorm moving statistics in a second buffer.
-    Returns (spec, offsets {name: (offset, size, shape)}, n_flat, nt_off {name: (offset, size)}, n_nt).  Pure host code:
-    parallel.py's collectives and the CPU tests use the same layout the engine does."""
-    spec: List[Tuple[str, Tuple[int, ...]]] = []
-    for i, (k, c, _) in enumerate(blocks):
-        cin = 1 if i == 0 else blocks[i - 1][1]
-        spec += [(f"conv{i+1}.kernel", (k, cin, c)), (f"conv{i+1}.bias", (c,)),
-                 (f"bn{i+1}.gamma", (c,)), (f"bn{i+1}.beta", (c,))]
-    cl = blocks[-1][1]
-    E = int(embedding_dimension)
-    spec += [("dense.kernel", (cl, E)), ("dense.bias", (E,))]
-    if head == "uniform_euclidean":
-        spec += [("head.kernel", (1, 1)), ("head.bias", (1,))]
-    elif head == "weighted_l1":
-        spec += [("head.kernel", (E, 1)), ("head.bias", (1,))]
-    elif head == "classifier":
-        spec += [("head.kernel", (E, num_classes)), ("head.bias", (num_classes,))]
-    elif head is not None:
-        raise NotImplementedError(head)
-    offsets: Dict[str, Tuple[int, int, Tuple[int, ...]]] = OrderedDict()
-    off = 0
-    for name, shape in spec:
-        n = int(np.prod(shape))
-        offsets[name] = (off, n, shape)
-        off += _align(n)
-    n_flat = off
-    nt_off: Dict[str, Tuple[int, int]] = OrderedDict()
-    off = 0
-    for i, (_, c, _) in enumerate(blocks):
-        nt_off[f"bn{i+1}.moving_mean"] = (off, c)
-        off += _align(c)
-        nt_off[f"bn{i+1}.moving_variance"] = (off, c)
-        off += _align(c)
-    return spec, offsets, n_flat, nt_off, off
-
-
-class FlatState:
-    """The flat buffers themselves (P parameters, G gradients, M / V Adam slots, NT moving statistics) on ``device``."""
-
-    def __init__(self, blocks, embedding_dimension, head, num_classes, device):
-        self.spec, self.offsets, self.n_flat, self.nt_off, n_nt = flat_layout(blocks, embedding_dimension, head, num_classes)
-        self.n_params = sum(n for _, n, _ in self.offsets.values())
-        self.P = torch.zeros(self.n_flat, dtype=torch.float32, device=device)
-        self.G = torch.zeros_like(self.P)
-        self.M = torch.zeros_like(self.P)
-        self.V = torch.zeros_like(self.P)
-        self.NT = torch.zeros(n_nt, dtype=torch.float32, device=device)
-        self.iterations = 0
-
-    def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if name in self.nt_off:
-            o, n = self.nt_off[name]
-            return self.NT[o:o + n]
-        o, n, shape = self.offsets[name]
-        return (self.P if buf is None else buf)[o:o + n].view(shape)
-
-    def refresh_weights(self):  # the engine re-derives its GEMM-layout weight copies here
-        pass
-
-
-# entry points whose launches bench.py books under another name: (name, index of an extra argument to drop so that the leading
-# arguments line up with that entry point's)
-# entry points timed under the name (and argument positions) of the plain form: name -> (plain name, argument indices to drop)
-_TIMED_AS = {"vm_conv_dgrad_bnred": ("vm_conv_dgrad", ()), "vm_conv_fwd_e": ("vm_conv_fwd", (3,)),
-             "vm_conv_fwd_fold": ("vm_conv_fwd", (3, 4, 6, 15)), "vm_conv_wgrad_fold": ("vm_conv_wgrad", (3,)),
-             "vm_bn_pool_bwd_apply_pairs": ("vm_bn_pool_bwd_apply", (1,))}
-
-
-try:
-    _raw_stream = torch._C._cuda_getCurrentRawStream
-except AttributeError:   # older torch: the documented way
-    def _raw_stream(index):
-        return torch.cuda.current_stream(index).cuda_stream
-
-
-_SHARED_STREAMS: Dict[tuple, "torch.cuda.Stream"] = {}
-
-
-def _shared_stream(device: torch.device, role: str) -> "torch.cuda.Stream":
-    """The process's ONE stream per (device, role) -- every engine's tower / side / misc stream.  The runtime multiplexes streams onto a
-    few hardware queues (four by default): with three private streams per engine, the streams of the fourth and sixth engine of a
-    process landed on shared queues and their three-stream step ran 7.5 % slower than the first engine's (2.80 against 2.60 ms, every
-    launch as fast as before when run serially: tools/probe/placement_spread.py).  Engines of one process enqueue one after the other,
-    so sharing the streams costs them nothing."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    st = _SHARED_STREAMS.get((idx, role))
-    if st is None:
-        st = _SHARED_STREAMS[(idx, role)] = torch.cuda.Stream(device=device)
-    return st
 
 
 class StepInput(NamedTuple):
@@ -154,7 +41,7 @@ class StepInput(NamedTuple):
         return (self.kind, self.tensor.dtype, shape, self.downsampling, self.whitening)
 
 
-class HipEncoderEngine:
+class HipEncoderEngine(EngineCore):
     """The voicemap encoder (voicemap/models.py:6-41) + optional head on one MI355X.
 
     blocks: [(kernel_size, channels, pool)] -- first block must be (32, F, p) on a 1-channel waveform, the others
@@ -162,56 +49,27 @@ class HipEncoderEngine:
     'classifier'.  dtype: storage type of activations / GEMM operands: 'bf16', 'f16' (half, loss-scaled), 'f32' (fp32 MFMAs) or
     'f32s' (fp32 storage, split-bf16 products).
     """
-
-    # defaults for engines that borrow methods without running this __init__ (spectro_engine.py): no recording, no stream stack
-    _rec = None
-    _stream_stack = ()
-    replay = False
-    native_replay = True   # a recorded step is replayed by the library's own runner (vm_program_run) instead of a Python loop of ctypes calls
-    fused_tail = False
-    _packed_weights = False
+    losses = frozenset({"siamese", "classifier", "prototypical", "triplet", "margin"})
+    resident_input = True
 
     def __init__(self, blocks: Sequence[Tuple[int, int, int]], embedding_dimension: int, dropout: float = 0.05,
                  head: Optional[str] = None, num_classes: int = 0, dtype: str = DEFAULT_DTYPE, device="cuda",
                  bn_eps: float = 1e-3, bn_momentum: float = 0.99, unbiased_moving_variance: bool = True,
                  seed: Optional[int] = None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("HipEncoderEngine needs a GPU (torch.cuda.is_available() is False); there is no CPU path")
-        self.lib = _lib.lib()
-        self.timed = {}
-        self._call("vm_check_device")
-        self.blocks = [tuple(int(v) for v in b) for b in blocks]
-        assert self.blocks[0][0] == 32, "first block must be the k=32 waveform conv"
-        assert all(b[0] == 3 for b in self.blocks[1:]), "blocks 2.. must be k=3"
-        assert all(b[1] % 8 == 0 for b in self.blocks), "channel counts must be multiples of 8"
-        self.E = int(embedding_dimension)
-        self.dropout = float(dropout)
-        self.head = head
-        self.num_classes = int(num_classes)
-        self.dtype = _DT[dtype]
-        self.tdt = _TORCH_DT[self.dtype]
-        self.device = torch.device(device)
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self._views = {}
-        self.bn_eps, self.bn_momentum = float(bn_eps), float(bn_momentum)
-        self.unbiased = bool(unbiased_moving_variance)
-        self.nb = len(self.blocks)
-        # bf16 storage: block 1 runs the fused MFMA kernels (no full-resolution z1 / du1 in HBM); fp32 storage keeps
-        # the exact fp32 vector-ALU path
-        self.is16 = self.dtype in (VM_BF16, VM_F16)
-        self.fuse_block1 = self.is16 and self.blocks[0][2] in (2, 4)
-        self._init_loss_scale()
-
-        # ---- flat parameter store, Keras trainable_weights order -------------------------------------
+        self._require_gpu()
+        blocks = [tuple(int(v) for v in b) for b in blocks]
+        assert blocks[0][0] == 32, "first block must be the k=32 waveform conv"
+        assert all(b[0] == 3 for b in blocks[1:]), "blocks 2.. must be k=3"
+        assert all(b[1] % 8 == 0 for b in blocks), "channel counts must be multiples of 8"
         if head not in (None, "uniform_euclidean", "weighted_l1", "classifier"):
             raise NotImplementedError(head)
         assert head != "classifier" or num_classes > 0
-        st = FlatState(self.blocks, self.E, head, self.num_classes, self.device)
-        self.spec, self.offsets, self.n_flat, self.n_params = st.spec, st.offsets, st.n_flat, st.n_params
-        self.P, self.G, self.M, self.V = st.P, st.G, st.M, st.V
-        self.nt_off, self.NT = st.nt_off, st.NT
+        super().__init__(blocks, embedding_dimension, dropout, head, num_classes, dtype, device, bn_eps, bn_momentum,
+                         unbiased_moving_variance, FlatState(blocks, embedding_dimension, head, int(num_classes), torch.device(device)))
         dev = self.device
-        self._init_zero_debias()
+        # bf16 storage: block 1 runs the fused MFMA kernels (no full-resolution z1 / du1 in HBM); fp32 storage keeps
+        # the exact fp32 vector-ALU path
+        self.fuse_block1 = self.is16 and self.blocks[0][2] in (2, 4)
         self.wf: Dict[int, torch.Tensor] = {}
         self.wd: Dict[int, torch.Tensor] = {}
         self.wt: Dict[int, torch.Tensor] = {}   # fp32 kernels in wf's layout: the input of the per-step BatchNorm fold (16-bit storage)
@@ -232,17 +90,6 @@ class HipEncoderEngine:
                 self.wfp[i] = torch.empty(cout * 3 * cin, dtype=self.tdt, device=dev)
             if self.is16 and self.lib.query("vm_pack_nt_weights_supported", cin, cout, self.dtype):
                 self.wdp[i] = torch.empty(cin * 3 * cout, dtype=self.tdt, device=dev)
-        self._sq_ws = torch.empty(self.lib.query("vm_sqnorm_workspace_bytes", self.n_flat) // 8, dtype=torch.float64, device=dev)
-        self._sqnorm = torch.zeros(1, dtype=torch.float32, device=dev)
-        # Adam(clipnorm=1.) defaults of the reference scripts
-        self.lr, self.beta_1, self.beta_2, self.adam_eps, self.decay, self.clipnorm = 1e-3, 0.9, 0.999, 1e-7, 0.0, 1.0
-        self.iterations = 0
-        self.last_infer_l0 = 0
-        # weight-gradient GEMMs only feed the optimizer: they run on a side stream, concurrently with the dgrad -> BN-backward
-        # chain of the earlier blocks (the critical path of backward).  Measured +4.5 % step throughput at cfg-A (4.29 -> 4.11
-        # ms); the results are bit-identical either way (tests/test_gpu_e2e.py).  Per-kernel timings of the backward pass are
-        # only attributable with it off (bench.py --breakdown / --no-overlap-wgrad).
-        self.overlap_wgrad = True
         # BN-backward reduce of blocks 2..n-1 from the pooled forward output instead of z (vm_bn_pool_bwd_reduce_pooled): -0.34 GB
         # of reads per step at cfg-A.  Changes the two sums by the storage rounding of the pooled tensor (1e-3 relative in
         # bf16), so it is on for bf16 storage (the throughput mode) and off for fp32 (the exact-parity mode).
@@ -300,9 +147,7 @@ class HipEncoderEngine:
         # parameter gradients on the side stream (vm_tail_param_grads) instead of six; bit-identical (tests/test_gpu_kernels.py)
         self.fused_tail = True
         self._seg_rows = self.lib.query("vm_bn_part_rows")
-        self.defer_head_reduce = True   # backward() enqueues the head's sums on the side stream (engines that borrow siamese_head: no)
-        self.grad_sync = None       # callable(flat_grad_tensor) for data parallelism (parallel.py)
-        self.grad_prescale = 1.0
+        self.defer_head_reduce = True   # backward() enqueues the head's sums on the side stream
         # SyncBN (optional; off by default as in the reference, whose BatchNormalization is per process): under data
         # parallelism the batch statistics and the two BatchNorm-backward means are taken over the GLOBAL batch -- one small all-reduce
         # per BatchNorm and direction (8 + 8 per siamese step) -- which makes N ranks x B pairs the same arithmetic as one device with
@@ -310,69 +155,13 @@ class HipEncoderEngine:
         self.sync_bn = False
         self.sync_bn_world = 1
         self._sync_bufs = {}
-        self._plans: Dict[Tuple, dict] = {}
         # recorded training steps (program.py): on by default; a configuration is recorded on its second sighting and replayed from
         # the third on.  Off: data parallelism (the gradient hook runs torch.distributed calls), SyncBN, per-kernel timing (bench.py)
         self.replay = True
-        self._rec: Optional[Program] = None   # the step being recorded
+        self.native_replay = True   # ... by the library's own runner (vm_program_run) instead of a Python loop of ctypes calls
         self._programs = ProgramStore(self.lib, functools.partial(torch.cuda.synchronize, self.device))
-        self._stream_stack: List[int] = []
         self._drop_bufs: Dict[int, tuple] = {}
         self.init_params(seed)
-
-    def _init_loss_scale(self):
-        """f16 storage: activation gradients of this net are 1e-5 .. 1e-8 per element -- under half's normal range (6e-5) -- so the
-        loss gradient is multiplied by loss_scale in the head kernel (every kernel between the head and the optimizer is linear in
-        it), the flat gradient buffer G then holds loss_scale x the gradients and the optimizer kernel divides it out again
-        (grad_prescale) before the clip; a step whose scaled gradients overflowed (non-finite norm) is skipped on the device and
-        counted in ``skipped_steps()``.  1.0 for the other storage types: their arithmetic is untouched."""
-        self.loss_scaled = (self.dtype == VM_F16)   # the switch for scaling / skipping -- NOT the scale's value (ADVICE r3)
-        self.loss_scale = DEFAULT_F16_LOSS_SCALE if self.loss_scaled else 1.0
-        self._skipped = torch.zeros(1, dtype=torch.int32, device=self.device)   # running count, incremented by the optimizer kernel
-        self._skip_seen, self._clean_checks = 0, 0
-        # dynamic scale driven from optimizer_step (every train_on_batch loop gets it, not only fit_generator): every
-        # ``scale_poll_every`` steps the count is copied to pinned memory behind the step; ``scale_poll_lag`` steps later -- a fixed
-        # lag, so data-parallel replicas change their scale at the same step -- it is read (the copy is long done: no drain)
-        self.scale_poll_every, self.scale_poll_lag = 16, 8
-        self.scale_grow_after, self.scale_max, self.scale_min = 2000, 2.0 ** 24, 1.0
-        # ... and the scale follows the gradient's SIZE, not only its overflows: the same poll reads the squared norm of the scaled
-        # gradient buffer the optimizer kernel leaves behind; under ``scale_norm_low`` (a gradient of norm 1e-6 -- a net whose pairs
-        # sit past the contrastive margin -- leaves activation gradients of 1e-10 that 4096 does not lift into half's range: measured
-        # 58 % error on the first layer's gradient, 5 % with a scale of 2^20) the scale is multiplied by 8 per poll.  A scaled norm of
-        # 2^6 keeps every element 2^10 under half's maximum, so the growth itself cannot overflow the parameter gradients.
-        self.scale_norm_low = 64.0
-        self.scale_norm_hold_polls, self._norm_growth_hold = 8, 0   # polls without a norm-driven lift after a skipped step
-        self._opt_calls, self._clean_steps, self._poll = 0, 0, None
-        self._skip_host = torch.zeros(1, dtype=torch.int32).pin_memory() if self.loss_scaled else None
-        self._norm_host = torch.zeros(1, dtype=torch.float32).pin_memory() if self.loss_scaled else None
-
-    def _init_zero_debias(self):
-        """Keras 2.2.2 BatchNormalization updates its moving statistics with TF 1.10's assign_moving_average(zero_debias=True)
-        (keras/backend/tensorflow_backend.py moving_average_update [3P]): per encoder call (tower) and statistic a zero-initialised
-        "biased" accumulator and a step counter, moving = biased / (1 - momentum^step).  ZD holds the accumulators of every
-        BatchNorm layer as (2 towers, 2 statistics, C) blocks; they are NOT Keras weights (a Keras checkpoint does not carry them:
-        after load_model the first update overwrites the moving statistics with the de-biased batch statistics, here as there).
-        ``bn_zero_debias = False`` gives the plain exponential average."""
-        self.bn_zero_debias = True
-        self.zd_off = OrderedDict()
-        off = 0
-        for i, (_, c, _) in enumerate(self.blocks):
-            self.zd_off[i] = (off, c)
-            off += 4 * _align(c)
-        self.ZD = torch.zeros(off, dtype=torch.float32, device=self.device)
-        self.bn_steps = 0
-
-    def _zd(self, i: int):
-        """(pointer to the block's accumulators, 1 / (1 - momentum^t)) for the training forward in progress, or (None, 0)."""
-        if not self.bn_zero_debias:
-            return None, 0.0
-        o, c = self.zd_off[i]
-        return self.ZD[o:o + 4 * c].data_ptr(), 1.0 / (1.0 - self.bn_momentum ** self._bn_t)
-
-    # ------------------------------------------------------------------------------------------------
-    def stream(self):
-        # the raw HIP stream of torch's current stream (asked ~25 times per step; torch.cuda.current_stream() costs 8 us a call)
-        return self._stream_stack[-1] if self._stream_stack else _raw_stream(self._dev_index)
 
     def _sync_rows(self, key, a_ptr, b_ptr, rows_per_tower, ntw, c, row_stride, cr_ws, st):
         """SyncBN: two partial-sum tensors of ``rows_per_tower`` rows per tower -> one row per tower (vm_colsum), summed over the ranks
@@ -405,70 +194,6 @@ class HipEncoderEngine:
         self._call("vm_bn_bwd_finalize", ga, gb, ntw, 1, c, count * self.sync_bn_world, c1, c2, scratch[0].data_ptr(), scratch[1].data_ptr(),
                    cr_ws, st)
 
-    def _call(self, name, *args):
-        """Enqueue one C-ABI entry point; entry points listed in ``self.timed`` are bracketed by HIP events on the
-        launch stream (bench.py uses this for the per-kernel roofline figure)."""
-        as_name, drop = _TIMED_AS.get(name, (name, ()))
-        rec = self.timed.get(as_name) if self.timed else None
-        if rec is None:
-            self.lib.call(name, *args)
-            if self._rec is not None:
-                self._rec.call(getattr(self.lib.cdll, name), name, args)
-            return
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        self.lib.call(name, *args)
-        e1.record()
-        rec.append((e0, e1, tuple(a for k, a in enumerate(args) if k not in drop) + ((name,) if as_name != name else ())))
-
-    # ---- stream hand-overs: through these, so that a recorded step (program.py) carries them ----------------------------------
-    def _dyn(self, key, value):
-        """Mark a C-ABI argument whose value changes from step to step (None stays None: its presence is part of the configuration)."""
-        if self._rec is None or value is None:
-            return value
-        return DynF(value, key) if isinstance(value, float) else DynI(value, key)
-
-    class _On:
-        def __init__(self, eng, stream):
-            self.eng, self.stream, self.ctx = eng, stream, torch.cuda.stream(stream)
-
-        def __enter__(self):
-            self.ctx.__enter__()
-            self.eng._stream_stack.append(self.stream.cuda_stream)
-
-        def __exit__(self, *exc):
-            self.eng._stream_stack.pop()
-            return self.ctx.__exit__(*exc)
-
-    def _on(self, stream):
-        """``with torch.cuda.stream(stream)`` + the raw handle for stream() (no torch lookups inside)."""
-        return HipEncoderEngine._On(self, stream)
-
-    def _record(self, ev):
-        """ev.record() on the current stream."""
-        ev.record()
-        if self._rec is not None:
-            self._rec.record(id(ev), self.stream())
-
-    def _wait(self, stream, ev):
-        """stream.wait_event(ev)"""
-        stream.wait_event(ev)
-        if self._rec is not None:
-            self._rec.wait(stream.cuda_stream, id(ev))
-
-    def _join(self, waiter, waited):
-        """waiter.wait_stream(waited): everything enqueued on ``waited`` so far precedes what ``waiter`` gets from here on."""
-        waiter.wait_stream(waited)
-        if self._rec is not None:
-            self._rec.join(waiter.cuda_stream, waited.cuda_stream)
-
-    def _host_call(self, fn):
-        """A step's host-side call that is not a C-ABI entry point (torch.distributed collectives): run now and, in a step being
-        recorded, kept in the program at this position -- a replay calls it again between the same launches."""
-        fn()
-        if self._rec is not None:
-            self._rec.host_call(fn)
-
     def _begin_grad_tail(self, pl: dict):
         """Data parallelism: every gradient of G[conv2.kernel:] that the main stream writes is enqueued -- hand that range to the
         gradient hook's early collective (parallel.GradAllReduce.begin_tail), ordered behind the main stream's position and the side
@@ -485,167 +210,6 @@ class HipEncoderEngine:
         self._wait(self.side_stream, pl["sync_ev"])
         self._host_call(lambda: gs.ordered_begin(self))
 
-    def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
-        # (memoised per (name, buffer): a training step asks ~70 times, and at small batches the step is bound by the host)
-        nt = name in self.nt_off
-        base = self.NT if nt else (self.P if buf is None else buf)
-        key = (name, None if (nt or buf is None) else id(buf))
-        v = self._views.get(key)
-        if v is not None and v[0] is base:
-            return v[1]
-        if nt:
-            o, n = self.nt_off[name]
-            out = self.NT[o:o + n]
-        else:
-            o, n, shape = self.offsets[name]
-            out = base[o:o + n].view(shape)
-        self._views[key] = (base, out)
-        return out
-
-    def init_params(self, seed: Optional[int] = None):
-        """Keras default initialisers (glorot_uniform kernels, zero biases, gamma 1, beta 0, moving 0 / 1)."""
-        if seed is None:
-            # like Keras' unseeded initialisers: a fresh draw per model, reproducible through torch.manual_seed
-            # (experiments/_common.seed_everything sets it)
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-        self.seed = int(seed)
-        g = torch.Generator().manual_seed(self.seed)
-        # SpatialDropout1D masks come from an engine-owned generator: reproducible under the same seed, decorrelated across
-        # data-parallel ranks (every rank holds the same weights but must drop different channels)
-        import os as _os
-        self._drop_gen = torch.Generator(device=self.device)
-        self._drop_gen.manual_seed(self.seed * 1000003 + 7919 * (int(_os.environ.get("RANK", "0")) + 1))
-        self.P.zero_()
-        for name, (o, n, shape) in self.offsets.items():
-            if name.endswith(".kernel"):
-                if len(shape) == 3:
-                    fan_in, fan_out = shape[0] * shape[1], shape[0] * shape[2]
-                else:
-                    fan_in, fan_out = shape
-                lim = math.sqrt(6.0 / (fan_in + fan_out))
-                w = (torch.rand(shape, generator=g, dtype=torch.float64) * 2 - 1) * lim
-                self.P[o:o + n] = w.flatten().to(torch.float32).to(self.device)
-            elif name.endswith(".gamma"):
-                self.P[o:o + n] = 1.0
-        for name, (o, n) in self.nt_off.items():
-            self.NT[o:o + n] = 1.0 if name.endswith("moving_variance") else 0.0
-        self.M.zero_()
-        self.V.zero_()
-        self.iterations = 0
-        if hasattr(self, "ZD"):
-            self.ZD.zero_()
-            self.bn_steps = 0
-        self.refresh_weights()
-
-    def set_params(self, params: Dict[str, "np.ndarray"]):
-        for name, val in params.items():
-            t = torch.as_tensor(np.asarray(val, dtype=np.float32)).to(self.device)
-            v = self.view(name)
-            v.copy_(t.reshape(v.shape))
-        self.refresh_weights()
-
-    def get_params(self) -> "OrderedDict[str, np.ndarray]":
-        out = OrderedDict()
-        for name in list(self.offsets) + list(self.nt_off):
-            out[name] = self.view(name).detach().cpu().numpy().copy()
-        return out
-
-    def get_grads(self) -> "OrderedDict[str, np.ndarray]":
-        """The gradients of the last backward pass (G holds loss_scale x them with f16 storage: divided out here)."""
-        inv = 1.0 / float(self.loss_scale)
-        return OrderedDict((name, self.view(name, self.G).detach().cpu().numpy().copy() * np.float32(inv)) for name in self.offsets)
-
-    def skipped_steps(self) -> int:
-        """Optimizer steps skipped because the loss-scaled gradients were not finite (f16 storage only; synchronises)."""
-        return int(self._skipped.item())
-
-    def _account_skips(self, total: int) -> int:
-        """``total`` skipped steps so far: the new ones are taken off ``iterations`` again (a skipped step is not an Adam step: its
-        bias correction and lr decay must not advance) and reported once."""
-        # two readers feed this (the lagged pinned copy of _poll_loss_scale and the live counter of adjust_loss_scale /
-        # skipped_steps): a stale total must neither move the watermark backwards nor count a step twice (ADVICE r4)
-        new = max(0, total - self._skip_seen)
-        self._skip_seen = max(self._skip_seen, total)
-        if new > 0:
-            self.iterations = max(0, self.iterations - new)
-            import warnings
-            warnings.warn("f16 storage: %d optimizer step(s) skipped (non-finite loss-scaled gradients, scale %g); %d in total"
-                          % (new, self.loss_scale, total), RuntimeWarning, stacklevel=3)
-        return new
-
-    def adjust_loss_scale(self, grow_after: int = 4, max_scale: float = 65536.0) -> float:
-        """Dynamic loss scaling at the caller's cadence (one device read per call; ``optimizer_step`` does the same on its own
-        without a read on the critical path, see ``_poll_loss_scale``): steps were skipped since the last look -> halve the scale
-        once per skipped step (at most 2^-4); none for ``grow_after`` calls in a row -> double it.  No-op for the storage types
-        that do not scale.  The scale may reach ``scale_min`` (1.0) and grows back from there."""
-        if not self.loss_scaled:
-            return 1.0
-        new = self._account_skips(self.skipped_steps())
-        self._poll = None   # a copy in flight predates this read: consumed here, not a second time 8 steps later
-        if new > 0:
-            self.loss_scale = max(self.loss_scale / float(2 ** min(new, 4)), self.scale_min)
-            self._clean_checks = self._clean_steps = 0
-            self._norm_growth_hold = self.scale_norm_hold_polls
-        else:
-            self._clean_checks += 1
-            if self._clean_checks >= grow_after:
-                self.loss_scale = min(self.loss_scale * 2.0, max_scale)
-                self._clean_checks = 0
-        return self.loss_scale
-
-    def calibrate_loss_scale(self, run_backward, max_rounds: int = 8) -> float:
-        """The norm-driven part of the loss-scale search, synchronously: ``run_backward()`` runs one forward + backward (no update)
-        and leaves the scaled gradient in G; while its norm (as Adam will see it after grad_prescale) is under ``scale_norm_low`` the
-        scale is multiplied by 8 -- what ``_poll_loss_scale`` does every ``scale_poll_every`` steps of a training loop -- and halved
-        on an overflow.  For callers that take ONE step from a cold start (tests, a first evaluation of gradients)."""
-        if not self.loss_scaled:
-            return 1.0
-        for _ in range(max_rounds):
-            run_backward()
-            g = float(self.G.double().norm().item()) * float(self.grad_prescale)
-            if not math.isfinite(g):
-                self.loss_scale = max(self.loss_scale / 2.0, self.scale_min)
-            elif 0.0 < g < self.scale_norm_low and self.loss_scale < self.scale_max:
-                self.loss_scale = min(self.loss_scale * 8.0, self.scale_max)
-            else:
-                break
-        return self.loss_scale
-
-    def _poll_loss_scale(self):
-        """Called once per optimizer step (f16 storage).  Step k with k % scale_poll_every == 0 enqueues a copy of the device's skip
-        count to pinned memory; step k + scale_poll_lag consumes it."""
-        k = self._opt_calls
-        self._opt_calls += 1
-        if self._poll is not None and k >= self._poll[0] + self.scale_poll_lag:
-            k0, ev = self._poll
-            self._poll = None
-            ev.synchronize()   # enqueued scale_poll_lag steps ago
-            new = self._account_skips(int(self._skip_host[0]))
-            sq = float(self._norm_host[0])   # sum of squares of the scaled gradient buffer at the polled step (inf / nan: a skipped one)
-            # G holds the SUM over data-parallel ranks; grad_prescale (1 / world) is applied in the clip: compare what Adam sees
-            sq *= float(getattr(self, "grad_prescale", 1.0)) ** 2
-            if new > 0:
-                self.loss_scale = max(self.loss_scale / float(2 ** min(new, 4)), self.scale_min)
-                self._clean_steps = 0
-                self._norm_growth_hold = self.scale_norm_hold_polls   # no x8 lifts right after an overflow (limit cycle, ADVICE r4)
-            elif (math.isfinite(sq) and 0.0 < sq < self.scale_norm_low ** 2 and self.loss_scale < self.scale_max
-                  and self._norm_growth_hold == 0):
-                self.loss_scale = min(self.loss_scale * 8.0, self.scale_max)   # a tiny gradient: lift it (see _init_loss_scale)
-                self._clean_steps = 0
-            else:
-                self._norm_growth_hold = max(0, self._norm_growth_hold - 1)
-                self._clean_steps += self.scale_poll_every
-                if self._clean_steps >= self.scale_grow_after:
-                    self.loss_scale = min(self.loss_scale * 2.0, self.scale_max)
-                    self._clean_steps = 0
-        if self._poll is None and k % self.scale_poll_every == 0:
-            with torch.cuda.stream(torch.cuda.current_stream(self.device)):
-                self._skip_host.copy_(self._skipped, non_blocking=True)
-                self._norm_host.copy_(self._sqnorm, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-            self._poll = (k, ev)
-
     @property
     def packed_weights(self):
         return self._packed_weights
@@ -657,7 +221,7 @@ class HipEncoderEngine:
         packed operand can reach a kernel."""
         changed = bool(v) != getattr(self, "_packed_weights", None)
         self._packed_weights = bool(v)
-        if changed and hasattr(self, "_plans"):   # (during __init__ the copies are made by init_params -> refresh_weights)
+        if changed and hasattr(self, "_programs"):   # (during __init__ the copies are made by init_params -> refresh_weights)
             self._programs.drop_all()   # recorded steps point into the fold buffers dropped below
             self._fold = {}
             self._pack_args = None
@@ -1317,34 +881,6 @@ class HipEncoderEngine:
                 lo[nm] = torch.empty(pl["n"] * lo["rs_rows"], self.blocks[i - 1][1], dtype=torch.float32, device=self.device)
 
     # ------------------------------------------------------------------------------------------------
-    def siamese_head(self, pl: dict, y: Optional[torch.Tensor], loss: str = "contrastive"):
-        """Twin distance -> Dense(1, sigmoid) -> loss (+ backward into pl['demb'] and the head gradients)."""
-        assert self.head in HEADS, "engine was built without a siamese head"
-        pairs = pl["n"] // 2
-        G = self.G
-        train = y is not None
-        # training with the side stream on: only the per-pair pass here; the fixed-order sums (loss, accuracy, head gradients --
-        # nobody's input before the optimizer) are enqueued on the side stream by backward()
-        if pl.get("tail_pending"):
-            assert train, "forward(defer_tail=True) must be followed by siamese_head with labels"
-            cl, parts, seg = self.blocks[-1][1], pl["gmax_ws"], self._seg_rows
-            pv = parts.data_ptr() if pl["tail_parts"] else None
-            pi = parts.data_ptr() + pl["n"] * seg * cl * 4 if pl["tail_parts"] else None
-            self._call("vm_tail_fwd_bwd", pv, pi, seg, _p(pl["gmax"]), _p(pl["gidx"]), _p(self.view("dense.kernel")), _p(self.view("dense.bias")),
-                       _p(self.view("head.kernel")), _p(self.view("head.bias")), self._dyn("y", _p(y)), pairs, cl, self.E, HEADS[self.head],
-                       LOSSES[loss], self._dyn("loss_scale", float(self.loss_scale)), _p(pl["emb"]), _p(pl["pred"]), _p(pl["demb"]), _p(pl["dgmax"]), _p(pl["head_ws"]), self.stream())
-            pl["tail_pending"], pl["tail_grads_pending"], pl["head_pending"] = False, True, False
-            return pl["pred"][:pairs]
-        defer = train and self.overlap_wgrad and pl["training"] and getattr(self, "defer_head_reduce", False)
-        self._call("vm_siamese_head_loss", _p(pl["emb"]), _p(self.view("head.kernel")), _p(self.view("head.bias")),
-                      self._dyn("y", _p(y)), pairs, self.E, HEADS[self.head], LOSSES[loss], self._dyn("loss_scale", float(self.loss_scale)),
-                      _p(pl["pred"]),
-                      _p(pl["loss_acc"]) if (train and not defer) else None, _p(pl["demb"]) if train else None,
-                      _p(self.view("head.kernel", G)) if train else None, _p(self.view("head.bias", G)) if train else None,
-                      _p(pl["head_ws"]), self.stream())
-        pl["head_pending"] = defer
-        return pl["pred"][:pairs]
-
     def classifier_head(self, pl: dict, labels: Optional[torch.Tensor]):
         """Dense(num_classes, softmax) + categorical CE (+ backward into pl['demb'] and the head gradients)."""
         assert self.head == "classifier"
@@ -1443,35 +979,6 @@ class HipEncoderEngine:
                    _p(pl["demb"]) if train else None, _p(self.view("head.kernel", G)) if train else None,
                    _p(self.view("head.bias", G)) if train else None, _p(b["ws"]), self.stream())
         return pl["prob"]
-
-    def _adam_scalars(self):
-        """(t, lr_t) of the Adam step about to run (Keras: lr decays with the iteration count BEFORE this step)."""
-        lr = self.lr
-        if self.decay > 0:
-            lr = lr * (1.0 / (1.0 + self.decay * self.iterations))
-        t = self.iterations + 1
-        return t, lr * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
-
-    def optimizer_step(self):
-        """Keras Adam(clipnorm) on the flat buffers (after the optional data-parallel gradient sum)."""
-        if self.grad_sync is not None:
-            gs, G = self.grad_sync, self.G
-            self._host_call(lambda: gs(G))
-        lib, st = self.lib, self.stream()
-        skip = self.loss_scaled   # loss-scaled storage: a non-finite gradient norm skips the update on the device
-        if (self.clipnorm and self.clipnorm > 0) or skip:
-            self._call("vm_grad_sqnorm", _p(self.G), self.n_flat, _p(self._sq_ws), None, st)   # partials; the optimizer kernel adds them
-        t, lr_t = self._adam_scalars()
-        self._call("vm_adam_clip_step", _p(self.P), _p(self.G), _p(self.M), _p(self.V), self.n_flat, self._dyn("lr_t", float(lr_t)), self.beta_1,
-                 self.beta_2, self.adam_eps, float(self.clipnorm or 0.0),
-                 self._dyn("gpre", float(self.grad_prescale) / float(self.loss_scale)),
-                 _p(self._sqnorm), _p(self._sq_ws), int(skip), _p(self._skipped) if skip else None, st)
-        self.iterations = t
-        if skip and self._rec is None:
-            self._poll_loss_scale()   # after the launch: the copy it may enqueue sees this step's count
-        self.refresh_weights()
-        if skip and self._rec is not None:
-            self._poll_loss_scale()   # a step being recorded: torch's copies stay out of the recorded list and go behind it, as in a replay
 
     # ------------------------------------------------------------------------------------------------
     def make_drop_masks(self, n_windows: int, generator: Optional[torch.Generator] = None):
@@ -1685,12 +1192,6 @@ class HipEncoderEngine:
             drop_masks = self.make_drop_masks(pl["n"])
         self._train_step(pl, wpt, self._target(y, n_lab, dt), loss, drop_masks, apply_update, pre)
         return pl
-
-    def _target(self, y, n: int, dt) -> torch.Tensor:
-        """Labels -> (n,) device tensor: fp32 for the siamese losses (converted on the host), int32 class ids (on the device)."""
-        if dt == torch.float32:
-            return torch.as_tensor(y, dtype=dt).reshape(n).to(self.device).contiguous()
-        return torch.as_tensor(y).reshape(n).to(self.device, dt).contiguous()
 
     def _offsets_step(self, audio: torch.Tensor, offsets: tuple, y, raw_len: int, loss: tuple, downsampling: int, whitening: bool,
                       drop_masks, apply_update: bool, aug=None):
@@ -2021,23 +1522,6 @@ class HipEncoderEngine:
         self._call("vm_dense_fwd", _p(gmax), _p(self.view("dense.kernel")), _p(self.view("dense.bias")), m, cl, self.E,
                    _p(ar["emb"][:m]), st)
 
-    def siamese_eval(self, x1, x2, y, loss: str = "contrastive", preprocessed: bool = True, downsampling: int = 4,
-                     whitening: bool = True):
-        """test_on_batch of the siamese model: inference-mode forward + loss / accuracy (no gradients are used; the
-        head kernel writes its backward outputs into scratch)."""
-        x = self._pair_windows(x1, x2)
-        pairs = x.shape[0] // 2
-        pl = self._infer(x, preprocessed, downsampling, whitening, pairs)
-        yd = self._target(y, pairs, torch.float32)
-        if "scratch" not in pl:
-            pl["scratch"] = torch.empty(2 * pairs * self.E + self.E + 8, dtype=torch.float32, device=self.device)
-        sc = pl["scratch"]
-        off = 2 * pairs * self.E
-        self._call("vm_siamese_head_loss", _p(pl["emb"]), _p(self.view("head.kernel")), _p(self.view("head.bias")), _p(yd),
-                   pairs, self.E, HEADS[self.head], LOSSES[loss], 1.0, _p(pl["pred"]), _p(pl["loss_acc"]), _p(sc),
-                   sc.data_ptr() + 4 * off, sc.data_ptr() + 4 * (off + self.E), _p(pl["head_ws"]), self.stream())
-        return pl
-
     def classifier_head_eval(self, pl: dict, labels: torch.Tensor):
         """Dense(num_classes, softmax) + categorical CE / accuracy on the embeddings of an inference plan."""
         n = pl["n"]
@@ -2052,9 +1536,3 @@ class HipEncoderEngine:
         pl = self._infer(x, preprocessed, downsampling, whitening)
         self.classifier_head_eval(pl, torch.as_tensor(labels).to(self.device, torch.int32))
         return pl
-
-    def siamese_predict(self, x1, x2, preprocessed: bool = True, downsampling: int = 4, whitening: bool = True):
-        """siamese.predict([x1, x2]) -> (pairs, 1) probabilities (inference-mode BN)."""
-        x = self._pair_windows(x1, x2)
-        pairs = x.shape[0] // 2
-        return self.siamese_head(self._infer(x, preprocessed, downsampling, whitening, pairs), None).reshape(pairs, 1)

@@ -72,9 +72,18 @@ class _TrainableModel:
     def _engine_args(self):
         raise NotImplementedError
 
-    def _make_engine(self):
+    def _engine_cls(self):
+        """The engine class behind this model: what it serves (``losses``, ``resident_input``) is asked of it before an engine exists."""
         from .engine import HipEncoderEngine
-        return HipEncoderEngine(**self._engine_args())
+        return HipEncoderEngine
+
+    def _require_resident_input(self):
+        """Before offsets into a device-resident buffer (or preprocessed windows) are handed to the engine."""
+        from .engine_core import require_resident_input
+        require_resident_input(self._engine_cls())
+
+    def _make_engine(self):
+        return self._engine_cls()(**self._engine_args())
 
     def _ensure_engine(self):
         if self.engine is None:
@@ -435,11 +444,10 @@ class ConvolutionalEncoder(_TrainableModel):
     def _make_engine(self, head="__own__"):
         """The engine of this encoder on its own (``head='__own__'``: classifier head if one was added) or as the shared encoder of
         a siamese model (``head`` = its distance metric)."""
-        from .engine import HipEncoderEngine
         args = self._engine_args()
         if head != "__own__":
             args.update(head=head, num_classes=0)
-        return HipEncoderEngine(**args)
+        return self._engine_cls()(**args)
 
     def get_config(self):
         return {"class_name": "ConvolutionalEncoder", "filters": self.filters, "embedding_dimension": self.embedding_dimension,
@@ -534,6 +542,11 @@ class ConvolutionalEncoder(_TrainableModel):
         w, kw = _windows(x)
         return self._ensure_engine().classifier_train_step(w, self._labels(y), **kw)
 
+    def _require_loss(self, name: str):
+        """Before the engine is built: does its class serve the compiled loss at all?"""
+        if name not in self._engine_cls().losses:
+            raise NotImplementedError("the %s loss is implemented for the 1-D encoder" % name)
+
     def _proto_loss(self):
         """The compiled utils.PrototypicalLoss of a bare encoder, or None."""
         from .utils import PrototypicalLoss
@@ -541,9 +554,8 @@ class ConvolutionalEncoder(_TrainableModel):
 
     def _proto_step(self, x, y, proto):
         """One optimizer step on an episode batch (x: k n + m windows, support set first; y: the m queries' classes)."""
+        self._require_loss("prototypical")
         eng = self._ensure_engine()
-        if not hasattr(eng, "prototypical_train_step"):
-            raise NotImplementedError("the prototypical loss is implemented for the 1-D encoder")
         k, n, alpha = proto.k_way, proto.n_shot, proto.alpha
         if _is_lazy(x) and _resident(x.raw):   # device data path
             return eng.prototypical_train_step_from_offsets(x.raw.audio, x.raw.offsets_host, self._labels(y), x.raw.length, k, n, alpha,
@@ -558,9 +570,8 @@ class ConvolutionalEncoder(_TrainableModel):
 
     def _triplet_step(self, x, y, trip):
         """One optimizer step on a labelled batch (x: N windows, y: their speakers), the triplets mined inside it."""
+        self._require_loss("triplet")
         eng = self._ensure_engine()
-        if not hasattr(eng, "triplet_train_step"):
-            raise NotImplementedError("the triplet loss is implemented for the 1-D encoder")
         kw = dict(mining=trip.mining_code, soft=int(trip.soft), margin=trip.margin_value)
         if _is_lazy(x) and _resident(x.raw):   # device data path
             return eng.triplet_train_step_from_offsets(x.raw.audio, x.raw.offsets_host, self._labels(y), x.raw.length,
@@ -572,11 +583,11 @@ class ConvolutionalEncoder(_TrainableModel):
         return _loss_acc(self._train_step(x, y))
 
     def test_on_batch(self, x, y):
-        eng = self._ensure_engine()
         trip, proto = self._triplet_loss(), self._proto_loss()
+        if trip is not None or proto is not None:
+            self._require_loss("triplet" if trip is not None else "prototypical")
+        eng = self._ensure_engine()
         if trip is not None:
-            if not hasattr(eng, "triplet_eval"):
-                raise NotImplementedError("the triplet loss is implemented for the 1-D encoder")
             w, kw = _windows(x, materialise=True)
             return _loss_acc(eng.triplet_eval(w, self._labels(y), mining=trip.mining_code, soft=int(trip.soft), margin=trip.margin_value, **kw))
         if proto is not None:
@@ -623,10 +634,13 @@ class SpectrogramEncoder(ConvolutionalEncoder):
     def clone(self):
         return SpectrogramEncoder(self.filters, self.embedding_dimension, self.input_shape, self.dropout, self.dtype, self.n_mels)
 
-    def _make_engine(self, head="__own__"):
+    def _engine_cls(self):
         from .spectro_engine import HipSpectrogramEncoderEngine
-        return HipSpectrogramEncoderEngine(self.filters, self.embedding_dimension, dropout=self.dropout,
-                                           head=None if head == "__own__" else head, dtype=self.dtype, n_mels=self.n_mels)
+        return HipSpectrogramEncoderEngine
+
+    def _make_engine(self, head="__own__"):
+        return self._engine_cls()(self.filters, self.embedding_dimension, dropout=self.dropout,
+                                   head=None if head == "__own__" else head, dtype=self.dtype, n_mels=self.n_mels)
 
     def get_config(self):
         return {"class_name": "SpectrogramEncoder", "filters": self.filters, "embedding_dimension": self.embedding_dimension,
@@ -674,6 +688,9 @@ class SiameseNet(_TrainableModel):
         e = self.encoder
         return dict(blocks=e.blocks, embedding_dimension=e.embedding_dimension, dropout=e.dropout, head=self.distance_metric,
                     dtype=e.dtype)
+
+    def _engine_cls(self):
+        return self.encoder._engine_cls()
 
     def _make_engine(self):
         return self.encoder._make_engine(head=self.distance_metric)
@@ -752,6 +769,7 @@ class SiameseNet(_TrainableModel):
         loss = self._loss_name()
         if _is_lazy(x1) and _is_lazy(x2) and _resident(x1.raw, True) and _resident(x2.raw, True) and x1.raw.audio is x2.raw.audio:
             # device data path: the crop happens inside the preprocessing kernel (vm_crop_decimate_whiten)
+            self._require_resident_input()
             assert (x1.downsampling, x1.whitening) == (x2.downsampling, x2.whitening)
             a1, a2 = getattr(x1.raw, "aug", None), getattr(x2.raw, "aug", None)
             if (a1 is None) != (a2 is None):

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _lib, parallel
+from .engine_core import require_resident_input
 
 _DIST = _lib.DIST
 
@@ -92,6 +93,8 @@ def embed_corpus(model, dataset, preprocessor, network_type: str = "siamese", ba
     probe = inst(np.zeros((1, 8, 1)))
     ds, wh = getattr(probe, "downsampling", 1), getattr(probe, "whitening", False)
     lazy_ok = hasattr(probe, "raw")
+    if dev_audio is not None and lazy_ok:
+        require_resident_input(type(eng))   # the windows are offsets into the resident corpus
     if whole_utterance:
         if not lazy_ok:
             raise ValueError("whole_utterance needs a preprocessor that decimates and whitens on the device (utils.preprocess_instances)")

@@ -15,89 +15,68 @@ Parameters live in the same flat fp32 buffers as the 1-D engine's (one clip-norm
 """
 from __future__ import annotations
 
-import math
-from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence
+from typing import Optional
 
 import numpy as np
 import torch
 
 from . import _lib, spectro
-from .engine import FlatState, HipEncoderEngine, _DT, _TORCH_DT, _align, _p, _shared_stream
+from .engine_core import EngineCore, FlatState, _align, _p, _shared_stream, head_spec
 
 
-class HipSpectrogramEncoderEngine(HipEncoderEngine):
-    """filters F -> channels F, 2F, 3F, 4F; head: None | 'uniform_euclidean' | 'weighted_l1'."""
+def band_stacked_spec(filters: int, embedding_dimension: int, head: Optional[str]):
+    """(spec, chan, cin, cs) of the variant: channels F, 2F, 3F, 4F; a Conv2D kernel (kT, kM, C_in, C_out) is stored as the k = 3
+    kernel (3, Cs, C_out) over three stacked bands, Cs = 3 C_in padded with zeros to a multiple of 8 (block 1: 3 -> 8)."""
+    chan = [int(filters) * (i + 1) for i in range(4)]
+    cin = [1] + chan[:-1]
+    cs = [_align(3 * c, 8) for c in cin]
+    spec = []
+    for i, c in enumerate(chan):
+        spec += [(f"conv{i+1}.kernel", (3, cs[i], c)), (f"conv{i+1}.bias", (c,)), (f"bn{i+1}.gamma", (c,)), (f"bn{i+1}.beta", (c,))]
+    E = int(embedding_dimension)
+    spec += [("dense.kernel", (chan[-1], E)), ("dense.bias", (E,))] + head_spec(head, E)
+    return spec, chan, cin, cs
+
+
+def stack_bands(a: np.ndarray, cs: int) -> np.ndarray:
+    """A public Conv2D kernel (kT, kM, C_in, C_out) in its stored form (kT, Cs, C_out); a stored one as it is."""
+    if a.ndim != 4:
+        return a
+    kt, km, cin, cout = a.shape
+    buf = np.zeros((kt, cs, cout), np.float32)
+    buf[:, :km * cin, :] = a.reshape(kt, km * cin, cout)
+    return buf
+
+
+def unstack_bands(a: np.ndarray, cin: int) -> np.ndarray:
+    """The stored form (kT, Cs, C_out) back as (kT, 3, C_in, C_out)."""
+    return a[:, :3 * cin, :].reshape(a.shape[0], 3, cin, a.shape[2])
+
+
+class HipSpectrogramEncoderEngine(EngineCore):
+    """filters F -> channels F, 2F, 3F, 4F; head: None | 'uniform_euclidean' | 'weighted_l1'.  Takes raw 16 kHz windows (its
+    front end is vm_stft_logmel): no offsets into a resident corpus, no preprocessed windows, the siamese losses only."""
+    losses = frozenset({"siamese"})
+    resident_input = False
 
     def __init__(self, filters: int, embedding_dimension: int, dropout: float = 0.05, head: Optional[str] = None, dtype: str = "f16",
                  device="cuda", bn_eps: float = 1e-3, bn_momentum: float = 0.99, unbiased_moving_variance: bool = True,
                  seed: Optional[int] = None, n_mels: int = spectro.N_MELS, win_length: int = spectro.WIN_LENGTH,
                  hop: int = spectro.HOP, log_floor: float = spectro.LOG_FLOOR):
-        if not torch.cuda.is_available():
-            raise RuntimeError("HipSpectrogramEncoderEngine needs a GPU (torch.cuda.is_available() is False); there is no CPU path")
+        self._require_gpu()
         if head not in (None, "uniform_euclidean", "weighted_l1"):
             raise NotImplementedError(head)
-        self.lib = _lib.lib()
-        self.timed = {}
-        self._call("vm_check_device")
         self.filters = int(filters)
-        self.chan = [self.filters * (i + 1) for i in range(4)]
+        # cs: stacked channel counts of the four convolutions
+        spec, self.chan, self.cin, self.cs = band_stacked_spec(filters, embedding_dimension, head)
         assert all(c % 8 == 0 for c in self.chan), "filters must be a multiple of 8"
-        self.nb = 4
-        self.E = int(embedding_dimension)
-        self.dropout = float(dropout)
-        self.head = head
-        self.num_classes = 0
-        self.dtype = _DT[dtype]
-        self.tdt = _TORCH_DT[self.dtype]
-        self.device = torch.device(device)
-        self._dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self._views = {}
-        self.bn_eps, self.bn_momentum = float(bn_eps), float(bn_momentum)
-        self.unbiased = bool(unbiased_moving_variance)
-        self.n_mels, self.win_length, self.hop, self.log_floor = int(n_mels), int(win_length), int(hop), float(log_floor)
-        # stacked channel counts of the four convolutions: 3 bands x C_in, padded to a multiple of 8 (block 1: 3 -> 8)
-        self.cin = [1] + self.chan[:-1]
-        self.cs = [_align(3 * c, 8) for c in self.cin]
-        # 1-D view of the architecture for the shared flat layout: k = 3 kernels of shape (3, Cs_i, C_i)
-        self.blocks = [(3, c, 2) for c in self.chan]
-        spec = []
-        for i, c in enumerate(self.chan):
-            spec += [(f"conv{i+1}.kernel", (3, self.cs[i], c)), (f"conv{i+1}.bias", (c,)), (f"bn{i+1}.gamma", (c,)), (f"bn{i+1}.beta", (c,))]
-        spec += [("dense.kernel", (self.chan[-1], self.E)), ("dense.bias", (self.E,))]
-        if head == "uniform_euclidean":
-            spec += [("head.kernel", (1, 1)), ("head.bias", (1,))]
-        elif head == "weighted_l1":
-            spec += [("head.kernel", (self.E, 1)), ("head.bias", (1,))]
-        st = FlatState.__new__(FlatState)
-        st.spec = spec
-        st.offsets = OrderedDict()
-        off = 0
-        for name, shape in spec:
-            n = int(np.prod(shape))
-            st.offsets[name] = (off, n, shape)
-            off += _align(n)
-        self.spec, self.offsets, self.n_flat = spec, st.offsets, off
-        self.n_params = sum(int(np.prod(self.public_shape(n_))) for n_, _ in spec)
+        # blocks: the 1-D view of the architecture, k = 3 kernels of shape (3, Cs_i, C_i)
+        super().__init__([(3, c, 2) for c in self.chan], embedding_dimension, dropout, head, 0, dtype, device, bn_eps, bn_momentum,
+                         unbiased_moving_variance, FlatState.from_spec(spec, self.chan, torch.device(device)))
         dev = self.device
-        self.P = torch.zeros(self.n_flat, dtype=torch.float32, device=dev)
-        self.G, self.M, self.V = torch.zeros_like(self.P), torch.zeros_like(self.P), torch.zeros_like(self.P)
-        self.nt_off: Dict[str, tuple] = OrderedDict()
-        off = 0
-        for i, c in enumerate(self.chan):
-            self.nt_off[f"bn{i+1}.moving_mean"] = (off, c)
-            off += _align(c)
-            self.nt_off[f"bn{i+1}.moving_variance"] = (off, c)
-            off += _align(c)
-        self.NT = torch.zeros(off, dtype=torch.float32, device=dev)
+        self.n_mels, self.win_length, self.hop, self.log_floor = int(n_mels), int(win_length), int(hop), float(log_floor)
         self.wf = {i: torch.empty(self.chan[i] * 3 * self.cs[i], dtype=self.tdt, device=dev) for i in range(4)}
         self.wd = {i: torch.empty(self.cs[i] * 3 * self.chan[i], dtype=self.tdt, device=dev) for i in range(4)}
-        self._sq_ws = torch.empty(self.lib.query("vm_sqnorm_workspace_bytes", self.n_flat) // 8, dtype=torch.float64, device=dev)
-        self._sqnorm = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.lr, self.beta_1, self.beta_2, self.adam_eps, self.decay, self.clipnorm = 1e-3, 0.9, 0.999, 1e-7, 0.0, 1.0
-        self.iterations = 0
-        self.last_infer_l0 = 0
-        self.overlap_wgrad = True
         # block 1 (one input channel) on the vector ALUs (vm_conv2d_first_fwd / _wgrad) instead of as a band-stacked GEMM
         self.first_layer_direct = bool(self.lib.query("vm_conv2d_first_supported", self.chan[0], self.dtype))
         self.flat_dgrad = True   # dgrad over the concatenated windows (see backward)
@@ -106,12 +85,6 @@ class HipSpectrogramEncoderEngine(HipEncoderEngine):
         self.fuse_boundary = True   # BatchNorm + 2 x 2 pooling + band stacking as one pass per block boundary, and its adjoint
         self.fused_bn_sums = True   # ... which also leaves the two BatchNorm-backward sums of the block below (no reduce pass)
         self.side_stream = _shared_stream(self.device, "side")
-        self.grad_sync = None
-        self.grad_prescale = 1.0
-        self._plans: Dict[tuple, dict] = {}
-        self.is16 = self.dtype in (_lib.VM_BF16, _lib.VM_F16)
-        self._init_loss_scale()
-        self._init_zero_debias()
         self.basis = torch.from_numpy(spectro.dft_basis(self.win_length)).to(dev)
         self.melw = torch.from_numpy(spectro.mel_filterbank(self.n_mels)).to(dev)
         # 16-bit storage: the DFT on the f16 matrix pipe from hi / lo halves of basis and samples (vm_stft_logmel_f16s)
@@ -129,70 +102,21 @@ class HipSpectrogramEncoderEngine(HipEncoderEngine):
         self.init_params(seed)
 
     # ---- parameters: the flat store keeps Conv2D kernels as (3, Cs, C_out) = (kT, [kM x C_in, zero padding], C_out) ----------------
+    def _conv(self, name: str) -> Optional[int]:
+        """The 0-based block of a trainable Conv2D kernel's name, None for every other tensor."""
+        return int(name[4]) - 1 if name.startswith("conv") and name.endswith(".kernel") else None
+
     def public_shape(self, name):
-        if name.startswith("conv") and name.endswith(".kernel"):
-            i = int(name[4]) - 1
-            return (3, 3, self.cin[i], self.chan[i])
-        return self.offsets[name][2]
+        i = self._conv(name)
+        return self.offsets[name][2] if i is None else (3, 3, self.cin[i], self.chan[i])
 
-    def init_params(self, seed: Optional[int] = None):
-        """Keras defaults: glorot_uniform Conv2D kernels (fan = 9 C), zero biases, gamma 1, beta 0, moving 0 / 1."""
-        import os
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-        self.seed = int(seed)
-        g = torch.Generator().manual_seed(self.seed)
-        self._drop_gen = torch.Generator(device=self.device)
-        self._drop_gen.manual_seed(self.seed * 1000003 + 7919 * (int(os.environ.get("RANK", "0")) + 1))
-        params = OrderedDict()
-        for name, (o, n, shape) in self.offsets.items():
-            if name.endswith(".kernel"):
-                ps = self.public_shape(name)
-                if len(ps) == 4:
-                    fan_in, fan_out = 9 * ps[2], 9 * ps[3]
-                else:
-                    fan_in, fan_out = ps
-                lim = math.sqrt(6.0 / (fan_in + fan_out))
-                params[name] = ((torch.rand(ps, generator=g, dtype=torch.float64) * 2 - 1) * lim).numpy()
-            elif name.endswith(".gamma"):
-                params[name] = np.ones(shape)
-            else:
-                params[name] = np.zeros(shape)
-        for name, (o, n) in self.nt_off.items():
-            self.NT[o:o + n] = 1.0 if name.endswith("moving_variance") else 0.0
-        self.M.zero_()
-        self.V.zero_()
-        self.iterations = 0
-        if hasattr(self, "ZD"):
-            self.ZD.zero_()
-            self.bn_steps = 0
-        self.set_params(params)
+    def _to_stored(self, name, a):
+        i = self._conv(name)
+        return a if i is None else stack_bands(a, self.cs[i])
 
-    def set_params(self, params):
-        for name, val in params.items():
-            a = np.asarray(val, dtype=np.float32)
-            v = self.view(name)
-            if name.startswith("conv") and name.endswith(".kernel") and a.ndim == 4:   # (kT, kM, C_in, C_out) -> (kT, Cs, C_out)
-                i = int(name[4]) - 1
-                buf = np.zeros((3, self.cs[i], self.chan[i]), np.float32)
-                buf[:, :3 * self.cin[i], :] = a.reshape(3, 3 * self.cin[i], self.chan[i])
-                a = buf
-            v.copy_(torch.as_tensor(a).to(self.device).reshape(v.shape))
-        self.refresh_weights()
-
-    def _public(self, name, t: torch.Tensor) -> np.ndarray:
-        a = t.detach().cpu().numpy().copy()
-        if name.startswith("conv") and name.endswith(".kernel"):
-            i = int(name[4]) - 1
-            a = a[:, :3 * self.cin[i], :].reshape(3, 3, self.cin[i], self.chan[i])
-        return a
-
-    def get_params(self):
-        return OrderedDict((name, self._public(name, self.view(name))) for name in list(self.offsets) + list(self.nt_off))
-
-    def get_grads(self):
-        inv = np.float32(1.0 / float(self.loss_scale))   # G holds loss_scale x the gradients with f16 storage
-        return OrderedDict((name, self._public(name, self.view(name, self.G)) * inv) for name in self.offsets)
+    def _to_public(self, name, a):
+        i = self._conv(name)
+        return a if i is None else unstack_bands(a, self.cin[i])
 
     def refresh_weights(self):
         for i in range(4):
@@ -535,11 +459,3 @@ class HipSpectrogramEncoderEngine(HipEncoderEngine):
 
     def embed(self, x, preprocessed: bool = False, downsampling: int = 1, whitening: bool = False, windows_per_tower=None) -> torch.Tensor:
         return self._infer(x)["emb"]
-
-    # the 1-D engine's data paths that have no meaning here
-    def preprocess(self, *a, **k):
-        raise NotImplementedError("the spectrogram engine takes raw windows; its front-end is vm_stft_logmel")
-
-    load_preprocessed = siamese_train_step_from_offsets = embed_from_offsets = classifier_train_step = preprocess
-    triplet_train_step = triplet_train_step_from_offsets = triplet_eval = preprocess   # the triplet loss is the 1-D encoder's
-    margin_train_step = margin_eval = preprocess   # the margin softmax is the 1-D classifier's

@@ -346,6 +346,7 @@ def _n_shot_device(model, dataset, preprocessor, num_tasks, n, k, network_type, 
     """n_shot_task_evaluation over ``ShardedSpeechDataset.build_n_shot_tasks_device``: identical task semantics and
     whitening batches (query alone / repeated k times, support set of a task as one batch), windows addressed by offset."""
     import torch
+    model._require_resident_input()   # every window below is an offset into the resident corpus
     q, s, _, _ = dataset.build_n_shot_tasks_device(num_tasks, k, n)
     lazy = preprocessor.instance_preprocessor(q) if hasattr(preprocessor, "instance_preprocessor") else None
     if not isinstance(lazy, LazyWindows):
