@@ -1,0 +1,149 @@
+"""Speaker diarization of synthetic conversations (new; the reference has no such experiment): conversations are cut together from the
+single-speaker files of a dataset (voicemap_amd/diarization.py make_conversations), every conversation is cut into sliding windows,
+the windows are embedded and clustered on the chip (diarize: vm_ahc, one workgroup per conversation) and the hypothesis is scored by
+the sample-exact diarization error rate against the turns that were planted.  One of three stop rules:
+    --threshold T              merging stops at the first height above T
+    --oracle-speakers          every conversation is merged down to its true number of speakers
+    --tune-conversations K     T is the recorded height that minimises the mean DER of the first K conversations (one full dendrogram
+                               each, then diarization.cut over the recorded heights) and is applied to the rest
+    python -m experiments.diarization --synthetic [--device-data DIR] [--siamese models/x.hdf5] --conversations 64 --speakers 2-4
+        --window-seconds 1.5 --hop-seconds 0.75 --linkage average --distance cosine --tune-conversations 16
+Prints one JSON line: the mean DER and its three parts (shares of the reference speech), and how many clusters were found against how
+many speakers were present.  With --synthetic and no --siamese the encoder is untrained: the line then says how the pipeline runs, not
+how well a model diarizes."""
+import argparse
+import json
+import os
+
+import numpy as np
+
+from voicemap_amd import diarization as DZ
+from voicemap_amd.librispeech import LibriSpeechDataset, SyntheticSpeechDataset
+from voicemap_amd.utils import BatchPreProcessor, preprocess_instances
+
+
+def parse_range(text):
+    """LO-HI or N -> (lo, hi)."""
+    try:
+        lo, _, hi = text.partition("-")
+        lo, hi = int(lo), int(hi or lo)
+        if lo < 2 or hi < lo:
+            raise ValueError
+        return lo, hi
+    except ValueError:
+        raise argparse.ArgumentTypeError("a range LO-HI with 2 <= LO <= HI, not %r" % text)
+
+
+def _parser():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--siamese", default=None, help="a saved siamese network (optional with --synthetic: a fresh, untrained one is built)")
+    p.add_argument("--synthetic", action="store_true", help="generated speakers instead of LibriSpeech on disk")
+    p.add_argument("--device-data", metavar="DIR", default="",
+                   help="decode the files once into int16 shards under DIR (reused if present) and keep them resident: the conversations "
+                        "are then assembled on the device")
+    p.add_argument("--dataset", default="dev-clean", help="the LibriSpeech subset the conversations are cut from")
+    p.add_argument("--conversations", type=int, default=64)
+    p.add_argument("--speakers", type=parse_range, default=(2, 4), metavar="LO-HI")
+    p.add_argument("--turns", type=parse_range, default=(6, 12), metavar="LO-HI")
+    p.add_argument("--window-seconds", type=float, default=1.5)
+    p.add_argument("--hop-seconds", type=float, default=0.75)
+    p.add_argument("--downsampling", type=int, default=4)
+    p.add_argument("--linkage", default="average", choices=list(DZ.LINKAGES))
+    p.add_argument("--distance", default="cosine", choices=["euclidean", "cosine", "dot_product"])
+    p.add_argument("--seed", type=int, default=0)
+    stop = p.add_mutually_exclusive_group(required=True)
+    stop.add_argument("--threshold", type=float, default=None)
+    stop.add_argument("--oracle-speakers", action="store_true")
+    stop.add_argument("--tune-conversations", type=int, default=0, metavar="K")
+    return p
+
+
+def score(conv, rows, segments):
+    """The error of conversations ``rows`` under ``segments`` (one table per row): the mean DER and its parts as shares of the reference."""
+    ds = [DZ.der(conv.segments[r], seg) for r, seg in zip(rows, segments)]
+    part = lambda k: float(np.mean([d[k] / d["total"] for d in ds])) if ds else float("nan")
+    return {"mean_der": part("missed") + part("false_alarm") + part("confusion") if ds else float("nan"),
+            "missed": part("missed"), "false_alarm": part("false_alarm"), "confusion": part("confusion")}
+
+
+def segments_at(conv, res, rows, threshold):
+    """(hypothesis segments, clusters found) of conversations ``rows`` from their FULL dendrograms cut at ``threshold``."""
+    segs, found = [], []
+    for r in rows:
+        rec = res.recording(r)
+        labels, c = DZ.cut(rec.merge_a, rec.merge_b, rec.merge_h, len(rec.labels), threshold=threshold)
+        segs.append(DZ.window_segments(res.starts[r], res.window, int(conv.lens[r]), labels))
+        found.append(c)
+    return segs, found
+
+
+def tune_threshold(conv, res, rows, candidates=64):
+    """The threshold with the lowest mean DER over conversations ``rows``, among up to ``candidates`` quantiles of their recorded
+    heights (a cut can only change at a recorded height); ties go to the lower threshold."""
+    heights = np.concatenate([res.recording(r).merge_h for r in rows])
+    heights = np.unique(heights[~np.isnan(heights)])
+    if heights.size == 0:
+        raise SystemExit("--tune-conversations: the development conversations recorded no merge")
+    if heights.size > candidates:
+        heights = np.unique(np.quantile(heights, np.linspace(0, 1, candidates), method="nearest"))
+    errs = [score(conv, rows, segments_at(conv, res, rows, float(h))[0])["mean_der"] for h in heights]
+    return float(heights[int(np.argmin(errs))])
+
+
+def main(argv=None):
+    p = _parser()
+    a = p.parse_args(argv)
+    from experiments._common import setup
+    setup(a.seed)
+    from voicemap_amd import models
+    window = int(round(a.window_seconds * DZ.SAMPLING_RATE))
+    if a.synthetic:
+        data = SyntheticSpeechDataset(num_speakers=24, files_per_speaker=6, seconds=a.window_seconds, stochastic=False, seed=1,
+                                      subset="synthetic-diarization")
+    else:
+        data = LibriSpeechDataset(a.dataset, a.window_seconds, stochastic=False)
+    if a.siamese:
+        net = models.load_model(a.siamese)
+    elif a.synthetic:
+        enc = models.get_baseline_convolutional_encoder(16, 32, dropout=0.0, dtype="f32")
+        net = models.build_siamese_net(enc, (window // a.downsampling, 1), distance_metric="uniform_euclidean")
+    else:
+        p.error("--siamese is required without --synthetic")
+    if a.device_data:
+        from voicemap_amd import shards
+        if not os.path.exists(os.path.join(a.device_data, "index.csv")):
+            shards.write_shards(data, a.device_data)
+        data = shards.ShardedSpeechDataset(a.device_data, a.window_seconds, stochastic=False, pad=False)
+        data.to_device("cuda")
+    pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
+    conv = DZ.make_conversations(data, a.conversations, speakers=a.speakers, turns=a.turns, seed=a.seed)
+    kw = dict(distance=a.distance, linkage=a.linkage)
+    rows = list(range(len(conv)))
+    out = {"conversations": len(conv), "linkage": a.linkage, "distance": a.distance, "window_seconds": a.window_seconds,
+           "hop_seconds": a.hop_seconds}
+    if a.tune_conversations:
+        if not 0 < a.tune_conversations < len(conv):
+            p.error("--tune-conversations K needs 0 < K < --conversations")
+        _, res = DZ.diarize(net, conv.audio, conv.offsets, conv.lens, pre, a.window_seconds, a.hop_seconds, **kw)   # full dendrograms
+        dev, rows = rows[:a.tune_conversations], rows[a.tune_conversations:]
+        threshold = tune_threshold(conv, res, dev)
+        segments, found = segments_at(conv, res, rows, threshold)
+        out.update(threshold=threshold, tuned_on=len(dev), dev_mean_der=score(conv, dev, segments_at(conv, res, dev, threshold)[0])["mean_der"])
+    else:
+        n_speakers = conv.speakers if a.oracle_speakers else None
+        segments, res = DZ.diarize(net, conv.audio, conv.offsets, conv.lens, pre, a.window_seconds, a.hop_seconds, threshold=a.threshold,
+                                   n_speakers=n_speakers, **kw)
+        found = res.host().n_clusters.tolist()
+        out.update(threshold=a.threshold, oracle_speakers=bool(a.oracle_speakers))
+    out.update(score(conv, rows, segments), scored=len(rows), windows=int(res.row0[-1]))
+    table = {}
+    for r, c in zip(rows, found):
+        table.setdefault(int(conv.speakers[r]), {}).setdefault(int(c), 0)
+        table[int(conv.speakers[r])][int(c)] += 1
+    out["clusters_found_by_speakers_present"] = {str(s): {str(c): k for c, k in sorted(row.items())} for s, row in sorted(table.items())}
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -863,6 +863,41 @@ int64_t vm_mine_pairs_workspace_bytes(int64_t N, int E, int64_t row_lo, int64_t 
 int vm_mine_pairs(const float* emb, const int32_t* label, int64_t N, int E, int score_kind, int64_t row_lo, int64_t row_hi, int k_neg,
                   int k_pos, const float* neg_floor, int32_t* neg_idx, float* neg_val, int32_t* pos_idx, float* pos_val, void* ws,
                   void* stream);
+/* vm_ahc: batched agglomerative clustering for speaker diarization (csrc/cluster.hip, voicemap_amd/diarization.py; ahc_reference there is
+ * the numpy statement, matched bit for bit).  emb (N, E) fp32 holds the windows of R recordings back to back.  row0 / mat0: R + 1 int64
+ * each ON THE DEVICE, the exclusive cumulative sums of the recordings' window counts n_r and of n_r^2 (row0[R] == N, mat0[R] ==
+ * sq_total; the host holds the lengths, as with vm_vad_frames' frame_base).  dist_kind is VM_DIST_EUCLIDEAN, VM_DIST_COSINE or VM_DIST_DOT,
+ * lower = more alike; linkage is one of VM_LINK_*.
+ * Per recording, its rows renumbered 0 .. n - 1 ("slots"):
+ *   D[i][j] (i != j) is bit-identical to dist[i][j] of vm_pairdist_argmin on the same rows (symmetric bit for bit).  Every slot starts as
+ *   an active cluster of size 1; c = the number of active clusters, T = max(1, target[r]) (target: R int32 on the device; NULL = 1).
+ *   While c > T:  among the active pairs a < b take the smallest by (key(D[a][b]), a, b), key = vm_pair_score_hist's uint32 key with -0.0 as
+ *   +0.0 and every NaN last;  h = D[a][b];  if threshold is not NaN and !(h <= threshold): stop (so a NaN h stops);  record merge t as
+ *   (a, b, h, size_a + size_b);  for every other active k set D[k][a] = D[a][k] =
+ *     single:   the one of D[k][a], D[k][b] with the smaller key (NaN loses; equal keys keep D[k][a]),
+ *     complete: the one with the larger key (NaN wins; equal keys keep D[k][a]),
+ *     average:  (size_a * D[k][a] + size_b * D[k][b]) / (size_a + size_b) in fp32, the sizes converted exactly, each product, the sum and
+ *               the IEEE quotient rounded on its own (no FMA); a NaN result is stored as the quiet NaN 0x7fc00000;
+ *   slot b is retired, size_a += size_b, c -= 1.
+ * Outputs, on the device.  merge_a, merge_b, merge_size (N) int32 and merge_h (N) fp32: merge t of recording r at row0[r] + t; every index
+ * of the recording that holds no merge (always row0[r] + n_r - 1) gets -1 / NaN.  labels (N) int32: the final clusters numbered 0 .. c - 1
+ * in ascending order of their slot (= their lowest member row).  n_clusters (R) int32: the final c, 0 for an empty recording.
+ * (key, a, b) is a total order: the outputs are a function of the inputs alone -- no atomics, bit-identical from run to run.
+ * Limits.  0 <= n_r <= VM_AHC_MAX_N, E <= 256, N < 2^31; emb 16-byte aligned when E % 4 == 0; ws 16-byte aligned; a bad argument is an
+ * error before any launch; R == 0 or N == 0 returns without a launch (nothing is written: the caller knows every recording is empty).
+ * The launcher cannot see the device tables: n_r > VM_AHC_MAX_N, a negative n_r or a mat0 that does not go with row0 must be refused
+ * by the caller (voicemap_amd/diarization.py cluster does).  The merge kernel leaves n_clusters[r] = -1 and nothing else for a recording
+ * whose n_r is out of range.
+ * Launches: the squared norms (cosine) and the scalar-path copy of all rows; the block-diagonal distances (one workgroup per 64 rows);
+ * the merge loop, one workgroup per recording, O(n^2) typically and O(n^3) at worst.
+ * ws >= vm_ahc_workspace_bytes(N, E, R, sq_total).  Its first sq_total floats are the matrices, D_r[i][j] at mat0[r] + i n_r + j, as the
+ * merge loop left them (the diagonal is NaN); then N squared norms and the rows in scalar-path layout. */
+enum { VM_LINK_SINGLE = 0, VM_LINK_COMPLETE = 1, VM_LINK_AVERAGE = 2 };
+enum { VM_AHC_MAX_N = 2048 };
+int64_t vm_ahc_workspace_bytes(int64_t N, int E, int64_t R, int64_t sq_total);
+int vm_ahc(const float* emb, int64_t N, int E, const int64_t* row0, const int64_t* mat0, int64_t R, int64_t sq_total, int dist_kind,
+           int linkage, float threshold, const int32_t* target, int32_t* merge_a, int32_t* merge_b, float* merge_h, int32_t* merge_size,
+           int32_t* labels, int32_t* n_clusters, void* ws, void* stream);
 
 /* ---- a10 / f4: log-mel front-end and the 2-D CNN encoder variant (BASELINE.json config 4) -------------------
  * NOT in the reference (nothing to cite under /root/reference); the specification is DESIGN.md section 9 and the

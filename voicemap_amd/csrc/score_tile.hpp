@@ -1,5 +1,5 @@
 // The tile loop of everything that scores cached embeddings -- pairdist_kernel (eval.hip), cohort_score_kernel (cohort.hip), mine_kernel
-// (mine.hip), pair_calib_kernel (calib.hip) call it; pair_hist_kernel (verif.hip) keeps a copy, because it measured slower through the
+// (mine.hip), pair_calib_kernel (calib.hip), ahc_dist_kernel (cluster.hip) call it; pair_hist_kernel (verif.hip) keeps a copy, because it measured slower through the
 // call -- and the small helpers around it.  Every score of theirs is bit-identical to dist[i][j] of vm_pairdist_argmin because they run
 // THIS text; what a kernel does with a finished tile (argmin, histogram, score tile, selection lists, calibration sums) is its own
 // epilogue in its own file.

@@ -1,0 +1,459 @@
+"""Speaker diarization: who spoke when in a recording nobody has labelled (new; the reference has nothing like it).
+
+A recording is cut into sliding windows (``sliding_windows``), every window is embedded alone (``embed_from_offsets``: windows are
+offsets into the resident int16 buffer), the windows of each recording are clustered agglomeratively on the chip (``cluster``:
+``vm_ahc``, voicemap_amd/csrc/cluster.hip -- one launch, one workgroup per recording, only merge lists and labels leave the chip)
+and the window labels become segments (``window_segments``).  ``der`` scores a hypothesis against reference segments;
+``make_conversations`` builds synthetic conversations from single-speaker files; ``diarize`` is the whole path.
+
+The contract of the clustering, for ONE recording of n windows ("slots" 0 .. n - 1) and a symmetric distance matrix D (lower = more
+alike), is ``ahc_reference`` -- the numpy statement every device test compares against, bit for bit:
+
+  every slot starts as an active cluster of size 1; c = active clusters, T = max(1, target).  While c > T:
+    among the active pairs a < b take the smallest by (key(D[a][b]), a, b); key = ``verification.score_keys`` with every NaN last;
+    h = D[a][b]; if a threshold is given and not (h <= threshold): stop (a NaN h stops);
+    record merge t = (a, b, h, size_a + size_b); for every other active k, D[k][a] = D[a][k] =
+      single    the one of D[k][a], D[k][b] with the smaller key (equal keys keep D[k][a]);
+      complete  the one with the larger key (equal keys keep D[k][a]);
+      average   (size_a * D[k][a] + size_b * D[k][b]) / (size_a + size_b), every operation rounded on its own in the matrix's
+                precision, a NaN result stored as the canonical quiet NaN;
+    slot b is retired, size_a += size_b, c -= 1.
+  merge lists have n entries, -1 / NaN where no merge is recorded (always the last); labels number the final clusters 0 .. c - 1 in
+  ascending order of their slot (their lowest member).
+
+What is checked: the kernel against this statement at equality, the statement against scipy's linkage in float64, ``der`` against
+hand-computed cases.  NO claim about the DER of a trained model on real conversations: that has not been measured.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+from typing import List, Optional, Tuple
+
+import numpy as np
+
+MAX_N = 2048   # VM_AHC_MAX_N of include/voicemap_hip.h: a recording's matrix belongs to one workgroup
+LINKAGES = ("single", "complete", "average")
+SAMPLING_RATE = 16000
+
+Ahc = namedtuple("Ahc", "merge_a merge_b merge_h merge_size labels n_clusters")
+
+
+# ---- the contract --------------------------------------------------------------------------------------------------------------------
+def _keys(x: np.ndarray, dtype) -> np.ndarray:
+    """What the pair search and the single / complete updates compare: the uint32 score keys with every NaN last (float32), or the
+    values themselves with a NaN taken as +inf (float64: the form that is compared with scipy)."""
+    if dtype == np.float32:
+        from .verification import score_keys
+        return np.where(np.isnan(x), 0xFFFFFFFF, score_keys(x).astype(np.int64).reshape(x.shape))
+    return np.where(np.isnan(x), np.inf, x) + 0.0
+
+
+def _thr(threshold, dtype):
+    return None if threshold is None or np.isnan(threshold) else dtype(threshold)
+
+
+def labels_of(rep: np.ndarray) -> np.ndarray:
+    """rep[k] = k for an active slot, else the (lower) slot it was merged into -> the final clusters numbered in ascending slot order."""
+    n = len(rep)
+    root = np.arange(n)
+    for k in range(n):            # rep[k] < k for a retired slot: its root is already known
+        root[k] = k if rep[k] == k else root[rep[k]]
+    number = np.cumsum(rep == np.arange(n)) - 1
+    return number[root].astype(np.int32)
+
+
+def ahc_reference(D, linkage: str, threshold: Optional[float] = None, target: int = 1, dtype=np.float32) -> Ahc:
+    """The statement of the module docstring on an (n, n) matrix, written for obviousness: a full masked search per step.  Only the
+    upper triangle of ``D`` is read (the matrix is taken as symmetric).  Returns ``Ahc(merge_a, merge_b, merge_h, merge_size,
+    labels, n_clusters)``."""
+    if linkage not in LINKAGES:
+        raise ValueError("linkage must be in %r" % (LINKAGES,))
+    dtype = np.dtype(dtype).type
+    D = np.array(D, dtype=dtype)
+    n = D.shape[0]
+    assert D.shape == (n, n)
+    iu = np.triu_indices(n, 1)
+    D[iu[1], iu[0]] = D[iu]
+    merge_a, merge_b = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+    merge_h, merge_size = np.full(n, np.nan, dtype), np.full(n, -1, np.int32)
+    active, size, rep = np.ones(n, bool), np.ones(n, np.int64), np.arange(n)
+    thr = _thr(threshold, dtype)
+    upper = np.triu(np.ones((n, n), bool), 1)
+    c, T, t = n, max(1, int(target)), 0
+    with np.errstate(all="ignore"):
+        while c > T:
+            pairs = np.flatnonzero((upper & active[:, None] & active[None, :]).ravel())   # row-major: ascending (a, b)
+            p = pairs[np.argmin(_keys(D.ravel()[pairs], dtype))]                          # the first minimum
+            a, b = divmod(int(p), n)
+            h = D[a, b]
+            if thr is not None and not (h <= thr):
+                break
+            merge_a[t], merge_b[t], merge_h[t], merge_size[t] = a, b, h, size[a] + size[b]
+            ks = np.flatnonzero(active)
+            ks = ks[(ks != a) & (ks != b)]
+            da, db = D[ks, a], D[ks, b]
+            if linkage == "single":
+                new = np.where(_keys(db, dtype) < _keys(da, dtype), db, da)
+            elif linkage == "complete":
+                new = np.where(_keys(db, dtype) > _keys(da, dtype), db, da)
+            else:
+                x = dtype(size[a]) * da
+                y = dtype(size[b]) * db
+                new = (x + y) / dtype(size[a] + size[b])
+                new[np.isnan(new)] = dtype(np.nan)
+            D[ks, a] = D[a, ks] = new
+            active[b], rep[b] = False, a
+            size[a] += size[b]
+            c, t = c - 1, t + 1
+    return Ahc(merge_a, merge_b, merge_h, merge_size, labels_of(rep), c)
+
+
+def to_linkage(merge_a, merge_b, merge_h, merge_size, n: int) -> np.ndarray:
+    """The recorded merges as scipy's ``Z`` matrix (one row per merge: the two cluster ids in ascending order, the height, the size);
+    the cluster merge t creates is id n + t."""
+    m = int((np.asarray(merge_a)[:n] >= 0).sum())
+    ident = np.arange(n)
+    Z = np.zeros((m, 4), np.float64)
+    for t in range(m):
+        a, b = int(merge_a[t]), int(merge_b[t])
+        Z[t] = (min(ident[a], ident[b]), max(ident[a], ident[b]), merge_h[t], merge_size[t])
+        ident[a] = n + t
+    return Z
+
+
+def cut(merge_a, merge_b, merge_h, n: int, threshold: Optional[float] = None, n_clusters: Optional[int] = None):
+    """(labels, clusters) of a recorded dendrogram replayed under the stop rule of the statement: merges are taken in order while more
+    than ``max(1, n_clusters)`` clusters remain and the height passes ``h <= threshold``.  On a FULL dendrogram (no threshold, target
+    1) this is what a run with that threshold / target gives: the stop rule only ever cuts the merge list short."""
+    merge_h = np.asarray(merge_h)
+    thr = _thr(threshold, merge_h.dtype.type)
+    rep = np.arange(n)
+    c, T = n, max(1, int(n_clusters) if n_clusters is not None else 1)
+    for t in range(n):
+        if c <= T or merge_a[t] < 0 or (thr is not None and not (merge_h[t] <= thr)):
+            break
+        rep[merge_b[t]] = merge_a[t]
+        c -= 1
+    return labels_of(rep), c
+
+
+# ---- the device call -------------------------------------------------------------------------------------------------------------------
+class Clustering:
+    """What ``cluster`` leaves on the device: ``merge_a`` / ``merge_b`` / ``merge_size`` (N,) int32 and ``merge_h`` (N,) fp32 with merge
+    t of recording r at ``row0[r] + t`` (-1 / NaN where there is none), ``labels`` (N,) int32, ``n_clusters`` (R,) int32; ``row0`` is the
+    host's (R + 1,) table.  ``recording(r)`` is recording r's part as numpy arrays (one read-back for all)."""
+
+    def __init__(self, row0, merge_a, merge_b, merge_h, merge_size, labels, n_clusters, distance, linkage):
+        self.row0, self.distance, self.linkage = row0, distance, linkage
+        self.merge_a, self.merge_b, self.merge_h, self.merge_size = merge_a, merge_b, merge_h, merge_size
+        self.labels, self.n_clusters = labels, n_clusters
+        self._host = None
+
+    def host(self) -> Ahc:
+        if self._host is None:
+            self._host = Ahc(*(t.cpu().numpy() for t in (self.merge_a, self.merge_b, self.merge_h, self.merge_size, self.labels,
+                                                          self.n_clusters)))
+        return self._host
+
+    def recording(self, r: int) -> Ahc:
+        h, lo, hi = self.host(), int(self.row0[r]), int(self.row0[r + 1])
+        return Ahc(h.merge_a[lo:hi], h.merge_b[lo:hi], h.merge_h[lo:hi], h.merge_size[lo:hi], h.labels[lo:hi], int(h.n_clusters[r]))
+
+
+def _row_table(row0, N: int) -> np.ndarray:
+    row0 = np.ascontiguousarray(np.asarray(row0.cpu() if hasattr(row0, "cpu") else row0, dtype=np.int64).reshape(-1))
+    if row0.size < 1 or row0[0] != 0 or row0[-1] != N:
+        raise ValueError("row0 must run from 0 to the number of rows (%d)" % N)
+    n_r = np.diff(row0)
+    if n_r.size and n_r.min() < 0:
+        raise ValueError("row0 must not decrease")
+    if n_r.size and n_r.max() > MAX_N:
+        raise ValueError("recording %d holds %d windows: at most %d can be clustered" % (int(n_r.argmax()), int(n_r.max()), MAX_N))
+    return row0
+
+
+def cluster(emb, row0, distance: str = "cosine", linkage: str = "average", threshold: Optional[float] = None,
+            n_speakers=None) -> Clustering:
+    """Cluster the windows of R recordings in one ``vm_ahc`` call.  ``emb``: (N, E) fp32 device tensor, recording r's windows at rows
+    ``row0[r] .. row0[r + 1]`` (``row0``: R + 1 host values).  Merging stops at the first height that fails ``h <= threshold`` and
+    when ``n_speakers`` clusters are left (an int, or one per recording); with neither, the full dendrogram is recorded (``cut``
+    then gives any stop on the host)."""
+    import torch
+    from . import _lib
+    if distance not in _lib.DIST:
+        raise ValueError("Distance must be in (euclidean, cosine, dot_product)")
+    if linkage not in LINKAGES:
+        raise ValueError("linkage must be in %r" % (LINKAGES,))
+    if emb.dim() != 2 or emb.dtype != torch.float32:
+        raise TypeError("emb must be an (N, E) fp32 tensor")
+    emb = emb.contiguous()
+    N, E = int(emb.shape[0]), int(emb.shape[1])
+    row0 = _row_table(row0, N)
+    R, dev = row0.size - 1, emb.device
+    mat0 = np.concatenate([[0], np.cumsum(np.diff(row0) ** 2)]).astype(np.int64)
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    res = Clustering(row0, i32(N), i32(N), torch.empty(N, dtype=torch.float32, device=dev), i32(N), i32(N),
+                     torch.zeros(R, dtype=torch.int32, device=dev), distance, linkage)
+    if R == 0 or N == 0:
+        return res
+    target = None
+    if n_speakers is not None:
+        t = np.broadcast_to(np.asarray(n_speakers, dtype=np.int64), (R,)) if np.ndim(n_speakers) == 0 else np.asarray(n_speakers, dtype=np.int64)
+        if t.shape != (R,):
+            raise ValueError("n_speakers must be one number or one per recording")
+        target = torch.from_numpy(np.clip(t, 0, MAX_N).astype(np.int32)).to(dev)
+    tab = torch.from_numpy(np.concatenate([row0, mat0])).to(dev)   # one upload
+    lib = _lib.lib()
+    ws = lib.workspace("vm_ahc_workspace_bytes", N, E, R, int(mat0[-1]), device=dev)
+    lib.call("vm_ahc", emb.data_ptr(), N, E, tab.data_ptr(), tab[R + 1:].data_ptr(), R, int(mat0[-1]), _lib.DIST[distance],
+             _lib._ENUMS["VM_LINK_" + linkage.upper()], float("nan") if threshold is None else float(threshold),
+             None if target is None else target.data_ptr(), res.merge_a.data_ptr(), res.merge_b.data_ptr(), res.merge_h.data_ptr(),
+             res.merge_size.data_ptr(), res.labels.data_ptr(), res.n_clusters.data_ptr(), ws.data_ptr(),
+             torch.cuda.current_stream(dev).cuda_stream)
+    return res
+
+
+# ---- windows and segments ------------------------------------------------------------------------------------------------------------
+def sliding_windows(lens, window: int, hop: int) -> List[np.ndarray]:
+    """Per recording the start offsets 0, hop, 2 hop, ... of every window of ``window`` samples that fits, plus one last window flush
+    with the end when those leave a tail uncovered.  A recording shorter than ``window`` raises ``ValueError`` naming it."""
+    window, hop = int(window), int(hop)
+    if window < 1 or hop < 1:
+        raise ValueError("window and hop must be at least one sample")
+    out = []
+    for r, n in enumerate(np.asarray(lens, dtype=np.int64).reshape(-1)):
+        n = int(n)
+        if n < window:
+            raise ValueError("recording %d holds %d samples: shorter than the window of %d" % (r, n, window))
+        starts = np.arange(0, n - window + 1, hop, dtype=np.int64)
+        if starts[-1] + window < n:
+            starts = np.append(starts, n - window)
+        out.append(starts)
+    return out
+
+
+def window_segments(starts, window: int, length: int, labels) -> np.ndarray:
+    """Window labels -> hypothesis segments, (k, 3) int64 rows (start, end, label) that tile [0, length).  Sample s takes the label
+    of the window whose centre ``start + window / 2`` is nearest, a tie going to the earlier window: the boundary between two
+    consecutive windows is the midpoint of their centres, the sample ON it staying with the earlier one.  Neighbouring pieces with
+    one label are joined.  ``starts`` ascending."""
+    starts, labels = np.asarray(starts, dtype=np.int64).reshape(-1), np.asarray(labels).reshape(-1)
+    if starts.size == 0 or starts.size != labels.size:
+        raise ValueError("one label per window, at least one window")
+    if np.any(np.diff(starts) <= 0):
+        raise ValueError("starts must ascend")
+    # s <= (c_i + c_j) / 2 with c = start + window / 2  <=>  s <= floor((start_i + start_j + window) / 2)
+    first = np.clip((starts[:-1] + starts[1:] + int(window)) // 2 + 1, 0, int(length))
+    edges = np.concatenate([[0], first, [int(length)]])
+    segs = []
+    for i, lab in enumerate(labels):
+        b, e = int(edges[i]), int(edges[i + 1])
+        if e <= b:
+            continue
+        if segs and segs[-1][2] == int(lab) and segs[-1][1] == b:
+            segs[-1][1] = e
+        else:
+            segs.append([b, e, int(lab)])
+    return np.array(segs, dtype=np.int64).reshape(-1, 3)
+
+
+# ---- scoring ---------------------------------------------------------------------------------------------------------------------------
+def assign_max(weights) -> np.ndarray:
+    """The one-to-one mapping of rows to columns that maximises the mapped weight: ``col[i]`` for every row, -1 for a row left out
+    (more rows than columns).  The O(n^3) shortest-augmenting-path form of the Hungarian method on ``max - weights``; integer weights
+    are solved exactly."""
+    W = np.asarray(weights)
+    if W.ndim != 2:
+        raise ValueError("a weight matrix")
+    if W.shape[0] > W.shape[1]:   # rows <= columns below
+        col_of = assign_max(W.T)
+        out = np.full(W.shape[0], -1, np.int64)
+        out[col_of[col_of >= 0]] = np.flatnonzero(col_of >= 0)
+        return out
+    n, m = W.shape
+    if n == 0:
+        return np.zeros(0, np.int64)
+    C = (W.max() - W).astype(np.int64 if np.issubdtype(W.dtype, np.integer) else np.float64)
+    inf = np.iinfo(np.int64).max // 4 if C.dtype == np.int64 else np.inf
+    u, v = np.zeros(n + 1, C.dtype), np.zeros(m + 1, C.dtype)
+    p, way = np.zeros(m + 1, np.int64), np.zeros(m + 1, np.int64)   # p[j]: the row (1-based) matched to column j
+    for i in range(1, n + 1):
+        p[0], j0 = i, 0
+        minv, used = np.full(m + 1, inf, C.dtype), np.zeros(m + 1, bool)
+        while True:
+            used[j0] = True
+            i0 = p[j0]
+            free = ~used[1:]
+            cur = C[i0 - 1] - u[i0] - v[1:]
+            better = free & (cur < minv[1:])
+            minv[1:][better] = cur[better]
+            way[1:][better] = j0
+            cand = np.where(free, minv[1:], inf)
+            j1 = int(np.argmin(cand)) + 1
+            delta = cand[j1 - 1]
+            u[p[used]] += delta
+            v[used] -= delta
+            minv[1:][free] -= delta
+            j0 = j1
+            if p[j0] == 0:
+                break
+        while j0:
+            j1 = way[j0]
+            p[j0] = p[j1]
+            j0 = j1
+    out = np.full(n, -1, np.int64)
+    for j in range(1, m + 1):
+        if p[j]:
+            out[p[j] - 1] = j - 1
+    return out
+
+
+def _seg_table(segments) -> np.ndarray:
+    s = np.asarray(segments, dtype=np.int64).reshape(-1, 3)
+    if np.any(s[:, 1] < s[:, 0]):
+        raise ValueError("a segment ends before it starts")
+    return s[s[:, 1] > s[:, 0]]
+
+
+def der(reference_segments, hypothesis_segments) -> dict:
+    """Diarization error between two segment tables ((k, 3) rows of start, end, label; samples, end exclusive), sample-exact, no
+    collar.  Per sample with R reference speakers and H hypothesis clusters active: ``missed`` += max(0, R - H), ``false_alarm`` +=
+    max(0, H - R), ``confusion`` += min(R, H) - (reference speakers whose mapped cluster is active), ``total`` += R.  The mapping is the
+    one-to-one assignment of speakers to clusters with the largest mapped overlap (``assign_max`` on the overlap matrix in samples).
+    ``der`` = (missed + false_alarm + confusion) / total (NaN when the reference is empty).  Segments of one table may overlap."""
+    ref, hyp = _seg_table(reference_segments), _seg_table(hypothesis_segments)
+    spk, ri = np.unique(ref[:, 2], return_inverse=True)
+    clu, hi = np.unique(hyp[:, 2], return_inverse=True)
+    cuts = np.unique(np.concatenate([ref[:, :2].ravel(), hyp[:, :2].ravel()]))
+    dur = np.diff(cuts)
+    K = len(dur)
+    RA, HA = np.zeros((K, len(spk)), np.int64), np.zeros((K, len(clu)), np.int64)
+    for tab, idx, act in ((ref, ri.reshape(-1), RA), (hyp, hi.reshape(-1), HA)):
+        lo, hi_ = np.searchsorted(cuts, tab[:, 0]), np.searchsorted(cuts, tab[:, 1])
+        for k in range(len(tab)):
+            act[lo[k]:hi_[k], idx[k]] = 1
+    overlap = (RA * dur[:, None]).T @ HA if K else np.zeros((len(spk), len(clu)), np.int64)
+    mapping = assign_max(overlap) if overlap.size else np.full(len(spk), -1, np.int64)
+    nr, nh = RA.sum(axis=1), HA.sum(axis=1)
+    correct = np.zeros(K, np.int64)
+    for i, j in enumerate(mapping):
+        if j >= 0:
+            correct += RA[:, i] * HA[:, j]
+    missed = int((np.maximum(nr - nh, 0) * dur).sum())
+    false_alarm = int((np.maximum(nh - nr, 0) * dur).sum())
+    confusion = int(((np.minimum(nr, nh) - correct) * dur).sum())
+    total = int((nr * dur).sum())
+    return {"missed": missed, "false_alarm": false_alarm, "confusion": confusion, "total": total,
+            "der": (missed + false_alarm + confusion) / total if total else float("nan"),
+            "mapping": {int(spk[i]): int(clu[j]) for i, j in enumerate(mapping) if j >= 0}}
+
+
+# ---- synthetic conversations -----------------------------------------------------------------------------------------------------------
+class Conversations:
+    """``audio``: the int16 buffer of all conversations back to back (a device tensor when the corpus is resident, else what
+    ``to('cuda')`` uploads); ``offsets`` / ``lens`` (n,) int64; ``segments``: per conversation the reference table (turns, 3) of (start,
+    end, speaker code), samples relative to the conversation; ``speakers``: per conversation the number of speakers present."""
+
+    def __init__(self, audio, offsets, lens, segments, turns):
+        self.audio, self.offsets, self.lens, self.segments, self.turns = audio, offsets, lens, segments, turns
+        self.speakers = np.array([len(np.unique(s[:, 2])) for s in segments], dtype=np.int64)
+
+    def __len__(self):
+        return len(self.lens)
+
+
+def make_conversations(dataset, n: int, speakers: Tuple[int, int] = (2, 4), turns: Tuple[int, int] = (6, 12),
+                       turn_seconds: Tuple[float, float] = (1.0, 6.0), seed: int = 0) -> Conversations:
+    """``n`` synthetic conversations from the single-speaker files of ``dataset``.  Per conversation: a speaker count in ``speakers`` and
+    a turn count in ``turns`` (both inclusive) are drawn, that many distinct speakers, then per turn a speaker that is not the previous
+    turn's, one of its files, a length in ``turn_seconds`` clamped to the file, and a crop position.  Turns follow each other without
+    pause or overlap, so the reference segments tile the conversation.  The draws come from this function's own
+    ``numpy.random.Generator(seed)``: the dataset's stream (``np.random``) is not touched.  On a resident corpus
+    (``dataset.device_audio``) the buffer is assembled on the device from slices; otherwise in numpy, and uploaded."""
+    rng = np.random.default_rng(seed)
+    code = np.asarray(dataset._code).astype(np.int64)
+    length = np.asarray(getattr(dataset, "file_length", None) if getattr(dataset, "file_length", None) is not None
+                        else dataset.df["length"].values, dtype=np.int64)
+    files_of = [np.flatnonzero(code == s) for s in range(int(code.max()) + 1)]
+    have = np.array([s for s, f in enumerate(files_of) if len(f)])
+    if speakers[0] < 2 or speakers[1] < speakers[0] or speakers[1] > len(have):
+        raise ValueError("speakers must be a range within 2 .. %d (the dataset's speakers)" % len(have))
+    if turns[0] < 1 or turns[1] < turns[0] or not 0 < turn_seconds[0] <= turn_seconds[1]:
+        raise ValueError("bad turn count or turn length range")
+    plan, segments, lens = [], [], []
+    for _ in range(int(n)):
+        cast = rng.choice(have, size=int(rng.integers(speakers[0], speakers[1] + 1)), replace=False)
+        prev, pos, seg, turn = -1, 0, [], []
+        for _ in range(int(rng.integers(turns[0], turns[1] + 1))):
+            who = int(rng.choice(cast[cast != prev]))
+            f = int(rng.choice(files_of[who]))
+            want = int(round(rng.uniform(turn_seconds[0], turn_seconds[1]) * SAMPLING_RATE))
+            take = max(1, min(want, int(length[f])))
+            start = int(rng.integers(0, int(length[f]) - take + 1))
+            turn.append((f, start, take))
+            seg.append((pos, pos + take, who))
+            pos, prev = pos + take, who
+        plan.append(turn)
+        segments.append(np.array(seg, dtype=np.int64))
+        lens.append(pos)
+    lens = np.array(lens, dtype=np.int64)
+    offsets = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64) if len(lens) else np.zeros(0, np.int64)
+    import torch
+    dev_audio = getattr(dataset, "device_audio", None)
+    if dev_audio is not None:
+        go = dataset.global_offset
+        parts = [dev_audio[int(go[f]) + s:int(go[f]) + s + k] for turn in plan for f, s, k in turn]
+        audio = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int16, device=dev_audio.device)
+    else:
+        from .shards import to_int16
+        cache = {}
+
+        def pcm(f):
+            if f not in cache:
+                cache[f] = np.asarray(dataset._pcm(f)) if hasattr(dataset, "_pcm") else to_int16(dataset._load(f))
+            return cache[f]
+        parts = [pcm(f)[s:s + k] for turn in plan for f, s, k in turn]
+        host = np.concatenate(parts).astype(np.int16) if parts else np.zeros(0, np.int16)
+        audio = torch.from_numpy(host)
+        if torch.cuda.is_available():
+            audio = audio.to("cuda")
+    return Conversations(audio, offsets, lens, segments, plan)
+
+
+# ---- the whole path --------------------------------------------------------------------------------------------------------------------
+def diarize(model, audio, offsets, lens, preprocessor, window_seconds: float, hop_seconds: float, network_type: str = "siamese",
+            distance: str = "cosine", linkage: str = "average", threshold: Optional[float] = None, n_speakers=None, batch: int = 256):
+    """Diarize the recordings ``audio[offsets[r] : offsets[r] + lens[r]]`` of a resident int16 buffer: sliding windows, every window
+    embedded alone (``embed_from_offsets(..., windows_per_tower=1)``, ``batch`` windows per call), ``cluster``, ``window_segments``.
+    Returns (segments per recording, the ``Clustering``); the clustering also carries ``emb`` (N, E), ``starts`` (per recording, relative
+    to it) and ``window``.  An engine without resident input raises what ``require_resident_input`` raises."""
+    import torch
+    from .engine_core import require_resident_input
+    from .retrieval import _encoder_engine
+    eng = _encoder_engine(model, network_type)
+    require_resident_input(type(eng))
+    inst = preprocessor.instance_preprocessor if hasattr(preprocessor, "instance_preprocessor") else preprocessor
+    probe = inst(np.zeros((1, 8, 1)))
+    if not hasattr(probe, "raw"):
+        raise ValueError("diarize needs a preprocessor that decimates and whitens on the device (utils.preprocess_instances)")
+    ds, wh = probe.downsampling, probe.whitening
+    offsets = np.asarray(offsets.cpu() if hasattr(offsets, "cpu") else offsets, dtype=np.int64).reshape(-1)
+    lens = np.asarray(lens.cpu() if hasattr(lens, "cpu") else lens, dtype=np.int64).reshape(-1)
+    if offsets.size != lens.size:
+        raise ValueError("offsets and lens differ in length")
+    if lens.size and (offsets.min() < 0 or int((offsets + lens).max()) > audio.numel()):
+        raise ValueError("a recording lies outside the audio buffer")
+    window, hop = int(round(window_seconds * SAMPLING_RATE)), int(round(hop_seconds * SAMPLING_RATE))
+    starts = sliding_windows(lens, window, hop)
+    row0 = np.concatenate([[0], np.cumsum([len(s) for s in starts])]).astype(np.int64)
+    _row_table(row0, int(row0[-1]))   # a recording with too many windows fails before anything is embedded
+    flat = np.concatenate([o + s for o, s in zip(offsets, starts)]) if len(starts) else np.zeros(0, np.int64)
+    emb = torch.empty(len(flat), eng.E, dtype=torch.float32, device=eng.device)
+    for b0 in range(0, len(flat), batch):
+        offs = torch.as_tensor(flat[b0:b0 + batch])
+        emb[b0:b0 + len(offs)].copy_(eng.embed_from_offsets(audio, offs, window, ds, wh, windows_per_tower=1))
+    res = cluster(emb, row0, distance, linkage, threshold, n_speakers)
+    res.emb, res.starts, res.window = emb, starts, window
+    labels = res.host().labels
+    segments = [window_segments(starts[r], window, int(lens[r]), labels[row0[r]:row0[r + 1]]) for r in range(len(lens))]
+    return segments, res
