@@ -409,6 +409,209 @@ def conv1_case(shape, regime, dt):
     return _conv1_case(tuple(shape), regime, case_key(dt, regime))
 
 
+# ---- block 1, fused backward: vm_conv1_fused_bwd -----------------------------------------------------------------------------------------
+# ((n, L, F), windows per tower).  256-position chunks, 32-position tiles, 32-channel column tiles (CT of them per 128 channels), Lq = L //
+# pool; a tile takes the fast path when all its 32 positions are pooled.
+CONV1_BWD_SHAPES = [
+    ((4, 701, 16), 2),      # 3 chunks, the last tile ragged (L % 2 = L % 4 = 1); one column tile shared by four waves
+    ((2, 534, 40), 2),      # L % 4 = 2; CT = 2 with an 8-channel second tile
+    ((3, 1283, 160), 3),    # 6 chunks, the last of 3 positions (pool 4: no pooled position in it at all); a second blockIdx.y
+    ((3, 1283, 160), 1),    # ... and three towers
+    ((2, 291, 96), 1),      # CT = 3 with one idle wave; L % 4 = 3
+    ((1, 512, 32), 1),      # exactly two chunks, no remainder: the `more` prefetch must not read a chunk that does not exist
+    ((1, 5, 8), 1),         # L just above pool: one (pool 4) or two pooled positions and a remainder row, no fast tile
+]
+CONV1_BWD_LO_SHAPES = [CONV1_BWD_SHAPES[1], CONV1_BWD_SHAPES[5]]      # the lo regimes: also test_conv1_fused_bwd_products' shapes
+CONV1_BWD_REGIMES = ("small", "rounded", "lo-x", "lo-w")
+CONV1_BWD_GRIDS = ("default", "window", "split")      # vm_set_tuning("f1_blocks", .): untouched (1024), n, 2 n
+
+
+def f1_splits(n, chunks, target):
+    """(workgroups per window, chunks per workgroup) of the fused block-1 backward (csrc/conv1_fused.hip f1_splits)."""
+    s = min(max(-(-target // n), 1), chunks)
+    cps = -(-chunks // s)
+    return -(-chunks // cps), cps
+
+
+def f1_grid(n, l, form):
+    return f1_splits(n, -(-l // 256), {"default": 1024, "window": n, "split": 2 * n}[form])
+
+
+def conv1_bwd_grids(n, l):
+    """The grid forms that differ at this shape: `window` walks every chunk of a window in one workgroup (the double-buffered loop),
+    `split` gives two workgroups per window -- of 2 + 1 chunks at three chunks (a short last split), 3 + 3 at six."""
+    forms, seen = [], set()
+    for form in CONV1_BWD_GRIDS:
+        g = f1_grid(n, l, form)
+        if g not in seen:
+            seen.add(g)
+            forms.append(form)
+    return forms
+
+
+def _conv1_bwd_cases():
+    """(dt, regime, n, L, F, wpt, pool, drop, grid form).  Every (pool, drop) pair on the default grid; the other grid forms where they
+    differ from it, on the diagonal (pool 2, no drop), (pool 4, drop).  The lo regimes at two shapes; `rounded` not at (1, 5, 8), whose
+    40 elements cannot hold the census it asserts.  Ordered so that the cases of one reference are neighbours (the caches are small)."""
+    out = []
+    for (shape, wpt) in CONV1_BWD_SHAPES:
+        for regime in CONV1_BWD_REGIMES:
+            if (regime in ("lo-x", "lo-w") and (shape, wpt) not in CONV1_BWD_LO_SHAPES) or (regime == "rounded" and shape[1] < 256):
+                continue
+            for pool in (2, 4):
+                for drop in (False, True):
+                    for form in conv1_bwd_grids(shape[0], shape[1]):
+                        if form == "default" or drop == (pool == 4):
+                            out += [(dt, regime) + shape + (wpt, pool, drop, form) for dt in DT16]
+    return out
+
+
+CONV1_BWD_CASES = _conv1_bwd_cases()
+CONV1_BWD_PRODUCT_CASES = [(regime,) + shape + (wpt, pool, pool == 4) for shape, wpt in CONV1_BWD_LO_SHAPES for pool in (2, 4)
+                           for regime in ("small", "lo-x", "lo-w")]
+# every (shape, wpt, regime, pool, drop) the device file builds a reference for: the host file walks it
+ALL_CONV1_BWD_CASES = sorted({c[2:5] + (c[5], c[1], c[6], c[7]) for c in CONV1_BWD_CASES} |
+                             {c[1:4] + (c[4], c[0], c[5], c[6]) for c in CONV1_BWD_PRODUCT_CASES})
+
+
+def dyadic_grid(a):
+    """The largest power of two that every element of `a` is a multiple of (1 for an array of integers or of zeros)."""
+    a = np.asarray(a, dtype=np.float64)
+    g = 1.0
+    while not np.array_equal(a / g, np.round(a / g)):
+        g /= 2
+        assert g > 2.0 ** -40
+    return g
+
+
+def conv1_wgrad(xp, du):
+    """xp (n, L + 31) padded waveform, du (n, L, F) -> (32, 1, F): gw[k] = sum_{n, t} xp[n][t + k] * du[n][t]."""
+    win = np.lib.stride_tricks.sliding_window_view(xp, 32, axis=1)                  # (n, L, 32)
+    return (win.reshape(-1, 32).T @ du.reshape(-1, du.shape[2]))[:, None, :]
+
+
+class Conv1BwdCase:
+    """vm_conv1_fused_bwd on the waveform, filters and bias of a Conv1Case: per-tower scale, mean, invstd, c1, c2 (towers, F), drop (n, F)
+    in {0, 2} or None, dp (n, L // pool, F) small integers.  The kernel folds ga = scale * drop, gb0 = scale * (invstd * c2 * mean - c1),
+    gc = -scale * invstd * c2 in fp32 and forms du = [z > 0] * (gc * z + gb0 + [first extreme] * ga * dp) by fmas; with scale in +-{1, 2}
+    (one 0), invstd in {0.5, 1}, c2 = +-1 / (invstd * |scale|) (so gc = +-1) and integer mean, c1 in [-2, 2] every one of them is exact.
+    References (float64): z = the UNROUNDED relu(conv + b), du_exact from bn_exact.backward, du = bf16(du_exact) under both storage types
+    (the kernel hands du to the weight-gradient MFMA as bf16 whatever the storage type is), gw[k] = sum bf16(x)[t + k] * du[t], gb = sum du.
+
+    Regimes: `small` (Conv1Case small: du exact in bf16, a census of tied and of all-non-positive pool windows), `rounded` (Conv1Case wide
+    of the bf16 class for both storage types: du rounded, a census of its rounding), lo-x / lo-w (the recompute of z needs the cross
+    product; dropping it must change gw).  The lo regimes take c2 = 0 (gc = 0), so that du is an integer which the lo product decides
+    through the ReLU mask and the routing of near-ties.  With gc = +-1 du inherits the 2^-9 / 2^-12 grid of z and the sums miss the
+    precondition at these shapes: lo-x (bf16(x) on a 2^-8 grid) sum |bf16(x)| |du| = 6.9e8 units of 2^-17 at (2, 534, 40), 41 times 2^24;
+    lo-w sum |du| = 1.8e7 .. 2.9e7 units of 2^-12, 1.1 .. 1.7 times 2^24.  gc * z itself is covered by `small` and `rounded`.
+
+    The scale signs by (tower, 32-channel tile), the unit of the kernel's wave-uniform choice: the first is all >= 0 with the zero (the
+    all_max path), the second mixed (use_min), the rest as drawn.  A shape with one tower and one tile takes its one path from `drop`:
+    all_max with dropout, mixed without."""
+
+    def __init__(self, shape, regime, pool, wpt, drop):
+        from tests import bn_exact as B
+        n, l, f = shape
+        assert n % wpt == 0 and l >= pool and f % 8 == 0
+        self.shape, self.regime, self.pool, self.wpt = shape, regime, pool, wpt
+        self.towers, self.lq = n // wpt, l // pool
+        self.c = c = conv1_case(shape, "wide", "bf16") if regime == "rounded" else conv1_case(shape, regime, "f16")
+        r = np.random.default_rng([n, l, f, pool, wpt, int(drop), sum(map(ord, regime))])
+        towers, tiles = self.towers, -(-f // 32)
+        scale = r.choice([1.0, 2.0], (towers, f)) * r.choice([-1.0, 1.0], (towers, f))
+        units = [(t, j) for t in range(towers) for j in range(tiles)]
+        plan = ["max" if drop else "min"] if len(units) == 1 else ["max", "min"]
+        for (t, j), kind in zip(units, plan):
+            ch = slice(32 * j, min(32 * j + 32, f))
+            width = ch.stop - ch.start
+            if kind == "max":
+                scale[t, ch] = np.abs(scale[t, ch])
+                scale[t, ch.start + 5 % width] = 0.0
+            else:
+                scale[t, ch.start], scale[t, ch.start + 1] = -abs(scale[t, ch.start]), abs(scale[t, ch.start + 1])
+                if len(units) == 1:
+                    scale[t, ch.start + 5 % width] = 0.0
+        self.scale = scale
+        self.invstd = r.choice([0.5, 1.0], (towers, f))
+        mag = np.where(scale == 0, 1.0, 1.0 / (self.invstd * np.maximum(np.abs(scale), 1.0)))
+        self.c2 = r.choice([-1.0, 1.0], (towers, f)) * mag * (0.0 if regime in ("lo-x", "lo-w") else 1.0)
+        self.mean, self.c1 = _ints(r, (towers, f), 2), _ints(r, (towers, f), 2)
+        self.drop = None
+        if drop:
+            self.drop = 2.0 * (r.random((n, f)) < 0.75)
+            self.drop[0, 0], self.drop[0, 2 % f] = 2.0, 0.0
+        self.dp = _ints(r, (n, self.lq, f), 3)
+        self.paths = {(t, j): "min" if (scale[t, 32 * j:32 * j + 32] < 0).any() else "max" for t, j in units}
+        assert (scale == 0).any() and all(self.paths[u] == k for u, k in zip(units, plan))
+        assert any(k == "max" and (scale[t, 32 * j:32 * j + 32] == 0).any() for (t, j), k in self.paths.items()) or plan == ["min"]
+
+        # ---- the constants the kernel folds and every intermediate of du: fp32 numbers, in any association
+        pw = lambda a: B.per_window(a, wpt)
+        sc, mu, is_, k1, k2 = pw(self.scale), pw(self.mean), pw(self.invstd), pw(self.c1), pw(self.c2)
+        dr = np.ones((n, 1, f)) if self.drop is None else self.drop[:, None, :]
+        self.ga, self.gb0, self.gc = sc * dr, sc * (is_ * k2 * mu - k1), -sc * is_ * k2
+        for v in (self.scale, self.mean, self.invstd, self.c1, self.c2, self.ga, self.gb0, self.gc, is_ * k2, k2 * mu, is_ * k2 * mu,
+                  is_ * k2 * mu - k1, sc * is_, sc * k2):
+            assert exact_in(v, "f32")
+        assert exact_in(self.dp, "bf16") and exact_in(self.dp, "f16") and exact_in(bf16_halves(c.x)[0], "bf16")
+        assert set(np.unique(np.abs(self.gc))) <= ({0.0} if regime in ("lo-x", "lo-w") else {0.0, 1.0})
+        self.xh = pad_wave(bf16_halves(c.x)[0])
+        self.du_exact, self.du, self.gw, self.gb = self.reference(c.z, check=True)
+
+        # ---- the censuses and the discriminating power, from the inputs and the references alone
+        g = B.groups(c.z, pool)
+        self.windows = g.shape[0] * g.shape[1] * f
+        ext, _ = B.route(c.z, np.broadcast_to(sc, (n, 1, f)), pool)
+        self.tied = float(((g == ext[:, :, None, :]).sum(2) >= 2).mean()) if self.windows else 0.0
+        live = (ext > 0) & (self.dp != 0) & np.broadcast_to(self.ga != 0, ext.shape)
+        self.tied_live = float((((g == ext[:, :, None, :]).sum(2) >= 2) & live).mean()) if self.windows else 0.0
+        self.all_nonpositive = float((g.max(2) <= 0).mean()) if self.windows else 0.0
+        if regime == "small":
+            assert exact_in(self.du_exact, "bf16"), "small: du must be exact in bf16"
+            if self.windows >= 1000:
+                assert self.tied >= 0.05 and self.all_nonpositive >= 0.05 and self.tied_live >= 0.01, (
+                    self.tied, self.all_nonpositive, self.tied_live)
+            assert self.head >= 6.0, self.head
+        if regime == "rounded":
+            self.census = rounding_census(self.du_exact[self.du_exact != 0], "bf16")
+            assert self.census[0] >= 0.05 and self.census[1] >= 100, self.census
+        if regime == "lo-x":
+            self.gw_dropped = self.reference(c.z_xhi)[2]               # x_lo * w_hi left out of the recompute
+            self.gw_full_x = conv1_wgrad(pad_wave(c.x), self.du)       # the filter gradient formed from x, not bf16(x)
+            assert not np.array_equal(self.gw_full_x, self.gw)
+        if regime == "lo-w":
+            self.du_hi, self.gw_hi, self.gb_hi = self.reference(c.z_hi, check=True)[1:]    # f1_products = 1: x_hi * w_hi alone
+            self.gw_dropped = self.gw_hi
+        if regime in ("lo-x", "lo-w"):
+            self.dropped_share = float((self.gw_dropped != self.gw).mean())
+            assert self.dropped_share >= 0.01, self.dropped_share
+
+    def reference(self, z, check=False):
+        """(du_exact, du, gw, gb) for the recomputed activations z; check: assert the preconditions of this reference (head: the
+        smaller head-room of the two sums, a factor)."""
+        from tests import bn_exact as B
+        n, l, f = self.shape
+        du_exact = B.backward(z, self.dp, self.scale, self.mean, self.invstd, self.drop, self.c1, self.c2, self.wpt, self.pool)[2]
+        du = store(du_exact, "bf16")
+        if check:
+            # every intermediate of the three evaluation orders of the kernel: fma(gc, z, gb0 or gb1), fma(gc, z, gb0) + ga * dp
+            dpr = np.zeros((n, l, f))
+            dpr[:, :self.lq * self.pool] = np.repeat(self.dp, self.pool, axis=1)
+            for v in (self.gc * z, self.ga * dpr, self.ga * dpr + self.gb0, self.gc * z + self.gb0, self.gc * z + self.gb0 + self.ga * dpr,
+                      du_exact):
+                assert exact_in(v, "f32"), "an intermediate of du is not an fp32 number"
+            grid = dyadic_grid(self.xh) * dyadic_grid(du)
+            heads = (require_exact_sums(conv1_wgrad(np.abs(self.xh), np.abs(du)), grid, "conv1 fused bwd: sum |bf16(x)| |du|"),
+                     require_exact_sums(np.abs(du).sum((0, 1)), dyadic_grid(du), "conv1 fused bwd: sum |du|"))
+            self.head = min(getattr(self, "head", np.inf), LIMIT / max(max(heads), 1.0))
+        return du_exact, du, conv1_wgrad(self.xh, du), du.sum((0, 1))
+
+
+@functools.lru_cache(maxsize=4)
+def conv1_bwd_case(shape, regime, pool, wpt, drop):
+    return Conv1BwdCase(tuple(shape), regime, pool, wpt, bool(drop))
+
+
 # ---- the comparator ------------------------------------------------------------------------------------------------------------------
 LAYOUTS = {"nlc": ("window", "position", "channel"), "kio": ("tap", "c_in", "c_out"), "nc": ("window", "channel"),
            "tkc": ("tower", "tap", "channel"), "c": ("channel",), "k1f": ("filter tap", "one", "filter"), "tc": ("tower", "channel"),

@@ -207,3 +207,87 @@ def test_comparator_zero_signs_and_report():
     assert "worst at (window 1, position 599, channel 2 [128-tile 4, 254-tile 2, 0 from the window edge]" in msg
     with pytest.raises(AssertionError, match="1 of 3 elements differ"):
         assert_exact(torch.tensor([1.0, float("nan"), 3.0]), np.array([1.0, 2.0, 3.0]), "c")
+
+
+# ---- the fused block-1 backward ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,l,f,wpt,regime,pool,drop", G.ALL_CONV1_BWD_CASES)
+def test_conv1_bwd_cases_meet_their_preconditions(n, l, f, wpt, regime, pool, drop):
+    """Constructing a case asserts: the folded constants and every intermediate of du are fp32 numbers; sum |bf16(x)| |du| and sum |du|
+    < 2^24 grid units; the sign plan by (tower, 32-channel tile); `small`: du exact in bf16, >= 5 % of the pool windows tied for the
+    extreme (>= 1 % with a positive extreme and a gradient on it), >= 5 % with no positive pre-activation, >= 6 x head-room; `rounded`:
+    >= 5 % of the non-zero du changed by the bf16 rounding, >= 100 exact ties; lo-x / lo-w: leaving the lo product out of the recompute
+    changes >= 1 % of gw, and (lo-x) the filter gradient of x differs from that of bf16(x)."""
+    c = G.Conv1BwdCase((n, l, f), regime, pool, wpt, drop)
+    kinds = set(c.paths.values())
+    assert kinds == {"max", "min"} or (len(c.paths) == 1 and kinds == {"max" if drop else "min"})
+    if f == 16:
+        assert c.paths[(0, 0)] == "max" and c.paths[(1, 0)] == "min"         # one tile per tower: the two paths in different towers
+    for u, kind in c.paths.items():                                          # the kernel's own rule, per wave
+        t, j = u
+        assert (kind == "max") == (not (c.scale[t, 32 * j:32 * j + 32] < 0).any())
+    assert (c.drop is None) == (not drop) and (not drop or ({0.0, 2.0} == set(np.unique(c.drop))))
+    assert c.du.shape == (n, l, f) and c.gw.shape == (32, 1, f) and c.gb.shape == (f,)
+    assert np.array_equal(c.du, G.store(c.du_exact, "bf16")) and (regime != "rounded" or not G.exact_in(c.du_exact, "bf16"))
+    rem = c.du[:, c.lq * pool:]
+    assert l % pool == 0 or rem.any(), "the remainder rows carry no du: dropping them would go unseen"
+
+
+def test_conv1_bwd_tables_reach_what_they_name():
+    """Every regime, pool, drop form and sign path at every shape it can differ on, both storage types; the grid forms: `window` one
+    workgroup per window wherever there is more than one chunk, `split` a short last split at three chunks and 3 + 3 at six."""
+    cases = G.CONV1_BWD_CASES
+    for shape, wpt in G.CONV1_BWD_SHAPES:
+        mine = [c for c in cases if c[2:6] == shape + (wpt,)]
+        regimes = {"small"} | ({"rounded"} if shape[1] >= 256 else set()) | ({"lo-x", "lo-w"} if (shape, wpt) in G.CONV1_BWD_LO_SHAPES else set())
+        assert {c[1] for c in mine} == regimes
+        for regime in regimes:
+            sub = [c for c in mine if c[1] == regime]
+            for dt in G.DT16:
+                assert {(c[6], c[7]) for c in sub if c[0] == dt and c[8] == "default"} == {(2, False), (2, True), (4, False), (4, True)}
+                forms = {c[8] for c in sub if c[0] == dt}
+                assert forms == set(G.conv1_bwd_grids(shape[0], shape[1]))
+                for form in forms - {"default"}:
+                    assert {(c[6], c[7]) for c in sub if c[0] == dt and c[8] == form} == {(2, False), (4, True)}
+    chunks = lambda l: -(-l // 256)
+    assert [chunks(s[1]) for s, _ in G.CONV1_BWD_SHAPES] == [3, 3, 6, 6, 2, 2, 1]
+    assert G.f1_grid(4, 701, "default") == (3, 1) and G.f1_grid(4, 701, "window") == (1, 3)
+    assert G.f1_grid(4, 701, "split") == (2, 2) and G.f1_grid(2, 534, "split") == (2, 2)      # 2 + 1 chunks: the clamp of ch_hi
+    assert G.f1_grid(3, 1283, "split") == (2, 3) and G.f1_grid(3, 1283, "window") == (1, 6)
+    assert G.conv1_bwd_grids(1, 512) == ["default", "window"] and G.conv1_bwd_grids(1, 5) == ["default"]
+    # the single-unit shapes take both sign paths across their (pool, drop) pairs
+    for shape in ((1, 512, 32), (1, 5, 8)):
+        for pool in (2, 4):
+            assert {tuple(G.conv1_bwd_case(shape, "small", pool, 1, d).paths.values()) for d in (False, True)} == {("max",), ("min",)}
+    assert all(c in G.ALL_CONV1_BWD_CASES for c in {k[1:4] + (k[4], k[0], k[5], k[6]) for k in G.CONV1_BWD_PRODUCT_CASES})
+
+
+def test_conv1_bwd_du_is_the_autograd_gradient():
+    """du_exact against an independent derivation: torch autograd in float64 through conv -> ReLU -> per-tower BatchNorm -> dropout ->
+    max-pool, at the pre-activation.  The gradient formula holds for the TRUE batch statistics, so this sub-case takes mean / invstd
+    from z and c1 / c2 from bn_exact.finalize (which casts them to fp32 once: the comparison is at that round-off, not equality)."""
+    from tests import bn_exact as B
+    shape, pool, wpt = (4, 701, 16), 2, 2
+    n, l, f = shape
+    c = G.Conv1BwdCase(shape, "small", pool, wpt, True)
+    u = G.conv32(c.c.x, c.c.w) + c.c.b
+    z = np.maximum(u, 0.0)
+    assert np.array_equal(z, c.c.z)
+    zt = z.reshape(n // wpt, wpt * l, f)
+    mean, invstd = zt.mean(1), 1.0 / np.sqrt(zt.var(1) + 1e-3)
+    gamma = c.scale                                                        # (towers, F): any per-tower factor of both signs, one 0
+    scale = gamma * invstd
+    dy, zhat, _, sdy, sdyz = B.backward(z, c.dp, scale, mean, invstd, c.drop, 0.0 * mean, 0.0 * mean, wpt, pool)
+    c1, c2, _, _ = B.finalize(sdy, sdyz, wpt, float(wpt * l))
+    du = B.backward(z, c.dp, scale, mean, invstd, c.drop, c1, c2, wpt, pool)[2]
+
+    ut = torch.tensor(u, dtype=torch.float64, requires_grad=True)
+    zz = torch.relu(ut).view(n // wpt, wpt * l, f)
+    m, v = zz.mean(1, keepdim=True), zz.var(1, unbiased=False, keepdim=True)
+    y = ((zz - m) / torch.sqrt(v + 1e-3) * torch.tensor(gamma)[:, None, :]).view(n, l, f) * torch.tensor(c.drop)[:, None, :]
+    out = torch.nn.functional.max_pool1d(y.transpose(1, 2), pool).transpose(1, 2)
+    (out * torch.tensor(c.dp)).sum().backward()
+    want = ut.grad.numpy()
+    # c1, c2 carry one fp32 rounding each (2^-24 relative); everything else is float64
+    bound = 2.0 ** -23 * np.abs(B.per_window(scale, wpt)) * (np.abs(B.per_window(c1, wpt)) + np.abs(zhat * B.per_window(c2, wpt))) + 1e-12
+    assert want.any() and (np.abs(du - want) <= bound).all(), float(np.abs(du - want).max())
+    assert np.abs(du - want).max() < 1e-6 * np.abs(want).max()

@@ -28,6 +28,8 @@ Which test reaches which kernel form (vm_set_tuning's GEMM keys; conv_gemm.hip /
   vm_conv_wgrad_fold_finish                          and two-call forms bit-identical)
   block 1: conv1 fwd / wgrad, fused fwd modes 0-2    test_conv1_fwd_wgrad, test_conv1_fused_fwd, test_conv1_fused_fwd_products (f1_products
                                                      1 / 2 / 3)
+  block 1: conv1_fused_bwd_kernel (all_max and       test_conv1_fused_bwd (three grid forms of f1_blocks), test_conv1_fused_bwd_products
+  use_min fast tiles, the ragged slow tile, slabs)   (f1_products 1 / 2 / 3), test_conv1_fused_bwd_refuses
 """
 import numpy as np
 import pytest
@@ -451,3 +453,72 @@ def test_conv1_fused_fwd_products(n, l, f, pool, products, f1_tuning):
         c = G.conv1_case((n, l, f), regime, "f16")
         z = c.z_hi if (regime == "lo-w" and products == 1) else c.z
         _conv1_fused_modes("f16", c, z, (n, l, f), pool, "f16 %s %s pool %d f1_products %d" % (regime, (n, l, f), pool, products))
+
+
+# ---- block 1, the fused backward -----------------------------------------------------------------------------------------------------------
+GUARD = 64                  # fp32 words behind the queried workspace size
+GUARD_WORD = -12345.0
+
+
+def _conv1_fused_bwd(dt, c, n, l, f, wpt, pool, want_gw, want_gb, tag):
+    """One call of vm_conv1_fused_bwd on the operands of a Conv1BwdCase: grad_w and grad_b (NaN before the call: it overwrites them)
+    bit for bit, the words behind the queried workspace size and every input untouched.  The workspace size is queried here, after
+    the caller has set its tuning."""
+    vm, tdt = DTYPES[dt]
+    words = L().query("vm_conv1_fused_bwd_workspace_bytes", n, l, f) // 4
+    ws = torch.full((words + GUARD,), GUARD_WORD, dtype=torch.float32, device="cuda")
+    ins = [dev(G.pad_wave(c.c.x)), dev(c.c.w), dev(c.c.b), dev(c.dp, tdt), dev(c.scale), dev(c.mean), dev(c.invstd),
+           None if c.drop is None else dev(c.drop), dev(c.c1), dev(c.c2)]
+    before = [None if t is None else t.clone() for t in ins]
+    gw, gb = _nan(32, 1, f), _nan(f)
+    L().call("vm_conv1_fused_bwd", *[p(t) for t in ins], n, wpt, l, f, pool, vm, p(ws), p(gw), p(gb), stream())
+    assert_exact(gw, want_gw, "k1f", what="vm_conv1_fused_bwd grad_w " + tag)
+    assert_exact(gb, want_gb, "c", what="vm_conv1_fused_bwd grad_b " + tag)
+    assert (ws[words:] == GUARD_WORD).all(), "vm_conv1_fused_bwd wrote behind its workspace " + tag
+    for name, t, t0 in zip(("x", "w", "bias", "dp", "scale", "mean", "invstd", "drop", "c1", "c2"), ins, before):
+        assert t is None or torch.equal(t.view(G.INT_VIEW[t.dtype]), t0.view(G.INT_VIEW[t.dtype])), "vm_conv1_fused_bwd changed %s %s" % (name, tag)
+
+
+@pytest.mark.parametrize("dt,regime,n,l,f,wpt,pool,drop,form", G.CONV1_BWD_CASES)
+def test_conv1_fused_bwd(dt, regime, n, l, f, wpt, pool, drop, form, f1_tuning):
+    """vm_conv1_fused_bwd against gemm_exact.Conv1BwdCase: grad_w = sum bf16(x)[t + k] * bf16(du)[t] and grad_b = sum bf16(du) with du
+    from bn_exact.backward on the unrounded z -- the first maximum of a pool window, the first minimum where scale < 0, remainder rows
+    in the sums with no pooled gradient.  Grid forms (f1_blocks): the default (one workgroup per chunk), `window` (n: one workgroup
+    walks a window's chunks through the double-buffered loop), `split` (2 n: two workgroups per window, 2 + 1 chunks at three chunks).
+    The default f1_products = 2 under f16."""
+    if form != "default":
+        f1_tuning(b"f1_blocks", n if form == "window" else 2 * n)
+    c = G.conv1_bwd_case((n, l, f), regime, pool, wpt, drop)
+    tag = "%s %s %s wpt %d pool %d drop %d grid %s" % (dt, regime, (n, l, f), wpt, pool, drop, form)
+    _conv1_fused_bwd(dt, c, n, l, f, wpt, pool, c.gw, c.gb, tag)
+
+
+@pytest.mark.parametrize("products", [1, 2, 3])
+@pytest.mark.parametrize("regime,n,l,f,wpt,pool,drop", G.CONV1_BWD_PRODUCT_CASES)
+def test_conv1_fused_bwd_products(regime, n, l, f, wpt, pool, drop, products, f1_tuning):
+    """f1_products 1 / 2 / 3 (VM_F16): the same exact gradients under all three on filters of 8 bits (small) and a waveform a half
+    holds (lo-x: under 3 its bf16 lo half makes x_lo * w_hi necessary); lo-w filters, exact only as hi + lo, under 2 and 3 -- and
+    under 1 the gradients of z = relu(x * half(w) + b), which the host file has shown to differ: mask and routing follow the
+    recomputed z, and the lo product is issued exactly where it is asked for."""
+    f1_tuning(b"f1_products", products)
+    c = G.conv1_bwd_case((n, l, f), regime, pool, wpt, drop)
+    gw, gb = (c.gw_hi, c.gb_hi) if (regime == "lo-w" and products == 1) else (c.gw, c.gb)
+    _conv1_fused_bwd("f16", c, n, l, f, wpt, pool, gw, gb, "f16 %s %s pool %d f1_products %d" % (regime, (n, l, f), pool, products))
+
+
+@pytest.mark.parametrize("what,l,f,pool,dt", [("L < pool", 3, 8, 4, "bf16"), ("pool = 3", 64, 8, 3, "bf16"), ("VM_F32", 64, 8, 2, "f32"),
+                                              ("F % 8 != 0", 64, 12, 2, "f16")],
+                         ids=["short-window", "pool-3", "fp32-storage", "filters-not-by-8"])
+def test_conv1_fused_bwd_refuses(what, l, f, pool, dt):
+    """Bad arguments return non-zero before anything is launched: grad_w stays as it was."""
+    vm, tdt = DTYPES[dt]
+    n, lq = 2, max(l // pool, 1)
+    z = lambda *s: torch.zeros(*s, device="cuda")
+    gw, gb = _nan(32, 1, f), _nan(f)
+    ws = torch.zeros(L().query("vm_conv1_fused_bwd_workspace_bytes", n, 64, 16) // 4, device="cuda")
+    dp = torch.zeros(n, lq, f, dtype=tdt, device="cuda")
+    rc = L().query("vm_conv1_fused_bwd", p(z(n, l + 31)), p(z(32, 1, f)), p(z(f)), p(dp), p(z(n, f)), p(z(n, f)), p(z(n, f)), None,
+                   p(z(n, f)), p(z(n, f)), n, 1, l, f, pool, vm, p(ws), p(gw), p(gb), stream())
+    torch.cuda.synchronize()
+    assert rc != 0, what
+    assert torch.isnan(gw).all() and torch.isnan(gb).all(), what + ": the gradients were written"
