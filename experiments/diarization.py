@@ -10,7 +10,10 @@ the sample-exact diarization error rate against the turns that were planted.  On
         --window-seconds 1.5 --hop-seconds 0.75 --linkage average --distance cosine --tune-conversations 16
 Prints one JSON line: the mean DER and its three parts (shares of the reference speech), and how many clusters were found against how
 many speakers were present.  With --synthetic and no --siamese the encoder is untrained: the line then says how the pipeline runs, not
-how well a model diarizes."""
+how well a model diarizes.
+--distance plda: a PLDA back end (voicemap_amd/plda.py) is fitted on the embeddings of the single-speaker files the conversations are
+built from (one first-fragment window per file, --lda-dim / --no-length-norm as in experiments/verification_accuracy.py) and the
+windows are clustered on minus its log-likelihood ratio."""
 import argparse
 import json
 import os
@@ -49,7 +52,9 @@ def _parser():
     p.add_argument("--hop-seconds", type=float, default=0.75)
     p.add_argument("--downsampling", type=int, default=4)
     p.add_argument("--linkage", default="average", choices=list(DZ.LINKAGES))
-    p.add_argument("--distance", default="cosine", choices=["euclidean", "cosine", "dot_product"])
+    p.add_argument("--distance", default="cosine", choices=["euclidean", "cosine", "dot_product", "plda"])
+    p.add_argument("--lda-dim", type=int, default=None, help="--distance plda: LDA directions kept (default: all)")
+    p.add_argument("--no-length-norm", action="store_true", help="--distance plda: no length normalisation between LDA and PLDA")
     p.add_argument("--seed", type=int, default=0)
     stop = p.add_mutually_exclusive_group(required=True)
     stop.add_argument("--threshold", type=float, default=None)
@@ -118,6 +123,9 @@ def main(argv=None):
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
     conv = DZ.make_conversations(data, a.conversations, speakers=a.speakers, turns=a.turns, seed=a.seed)
     kw = dict(distance=a.distance, linkage=a.linkage)
+    if a.distance == "plda":
+        from voicemap_amd import plda, retrieval
+        kw["plda"] = plda.fit_plda(retrieval.embed_corpus(net, data, pre, "siamese"), lda_dim=a.lda_dim, length_norm=not a.no_length_norm)
     rows = list(range(len(conv)))
     out = {"conversations": len(conv), "linkage": a.linkage, "distance": a.distance, "window_seconds": a.window_seconds,
            "hop_seconds": a.hop_seconds}

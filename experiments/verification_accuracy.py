@@ -13,7 +13,11 @@ every set first (voicemap_amd/vad.py), the trimming summary is printed and joins
 --dcf P[,CMISS,CFA] (repeatable) adds the test set's exact minimum detection cost at each operating point (columns
 test_min_dcf_<point>, with its threshold), and the file name gains _dcf.  --calibrate [--calib-prior P] fits llr = a s + b on the
 validation trials (voicemap_amd/calibration.py) and adds Cllr of both sets and, per --dcf point (without one: (P, 1, 1) at the
-calibration prior), the test set's actDCF at the Bayes threshold beside its minDCF; the file name gains _calib."""
+calibration prior), the test set's actDCF at the Bayes threshold beside its minDCF; the file name gains _calib.
+--backend plda [--plda-train train|validation --plda-train-set train-clean-100 --lda-dim D --no-length-norm] puts a PLDA back end
+(voicemap_amd/plda.py: LDA, length normalisation, two-covariance PLDA) in front of everything: it is fitted on the training set
+(--plda-train train: --plda-train-set, a further generated set with --synthetic) or on the validation set itself, every set and the
+cohort are projected by it and scored by minus its log-likelihood ratio (--score is then not used); the file name gains _plda."""
 import argparse
 
 import numpy as np
@@ -64,12 +68,14 @@ def parse_dcf(text):
 
 
 def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort=None, top_k=300, whole_utterance=False, vad=None,
-             dcf=(), calibrate=False, calib_prior=0.5):
+             dcf=(), calibrate=False, calib_prior=0.5, backend="none", plda_train=None, lda_dim=None, length_norm=True):
     """Embed both sets once, take the best-balanced-accuracy threshold of the validation trials and apply it to the test trials.
     ``score_norm`` "s-norm" / "as-norm": both sets' scores are normalised against the embeddings of ``cohort`` (a dataset).
     ``vad`` (a ``vad.VadPolicy``): every set, the cohort included, is embedded with its pauses trimmed out.
     ``dcf``: detection-cost points for the test set; ``calibrate``: fit llr = a s + b on the validation trials at ``calib_prior`` and
-    report Cllr and, per point, actDCF on the test set (module docstring)."""
+    report Cllr and, per point, actDCF on the test set (module docstring).
+    ``backend`` "plda": a ``plda.PldaModel`` is fitted on the embeddings of ``plda_train`` (a dataset; None: the validation set) with
+    ``lda_dim`` / ``length_norm``, every set and the cohort are projected by it and the score is "plda"."""
     dcf = verification.as_dcf_points(dcf)
     if calibrate and not dcf:
         dcf = [(float(calib_prior), 1.0, 1.0)]
@@ -79,9 +85,19 @@ def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort
         wu["vad"] = vad
     cv = retrieval.embed_corpus(net, valid, pre, "siamese", **wu)
     ct = retrieval.embed_corpus(net, test, pre, "siamese", **wu)
+    back = None
+    if backend == "plda":
+        from voicemap_amd import plda
+        back = plda.fit_plda(cv if plda_train is None else retrieval.embed_corpus(net, plda_train, pre, "siamese", **wu), lda_dim=lda_dim,
+                             length_norm=length_norm)
+        cv, ct, score, model = back.project(cv), back.project(ct), "plda", None
+    elif backend != "none":
+        raise ValueError("backend must be none or plda")
     nv = nt = None
     if score_norm != "none":
         cc = retrieval.embed_corpus(net, cohort, pre, "siamese", **wu)
+        if back is not None:
+            cc = back.project(cc)
         k = None if score_norm == "s-norm" else top_k
         nv = verification.score_norm(cv, cc, score, top_k=k, model=model)
         nt = verification.score_norm(ct, cc, score, top_k=k, model=model)
@@ -110,6 +126,9 @@ def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort
         if calibrate:
             row["test_act_dcf_" + name] = d.get("act_dcf", float("nan"))
             row["test_act_threshold_" + name] = d.get("act_threshold", float("nan"))
+    if back is not None:
+        row.update(backend="plda", plda_dim=back.D, lda_dim=back.A1.shape[0], length_norm=back.length_norm,
+                   plda_train="validation" if plda_train is None else "train")
     if whole_utterance:
         row["whole_utterance"] = True
     if score_norm != "none":
@@ -125,7 +144,8 @@ def evaluate(net, valid, test, pre, score="euclidean", score_norm="none", cohort
 def result_name(a):
     """logs/ file name of a run (``a``: the parsed arguments)."""
     name = "verification_accuracy_{}_{}_{}".format("synthetic" if a.synthetic else a.validation_set,
-                                                   "synthetic" if a.synthetic else a.test_set, a.score)
+                                                   "synthetic" if a.synthetic else a.test_set,
+                                                   "plda" if getattr(a, "backend", "none") == "plda" else a.score)
     if a.score_norm != "none":
         name += "_" + a.score_norm.replace("-", "") + ("_k%d" % a.top_k if a.score_norm == "as-norm" else "") + "_c%d" % a.cohort_size
     if getattr(a, "whole_utterance", False):
@@ -161,6 +181,11 @@ def _parser():
                    help="a detection-cost operating point for the test set's minDCF (repeatable)")
     p.add_argument("--calibrate", action="store_true", help="fit llr = a s + b on the validation set; Cllr and actDCF on the test set")
     p.add_argument("--calib-prior", type=float, default=0.5, help="the target prior of the calibration fit")
+    p.add_argument("--backend", default="none", choices=["none", "plda"], help="a trained back end in front of the scorers (off by default)")
+    p.add_argument("--plda-train", default="train", choices=["train", "validation"], help="the set the PLDA back end is fitted on")
+    p.add_argument("--plda-train-set", default="train-clean-100", help="the training subset of --plda-train train")
+    p.add_argument("--lda-dim", type=int, default=None, help="LDA directions kept in front of PLDA (default: all)")
+    p.add_argument("--no-length-norm", action="store_true", help="no length normalisation between LDA and PLDA")
     add_vad_args(p)   # --vad ...: off by default; every set embedded, the cohort included, is trimmed first
     return p
 
@@ -198,9 +223,15 @@ def main(argv=None):
             cohort = LibriSpeechDataset(a.cohort_set, a.n_seconds, stochastic=False)
     if cohort is not None:
         cohort = cohort_subset(cohort, a.cohort_size)
+    plda_train = None
+    if a.backend == "plda" and a.plda_train == "train":
+        plda_train = (SyntheticSpeechDataset(num_speakers=20, files_per_speaker=8, seconds=a.n_seconds, stochastic=False, seed=4,
+                                             subset="synthetic-train")
+                      if a.synthetic else LibriSpeechDataset(a.plda_train_set, a.n_seconds, stochastic=False))
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
     row = evaluate(net, valid, test, pre, a.score, a.score_norm, cohort, a.top_k, a.whole_utterance, vad=vad, dcf=a.dcf,
-                   calibrate=a.calibrate, calib_prior=a.calib_prior)
+                   calibrate=a.calibrate, calib_prior=a.calib_prior, backend=a.backend, plda_train=plda_train, lda_dim=a.lda_dim,
+                   length_norm=not a.no_length_norm)
     results = pd.DataFrame([row])
     if rank == 0:
         results.to_csv(PATH + "/logs/" + result_name(a), index=False)

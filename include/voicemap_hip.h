@@ -50,10 +50,20 @@ enum { VM_HEAD_UNIFORM_EUCLIDEAN = 0, VM_HEAD_WEIGHTED_L1 = 1 };
 enum { VM_DIST_EUCLIDEAN = 0, VM_DIST_COSINE = 1, VM_DIST_DOT = 2 };
 /* score kinds of vm_pair_score_hist beside the three VM_DIST_*: the weighted_l1 head's sum (voicemap/models.py:55-60 before its bias and
  * sigmoid), and the uniform_euclidean head's distance negated (the order of sigmoid(w d + b) when the head kernel w is negative). */
-enum { VM_SCORE_WEIGHTED_L1 = 3, VM_SCORE_NEG_EUCLIDEAN = 4 };
+enum { VM_SCORE_WEIGHTED_L1 = 3, VM_SCORE_NEG_EUCLIDEAN = 4, VM_SCORE_PLDA = 6 };
+/* VM_SCORE_PLDA: the score of two PLDA-space rows (vm_plda_project with `quad`; voicemap_amd/plda.py): minus the two-covariance PLDA
+ * log-likelihood ratio, lower = more alike.  (The value is 6: 5 stays an unknown kind, which every scorer refuses with VM_ERR_ARG as before
+ * -- callers rely on that refusal.)  A row of width E (E % 4 == 0 and 4 <= E <= 256, else VM_ERR_ARG) holds its own term h in its
+ * LAST column.  For rows i, j:
+ *   acc = the dot kinds' chain: fmaf over components 0 .. E - 2 in ascending order, from 0;
+ *   t = h_i + h_j;  s = t - acc;  in fp32, each rounded on its own.
+ * NaN handling follows the dot kinds; a row term that is not finite (inf or NaN) gives a NaN score whichever side the row is on.
+ * Accepted by vm_pairdist_argmin, vm_pair_score_hist, vm_pair_score_hist_norm, vm_cohort_topk_stats, vm_pair_calib_sums and vm_ahc, with
+ * bit-identical scores in all of them; `weights` is not read.  vm_mine_pairs, the n-shot entry points and the speaker models (vm_speaker_*)
+ * do not take it: PLDA is a back end, not a training signal, and by-the-book multi-session scoring of speaker models is out of scope. */
 
 const char* vm_last_error(void);
-/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms), vm_cohort_topk_stats / vm_cohort_stats_workspace_bytes / vm_pair_score_hist_norm (cohort score normalisation, S-norm / AS-norm), the *_varlen forward entry points (whole utterances in length-masked buckets: vm_crop_decimate_whiten_varlen, vm_conv1_fused_fwd_varlen, vm_conv_fwd_pool_varlen, vm_bn_drop_pool_fwd_varlen, vm_bn_drop_pool_gmax_fwd_varlen, vm_global_maxpool_fwd_varlen); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
+/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms), vm_cohort_topk_stats / vm_cohort_stats_workspace_bytes / vm_pair_score_hist_norm (cohort score normalisation, S-norm / AS-norm), the *_varlen forward entry points (whole utterances in length-masked buckets: vm_crop_decimate_whiten_varlen, vm_conv1_fused_fwd_varlen, vm_conv_fwd_pool_varlen, vm_bn_drop_pool_fwd_varlen, vm_bn_drop_pool_gmax_fwd_varlen, vm_global_maxpool_fwd_varlen), VM_SCORE_PLDA / vm_scatter_f64[_workspace_bytes, _chunk_rows] / vm_plda_project (the PLDA back end); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
  * vm_conv_dgrad_bnred; `bias`, `wf_packed` and the fourth hb row of vm_fold_bn_weights), the centred block-1 extreme (`center_bias` /
  * `shift_adj` / `mean_adj` of vm_bn_finalize) (round 4).  Earlier: 1 = round 1; 2 = vm_bn_finalize gained the zero-debias arguments (round 2); 3 = VM_F16, `dtype` in vm_conv1_fused_*,
  * `grad_scale` in the loss entry points, `skip_nonfinite` in vm_adam_clip_step, vm_embed_* / vm_pairdist_* (round 3); 4 = the folded-BatchNorm training forward
@@ -740,7 +750,8 @@ int vm_nshot_indexed(const float* emb, int64_t n_rows, const int32_t* query_idx,
  * 1 - a.b / (|a| |b|), DOT -a.b.  q_row0 >= 0: query row m IS reference row q_row0 + m (q is a row shard of ref -- the
  * data-parallel form: all-gather the embeddings, every rank takes its rows) and is excluded from its own argmin; -1: no exclusion.
  * dist (M, N) may be NULL (argmin only: nothing but best_val / best_idx (M) leaves the chip; best_idx = -1 if every distance of the
- * row is NaN).  ws >= vm_pairdist_workspace_bytes(M, N).  E <= 256, N < 2^31. */
+ * row is NaN).  ws >= vm_pairdist_workspace_bytes(M, N).  E <= 256, N < 2^31.  dist_kind may also be VM_SCORE_PLDA (q and ref are
+ * PLDA-space rows; see the enum). */
 int64_t vm_pairdist_workspace_bytes(int64_t M, int64_t N);
 int vm_pairdist_argmin(const float* q, const float* ref, int64_t M, int64_t N, int E, int dist_kind, int64_t q_row0, float* dist,
                        float* best_val, int32_t* best_idx, void* ws, void* stream);
@@ -748,7 +759,7 @@ int vm_pairdist_argmin(const float* q, const float* ref, int64_t M, int64_t N, i
  * best verification distance threshold on the validation set and then ... estimate the true verification accuracy on the test set")
  * needs, without the N x N matrix.  Every pair {i, j}, row_lo <= i < row_hi, i < j < N, of emb (N, E) is scored -- score_kind
  * VM_DIST_* bit-identical to dist[i][j] of vm_pairdist_argmin, VM_SCORE_WEIGHTED_L1 = sum_e weights[e] |a_e - b_e| (ascending e, fmaf),
- * VM_SCORE_NEG_EUCLIDEAN = -euclidean -- and counted by class (0: label[i] == label[j], 1: otherwise) into the bins of each of
+ * VM_SCORE_NEG_EUCLIDEAN = -euclidean, VM_SCORE_PLDA as stated at the enum -- and counted by class (0: label[i] == label[j], 1: otherwise) into the bins of each of
  * n_windows (<= 4) windows on the order-preserving uint32 key of the score (-0.0 taken as +0.0; bits | 2^31 if non-negative, ~bits if
  * negative).  host_windows (n_windows, 2) int64 on the HOST: key_lo, shift (<= 31): key k goes to bin (k - key_lo) >> shift if k >= key_lo
  * and that is < bins, else to slot bins (k < key_lo) or bins + 1; a NaN score to slot bins + 2.  hist (n_windows, 2, bins + 3) uint64 is
@@ -866,8 +877,8 @@ int vm_mine_pairs(const float* emb, const int32_t* label, int64_t N, int E, int 
 /* vm_ahc: batched agglomerative clustering for speaker diarization (csrc/cluster.hip, voicemap_amd/diarization.py; ahc_reference there is
  * the numpy statement, matched bit for bit).  emb (N, E) fp32 holds the windows of R recordings back to back.  row0 / mat0: R + 1 int64
  * each ON THE DEVICE, the exclusive cumulative sums of the recordings' window counts n_r and of n_r^2 (row0[R] == N, mat0[R] ==
- * sq_total; the host holds the lengths, as with vm_vad_frames' frame_base).  dist_kind is VM_DIST_EUCLIDEAN, VM_DIST_COSINE or VM_DIST_DOT,
- * lower = more alike; linkage is one of VM_LINK_*.
+ * sq_total; the host holds the lengths, as with vm_vad_frames' frame_base).  dist_kind is VM_DIST_EUCLIDEAN, VM_DIST_COSINE, VM_DIST_DOT or
+ * VM_SCORE_PLDA (PLDA-space rows), lower = more alike; linkage is one of VM_LINK_*.
  * Per recording, its rows renumbered 0 .. n - 1 ("slots"):
  *   D[i][j] (i != j) is bit-identical to dist[i][j] of vm_pairdist_argmin on the same rows (symmetric bit for bit).  Every slot starts as
  *   an active cluster of size 1; c = the number of active clusters, T = max(1, target[r]) (target: R int32 on the device; NULL = 1).
@@ -898,6 +909,28 @@ int64_t vm_ahc_workspace_bytes(int64_t N, int E, int64_t R, int64_t sq_total);
 int vm_ahc(const float* emb, int64_t N, int E, const int64_t* row0, const int64_t* mat0, int64_t R, int64_t sq_total, int dist_kind,
            int linkage, float threshold, const int32_t* target, int32_t* merge_a, int32_t* merge_b, float* merge_h, int32_t* merge_size,
            int32_t* labels, int32_t* n_clusters, void* ws, void* stream);
+
+/* ---- the PLDA back end (csrc/plda.hip, voicemap_amd/plda.py): the statistics of the fit and the projection into PLDA space -----------
+ * vm_scatter_f64: out (D, D) float64 = sum over the rows r of x (N, D) fp32 with label[r] >= 0 (label NULL: all rows) of
+ * (x_r - mean)(x_r - mean)^T.  mean (D) float64 ON THE DEVICE.  Arithmetic: d = (double)x - mean, rounded once; per entry an fma chain over
+ * ascending rows within a chunk of vm_scatter_f64_chunk_rows() rows, the chunks' partials (in ws) summed in ascending chunk order by a
+ * second launch.  Only i <= j is computed and the entry is stored on both sides: out is exactly symmetric.  No float atomics:
+ * bit-identical from run to run.  0 < D <= 256, 0 < N < 2^31; mean, out, ws 8-byte aligned; ws >= vm_scatter_f64_workspace_bytes(N, D)
+ * (one (D, D) partial per chunk).  Per-speaker sums and counts are vm_speaker_sums' (euclidean kind).
+ * vm_plda_project: rows x (N, E) fp32 -> out (N, P) fp32.  mean (E), A (D, E) row-major, quad (D) or NULL: float64 on the device.
+ *   y_d = sum_e A[d][e] * ((double)x_e - mean_e), float64, ascending e (fma chain);
+ *   length_norm != 0:  y_d <- (y_d * sqrt((double)D)) / |y|,  |y| = sqrt(sum_d y_d^2), ascending d, every product and sum rounded on its
+ *   own; a row with |y| == 0 stays zero;
+ *   out[.][d] = (float)y_d.
+ *   quad == NULL: P == D.  Otherwise P == 4 * ceil((D + 1) / 4): a PLDA-space row (VM_SCORE_PLDA) -- columns D .. P - 2 are zero and
+ *   column P - 1 = (float)(sum_d quad[d] * (v_d * v_d) + c0), v_d the STORED fp32 value widened to float64, ascending d, every operation
+ *   rounded on its own.
+ * 0 < D, E <= 255, 0 < N < 2^31; c0 finite; out 16-byte aligned when P % 4 == 0 (then it is written 16 bytes at a time). */
+int vm_scatter_f64_chunk_rows(void);
+int64_t vm_scatter_f64_workspace_bytes(int64_t N, int D);
+int vm_scatter_f64(const float* x, const int32_t* label, const double* mean, int64_t N, int D, double* out, void* ws, void* stream);
+int vm_plda_project(const float* x, const double* mean, const double* A, int64_t N, int E, int D, int length_norm, const double* quad,
+                    double c0, float* out, int P, void* stream);
 
 /* ---- a10 / f4: log-mel front-end and the 2-D CNN encoder variant (BASELINE.json config 4) -------------------
  * NOT in the reference (nothing to cite under /root/reference); the specification is DESIGN.md section 9 and the

@@ -63,7 +63,10 @@ VM_LOSS_CONTRASTIVE, VM_LOSS_BCE = _ENUMS["VM_LOSS_CONTRASTIVE"], _ENUMS["VM_LOS
 VM_HEAD_UNIFORM_EUCLIDEAN, VM_HEAD_WEIGHTED_L1 = _ENUMS["VM_HEAD_UNIFORM_EUCLIDEAN"], _ENUMS["VM_HEAD_WEIGHTED_L1"]
 VM_DIST_EUCLIDEAN, VM_DIST_COSINE, VM_DIST_DOT = (_ENUMS[k] for k in ("VM_DIST_EUCLIDEAN", "VM_DIST_COSINE", "VM_DIST_DOT"))
 VM_SCORE_WEIGHTED_L1, VM_SCORE_NEG_EUCLIDEAN = _ENUMS["VM_SCORE_WEIGHTED_L1"], _ENUMS["VM_SCORE_NEG_EUCLIDEAN"]
+VM_SCORE_PLDA = _ENUMS["VM_SCORE_PLDA"]
 DIST = {"euclidean": VM_DIST_EUCLIDEAN, "cosine": VM_DIST_COSINE, "dot_product": VM_DIST_DOT}   # the one distance-name table
+# ... and the scorers that also take PLDA-space rows (voicemap_amd/plda.py): pairwise retrieval, clustering
+PAIR_DIST = {**DIST, "plda": VM_SCORE_PLDA}
 
 
 def header_functions(path=HEADER_PATH):

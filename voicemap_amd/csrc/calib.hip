@@ -73,6 +73,7 @@ __global__ __launch_bounds__(512) void pair_calib_kernel(const float* __restrict
     for (int i = 0; i < 8; ++i) {
         const bool ok = m0 + i < row_hi;
         qn[i] = (KIND == VM_DIST_COSINE && ok) ? sqrtf(rsq[m0 + i]) : 1.f;
+        if (KIND == VM_SCORE_PLDA) qn[i] = ok ? plda_row_term(rsq[m0 + i]) : 0.f;
         ql[i] = ok ? label[m0 + i] : 0;
     }
     float qmu[8], qrs[8];
@@ -99,6 +100,7 @@ __global__ __launch_bounds__(512) void pair_calib_kernel(const float* __restrict
         for (int j = 0; j < 2; ++j) {
             const int64_t nn = n0 + lane + 64 * j;
             if (KIND == VM_DIST_COSINE) rn[j] = sqrtf(nn < N ? rsq[nn] : 1.f);
+            if (KIND == VM_SCORE_PLDA) rn[j] = nn < N ? rsq[nn] : 0.f;
             rl[j] = nn < N ? label[nn] : 0;
             if constexpr (NORM) {
                 rmu[j] = nn < N ? mu[nn] : 0.f;
@@ -120,6 +122,8 @@ __global__ __launch_bounds__(512) void pair_calib_kernel(const float* __restrict
                     d = 1.f - acc[i][j] / (qn[i] * rn[j]);
                 } else if (KIND == VM_DIST_DOT) {
                     d = -acc[i][j];
+                } else if (KIND == VM_SCORE_PLDA) {
+                    d = plda_finish(qn[i], rn[j], acc[i][j]);
                 } else {
                     d = acc[i][j];
                 }
@@ -211,7 +215,9 @@ extern "C" int vm_pair_calib_sums(const float* emb, const int32_t* label, int64_
     VM_REQUIRE(emb && label && sums && ws, "%s: null pointer", what);
     VM_REQUIRE((mu == nullptr) == (rsig == nullptr), "%s: mu and rsig come together (both NULL: raw scores)", what);
     VM_REQUIRE(N > 0 && N < (1LL << 31) && E > 0 && E <= ST_MAX_E, "%s: bad sizes (N < 2^31, E <= %d)", what, ST_MAX_E);
-    VM_REQUIRE(score_kind >= VM_DIST_EUCLIDEAN && score_kind <= VM_SCORE_NEG_EUCLIDEAN, "%s: unknown score_kind %d", what, score_kind);
+    VM_REQUIRE((score_kind >= VM_DIST_EUCLIDEAN && score_kind <= VM_SCORE_NEG_EUCLIDEAN) || score_kind == VM_SCORE_PLDA,
+               "%s: unknown score_kind %d", what, score_kind);
+    VM_REQUIRE(plda_width_ok(score_kind, E), "%s: VM_SCORE_PLDA needs E %% 4 == 0 and E >= 4", what);
     VM_REQUIRE(score_kind != VM_SCORE_WEIGHTED_L1 || weights, "%s: weighted_l1 needs weights", what);
     VM_REQUIRE(0 <= row_lo && row_lo <= row_hi && row_hi <= N, "%s: bad row range", what);
     VM_REQUIRE((E & 3) != 0 || (((uintptr_t)emb) & 15) == 0, "%s: emb must be 16-byte aligned when E %% 4 == 0", what);
@@ -226,9 +232,9 @@ extern "C" int vm_pair_calib_sums(const float* emb, const int32_t* label, int64_
     double* part = (double*)(((uintptr_t)(qT + ((N + 7) / 8) * 8 * EP) + 255) & ~(uintptr_t)255);
     int64_t n_part = 0;
     if (M > 0) {
-        if (score_kind == VM_DIST_COSINE) launch_rowsq(emb, N, E, rsq, st);
+        launch_row_scalars(score_kind, emb, N, E, rsq, st);
         launch_pad_weights(score_kind == VM_SCORE_WEIGHTED_L1 ? weights : nullptr, E, wpad, st);
-        launch_pairdist_qt(emb + row_lo * (int64_t)E, M, E, qT, st);
+        launch_pairdist_qt(emb + row_lo * (int64_t)E, M, E, qT, st, score_kind == VM_SCORE_PLDA ? E - 1 : -1);
         const int splits = cal_splits(M, N);
         const dim3 grid((unsigned)((M + ST_T - 1) / ST_T), (unsigned)splits);
         n_part = (int64_t)grid.x * grid.y;
@@ -242,6 +248,7 @@ extern "C" int vm_pair_calib_sums(const float* emb, const int32_t* label, int64_
         case VM_DIST_COSINE: VM_CAL(VM_DIST_COSINE, NM); break;          \
         case VM_DIST_DOT: VM_CAL(VM_DIST_DOT, NM); break;                \
         case VM_SCORE_WEIGHTED_L1: VM_CAL(VM_SCORE_WEIGHTED_L1, NM); break; \
+        case VM_SCORE_PLDA: VM_CAL(VM_SCORE_PLDA, NM); break;            \
         default: VM_CAL(VM_SCORE_NEG_EUCLIDEAN, NM); break;              \
     }
         if (mu == nullptr) {

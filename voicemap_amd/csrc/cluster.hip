@@ -71,6 +71,7 @@ __global__ __launch_bounds__(512) void ahc_dist_kernel(const float* __restrict__
                 qlo[i] = (int)row0[r], qhi[i] = (int)row0[r + 1], qmat[i] = mat0[r];
             }
             if (KIND == VM_DIST_COSINE) qn[i] = sqrtf(rsq[m]);
+            if (KIND == VM_SCORE_PLDA) qn[i] = plda_row_term(rsq[m]);
         }
     }
     // the group's reference tiles: workgroup-uniform
@@ -86,6 +87,10 @@ __global__ __launch_bounds__(512) void ahc_dist_kernel(const float* __restrict__
 #pragma unroll
             for (int j = 0; j < 2; ++j) rn[j] = sqrtf(n0 + lane + 64 * j < N ? rsq[n0 + lane + 64 * j] : 1.f);
         }
+        if (KIND == VM_SCORE_PLDA) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) rn[j] = n0 + lane + 64 * j < N ? rsq[n0 + lane + 64 * j] : 0.f;
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int64_t nn = n0 + lane + 64 * j;
@@ -97,6 +102,8 @@ __global__ __launch_bounds__(512) void ahc_dist_kernel(const float* __restrict__
                     d = sqrtf(acc[i][j]);
                 } else if (KIND == VM_DIST_COSINE) {
                     d = 1.f - acc[i][j] / (qn[i] * rn[j]);
+                } else if (KIND == VM_SCORE_PLDA) {
+                    d = plda_finish(qn[i], rn[j], acc[i][j]);
                 } else {
                     d = -acc[i][j];
                 }
@@ -328,7 +335,9 @@ extern "C" int vm_ahc(const float* emb, int64_t N, int E, const int64_t* row0, c
     VM_REQUIRE(N >= 0 && N < (1LL << 31) && R >= 0 && R < (1LL << 31) && E > 0 && E <= ST_MAX_E,
                "vm_ahc: bad sizes (N < 2^31, R < 2^31, 0 < E <= %d)", ST_MAX_E);
     VM_REQUIRE(sq_total >= 0 && sq_total <= N * (int64_t)AHC_MAX_N, "vm_ahc: sq_total must be in [0, N * %d]", AHC_MAX_N);
-    VM_REQUIRE(dist_kind >= VM_DIST_EUCLIDEAN && dist_kind <= VM_DIST_DOT, "vm_ahc: dist_kind must be in (euclidean, cosine, dot_product)");
+    VM_REQUIRE((dist_kind >= VM_DIST_EUCLIDEAN && dist_kind <= VM_DIST_DOT) || dist_kind == VM_SCORE_PLDA,
+               "vm_ahc: dist_kind must be in (euclidean, cosine, dot_product, plda)");
+    VM_REQUIRE(plda_width_ok(dist_kind, E), "vm_ahc: VM_SCORE_PLDA needs E %% 4 == 0 and E >= 4");
     VM_REQUIRE(linkage >= VM_LINK_SINGLE && linkage <= VM_LINK_AVERAGE, "vm_ahc: linkage must be in (single, complete, average)");
     if (R == 0 || N == 0) return 0;
     VM_REQUIRE(emb && row0 && mat0 && ws, "vm_ahc: null pointer");
@@ -342,12 +351,13 @@ extern "C" int vm_ahc(const float* emb, int64_t N, int E, const int64_t* row0, c
     float* rsq = (float*)p;
     p += ahc_pad(N * 4);
     float* qT = (float*)p;
-    if (dist_kind == VM_DIST_COSINE) launch_rowsq(emb, N, E, rsq, st);
-    launch_pairdist_qt(emb, N, E, qT, st);
+    launch_row_scalars(dist_kind, emb, N, E, rsq, st);
+    launch_pairdist_qt(emb, N, E, qT, st, dist_kind == VM_SCORE_PLDA ? E - 1 : -1);
     const dim3 grid((unsigned)((N + ST_T - 1) / ST_T));
 #define VM_AD(KD) hipLaunchKernelGGL(ahc_dist_kernel<KD>, grid, dim3(512), 0, st, qT, emb, N, E, row0, mat0, (int)R, rsq, D)
     if (dist_kind == VM_DIST_EUCLIDEAN) VM_AD(VM_DIST_EUCLIDEAN);
     else if (dist_kind == VM_DIST_COSINE) VM_AD(VM_DIST_COSINE);
+    else if (dist_kind == VM_SCORE_PLDA) VM_AD(VM_SCORE_PLDA);
     else VM_AD(VM_DIST_DOT);
 #undef VM_AD
     hipLaunchKernelGGL(ahc_merge_kernel, dim3((unsigned)R), dim3(AHC_THREADS), 0, st, D, row0, mat0, linkage, threshold, target, merge_a,

@@ -37,7 +37,10 @@ __global__ __launch_bounds__(512) void cohort_score_kernel(const float* __restri
     const float* qg = qT + ((m0 >> 3) < last_group ? (m0 >> 3) : last_group) * (int64_t)E4 * 32;
     float qn[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) qn[i] = (KIND == VM_DIST_COSINE && m0 + i < R) ? sqrtf(qsq[m0 + i]) : 1.f;
+    for (int i = 0; i < 8; ++i) {
+        qn[i] = (KIND == VM_DIST_COSINE && m0 + i < R) ? sqrtf(qsq[m0 + i]) : 1.f;
+        if (KIND == VM_SCORE_PLDA) qn[i] = m0 + i < R ? plda_row_term(qsq[m0 + i]) : 0.f;
+    }
     const int n_tiles = (int)((C + RT - 1) / RT);
     const int t_lo = blockIdx.y * tiles_per_split;
     const int t_hi = min(n_tiles, t_lo + tiles_per_split);
@@ -46,6 +49,10 @@ __global__ __launch_bounds__(512) void cohort_score_kernel(const float* __restri
         if (KIND == VM_DIST_COSINE) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) rn[j] = sqrtf(n0 + lane + 64 * j < C ? rsq[n0 + lane + 64 * j] : 1.f);
+        }
+        if (KIND == VM_SCORE_PLDA) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) rn[j] = n0 + lane + 64 * j < C ? rsq[n0 + lane + 64 * j] : 0.f;
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
@@ -62,6 +69,8 @@ __global__ __launch_bounds__(512) void cohort_score_kernel(const float* __restri
                     d = 1.f - acc[i][j] / (qn[i] * rn[j]);
                 } else if (KIND == VM_DIST_DOT) {
                     d = -acc[i][j];
+                } else if (KIND == VM_SCORE_PLDA) {
+                    d = plda_finish(qn[i], rn[j], acc[i][j]);
                 } else {
                     d = acc[i][j];
                 }
@@ -327,8 +336,9 @@ extern "C" int vm_cohort_topk_stats(const float* q, int64_t M, const float* coho
     VM_REQUIRE(M > 0 && M < (1LL << 31) && C > 0 && C < (1LL << 31) && E > 0 && E <= ST_MAX_E,
                "vm_cohort_topk_stats: bad sizes (M, C < 2^31, E <= %d)", ST_MAX_E);
     VM_REQUIRE(K >= 1 && K < (1LL << 31), "vm_cohort_topk_stats: K must be in [1, 2^31)");
-    VM_REQUIRE(score_kind >= VM_DIST_EUCLIDEAN && score_kind <= VM_SCORE_NEG_EUCLIDEAN, "vm_cohort_topk_stats: unknown score_kind %d",
-               score_kind);
+    VM_REQUIRE((score_kind >= VM_DIST_EUCLIDEAN && score_kind <= VM_SCORE_NEG_EUCLIDEAN) || score_kind == VM_SCORE_PLDA,
+               "vm_cohort_topk_stats: unknown score_kind %d", score_kind);
+    VM_REQUIRE(plda_width_ok(score_kind, E), "vm_cohort_topk_stats: VM_SCORE_PLDA needs E %% 4 == 0 and E >= 4");
     VM_REQUIRE(score_kind != VM_SCORE_WEIGHTED_L1 || weights, "vm_cohort_topk_stats: weighted_l1 needs weights");
     VM_REQUIRE((E & 3) != 0 || (((uintptr_t)cohort) & 15) == 0, "vm_cohort_topk_stats: cohort must be 16-byte aligned when E %% 4 == 0");
     hipStream_t st = (hipStream_t)stream;
@@ -341,16 +351,14 @@ extern "C" int vm_cohort_topk_stats(const float* q, int64_t M, const float* coho
     const int64_t EP = ((E + 3) / 4) * 4;
     float* tile = (float*)(((uintptr_t)(qT + ((R + 7) / 8) * 8 * EP) + 255) & ~(uintptr_t)255);
     int32_t* list = (int32_t*)(tile + RT * C);   // with topk_idx: RT rows of C indices behind the RT score rows, within (R + 1) * C
-    if (score_kind == VM_DIST_COSINE) {
-        launch_rowsq(q, M, E, qsq, st);
-        launch_rowsq(cohort, C, E, rsq, st);
-    }
+    launch_row_scalars(score_kind, q, M, E, qsq, st);
+    launch_row_scalars(score_kind, cohort, C, E, rsq, st);
     launch_pad_weights(score_kind == VM_SCORE_WEIGHTED_L1 ? weights : nullptr, E, wpad, st);
     const int splits = score_splits(RT, C, 2048);
     const int tps = (int)(((C + ST_RT - 1) / ST_RT + splits - 1) / splits);
     for (int64_t row0 = 0; row0 < M; row0 += RT) {
         const int64_t rows = RT < M - row0 ? RT : M - row0;
-        launch_pairdist_qt(q + row0 * E, rows, E, qT, st);
+        launch_pairdist_qt(q + row0 * E, rows, E, qT, st, score_kind == VM_SCORE_PLDA ? E - 1 : -1);
         const int64_t self_col0 = self_row0 >= 0 ? self_row0 + row0 : -1;
         const dim3 grid((unsigned)((rows + ST_T - 1) / ST_T), (unsigned)splits);
 #define VM_CS(KD) hipLaunchKernelGGL(cohort_score_kernel<KD>, grid, dim3(512), 0, st, qT, cohort, rows, C, E, self_col0, qsq + row0, rsq, wpad, \
@@ -360,6 +368,7 @@ extern "C" int vm_cohort_topk_stats(const float* q, int64_t M, const float* coho
             case VM_DIST_COSINE: VM_CS(VM_DIST_COSINE); break;
             case VM_DIST_DOT: VM_CS(VM_DIST_DOT); break;
             case VM_SCORE_WEIGHTED_L1: VM_CS(VM_SCORE_WEIGHTED_L1); break;
+            case VM_SCORE_PLDA: VM_CS(VM_SCORE_PLDA); break;
             default: VM_CS(VM_SCORE_NEG_EUCLIDEAN); break;
         }
 #undef VM_CS

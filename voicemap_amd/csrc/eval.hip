@@ -207,7 +207,9 @@ __global__ __launch_bounds__(256) void rowsq_kernel(const float* __restrict__ x,
 
 // q (M, E) -> qT: per group of 8 queries and per 4 components the 8 x 4 values back to back (128 bytes): what a wave of
 // pairdist_kernel takes per component step through the SCALAR path.  [group][e4][query in group][4]; rows past M / components past E: 0.
-__global__ __launch_bounds__(256) void pairdist_qt_kernel(const float* __restrict__ q, int64_t M, int E, int EP, float* __restrict__ qT) {
+// zero_col >= 0: that component is written as zero (VM_SCORE_PLDA's row term, which the chain must skip).
+__global__ __launch_bounds__(256) void pairdist_qt_kernel(const float* __restrict__ q, int64_t M, int E, int EP, int zero_col,
+                                                          float* __restrict__ qT) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t groups = (M + 7) / 8;
     if (i >= groups * 8 * EP) return;
@@ -217,7 +219,13 @@ __global__ __launch_bounds__(256) void pairdist_qt_kernel(const float* __restric
     const int64_t g = r / (EP / 4);
     const int64_t m = g * 8 + qi;
     const int e = e4 * 4 + c;
-    qT[i] = (m < M && e < E) ? q[m * E + e] : 0.f;
+    qT[i] = (m < M && e < E && e != zero_col) ? q[m * E + e] : 0.f;
+}
+
+// out[r] = x[r][E - 1]: the row term of a PLDA-space row
+__global__ __launch_bounds__(256) void rowterm_kernel(const float* __restrict__ x, int64_t rows, int E, float* __restrict__ out) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r < rows) out[r] = x[r * E + E - 1];
 }
 
 __global__ __launch_bounds__(256) void pad_weights_kernel(const float* __restrict__ w, int E, float* __restrict__ wpad) {
@@ -245,6 +253,7 @@ __global__ __launch_bounds__(512) void pairdist_kernel(const float* __restrict__
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         qn[i] = (DIST == VM_DIST_COSINE && m0 + i < M) ? sqrtf(qsq[m0 + i]) : 1.f;
+        if (DIST == VM_SCORE_PLDA) qn[i] = m0 + i < M ? plda_row_term(qsq[m0 + i]) : 0.f;
         bestv[i] = INFINITY;
         besti[i] = 0x7fffffff;
     }
@@ -257,6 +266,10 @@ __global__ __launch_bounds__(512) void pairdist_kernel(const float* __restrict__
 #pragma unroll
             for (int j = 0; j < 2; ++j) rn[j] = sqrtf(n0 + lane + 64 * j < N ? rsq[n0 + lane + 64 * j] : 1.f);
         }
+        if (DIST == VM_SCORE_PLDA) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) rn[j] = n0 + lane + 64 * j < N ? rsq[n0 + lane + 64 * j] : 0.f;
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j) {   // ascending reference index within a lane: the first minimum is kept
             const int64_t nn = n0 + lane + 64 * j;
@@ -268,6 +281,8 @@ __global__ __launch_bounds__(512) void pairdist_kernel(const float* __restrict__
                     d = sqrtf(acc[i][j]);
                 } else if (DIST == VM_DIST_COSINE) {
                     d = 1.f - acc[i][j] / (qn[i] * rn[j]);
+                } else if (DIST == VM_SCORE_PLDA) {
+                    d = plda_finish(qn[i], rn[j], acc[i][j]);
                 } else {
                     d = -acc[i][j];
                 }
@@ -322,10 +337,13 @@ __global__ __launch_bounds__(256) void pairdist_final_kernel(const float* __rest
 void launch_rowsq(const float* x, int64_t rows, int E, float* out, hipStream_t st) {
     hipLaunchKernelGGL(rowsq_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, rows, E, out);
 }
-void launch_pairdist_qt(const float* q, int64_t M, int E, float* qT, hipStream_t st) {
+void launch_pairdist_qt(const float* q, int64_t M, int E, float* qT, hipStream_t st, int zero_col) {
     const int EP = ((E + 3) / 4) * 4;
     const int64_t qt_n = ((M + 7) / 8) * 8 * (int64_t)EP;
-    hipLaunchKernelGGL(pairdist_qt_kernel, dim3((unsigned)((qt_n + 255) / 256)), dim3(256), 0, st, q, M, E, EP, qT);
+    hipLaunchKernelGGL(pairdist_qt_kernel, dim3((unsigned)((qt_n + 255) / 256)), dim3(256), 0, st, q, M, E, EP, zero_col, qT);
+}
+void launch_rowterm(const float* x, int64_t rows, int E, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(rowterm_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, x, rows, E, out);
 }
 
 void launch_pad_weights(const float* w, int E, float* wpad, hipStream_t st) {
@@ -359,8 +377,9 @@ extern "C" int vm_pairdist_argmin(const float* q, const float* ref, int64_t M, i
     VM_REQUIRE(q && ref && best_val && best_idx && ws, "vm_pairdist_argmin: null pointer");
     VM_REQUIRE(M > 0 && N > 0 && E > 0 && E <= ST_MAX_E, "vm_pairdist_argmin: bad sizes (E <= %d)", ST_MAX_E);
     VM_REQUIRE(N < (1LL << 31) && (M + ST_T - 1) / ST_T < (1LL << 31), "vm_pairdist_argmin: matrix too large for one launch");
-    VM_REQUIRE(dist_kind >= VM_DIST_EUCLIDEAN && dist_kind <= VM_DIST_DOT,
-               "vm_pairdist_argmin: Distance must be in (euclidean, cosine, dot_product)");
+    VM_REQUIRE((dist_kind >= VM_DIST_EUCLIDEAN && dist_kind <= VM_DIST_DOT) || dist_kind == VM_SCORE_PLDA,
+               "vm_pairdist_argmin: Distance must be in (euclidean, cosine, dot_product, plda)");
+    VM_REQUIRE(plda_width_ok(dist_kind, E), "vm_pairdist_argmin: VM_SCORE_PLDA needs E %% 4 == 0 and E >= 4");
     const int splits = score_splits(M, N, 2048);
     float* part_val = (float*)ws;
     int32_t* part_idx = (int32_t*)(part_val + (int64_t)splits * M);
@@ -370,12 +389,13 @@ extern "C" int vm_pairdist_argmin(const float* q, const float* ref, int64_t M, i
     if (dist_kind == VM_DIST_COSINE) {
         hipLaunchKernelGGL(rowsq_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, q, M, E, qsq);
         hipLaunchKernelGGL(rowsq_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, ref, N, E, rsq);
+    } else if (dist_kind == VM_SCORE_PLDA) {
+        launch_rowterm(q, M, E, qsq, st);
+        launch_rowterm(ref, N, E, rsq, st);
     }
-    const int EP = ((E + 3) / 4) * 4;
     // the scalar-path copy of the queries behind the squared norms (16-byte aligned)
     float* qT = (float*)(((uintptr_t)(rsq + N) + 255) & ~(uintptr_t)255);
-    const int64_t qt_n = ((M + 7) / 8) * 8 * (int64_t)EP;
-    hipLaunchKernelGGL(pairdist_qt_kernel, dim3((unsigned)((qt_n + 255) / 256)), dim3(256), 0, st, q, M, E, EP, qT);
+    launch_pairdist_qt(q, M, E, qT, st, dist_kind == VM_SCORE_PLDA ? E - 1 : -1);
     const int n_tiles = (int)((N + ST_RT - 1) / ST_RT);
     const int tps = (n_tiles + splits - 1) / splits;
     VM_REQUIRE((E & 3) != 0 || (((uintptr_t)ref) & 15) == 0, "vm_pairdist_argmin: ref must be 16-byte aligned when E %% 4 == 0");
@@ -383,6 +403,7 @@ extern "C" int vm_pairdist_argmin(const float* q, const float* ref, int64_t M, i
 #define VM_PD(D) hipLaunchKernelGGL(pairdist_kernel<D>, grid, dim3(512), 0, st, qT, ref, M, N, E, q_row0, qsq, rsq, tps, dist, part_val, part_idx)
     if (dist_kind == VM_DIST_EUCLIDEAN) VM_PD(VM_DIST_EUCLIDEAN);
     else if (dist_kind == VM_DIST_COSINE) VM_PD(VM_DIST_COSINE);
+    else if (dist_kind == VM_SCORE_PLDA) VM_PD(VM_SCORE_PLDA);
     else VM_PD(VM_DIST_DOT);
 #undef VM_PD
     hipLaunchKernelGGL(pairdist_final_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, part_val, part_idx, M, splits, best_val,

@@ -33,10 +33,31 @@ __device__ inline float vh_norm(float s, float mi, float ri, float mj, float rj)
     return 0.5f * (x + y);
 }
 
+// VM_SCORE_PLDA: the rows are PLDA-space rows (voicemap_amd/plda.py) whose LAST column is the row's own term h.  The tile loop runs its
+// dot branch over all E components with the query copy's component E - 1 written as zero (fmaf(0, r, acc) == acc: the chain is that of
+// components 0 .. E - 2), and the finishing line is s = (h_q + h_r) - acc, each operation rounded on its own.  A row term that is not
+// finite makes the score NaN from either side: 0 * inf (or 0 * NaN) in the chain for the reference row, plda_row_term for the query row.
+__device__ inline float plda_row_term(float h) { return (__float_as_uint(h) & 0x7f800000u) == 0x7f800000u ? __uint_as_float(0x7fc00000u) : h; }
+__device__ inline float plda_finish(float hq, float hr, float acc) {
+#pragma clang fp contract(off)
+    const float t = hq + hr;
+    return t - acc;
+}
+
 // ---- preparation launches (defined in eval.hip) --------------------------------------------------------------------------------------
-// row squared norms (fmaf, ascending component per lane, wave sum) and the scalar-path query layout qT of the tile loop
+// row squared norms (fmaf, ascending component per lane, wave sum) and the scalar-path query layout qT of the tile loop; zero_col >= 0:
+// that component of every query is written as zero (VM_SCORE_PLDA: E - 1)
 void launch_rowsq(const float* x, int64_t rows, int E, float* out, hipStream_t st);
-void launch_pairdist_qt(const float* q, int64_t M, int E, float* qT, hipStream_t st);
+void launch_pairdist_qt(const float* q, int64_t M, int E, float* qT, hipStream_t st, int zero_col = -1);
+// VM_SCORE_PLDA's per-row scalar in place of the squared norm: out[r] = x[r][E - 1]
+void launch_rowterm(const float* x, int64_t rows, int E, float* out, hipStream_t st);
+// the per-row scalars of a score kind into `out` (cosine: squared norms, PLDA: row terms, every other kind: nothing)
+inline void launch_row_scalars(int kind, const float* x, int64_t rows, int E, float* out, hipStream_t st) {
+    if (kind == VM_DIST_COSINE) launch_rowsq(x, rows, E, out, st);
+    else if (kind == VM_SCORE_PLDA) launch_rowterm(x, rows, E, out, st);
+}
+// what every scorer asks of VM_SCORE_PLDA's width
+inline bool plda_width_ok(int kind, int E) { return kind != VM_SCORE_PLDA || (E >= 4 && (E & 3) == 0); }
 // wpad[0 .. ST_MAX_E) = w[0 .. E) followed by zeros (all zeros for w == NULL): the weights of VM_SCORE_WEIGHTED_L1
 void launch_pad_weights(const float* w, int E, float* wpad, hipStream_t st);
 
@@ -65,7 +86,7 @@ inline int score_splits(int64_t rows, int64_t refs, int64_t target) {
 // rs: the workgroup's LDS stage, ST_RT * ST_RP floats, 16-byte aligned.  ref (N, E); wpad is read only for VM_SCORE_WEIGHTED_L1.  Whole
 // 512-thread workgroup (two barriers per stage).  For every reference tile t of [t_lo, t_hi), tile(n0 = t * ST_RT, acc) is called once
 // with acc[i][j] = the ascending-component fmaf chain of query i and reference n0 + lane + 64 j: sum (q - r)^2 (euclidean and its
-// negation), sum w |q - r| (weighted L1) or sum q r (cosine, dot).  Rows past N and components past E enter as zeros.  `tile` is taken
+// negation), sum w |q - r| (weighted L1) or sum q r (cosine, dot, PLDA).  Rows past N and components past E enter as zeros.  `tile` is taken
 // BY VALUE: as a forwarding reference pairdist_kernel<cosine> went from 94 to 99 VGPRs and from 5 to 4 waves per SIMD.
 template <int KIND, typename Tile>
 __device__ __forceinline__ void score_tile_loop(float* rs, const float* __restrict__ qg, const float* __restrict__ ref, int64_t N, int E,

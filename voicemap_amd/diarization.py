@@ -177,11 +177,11 @@ def cluster(emb, row0, distance: str = "cosine", linkage: str = "average", thres
     """Cluster the windows of R recordings in one ``vm_ahc`` call.  ``emb``: (N, E) fp32 device tensor, recording r's windows at rows
     ``row0[r] .. row0[r + 1]`` (``row0``: R + 1 host values).  Merging stops at the first height that fails ``h <= threshold`` and
     when ``n_speakers`` clusters are left (an int, or one per recording); with neither, the full dendrogram is recorded (``cut``
-    then gives any stop on the host)."""
+    then gives any stop on the host).  distance="plda": the rows are PLDA-space rows (``plda.PldaModel.project``)."""
     import torch
     from . import _lib
-    if distance not in _lib.DIST:
-        raise ValueError("Distance must be in (euclidean, cosine, dot_product)")
+    if distance not in _lib.PAIR_DIST:
+        raise ValueError("Distance must be in (euclidean, cosine, dot_product, plda)")
     if linkage not in LINKAGES:
         raise ValueError("linkage must be in %r" % (LINKAGES,))
     if emb.dim() != 2 or emb.dtype != torch.float32:
@@ -205,7 +205,7 @@ def cluster(emb, row0, distance: str = "cosine", linkage: str = "average", thres
     tab = torch.from_numpy(np.concatenate([row0, mat0])).to(dev)   # one upload
     lib = _lib.lib()
     ws = lib.workspace("vm_ahc_workspace_bytes", N, E, R, int(mat0[-1]), device=dev)
-    lib.call("vm_ahc", emb.data_ptr(), N, E, tab.data_ptr(), tab[R + 1:].data_ptr(), R, int(mat0[-1]), _lib.DIST[distance],
+    lib.call("vm_ahc", emb.data_ptr(), N, E, tab.data_ptr(), tab[R + 1:].data_ptr(), R, int(mat0[-1]), _lib.PAIR_DIST[distance],
              _lib._ENUMS["VM_LINK_" + linkage.upper()], float("nan") if threshold is None else float(threshold),
              None if target is None else target.data_ptr(), res.merge_a.data_ptr(), res.merge_b.data_ptr(), res.merge_h.data_ptr(),
              res.merge_size.data_ptr(), res.labels.data_ptr(), res.n_clusters.data_ptr(), ws.data_ptr(),
@@ -422,14 +422,19 @@ def make_conversations(dataset, n: int, speakers: Tuple[int, int] = (2, 4), turn
 
 # ---- the whole path --------------------------------------------------------------------------------------------------------------------
 def diarize(model, audio, offsets, lens, preprocessor, window_seconds: float, hop_seconds: float, network_type: str = "siamese",
-            distance: str = "cosine", linkage: str = "average", threshold: Optional[float] = None, n_speakers=None, batch: int = 256):
+            distance: str = "cosine", linkage: str = "average", threshold: Optional[float] = None, n_speakers=None, batch: int = 256,
+            plda=None):
     """Diarize the recordings ``audio[offsets[r] : offsets[r] + lens[r]]`` of a resident int16 buffer: sliding windows, every window
     embedded alone (``embed_from_offsets(..., windows_per_tower=1)``, ``batch`` windows per call), ``cluster``, ``window_segments``.
     Returns (segments per recording, the ``Clustering``); the clustering also carries ``emb`` (N, E), ``starts`` (per recording, relative
-    to it) and ``window``.  An engine without resident input raises what ``require_resident_input`` raises."""
+    to it) and ``window``.  An engine without resident input raises what ``require_resident_input`` raises.  distance="plda" needs
+    ``plda``, a fitted ``plda.PldaModel``: the windows' embeddings are projected by it and clustered on minus the log-likelihood ratio;
+    the clustering then also carries the projected rows as ``rows``."""
     import torch
     from .engine_core import require_resident_input
     from .retrieval import _encoder_engine
+    if (distance == "plda") != (plda is not None):
+        raise ValueError('distance="plda" and a fitted ``plda`` model come together')
     eng = _encoder_engine(model, network_type)
     require_resident_input(type(eng))
     inst = preprocessor.instance_preprocessor if hasattr(preprocessor, "instance_preprocessor") else preprocessor
@@ -452,8 +457,9 @@ def diarize(model, audio, offsets, lens, preprocessor, window_seconds: float, ho
     for b0 in range(0, len(flat), batch):
         offs = torch.as_tensor(flat[b0:b0 + batch])
         emb[b0:b0 + len(offs)].copy_(eng.embed_from_offsets(audio, offs, window, ds, wh, windows_per_tower=1))
-    res = cluster(emb, row0, distance, linkage, threshold, n_speakers)
-    res.emb, res.starts, res.window = emb, starts, window
+    rows = plda.project(emb) if plda is not None else emb
+    res = cluster(rows, row0, distance, linkage, threshold, n_speakers)
+    res.emb, res.rows, res.starts, res.window = emb, rows, starts, window
     labels = res.host().labels
     segments = [window_segments(starts[r], window, int(lens[r]), labels[row0[r]:row0[r + 1]]) for r in range(len(lens))]
     return segments, res

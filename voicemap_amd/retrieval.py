@@ -397,9 +397,10 @@ def pairwise_retrieval(cache: EmbeddingCache, distance: str = "euclidean", retur
     """The pairwise-distance matrix of the corpus against itself, this rank's rows (``parallel.shard_range`` of N, or ``rows`` =
     (lo, hi)): nearest OTHER utterance per query row with ``vm_pairdist_argmin`` and the retrieval form of verification accuracy --
     the share of utterances whose nearest neighbour is the same speaker -- summed over ranks.  Returns a dict with ``n_correct``,
-    ``n_rows`` (global), ``accuracy``, this rank's ``best_idx`` / ``best_val`` and, on request, its (rows, N) block of the matrix."""
-    if distance not in _DIST:
-        raise ValueError("Distance must be in (euclidean, cosine, dot_product)")
+    ``n_rows`` (global), ``accuracy``, this rank's ``best_idx`` / ``best_val`` and, on request, its (rows, N) block of the matrix.
+    distance="plda": the rows of ``cache`` are PLDA-space rows (``plda.PldaModel.project``)."""
+    if distance not in _lib.PAIR_DIST:
+        raise ValueError("Distance must be in (euclidean, cosine, dot_product, plda)")
     rank, world = parallel.rank_world()
     lo, hi = rows if rows is not None else parallel.shard_range(cache.n, rank, world)
     dev = cache.emb.device
@@ -412,7 +413,7 @@ def pairwise_retrieval(cache: EmbeddingCache, distance: str = "euclidean", retur
         bi = torch.empty(M, dtype=torch.int32, device=dev)
         dist = torch.empty(M, N, dtype=torch.float32, device=dev) if return_matrix else None
         q = cache.emb[lo:hi]
-        lib.call("vm_pairdist_argmin", q.data_ptr(), cache.emb.data_ptr(), M, N, cache.E, _DIST[distance], lo,
+        lib.call("vm_pairdist_argmin", q.data_ptr(), cache.emb.data_ptr(), M, N, cache.E, _lib.PAIR_DIST[distance], lo,
                  None if dist is None else dist.data_ptr(), bv.data_ptr(), bi.data_ptr(), ws.data_ptr(),
                  torch.cuda.current_stream(dev).cuda_stream)
         same = cache.speaker_dev[bi.clamp_min(0).long()] == cache.speaker_dev[lo:hi]

@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib, parallel
-from ._lib import VM_SCORE_NEG_EUCLIDEAN
+from ._lib import VM_SCORE_NEG_EUCLIDEAN, VM_SCORE_PLDA
 
 SCORES = {**_lib.DIST, "weighted_l1": _lib.VM_SCORE_WEIGHTED_L1}
 KEY_SPACE = 1 << 32
@@ -245,10 +245,14 @@ def score_kind(cache, score: str, model) -> Tuple[int, Optional[torch.Tensor], O
     """(kernel score kind, weights, (w, b) of a uniform_euclidean head)."""
     if score in ("euclidean", "cosine", "dot_product"):
         return SCORES[score], None, None
+    if score == "plda":   # the rows of ``cache`` are PLDA-space rows (plda.PldaModel.project): no weights, no head
+        if cache.E < 4 or cache.E % 4:
+            raise ValueError('score "plda" takes PLDA-space rows (plda.PldaModel.project): a width that is a multiple of 4, not %d' % cache.E)
+        return VM_SCORE_PLDA, None, None
     if score == "weighted_l1":
         raise ValueError('score "weighted_l1" takes its weights from a model: use score="head" with a weighted_l1 siamese net')
     if score != "head":
-        raise ValueError("score must be one of (euclidean, cosine, dot_product, head)")
+        raise ValueError("score must be one of (euclidean, cosine, dot_product, head, plda)")
     from .retrieval import _siamese_head_engine
     eng = _siamese_head_engine(model) if model is not None else None
     if eng is None:
@@ -594,6 +598,16 @@ def bounds(cache, kind) -> Tuple[float, float]:
     """Cheap bounds of every pair score of ``cache`` under an embedding score kind, from the largest row norm."""
     if kind == SCORES["cosine"]:
         return 0.0, 2.0
+    if kind == VM_SCORE_PLDA:   # s = (h_i + h_j) - w_i . w_j
+        h = cache.emb[:, -1].double()
+        h = h[torch.isfinite(h)]
+        r = float(torch.linalg.vector_norm(cache.emb[:, :-1].double(), dim=1).max().item()) if cache.n else 0.0
+        r = r * r * 1.001 + 1e-30
+        if h.numel() == 0:
+            return -r, r
+        lo, hi = 2 * float(h.min().item()), 2 * float(h.max().item())
+        pad = 1e-3 * max(abs(lo), abs(hi))
+        return lo - pad - r, hi + pad + r
     norms = torch.linalg.vector_norm(cache.emb.double(), dim=1)
     r = float(norms.max().item()) if cache.n else 0.0
     r = r * 1.001 + 1e-30
@@ -613,6 +627,8 @@ def sample_scores(a: torch.Tensor, b: torch.Tensor, kind: int, weights=None) -> 
         return 1 - (a * b).sum(1) / (torch.linalg.vector_norm(a, dim=1) * torch.linalg.vector_norm(b, dim=1))
     if kind == SCORES["dot_product"]:
         return -(a * b).sum(1)
+    if kind == VM_SCORE_PLDA:
+        return (a[:, -1] + b[:, -1]) - (a[:, :-1] * b[:, :-1]).sum(1)
     return ((a - b).abs() * weights.double()).sum(1)
 
 
