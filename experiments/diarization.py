@@ -13,7 +13,16 @@ many speakers were present.  With --synthetic and no --siamese the encoder is un
 how well a model diarizes.
 --distance plda: a PLDA back end (voicemap_amd/plda.py) is fitted on the embeddings of the single-speaker files the conversations are
 built from (one first-fragment window per file, --lda-dim / --no-length-norm as in experiments/verification_accuracy.py) and the
-windows are clustered on minus its log-likelihood ratio."""
+windows are clustered on minus its log-likelihood ratio.
+Pauses, speech gating and resegmentation, all off by default:
+    --pause-seconds LO-HI --pause-prob P   digital silence of a drawn length in front of a turn, with probability P
+    --vad [--vad-...] --min-voiced S       one voice activity detection over the conversations; a window with less than the share S of
+                                           voiced frames is neither embedded nor clustered, no unvoiced frame carries a speaker
+    --reseg --switch-cost C --reseg-iters N [--reseg-hop-seconds H]
+                                           Viterbi resegmentation of the cluster labels (vm_reseg), at a finer hop H if given; the
+                                           line then carries the error before ("ahc_*") and after it
+With --tune-conversations the threshold is tuned on the clustering alone and the resegmentation runs on the labels it cuts (no
+--reseg-hop-seconds there: the tuned cut has no finer rows)."""
 import argparse
 import json
 import os
@@ -21,6 +30,7 @@ import os
 import numpy as np
 
 from voicemap_amd import diarization as DZ
+from voicemap_amd import vad as VAD
 from voicemap_amd.librispeech import LibriSpeechDataset, SyntheticSpeechDataset
 from voicemap_amd.utils import BatchPreProcessor, preprocess_instances
 
@@ -35,6 +45,18 @@ def parse_range(text):
         return lo, hi
     except ValueError:
         raise argparse.ArgumentTypeError("a range LO-HI with 2 <= LO <= HI, not %r" % text)
+
+
+def parse_seconds(text):
+    """LO-HI or X -> (lo, hi) in seconds."""
+    try:
+        lo, _, hi = text.partition("-")
+        lo, hi = float(lo), float(hi or lo)
+        if lo < 0 or hi < lo:
+            raise ValueError
+        return lo, hi
+    except ValueError:
+        raise argparse.ArgumentTypeError("a range LO-HI in seconds with 0 <= LO <= HI, not %r" % text)
 
 
 def _parser():
@@ -56,6 +78,14 @@ def _parser():
     p.add_argument("--lda-dim", type=int, default=None, help="--distance plda: LDA directions kept (default: all)")
     p.add_argument("--no-length-norm", action="store_true", help="--distance plda: no length normalisation between LDA and PLDA")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--pause-seconds", type=parse_seconds, default=(0.0, 0.0), metavar="LO-HI")
+    p.add_argument("--pause-prob", type=float, default=0.0)
+    VAD.add_vad_args(p)
+    p.add_argument("--min-voiced", type=float, default=0.5, help="--vad: the share of voiced frames a window needs to be kept")
+    p.add_argument("--reseg", action="store_true", help="resegment the cluster labels with a sticky HMM (vm_reseg)")
+    p.add_argument("--switch-cost", type=float, default=0.5, help="--reseg: the cost of a speaker change, in units of the distance")
+    p.add_argument("--reseg-iters", type=int, default=3)
+    p.add_argument("--reseg-hop-seconds", type=float, default=None, help="--reseg: cut, embed and decode at this finer hop")
     stop = p.add_mutually_exclusive_group(required=True)
     stop.add_argument("--threshold", type=float, default=None)
     stop.add_argument("--oracle-speakers", action="store_true")
@@ -71,15 +101,35 @@ def score(conv, rows, segments):
             "missed": part("missed"), "false_alarm": part("false_alarm"), "confusion": part("confusion")}
 
 
-def segments_at(conv, res, rows, threshold):
-    """(hypothesis segments, clusters found) of conversations ``rows`` from their FULL dendrograms cut at ``threshold``."""
-    segs, found = [], []
+def hyp_segments(conv, res, r, labels, starts=None):
+    """The hypothesis of conversation r from one label per window (``starts``: default all embedded windows), cut to the voiced frames
+    when the windows were gated."""
+    if len(labels) == 0:
+        return np.zeros((0, 3), np.int64)
+    seg = DZ.window_segments(res.starts[r] if starts is None else starts, res.window, int(conv.lens[r]), labels)
+    return seg if res.voiced is None else DZ.cut_to_voiced(seg, res.voiced[r], res.vad.policy.frame, int(conv.lens[r]))
+
+
+def ahc_segments(conv, res, rows):
+    """The hypothesis the clustering alone gives (its labels on the clustered windows): the "before" of a resegmentation."""
+    return [hyp_segments(conv, res, r, res.recording(r).labels, res.starts[r][res.clustered[r]]) for r in rows]
+
+
+def segments_at(conv, res, rows, threshold, reseg=None):
+    """(hypothesis segments, clusters found) of conversations ``rows`` from their FULL dendrograms cut at ``threshold``; with ``reseg``
+    (a ResegPolicy) the cut labels are resegmented first."""
+    cuts = []
     for r in rows:
         rec = res.recording(r)
-        labels, c = DZ.cut(rec.merge_a, rec.merge_b, rec.merge_h, len(rec.labels), threshold=threshold)
-        segs.append(DZ.window_segments(res.starts[r], res.window, int(conv.lens[r]), labels))
-        found.append(c)
-    return segs, found
+        cuts.append(DZ.cut(rec.merge_a, rec.merge_b, rec.merge_h, len(rec.labels), threshold=threshold))
+    if reseg is not None:
+        row0 = res.window_row0
+        lab, k = np.full(int(row0[-1]), -1, np.int32), np.ones(len(row0) - 1, np.int64)
+        for r, (labels, c) in zip(rows, cuts):
+            lab[row0[r]:row0[r + 1]], k[r] = labels, max(c, 1)
+        out = DZ.resegment(res.emb, row0, lab, k, res.chain_start, res.distance, reseg.switch_cost, reseg.iters, return_emis=False).host()
+        cuts = [(out.labels[row0[r]:row0[r + 1]], c) for r, (_, c) in zip(rows, cuts)]
+    return [hyp_segments(conv, res, r, labels) for r, (labels, _) in zip(rows, cuts)], [c for _, c in cuts]
 
 
 def tune_threshold(conv, res, rows, candidates=64):
@@ -121,8 +171,14 @@ def main(argv=None):
         data = shards.ShardedSpeechDataset(a.device_data, a.window_seconds, stochastic=False, pad=False)
         data.to_device("cuda")
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
-    conv = DZ.make_conversations(data, a.conversations, speakers=a.speakers, turns=a.turns, seed=a.seed)
-    kw = dict(distance=a.distance, linkage=a.linkage)
+    conv = DZ.make_conversations(data, a.conversations, speakers=a.speakers, turns=a.turns, seed=a.seed, pause_seconds=a.pause_seconds,
+                                 pause_prob=a.pause_prob)
+    policy = VAD.policy_from_args(a)
+    try:
+        reseg = DZ.ResegPolicy(a.switch_cost, a.reseg_iters, a.reseg_hop_seconds) if a.reseg else None
+    except ValueError as e:
+        p.error("--reseg: %s" % e)
+    kw = dict(distance=a.distance, linkage=a.linkage, vad=policy, min_voiced=a.min_voiced)
     if a.distance == "plda":
         from voicemap_amd import plda, retrieval
         kw["plda"] = plda.fit_plda(retrieval.embed_corpus(net, data, pre, "siamese"), lda_dim=a.lda_dim, length_norm=not a.no_length_norm)
@@ -132,18 +188,27 @@ def main(argv=None):
     if a.tune_conversations:
         if not 0 < a.tune_conversations < len(conv):
             p.error("--tune-conversations K needs 0 < K < --conversations")
+        if reseg is not None and reseg.hop_seconds is not None:
+            p.error("--reseg-hop-seconds does not go with --tune-conversations")
         _, res = DZ.diarize(net, conv.audio, conv.offsets, conv.lens, pre, a.window_seconds, a.hop_seconds, **kw)   # full dendrograms
         dev, rows = rows[:a.tune_conversations], rows[a.tune_conversations:]
         threshold = tune_threshold(conv, res, dev)
-        segments, found = segments_at(conv, res, rows, threshold)
+        segments, found = segments_at(conv, res, rows, threshold, reseg)
+        before = segments_at(conv, res, rows, threshold)[0] if reseg is not None else None
         out.update(threshold=threshold, tuned_on=len(dev), dev_mean_der=score(conv, dev, segments_at(conv, res, dev, threshold)[0])["mean_der"])
     else:
         n_speakers = conv.speakers if a.oracle_speakers else None
         segments, res = DZ.diarize(net, conv.audio, conv.offsets, conv.lens, pre, a.window_seconds, a.hop_seconds, threshold=a.threshold,
-                                   n_speakers=n_speakers, **kw)
+                                   n_speakers=n_speakers, reseg=reseg, **kw)
         found = res.host().n_clusters.tolist()
+        before = ahc_segments(conv, res, rows) if reseg is not None else None
         out.update(threshold=a.threshold, oracle_speakers=bool(a.oracle_speakers))
     out.update(score(conv, rows, segments), scored=len(rows), windows=int(res.row0[-1]))
+    if policy is not None:
+        out.update(vad=True, min_voiced=a.min_voiced, windows_kept=int(res.window_row0[-1]), windows_cut=int(sum(len(k) for k in res.kept)))
+    if reseg is not None:
+        out.update({"ahc_" + k: v for k, v in score(conv, rows, before).items()}, reseg=True, switch_cost=reseg.switch_cost,
+                   reseg_iters=reseg.iters, reseg_hop_seconds=reseg.hop_seconds, windows_decoded=int(res.window_row0[-1]))
     table = {}
     for r, c in zip(rows, found):
         table.setdefault(int(conv.speakers[r]), {}).setdefault(int(c), 0)

@@ -909,6 +909,46 @@ int64_t vm_ahc_workspace_bytes(int64_t N, int E, int64_t R, int64_t sq_total);
 int vm_ahc(const float* emb, int64_t N, int E, const int64_t* row0, const int64_t* mat0, int64_t R, int64_t sq_total, int dist_kind,
            int linkage, float threshold, const int32_t* target, int32_t* merge_a, int32_t* merge_b, float* merge_h, int32_t* merge_size,
            int32_t* labels, int32_t* n_clusters, void* ws, void* stream);
+/* vm_reseg: Viterbi resegmentation for speaker diarization (csrc/reseg.hip, voicemap_amd/diarization.py; reseg_reference there is the numpy
+ * statement).  emb (N, E) fp32 holds the windows of R recordings back to back IN TIME ORDER; recording r owns rows row0[r] .. row0[r + 1]
+ * (n_r of them) and K_r = n_models[r] models.  row0 / em0: R + 1 int64 each ON THE DEVICE, the exclusive cumulative sums of n_r and of
+ * n_r K_r (row0[R] == N, em0[R] == em_total; the host holds the lengths, as with vm_ahc's mat0).  n_models (R), labels_in (N) and
+ * chain_start (N, or NULL) int32 on the device.  labels_in[i] in [0, K_r) names the model row i belongs to; anything else (-1 by
+ * convention): the row belongs to no model yet.  A non-zero chain_start[i] starts a new chain at row i; the first row of a recording
+ * always starts one.  kind is VM_DIST_EUCLIDEAN, VM_DIST_COSINE or VM_DIST_DOT.  VM_SCORE_PLDA is refused: the mean of PLDA-space rows is
+ * not a PLDA-space row, because their last column is quadratic in the row.
+ * Per recording, its rows renumbered 0 .. n - 1, lab = labels_in; for it = 1 .. iters:
+ *   Models.  For k < K: sum_k, msum_k, count_k are exactly vm_speaker_sums' for the rows of this recording with lab == k (float64
+ *   contributions added in ascending row order); a row whose label is outside [0, K) enrols nowhere.
+ *   Emissions.  e[t][k] = the fp32 score vm_speaker_identify states for the trial (row t, model k) with leave_one_out = 0 (float64 until
+ *   the single rounding); count_k == 0 or a NaN score: e[t][k] = +inf.
+ *   Decode, per chain t0 .. t1, in float64, every operation rounded on its own:  c[t0][k] = (double)e[t0][k];  for t > t0:  j* = the
+ *   first minimum of c[t-1][.] (lowest index on ties),  sw = c[t-1][j*] + switch_cost,
+ *   c[t][k] = (double)e[t][k] + (c[t-1][k] <= sw ? c[t-1][k] : sw)  (a tie stays),  the back pointer of (t, k) is k or j* accordingly.
+ *   The chain ends in the first minimum of c[t1][.]; the labels are the back trace from there.
+ *   Stop rule.  n_changed[r] = the number of rows whose new label differs from lab; if it is 0: stop; else lab = the new labels.
+ * Outputs, on the device.  labels_out (N) int32: the last decode's labels -- model indices, never renumbered: a cluster that dies keeps
+ * its number.  path_cost (R) float64: the sum of the chains' final minima of the last decode, added in chain order from 0.0.  iters_run
+ * (R) int32: the number of decodes done.  n_changed (R) int32: the last decode's.  emis (em_total fp32, may be NULL): the emissions of
+ * the last iteration run, e[t][k] at em0[r] + t K_r + k.
+ *   No model with count > 0 (every label outside [0, K)):  labels_out = -1, path_cost = NaN, iters_run = 0, n_changed = 0, emis = +inf.
+ *   Empty recording:  nothing is written but iters_run = 0.
+ * The outputs are a function of the inputs alone -- no atomics, bit-identical from run to run.
+ * Limits.  1 <= K_r <= VM_RESEG_MAX_K, E <= 256, N < 2^31, switch_cost finite and >= 0, 1 <= iters <= 16; no cap on n_r; labels_out
+ * must not be labels_in; ws 16-byte aligned; a bad argument is an error before any launch; R == 0 returns without a launch.  The
+ * launcher cannot see the device tables: a K_r out of range, or row0 / em0 that do not go together (em0[r + 1] - em0[r] != n_r K_r, a
+ * range outside [0, N] / [0, em_total]), must be refused by the caller (voicemap_amd/diarization.py resegment does); the kernel leaves
+ * iters_run[r] = -1 and nothing else for such a recording.
+ * Launches: the row norms of all N rows; then one workgroup of 256 threads per recording for the whole loop.  The models live in LDS as
+ * float64, VM_RESEG_MAX_K (E + 1) x 8 bytes (132 KB at E = 256: the entry point compares it with the device's per-block limit, as
+ * vm_stft_logmel does); a decode step is one lane per model plus a wave-wide first minimum; the recording's chains are dealt to the
+ * four waves in turn.  O(n K E) per iteration for the emissions, O(n) sequential steps for the models and per chain.
+ * ws >= vm_reseg_workspace_bytes(N, E, R, em_total): N row norms, 9 bytes of back pointers and one float64 per row, em_total floats. */
+enum { VM_RESEG_MAX_K = 64 };
+int64_t vm_reseg_workspace_bytes(int64_t N, int E, int64_t R, int64_t em_total);
+int vm_reseg(const float* emb, int64_t N, int E, const int64_t* row0, const int64_t* em0, int64_t R, int64_t em_total,
+             const int32_t* n_models, const int32_t* labels_in, const int32_t* chain_start, int kind, double switch_cost, int iters,
+             int32_t* labels_out, double* path_cost, int32_t* iters_run, int32_t* n_changed, float* emis, void* ws, void* stream);
 
 /* ---- the PLDA back end (csrc/plda.hip, voicemap_amd/plda.py): the statistics of the fit and the projection into PLDA space -----------
  * vm_scatter_f64: out (D, D) float64 = sum over the rows r of x (N, D) fp32 with label[r] >= 0 (label NULL: all rows) of

@@ -11,6 +11,9 @@ namespace vm {
 // ---- error plumbing -----------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// the LDS bytes the current device grants one workgroup (64 KiB where it cannot be asked): launchers with more than 64 KiB of dynamic
+// LDS compare their need with it and refuse before launching
+size_t lds_per_block_limit();
 
 #define VM_REQUIRE(cond, ...)                 \
     do {                                      \

@@ -24,6 +24,15 @@ int check_launch(const char* what) {
     return VM_OK;
 }
 
+size_t lds_per_block_limit() {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) {
+        (void)hipGetLastError();
+        return 64 * 1024;
+    }
+    return (size_t)v;
+}
+
 }  // namespace vm
 
 extern "C" const char* vm_last_error(void) { return vm::g_err; }

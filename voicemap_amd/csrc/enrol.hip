@@ -24,13 +24,14 @@
 // the own-speaker cell takes en_own_kernel's score.  HIST = false: the score matrix, and per row the number of speakers before the own
 // one and the best (key, speaker) -- integer sums and minima kept in registers over all model tiles and merged over the 16 lanes of a
 // row at the end.  HIST = true: the counts by class, exactly as pair_hist_kernel (verif.hip) keeps them: u32 LDS bins, per-lane
-// under / over / NaN counts, one flush of 64-bit integer atomics per workgroup.  One template, one en_acc / en_finish: the two entry
-// points score bit-identically.
+// under / over / NaN counts, one flush of 64-bit integer atomics per workgroup.  One template, one en_acc / en_finish (enrol_score.hpp,
+// shared with reseg.hip): the two entry points score bit-identically.
+#include "enrol_score.hpp"
 #include "score_tile.hpp"
 
 namespace vm {
 
-constexpr int EN_MAX_E = 256, EN_TQ = 64, EN_TS = 64, EN_EC = 32, EN_LD = 66, EN_MAX_WIN = 4;
+constexpr int EN_TQ = 64, EN_TS = 64, EN_EC = 32, EN_LD = 66, EN_MAX_WIN = 4;
 constexpr int EN_LDS_HIST_WORDS = 2 * 4 * (1024 + 3);   // = VH_LDS_HIST_WORDS (verif.hip): the same limits on windows and bins
 typedef __attribute__((ext_vector_type(2))) double f64x2;
 
@@ -38,31 +39,6 @@ struct EnWindows {
     uint32_t lo[EN_MAX_WIN];
     uint32_t shift[EN_MAX_WIN];
 };
-
-// ---- the one scoring function of both entry points --------------------------------------------------------------------------------
-template <int KIND>
-__device__ inline double en_acc(double acc, double q, double p) {
-    if (KIND == VM_DIST_EUCLIDEAN) {
-        const double d = q - p;
-        return fma(d, d, acc);
-    }
-    return fma(q, p, acc);
-}
-template <int KIND>
-__device__ inline float en_finish(double acc, double qn, double pn) {
-    if (KIND == VM_DIST_EUCLIDEAN) return (float)__dsqrt_rn(acc);
-    if (KIND == VM_DIST_COSINE) return (float)(1.0 - acc / (qn * pn));
-    return (float)(-acc);
-}
-
-__device__ inline double en_row_norm(const float* __restrict__ x, int E) {
-    double s = 0.0;
-    for (int e = 0; e < E; ++e) {
-        const double v = (double)x[e];
-        s = fma(v, v, s);
-    }
-    return __dsqrt_rn(s);
-}
 
 __global__ __launch_bounds__(256) void en_rownorm_kernel(const float* __restrict__ x, int64_t rows, int E, double* __restrict__ out) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -100,7 +76,7 @@ __global__ __launch_bounds__(256) void en_sums_kernel(const float* __restrict__ 
             ms += nr;
             if (tid < E) {
                 const double v = (double)emb[r * E + tid];
-                acc += KIND == VM_DIST_EUCLIDEAN ? v : v / nr;
+                acc += en_contrib<KIND>(v, nr);
             }
         }
         cnt += total;
@@ -122,11 +98,7 @@ __global__ __launch_bounds__(256) void en_proto_kernel(const double* __restrict_
     const int64_t s = blockIdx.x;
     const int32_t n = count[s];
     if (tid < E) {
-        double p = 0.0;
-        if (n > 0) {
-            p = sums[s * E + tid] / (double)n;
-            if (KIND == VM_DIST_DOT) p = (msum[s] / (double)n) * p;
-        }
+        const double p = n > 0 ? en_model<KIND>(sums[s * E + tid], msum[s], (double)n) : 0.0;
         P[s * E + tid] = p;
         row[tid] = p;
     }
@@ -396,6 +368,10 @@ __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ 
     }
 }
 
+void launch_en_rownorm(const float* x, int64_t rows, int E, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(en_rownorm_kernel, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, st, x, rows, E, out);
+}
+
 static inline char* en_align(void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 
 static int en_check_models(const char* what, const void* q, const void* q_label, int64_t M, int E, const void* sums, const void* msum,
@@ -457,7 +433,7 @@ extern "C" int vm_speaker_sums(const float* emb, const int32_t* label, int64_t N
     VM_REQUIRE(kind >= VM_DIST_EUCLIDEAN && kind <= VM_DIST_DOT, "vm_speaker_sums: unknown kind %d", kind);
     hipStream_t st = (hipStream_t)stream;
     double* norm = (double*)en_align(ws);
-    hipLaunchKernelGGL(en_rownorm_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, emb, N, E, norm);
+    launch_en_rownorm(emb, N, E, norm, st);
 #define VM_EN_SUMS(K) hipLaunchKernelGGL((en_sums_kernel<K>), dim3((unsigned)S), dim3(256), 0, st, emb, label, N, E, norm, sums, msum, count)
     switch (kind) {
         case VM_DIST_EUCLIDEAN: VM_EN_SUMS(VM_DIST_EUCLIDEAN); break;

@@ -1302,15 +1302,8 @@ static dim3 ew_grid(int64_t windows, int64_t vectors_per_window) { return dim3((
 using namespace vm;
 
 // The frame matrices of a long window pass 64 KiB (fp32 kernel: win_length = 512; f16 kernels: win_length > 496): more dynamic LDS than
-// every device grants a workgroup.  The entry points ask the current device for its per-block limit and refuse before launching.
-static size_t lds_per_block_limit() {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0) {
-        (void)hipGetLastError();
-        return 64 * 1024;
-    }
-    return (size_t)v;
-}
+// every device grants a workgroup.  The entry points ask the current device for its per-block limit (lds_per_block_limit, common.hpp) and
+// refuse before launching.
 
 extern "C" int64_t vm_stft_frames(int64_t raw_len, int win_length, int hop) {
     if (raw_len < win_length || hop <= 0) return 0;

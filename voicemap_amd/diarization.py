@@ -4,7 +4,11 @@ A recording is cut into sliding windows (``sliding_windows``), every window is e
 offsets into the resident int16 buffer), the windows of each recording are clustered agglomeratively on the chip (``cluster``:
 ``vm_ahc``, voicemap_amd/csrc/cluster.hip -- one launch, one workgroup per recording, only merge lists and labels leave the chip)
 and the window labels become segments (``window_segments``).  ``der`` scores a hypothesis against reference segments;
-``make_conversations`` builds synthetic conversations from single-speaker files; ``diarize`` is the whole path.
+``make_conversations`` builds synthetic conversations from single-speaker files (with pauses, if asked); ``diarize`` is the whole path.
+Two optional stages around the clustering: speech gating in front (``vad``: windows that are mostly pause are neither embedded nor
+clustered, and no unvoiced frame carries a speaker) and Viterbi resegmentation behind (``resegment``: ``vm_reseg``,
+voicemap_amd/csrc/reseg.hip -- one model per cluster, every window scored against every model, the label sequence decoded by a sticky
+HMM, a few times over; ``reseg_reference`` is its numpy statement, the contract itself is in include/voicemap_hip.h).
 
 The contract of the clustering, for ONE recording of n windows ("slots" 0 .. n - 1) and a symmetric distance matrix D (lower = more
 alike), is ``ahc_reference`` -- the numpy statement every device test compares against, bit for bit:
@@ -35,7 +39,10 @@ MAX_N = 2048   # VM_AHC_MAX_N of include/voicemap_hip.h: a recording's matrix be
 LINKAGES = ("single", "complete", "average")
 SAMPLING_RATE = 16000
 
+MAX_K = 64     # VM_RESEG_MAX_K: a decode step is one lane per model
+MAX_ITERS = 16
 Ahc = namedtuple("Ahc", "merge_a merge_b merge_h merge_size labels n_clusters")
+Reseg = namedtuple("Reseg", "labels path_cost iters_run n_changed emis")
 
 
 # ---- the contract --------------------------------------------------------------------------------------------------------------------
@@ -160,15 +167,15 @@ class Clustering:
         return Ahc(h.merge_a[lo:hi], h.merge_b[lo:hi], h.merge_h[lo:hi], h.merge_size[lo:hi], h.labels[lo:hi], int(h.n_clusters[r]))
 
 
-def _row_table(row0, N: int) -> np.ndarray:
+def _row_table(row0, N: int, cap: Optional[int] = MAX_N) -> np.ndarray:
     row0 = np.ascontiguousarray(np.asarray(row0.cpu() if hasattr(row0, "cpu") else row0, dtype=np.int64).reshape(-1))
     if row0.size < 1 or row0[0] != 0 or row0[-1] != N:
         raise ValueError("row0 must run from 0 to the number of rows (%d)" % N)
     n_r = np.diff(row0)
     if n_r.size and n_r.min() < 0:
         raise ValueError("row0 must not decrease")
-    if n_r.size and n_r.max() > MAX_N:
-        raise ValueError("recording %d holds %d windows: at most %d can be clustered" % (int(n_r.argmax()), int(n_r.max()), MAX_N))
+    if cap is not None and n_r.size and n_r.max() > cap:
+        raise ValueError("recording %d holds %d windows: at most %d can be clustered" % (int(n_r.argmax()), int(n_r.max()), cap))
     return row0
 
 
@@ -210,6 +217,190 @@ def cluster(emb, row0, distance: str = "cosine", linkage: str = "average", thres
              None if target is None else target.data_ptr(), res.merge_a.data_ptr(), res.merge_b.data_ptr(), res.merge_h.data_ptr(),
              res.merge_size.data_ptr(), res.labels.data_ptr(), res.n_clusters.data_ptr(), ws.data_ptr(),
              torch.cuda.current_stream(dev).cuda_stream)
+    return res
+
+
+# ---- resegmentation: the contract of vm_reseg and the device call ------------------------------------------------------------------
+def _chain_table(chain_start, n: int) -> np.ndarray:
+    start = np.zeros(n, dtype=bool)
+    if chain_start is not None:
+        start |= np.asarray(chain_start).reshape(-1) != 0
+    if n:
+        start[0] = True
+    return start
+
+
+def viterbi_reference(emis, chain_start, switch_cost: float) -> Tuple[np.ndarray, float]:
+    """The decode of ``vm_reseg`` for ONE recording on its (n, K) fp32 emissions (lower = more alike): per chain, in float64,
+    ``c[t0] = e[t0]``; then ``j* = `` the first minimum of ``c[t - 1]``, ``sw = c[t - 1][j*] + switch_cost``, ``c[t][k] = e[t][k] +
+    (c[t - 1][k] if c[t - 1][k] <= sw else sw)`` (a tie stays); the chain ends in the first minimum of its last row and is traced back
+    from there.  Returns (labels (n,) int32, the sum of the chains' final minima in chain order)."""
+    e = np.asarray(emis, dtype=np.float32)
+    n, K = e.shape
+    start, sc = _chain_table(chain_start, n), np.float64(switch_cost)
+    bounds = np.append(np.flatnonzero(start), n)
+    labels, cost, ks = np.full(n, -1, np.int32), np.float64(0.0), np.arange(K)
+    for t0, t1 in zip(bounds[:-1], bounds[1:]):
+        c = e[t0].astype(np.float64)
+        back = []
+        for t in range(t0 + 1, t1):
+            j = int(np.argmin(c))
+            sw = c[j] + sc
+            stay = c <= sw
+            back.append(np.where(stay, ks, j))
+            c = e[t].astype(np.float64) + np.where(stay, c, sw)
+        k = int(np.argmin(c))
+        cost = cost + c[k]
+        for t in range(t1 - 1, t0 - 1, -1):
+            labels[t] = k
+            if t > t0:
+                k = int(back[t - t0 - 1][k])
+    return labels, float(cost)
+
+
+def emissions_reference(emb, labels, K: int, kind) -> np.ndarray:
+    """(n, K) fp32: every row of ONE recording against the models of its rows with ``labels == k`` -- the models and scores of
+    ``enrolment.speaker_sums_numpy`` / ``trial_scores_numpy`` (no leave-one-out), rounded to fp32 once; +inf where the model has no row
+    or the score is NaN."""
+    from .enrolment import trial_scores_numpy
+    emb = np.asarray(emb, dtype=np.float32)
+    scores, trial = trial_scores_numpy(emb, labels, emb, np.full(len(emb), -1), kind, False, S=K)
+    with np.errstate(over="ignore"):
+        e = scores.astype(np.float32)
+    e[~trial | np.isnan(e)] = np.inf
+    return e
+
+
+def reseg_reference(emb, row0, n_models, labels, chain_start, kind, switch_cost: float, iters: int) -> Reseg:
+    """The numpy statement of ``vm_reseg`` (include/voicemap_hip.h).  ``emb`` (N, E), ``row0`` (R + 1,), ``n_models`` (R,), ``labels``
+    (N,), ``chain_start`` (N,) or None.  Returns ``Reseg(labels (N,) int32, path_cost (R,) float64, iters_run (R,) int32, n_changed
+    (R,) int32, emis (sum n_r K_r,) fp32)``; an empty recording has path_cost NaN and zeros (the device writes nothing for it but
+    ``iters_run``)."""
+    emb, row0 = np.asarray(emb, dtype=np.float32), np.asarray(row0, dtype=np.int64)
+    labels_in, R = np.asarray(labels).astype(np.int32), len(row0) - 1
+    n_models = np.broadcast_to(np.asarray(n_models, dtype=np.int64), (R,))
+    if not (1 <= int(iters) <= MAX_ITERS and np.isfinite(switch_cost) and switch_cost >= 0):
+        raise ValueError("iters in [1, %d], switch_cost finite and >= 0" % MAX_ITERS)
+    out = np.full(len(emb), -1, np.int32)
+    cost, run, chg, emis = np.full(R, np.nan), np.zeros(R, np.int32), np.zeros(R, np.int32), []
+    for r in range(R):
+        lo, hi, K = int(row0[r]), int(row0[r + 1]), int(n_models[r])
+        if hi == lo:
+            continue
+        if not 1 <= K <= MAX_K:
+            raise ValueError("recording %d has %d models: 1 .. %d can be decoded" % (r, K, MAX_K))
+        x, lab = emb[lo:hi], labels_in[lo:hi]
+        cs = None if chain_start is None else np.asarray(chain_start)[lo:hi]
+        e = emissions_reference(x, lab, K, kind)
+        if not ((lab >= 0) & (lab < K)).any():   # no model at all
+            emis.append(e.ravel())
+            continue
+        for it in range(1, int(iters) + 1):
+            if it > 1:
+                e = emissions_reference(x, lab, K, kind)
+            new, cost[r] = viterbi_reference(e, cs, switch_cost)
+            run[r], chg[r] = it, int((new != lab).sum())
+            lab = new
+            if chg[r] == 0:
+                break
+        out[lo:hi] = lab
+        emis.append(e.ravel())
+    return Reseg(out, cost, run, chg, np.concatenate(emis).astype(np.float32) if emis else np.zeros(0, np.float32))
+
+
+class Resegmentation:
+    """What ``resegment`` leaves on the device: ``labels`` (N,) int32, ``path_cost`` (R,) float64, ``iters_run`` / ``n_changed`` (R,)
+    int32, ``emis`` (sum n_r K_r,) fp32 with recording r's (n_r, K_r) matrix at ``em0[r]``; ``row0`` / ``em0`` / ``n_models`` are the
+    host's tables.  ``host()`` is all of it as numpy arrays (one read-back), ``recording(r)`` recording r's part."""
+
+    def __init__(self, row0, em0, n_models, labels, path_cost, iters_run, n_changed, emis, distance, switch_cost, iters):
+        self.row0, self.em0, self.n_models = row0, em0, n_models
+        self.labels, self.path_cost, self.iters_run, self.n_changed, self.emis = labels, path_cost, iters_run, n_changed, emis
+        self.distance, self.switch_cost, self.iters = distance, switch_cost, iters
+        self._host = None
+
+    def host(self) -> Reseg:
+        if self._host is None:
+            self._host = Reseg(*(t.cpu().numpy() for t in (self.labels, self.path_cost, self.iters_run, self.n_changed, self.emis)))
+        return self._host
+
+    def recording(self, r: int) -> Reseg:
+        h, lo, hi, K = self.host(), int(self.row0[r]), int(self.row0[r + 1]), int(self.n_models[r])
+        return Reseg(h.labels[lo:hi], float(h.path_cost[r]), int(h.iters_run[r]), int(h.n_changed[r]),
+                     h.emis[int(self.em0[r]):int(self.em0[r + 1])].reshape(hi - lo, K) if hi > lo else np.zeros((0, K), np.float32))
+
+
+class ResegPolicy:
+    """How ``diarize`` resegments: the cost of a speaker change (in units of the distance), the number of model / decode rounds, and
+    -- optionally -- a finer hop at which the windows are cut, embedded and decoded while the clustering keeps the coarse one."""
+
+    def __init__(self, switch_cost: float, iters: int = 3, hop_seconds: Optional[float] = None):
+        self.switch_cost, self.iters, self.hop_seconds = float(switch_cost), int(iters), None if hop_seconds is None else float(hop_seconds)
+        _check_decode(self.switch_cost, self.iters)
+        if self.hop_seconds is not None and not self.hop_seconds > 0:
+            raise ValueError("hop_seconds must be positive")
+
+
+def _check_decode(switch_cost, iters):
+    if not (np.isfinite(switch_cost) and switch_cost >= 0):
+        raise ValueError("switch_cost must be finite and >= 0")
+    if not 1 <= iters <= MAX_ITERS:
+        raise ValueError("iters must be in [1, %d]" % MAX_ITERS)
+
+
+def resegment(emb, row0, labels, n_models, chain_start=None, distance: str = "cosine", switch_cost: float = 0.5, iters: int = 3,
+              return_emis: bool = True) -> Resegmentation:
+    """Resegment the windows of R recordings in one ``vm_reseg`` call.  ``emb``: (N, E) fp32 device tensor, recording r's windows IN TIME
+    ORDER at rows ``row0[r] .. row0[r + 1]``; ``labels`` (N,): the model (cluster) of every row within its recording, -1 for a row that
+    belongs to none yet; ``n_models``: one count or one per recording, 1 .. 64 wherever the recording has rows; ``chain_start`` (N,),
+    optional: non-zero where a row must not be tied to the row before it (a gap in time).  Any number of windows per recording.
+    distance="plda" is refused: the models are means of rows, and the mean of PLDA-space rows is not a PLDA-space row."""
+    import torch
+    from . import _lib
+    if distance == "plda":
+        raise ValueError('resegment: distance="plda" is refused: a model is the mean of its rows, and the mean of PLDA-space rows is not '
+                         "a PLDA-space row (their last column is quadratic in the row)")
+    if distance not in _lib.DIST:
+        raise ValueError("Distance must be in (euclidean, cosine, dot_product)")
+    _check_decode(float(switch_cost), int(iters))
+    if emb.dim() != 2 or emb.dtype != torch.float32:
+        raise TypeError("emb must be an (N, E) fp32 tensor")
+    emb = emb.contiguous()
+    N, E, dev = int(emb.shape[0]), int(emb.shape[1]), emb.device
+    row0 = _row_table(row0, N, cap=None)
+    R, n_r = row0.size - 1, np.diff(row0)
+    K = np.asarray(n_models.cpu() if hasattr(n_models, "cpu") else n_models, dtype=np.int64)
+    K = np.broadcast_to(K, (R,)).copy() if K.ndim == 0 else K.reshape(-1)
+    if K.shape != (R,):
+        raise ValueError("n_models must be one number or one per recording")
+    bad = np.flatnonzero((n_r > 0) & ((K < 1) | (K > MAX_K)))
+    if bad.size:
+        raise ValueError("recording %d has %d models: 1 .. %d can be decoded" % (int(bad[0]), int(K[bad[0]]), MAX_K))
+    K = np.where(n_r > 0, K, 0)
+
+    def rows(t, name):
+        t = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t).reshape(-1)))
+        if t.numel() != N:
+            raise ValueError("%s must hold one value per row of emb (%d), not %d" % (name, N, t.numel()))
+        return t.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    lab = rows(labels, "labels")
+    cs = None if chain_start is None else rows(chain_start, "chain_start")
+    em0 = np.concatenate([[0], np.cumsum(n_r * K)]).astype(np.int64)
+    total = int(em0[-1])
+    res = Resegmentation(row0, em0, K, torch.full((N,), -1, dtype=torch.int32, device=dev),
+                         torch.full((R,), float("nan"), dtype=torch.float64, device=dev), torch.zeros(R, dtype=torch.int32, device=dev),
+                         torch.zeros(R, dtype=torch.int32, device=dev),
+                         torch.empty(total if return_emis else 0, dtype=torch.float32, device=dev), distance, float(switch_cost), int(iters))
+    if R == 0 or N == 0:
+        return res
+    tab = torch.from_numpy(np.concatenate([row0, em0])).to(dev)   # one upload
+    km = torch.from_numpy(K.astype(np.int32)).to(dev)
+    lib = _lib.lib()
+    ws = lib.workspace("vm_reseg_workspace_bytes", N, E, R, total, device=dev)
+    lib.call("vm_reseg", emb.data_ptr(), N, E, tab.data_ptr(), tab[R + 1:].data_ptr(), R, total, km.data_ptr(), lab.data_ptr(),
+             None if cs is None else cs.data_ptr(), _lib.DIST[distance], float(switch_cost), int(iters), res.labels.data_ptr(),
+             res.path_cost.data_ptr(), res.iters_run.data_ptr(), res.n_changed.data_ptr(), res.emis.data_ptr() if return_emis else None,
+             ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     return res
 
 
@@ -255,6 +446,45 @@ def window_segments(starts, window: int, length: int, labels) -> np.ndarray:
         else:
             segs.append([b, e, int(lab)])
     return np.array(segs, dtype=np.int64).reshape(-1, 3)
+
+
+def lattice_windows(lens, window: int, hop: int, fine_hop: int) -> Tuple[List[np.ndarray], List[np.ndarray]]:
+    """The windows of ``sliding_windows(lens, window, fine_hop)`` and, per recording, which of them ``sliding_windows(lens, window,
+    hop)`` holds too: the ones on the coarse lattice plus the window flush with the end.  ``hop`` must be a multiple of ``fine_hop``
+    (the coarse windows are then all among the fine ones)."""
+    hop, fine_hop = int(hop), int(fine_hop)
+    if fine_hop < 1 or hop % fine_hop:
+        raise ValueError("the hop (%d samples) must be a multiple of the resegmentation hop (%d samples)" % (hop, fine_hop))
+    fine, coarse = sliding_windows(lens, window, fine_hop), sliding_windows(lens, window, hop)
+    return fine, [np.isin(f, c) for f, c in zip(fine, coarse)]
+
+
+def voiced_share(mask, frame: int, starts, window: int) -> np.ndarray:
+    """Per window [start, start + window) of ONE recording the share of its frames that ``mask`` (one value per frame of ``frame``
+    samples, non-zero = voiced) keeps; a window's frames are those it overlaps, ``start // frame .. (start + window - 1) // frame``."""
+    mask, starts = np.asarray(mask).reshape(-1) != 0, np.asarray(starts, dtype=np.int64).reshape(-1)
+    cum = np.concatenate([[0], np.cumsum(mask)])
+    first, last = starts // int(frame), np.minimum((starts + int(window) - 1) // int(frame), len(mask) - 1)
+    return (cum[last + 1] - cum[first]) / np.maximum(last + 1 - first, 1)
+
+
+def chain_starts(kept) -> np.ndarray:
+    """For the kept windows of ONE recording (``kept``: one bool per window, in time order) 1 where a chain starts: at the first kept
+    window and at every kept window with a dropped one between it and the kept window before."""
+    idx = np.flatnonzero(np.asarray(kept, dtype=bool))
+    return np.concatenate([[1], (np.diff(idx) > 1).astype(np.int32)]).astype(np.int32) if idx.size else np.zeros(0, np.int32)
+
+
+def cut_to_voiced(segments, mask, frame: int, length: int) -> np.ndarray:
+    """``segments`` ((k, 3) rows of start, end, label) cut to the voiced frames of ``mask``: every piece of a segment that lies in a run
+    of voiced frames is kept, nothing else -- an unvoiced frame carries no speaker.  Frame f covers the samples ``f frame .. min((f +
+    1) frame, length)``."""
+    seg = np.asarray(segments, dtype=np.int64).reshape(-1, 3)
+    edge = np.diff(np.concatenate([[0], (np.asarray(mask).reshape(-1) != 0).astype(np.int8), [0]]))
+    lo = np.minimum(np.flatnonzero(edge == 1) * int(frame), int(length))
+    hi = np.minimum(np.flatnonzero(edge == -1) * int(frame), int(length))
+    out = [(max(b, a), min(e, z), lab) for b, e, lab in seg for a, z in zip(lo, hi) if max(b, a) < min(e, z)]
+    return np.array(out, dtype=np.int64).reshape(-1, 3)
 
 
 # ---- scoring ---------------------------------------------------------------------------------------------------------------------------
@@ -352,10 +582,12 @@ def der(reference_segments, hypothesis_segments) -> dict:
 class Conversations:
     """``audio``: the int16 buffer of all conversations back to back (a device tensor when the corpus is resident, else what
     ``to('cuda')`` uploads); ``offsets`` / ``lens`` (n,) int64; ``segments``: per conversation the reference table (turns, 3) of (start,
-    end, speaker code), samples relative to the conversation; ``speakers``: per conversation the number of speakers present."""
+    end, speaker code), samples relative to the conversation; ``speakers``: per conversation the number of speakers present; ``turns``:
+    per conversation the (file, start, length) of every turn; ``pauses``: per conversation the samples of silence in front of every turn."""
 
-    def __init__(self, audio, offsets, lens, segments, turns):
+    def __init__(self, audio, offsets, lens, segments, turns, pauses=None):
         self.audio, self.offsets, self.lens, self.segments, self.turns = audio, offsets, lens, segments, turns
+        self.pauses = pauses if pauses is not None else [[0] * len(t) for t in turns]
         self.speakers = np.array([len(np.unique(s[:, 2])) for s in segments], dtype=np.int64)
 
     def __len__(self):
@@ -363,11 +595,15 @@ class Conversations:
 
 
 def make_conversations(dataset, n: int, speakers: Tuple[int, int] = (2, 4), turns: Tuple[int, int] = (6, 12),
-                       turn_seconds: Tuple[float, float] = (1.0, 6.0), seed: int = 0) -> Conversations:
+                       turn_seconds: Tuple[float, float] = (1.0, 6.0), seed: int = 0, pause_seconds: Tuple[float, float] = (0.0, 0.0),
+                       pause_prob: float = 0.0) -> Conversations:
     """``n`` synthetic conversations from the single-speaker files of ``dataset``.  Per conversation: a speaker count in ``speakers`` and
     a turn count in ``turns`` (both inclusive) are drawn, that many distinct speakers, then per turn a speaker that is not the previous
     turn's, one of its files, a length in ``turn_seconds`` clamped to the file, and a crop position.  Turns follow each other without
-    pause or overlap, so the reference segments tile the conversation.  The draws come from this function's own
+    overlap; at the defaults also without pause, so the reference segments tile the conversation.  With ``pause_prob`` > 0 every turn
+    but the first is, with that probability, preceded by digital silence (zeros) of a length drawn in ``pause_seconds``: the segments
+    then leave gaps.  (At ``pause_prob`` = 0 no extra number is drawn: the conversations are the same as without the option.)  The
+    draws come from this function's own
     ``numpy.random.Generator(seed)``: the dataset's stream (``np.random``) is not touched.  On a resident corpus
     (``dataset.device_audio``) the buffer is assembled on the device from slices; otherwise in numpy, and uploaded."""
     rng = np.random.default_rng(seed)
@@ -380,11 +616,18 @@ def make_conversations(dataset, n: int, speakers: Tuple[int, int] = (2, 4), turn
         raise ValueError("speakers must be a range within 2 .. %d (the dataset's speakers)" % len(have))
     if turns[0] < 1 or turns[1] < turns[0] or not 0 < turn_seconds[0] <= turn_seconds[1]:
         raise ValueError("bad turn count or turn length range")
-    plan, segments, lens = [], [], []
+    if not (0.0 <= pause_prob <= 1.0 and 0.0 <= pause_seconds[0] <= pause_seconds[1]):
+        raise ValueError("bad pause probability or pause length range")
+    plan, segments, lens, pauses = [], [], [], []
     for _ in range(int(n)):
         cast = rng.choice(have, size=int(rng.integers(speakers[0], speakers[1] + 1)), replace=False)
-        prev, pos, seg, turn = -1, 0, [], []
+        prev, pos, seg, turn, gaps = -1, 0, [], [], []
         for _ in range(int(rng.integers(turns[0], turns[1] + 1))):
+            gap = 0
+            if pause_prob > 0.0 and turn and rng.random() < pause_prob:
+                gap = int(round(rng.uniform(pause_seconds[0], pause_seconds[1]) * SAMPLING_RATE))
+            gaps.append(gap)
+            pos += gap
             who = int(rng.choice(cast[cast != prev]))
             f = int(rng.choice(files_of[who]))
             want = int(round(rng.uniform(turn_seconds[0], turn_seconds[1]) * SAMPLING_RATE))
@@ -394,6 +637,7 @@ def make_conversations(dataset, n: int, speakers: Tuple[int, int] = (2, 4), turn
             seg.append((pos, pos + take, who))
             pos, prev = pos + take, who
         plan.append(turn)
+        pauses.append(gaps)
         segments.append(np.array(seg, dtype=np.int64))
         lens.append(pos)
     lens = np.array(lens, dtype=np.int64)
@@ -403,6 +647,9 @@ def make_conversations(dataset, n: int, speakers: Tuple[int, int] = (2, 4), turn
     if dev_audio is not None:
         go = dataset.global_offset
         parts = [dev_audio[int(go[f]) + s:int(go[f]) + s + k] for turn in plan for f, s, k in turn]
+        if pause_prob > 0.0:
+            silence = torch.zeros(max([g for gaps in pauses for g in gaps] + [0]), dtype=torch.int16, device=dev_audio.device)
+            parts = [x for gap, part in zip((g for gaps in pauses for g in gaps), parts) for x in (silence[:gap], part)]
         audio = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.int16, device=dev_audio.device)
     else:
         from .shards import to_int16
@@ -413,23 +660,39 @@ def make_conversations(dataset, n: int, speakers: Tuple[int, int] = (2, 4), turn
                 cache[f] = np.asarray(dataset._pcm(f)) if hasattr(dataset, "_pcm") else to_int16(dataset._load(f))
             return cache[f]
         parts = [pcm(f)[s:s + k] for turn in plan for f, s, k in turn]
+        if pause_prob > 0.0:
+            parts = [x for gap, part in zip((g for gaps in pauses for g in gaps), parts) for x in (np.zeros(gap, np.int16), part)]
         host = np.concatenate(parts).astype(np.int16) if parts else np.zeros(0, np.int16)
         audio = torch.from_numpy(host)
         if torch.cuda.is_available():
             audio = audio.to("cuda")
-    return Conversations(audio, offsets, lens, segments, plan)
+    return Conversations(audio, offsets, lens, segments, plan, pauses)
 
 
 # ---- the whole path --------------------------------------------------------------------------------------------------------------------
 def diarize(model, audio, offsets, lens, preprocessor, window_seconds: float, hop_seconds: float, network_type: str = "siamese",
             distance: str = "cosine", linkage: str = "average", threshold: Optional[float] = None, n_speakers=None, batch: int = 256,
-            plda=None):
+            plda=None, vad=None, min_voiced: float = 0.5, reseg: Optional[ResegPolicy] = None):
     """Diarize the recordings ``audio[offsets[r] : offsets[r] + lens[r]]`` of a resident int16 buffer: sliding windows, every window
     embedded alone (``embed_from_offsets(..., windows_per_tower=1)``, ``batch`` windows per call), ``cluster``, ``window_segments``.
     Returns (segments per recording, the ``Clustering``); the clustering also carries ``emb`` (N, E), ``starts`` (per recording, relative
     to it) and ``window``.  An engine without resident input raises what ``require_resident_input`` raises.  distance="plda" needs
     ``plda``, a fitted ``plda.PldaModel``: the windows' embeddings are projected by it and clustered on minus the log-likelihood ratio;
-    the clustering then also carries the projected rows as ``rows``."""
+    the clustering then also carries the projected rows as ``rows``.
+
+    ``vad``: a ``vad.VadPolicy``.  One ``vad.detect`` call marks the frames of all recordings and the mask is read back once.  A window
+    whose ``voiced_share`` is below ``min_voiced`` is neither embedded nor clustered; the hypothesis segments are cut to the voiced
+    frames (``cut_to_voiced``); a recording left without a clustered window gets no segments.  (The detector keeps a recording it finds
+    no speech in whole: that is its fallback, and the mask read back says so.)
+    ``reseg``: a ``ResegPolicy``.  The cluster labels are resegmented (``resegment``, ``n_models`` = the clustering's ``n_clusters``, a
+    chain break wherever gating dropped a window) and the segments are made from the decoded labels.  With ``reseg.hop_seconds`` = h
+    (``hop_seconds`` a multiple of it) the windows are cut and embedded at hop h, the ones ``lattice_windows`` marks are clustered as
+    without it, and every other row enters the decode with label -1.  distance="plda" is refused with ``reseg``.
+    With either, the clustering also carries ``window_row0`` (the row table of ``emb``; ``row0`` is that of the clustered rows),
+    ``kept`` (per recording, one bool per window of the lattice: embedded or not), ``clustered`` (per recording, one bool per embedded
+    window), ``chain_start``, ``vad`` (the ``VadResult``), ``voiced`` (per recording, its frames' mask as read back) and ``reseg`` (the
+    ``Resegmentation``); ``starts`` are the embedded windows'.
+    With neither, the calls and the results are what they were without the two options."""
     import torch
     from .engine_core import require_resident_input
     from .retrieval import _encoder_engine
@@ -449,17 +712,56 @@ def diarize(model, audio, offsets, lens, preprocessor, window_seconds: float, ho
     if lens.size and (offsets.min() < 0 or int((offsets + lens).max()) > audio.numel()):
         raise ValueError("a recording lies outside the audio buffer")
     window, hop = int(round(window_seconds * SAMPLING_RATE)), int(round(hop_seconds * SAMPLING_RATE))
-    starts = sliding_windows(lens, window, hop)
+    fine_hop = hop
+    if reseg is not None:
+        if distance == "plda":
+            raise ValueError('diarize: reseg is refused with distance="plda": the mean of PLDA-space rows is not a PLDA-space row')
+        if reseg.hop_seconds is not None:
+            fine_hop = int(round(reseg.hop_seconds * SAMPLING_RATE))
+    if not 0.0 <= min_voiced <= 1.0:
+        raise ValueError("min_voiced is a share of a window's frames, in [0, 1]")
+    R = len(lens)
+    lattice, coarse = lattice_windows(lens, window, hop, fine_hop)
+    kept, det, masks = [np.ones(len(s), dtype=bool) for s in lattice], None, None
+    if vad is not None:
+        from .vad import detect
+        det = detect(audio, offsets, lens, vad)
+        mask, fb = det.mask.cpu().numpy(), det.frame_base_host   # the one read-back
+        masks = [mask[fb[r]:fb[r + 1]] for r in range(R)]
+        for r in range(R):
+            kept[r] = voiced_share(masks[r], vad.frame, lattice[r], window) >= min_voiced
+            if not (kept[r] & coarse[r]).any():   # nothing to cluster: nothing to decode against either
+                kept[r][:] = False
+    starts, coarse = [s[k] for s, k in zip(lattice, kept)], [c[k] for c, k in zip(coarse, kept)]
     row0 = np.concatenate([[0], np.cumsum([len(s) for s in starts])]).astype(np.int64)
-    _row_table(row0, int(row0[-1]))   # a recording with too many windows fails before anything is embedded
+    crow0 = np.concatenate([[0], np.cumsum([int(c.sum()) for c in coarse])]).astype(np.int64)
+    _row_table(crow0, int(crow0[-1]))   # a recording with too many windows fails before anything is embedded
     flat = np.concatenate([o + s for o, s in zip(offsets, starts)]) if len(starts) else np.zeros(0, np.int64)
     emb = torch.empty(len(flat), eng.E, dtype=torch.float32, device=eng.device)
     for b0 in range(0, len(flat), batch):
         offs = torch.as_tensor(flat[b0:b0 + batch])
         emb[b0:b0 + len(offs)].copy_(eng.embed_from_offsets(audio, offs, window, ds, wh, windows_per_tower=1))
     rows = plda.project(emb) if plda is not None else emb
-    res = cluster(rows, row0, distance, linkage, threshold, n_speakers)
+    pick = None   # the clustered rows among the embedded ones, where they are not all of them
+    if int(crow0[-1]) != len(flat):
+        pick = torch.from_numpy(np.flatnonzero(np.concatenate(coarse))).to(emb.device)
+    res = cluster(rows if pick is None else rows[pick], crow0, distance, linkage, threshold, n_speakers)
     res.emb, res.rows, res.starts, res.window = emb, rows, starts, window
-    labels = res.host().labels
-    segments = [window_segments(starts[r], window, int(lens[r]), labels[row0[r]:row0[r + 1]]) for r in range(len(lens))]
+    res.window_row0, res.kept, res.clustered, res.vad, res.voiced, res.reseg = row0, kept, coarse, det, masks, None
+    res.chain_start = np.concatenate([chain_starts(k) for k in kept]) if vad is not None and R else None
+    if reseg is None:
+        labels = res.host().labels
+    else:
+        lab_in = res.labels
+        if pick is not None:
+            lab_in = torch.full((len(flat),), -1, dtype=torch.int32, device=emb.device)
+            lab_in[pick] = res.labels
+        res.reseg = resegment(emb, row0, lab_in, res.host().n_clusters, res.chain_start, distance, reseg.switch_cost, reseg.iters)
+        labels = res.reseg.host().labels
+    segments = []
+    for r in range(R):
+        seg = np.zeros((0, 3), np.int64)
+        if row0[r + 1] > row0[r]:
+            seg = window_segments(starts[r], window, int(lens[r]), labels[row0[r]:row0[r + 1]])
+        segments.append(seg if masks is None else cut_to_voiced(seg, masks[r], vad.frame, int(lens[r])))
     return segments, res
