@@ -5,12 +5,17 @@ EER and thresholds.
     python -m experiments.speaker_identification --siamese models/x.hdf5 [--enrol-set dev-clean] [--test-set test-clean]
         [--per-speaker N] [--distance euclidean|cosine|dot_product] [--whole-utterance] [--synthetic]
         [--vad --vad-threshold-db 25 --vad-hang 10 --vad-min-run 3 --vad-frame-ms 10]
+        [--backend plda --plda-train train|validation --plda-train-set train-clean-100 --lda-dim D --no-length-norm]
 Without --test-set (or with the same set) the enrolled set is also the test set: leave-one-out (every utterance is scored against its own
 speaker's model built from the speaker's OTHER utterances), or with --per-speaker N a seeded choice of N utterances per speaker is
 enrolled and the others are the queries.  With another --test-set its utterances are scored against the enrolled set's models (its
 speakers that were not enrolled give non-target trials only), and the best threshold of the enrolled set is applied to it.  Under
 torchrun the query rows are sharded like the other evaluation scripts.  With --vad the pauses are trimmed out of every file first
-(voicemap_amd/vad.py); the trimming summary is printed and joins the row."""
+(voicemap_amd/vad.py); the trimming summary is printed and joins the row.
+--backend plda (off by default) puts a PLDA back end (voicemap_amd/plda.py) in front, as experiments/verification_accuracy.py does: it is
+fitted on the training set (--plda-train train: --plda-train-set, a further generated set with --synthetic) or on the enrolled set itself
+(--plda-train validation), both sets are projected by it, and every speaker model is scored by the book from ALL its enrolment rows
+(multi-session PLDA, enrolment.enrol(plda=...)); --distance is then not used and the row says distance "plda"."""
 import argparse
 import json
 
@@ -20,15 +25,30 @@ from voicemap_amd.utils import BatchPreProcessor, preprocess_instances
 from voicemap_amd.vad import add_vad_args, policy_from_args
 
 
-def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=None, whole_utterance=False, seed=0, vad=None):
+def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=None, whole_utterance=False, seed=0, vad=None,
+             backend="none", plda_train=None, lda_dim=None, length_norm=True):
     """The result row: identification and model-trial figures of ``test_set`` (None: the enrolled set itself) against the models of
-    ``enrol_set``.  ``vad`` (a ``vad.VadPolicy``): both sets are embedded with their pauses trimmed out."""
+    ``enrol_set``.  ``vad`` (a ``vad.VadPolicy``): both sets are embedded with their pauses trimmed out.  ``backend`` "plda": a
+    ``plda.PldaModel`` is fitted on the embeddings of ``plda_train`` (a dataset; None: the enrolled set) with ``lda_dim`` /
+    ``length_norm``, both sets are projected by it and the models are multi-session PLDA models (``distance`` is not used)."""
     wu = {"whole_utterance": True} if whole_utterance else {}
     if vad is not None:
         wu["vad"] = vad
     ce = retrieval.embed_corpus(net, enrol_set, pre, "siamese", **wu)
-    models = enrolment.enrol(ce, distance, per_speaker=per_speaker, seed=seed)
+    back = None
+    if backend == "plda":
+        from voicemap_amd import plda
+        back = plda.fit_plda(ce if plda_train is None else retrieval.embed_corpus(net, plda_train, pre, "siamese", **wu), lda_dim=lda_dim,
+                             length_norm=length_norm)
+        ce, distance = back.project(ce), "plda"
+        models = enrolment.enrol(ce, per_speaker=per_speaker, seed=seed, plda=back)
+    elif backend != "none":
+        raise ValueError("backend must be none or plda")
+    else:
+        models = enrolment.enrol(ce, distance, per_speaker=per_speaker, seed=seed)
     ct = ce if test_set is None else retrieval.embed_corpus(net, test_set, pre, "siamese", **wu)
+    if back is not None and test_set is not None:
+        ct = back.project(ct)
     ident = enrolment.identify(models, ct)
     mt = enrolment.model_trial_metrics(models, ct)
     cmc = ident["cmc"]
@@ -43,6 +63,9 @@ def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=No
         at = enrolment.model_trial_accuracy_at_threshold(models, ct, me["best_threshold"])
         row.update(enrol_best_threshold=me["best_threshold"], test_balanced_accuracy_at_enrol_threshold=at["balanced_accuracy"],
                    test_far=at["far"], test_frr=at["frr"])
+    if back is not None:
+        row.update(backend="plda", plda_dim=back.D, lda_dim=back.A1.shape[0], length_norm=back.length_norm,
+                   plda_train="validation" if plda_train is None else "train", model_rows_max=models.n_max)
     if vad is not None:
         from voicemap_amd.vad import summarise
         summary = summarise([c.vad_counts for c in ((ce,) if test_set is None else (ce, ct))])
@@ -63,6 +86,11 @@ def _parser():
     p.add_argument("--whole-utterance", action="store_true", help="embed every file whole, at its own length")
     p.add_argument("--synthetic", action="store_true", help="generated speaker sets and a freshly built model")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--backend", default="none", choices=["none", "plda"], help="a trained back end in front of the models (off by default)")
+    p.add_argument("--plda-train", default="train", choices=["train", "validation"], help="the set the PLDA back end is fitted on")
+    p.add_argument("--plda-train-set", default="train-clean-100", help="the training subset of --plda-train train")
+    p.add_argument("--lda-dim", type=int, default=None, help="LDA directions kept in front of PLDA (default: all)")
+    p.add_argument("--no-length-norm", action="store_true", help="no length normalisation between LDA and PLDA")
     add_vad_args(p)   # --vad ...: off by default; both sets are trimmed first
     return p
 
@@ -92,8 +120,14 @@ def main(argv=None):
         net = load_model(a.siamese)
         enrol_set = LibriSpeechDataset(a.enrol_set, a.n_seconds, stochastic=False)
         test_set = None if same else LibriSpeechDataset(a.test_set, a.n_seconds, stochastic=False)
+    plda_train = None
+    if a.backend == "plda" and a.plda_train == "train":
+        plda_train = (SyntheticSpeechDataset(num_speakers=20, files_per_speaker=8, seconds=a.n_seconds, stochastic=False, seed=4,
+                                             subset="synthetic-train")
+                      if a.synthetic else LibriSpeechDataset(a.plda_train_set, a.n_seconds, stochastic=False))
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
-    row = evaluate(net, enrol_set, test_set, pre, a.distance, a.per_speaker, a.whole_utterance, a.seed, vad=vad)
+    row = evaluate(net, enrol_set, test_set, pre, a.distance, a.per_speaker, a.whole_utterance, a.seed, vad=vad, backend=a.backend,
+                   plda_train=plda_train, lda_dim=a.lda_dim, length_norm=not a.no_length_norm)
     row.update(enrol_set="synthetic" if a.synthetic else a.enrol_set,
                test_set=("synthetic" if a.synthetic else a.enrol_set) if same else a.test_set)
     if rank == 0:

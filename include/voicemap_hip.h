@@ -60,10 +60,11 @@ enum { VM_SCORE_WEIGHTED_L1 = 3, VM_SCORE_NEG_EUCLIDEAN = 4, VM_SCORE_PLDA = 6 }
  * NaN handling follows the dot kinds; a row term that is not finite (inf or NaN) gives a NaN score whichever side the row is on.
  * Accepted by vm_pairdist_argmin, vm_pair_score_hist, vm_pair_score_hist_norm, vm_cohort_topk_stats, vm_pair_calib_sums and vm_ahc, with
  * bit-identical scores in all of them; `weights` is not read.  vm_mine_pairs, the n-shot entry points and the speaker models (vm_speaker_*)
- * do not take it: PLDA is a back end, not a training signal, and by-the-book multi-session scoring of speaker models is out of scope. */
+ * do not take it: PLDA is a back end, not a training signal, and a speaker model of several rows is not a PLDA-space row -- speaker
+ * models are scored by the book by vm_plda_speaker_identify / vm_plda_speaker_trial_hist below. */
 
 const char* vm_last_error(void);
-/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms), vm_cohort_topk_stats / vm_cohort_stats_workspace_bytes / vm_pair_score_hist_norm (cohort score normalisation, S-norm / AS-norm), the *_varlen forward entry points (whole utterances in length-masked buckets: vm_crop_decimate_whiten_varlen, vm_conv1_fused_fwd_varlen, vm_conv_fwd_pool_varlen, vm_bn_drop_pool_fwd_varlen, vm_bn_drop_pool_gmax_fwd_varlen, vm_global_maxpool_fwd_varlen), VM_SCORE_PLDA / vm_scatter_f64[_workspace_bytes, _chunk_rows] / vm_plda_project (the PLDA back end); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
+/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms), vm_cohort_topk_stats / vm_cohort_stats_workspace_bytes / vm_pair_score_hist_norm (cohort score normalisation, S-norm / AS-norm), the *_varlen forward entry points (whole utterances in length-masked buckets: vm_crop_decimate_whiten_varlen, vm_conv1_fused_fwd_varlen, vm_conv_fwd_pool_varlen, vm_bn_drop_pool_fwd_varlen, vm_bn_drop_pool_gmax_fwd_varlen, vm_global_maxpool_fwd_varlen), VM_SCORE_PLDA / vm_scatter_f64[_workspace_bytes, _chunk_rows] / vm_plda_project (the PLDA back end), vm_plda_speaker_identify / vm_plda_speaker_trial_hist[_workspace_bytes] (multi-session PLDA speaker models); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
  * vm_conv_dgrad_bnred; `bias`, `wf_packed` and the fourth hb row of vm_fold_bn_weights), the centred block-1 extreme (`center_bias` /
  * `shift_adj` / `mean_adj` of vm_bn_finalize) (round 4).  Earlier: 1 = round 1; 2 = vm_bn_finalize gained the zero-debias arguments (round 2); 3 = VM_F16, `dtype` in vm_conv1_fused_*,
  * `grad_scale` in the loss entry points, `skip_nonfinite` in vm_adam_clip_step, vm_embed_* / vm_pairdist_* (round 3); 4 = the folded-BatchNorm training forward
@@ -971,6 +972,42 @@ int64_t vm_scatter_f64_workspace_bytes(int64_t N, int D);
 int vm_scatter_f64(const float* x, const int32_t* label, const double* mean, int64_t N, int D, double* out, void* ws, void* stream);
 int vm_plda_project(const float* x, const double* mean, const double* A, int64_t N, int E, int D, int length_norm, const double* quad,
                     double c0, float* out, int P, void* stream);
+/* Multi-session PLDA speaker models (csrc/plda_enrol.hip, voicemap_amd/enrolment.py enrol(plda=...)): a query row against a speaker model
+ * of n enrolment rows, scored by minus the two-covariance log-likelihood ratio of the row against the n rows together.  In the
+ * diagonalised space z = V^T (x - mu) (within covariance I, between covariance diag(psi)) the ratio depends on the enrolment rows only
+ * through their sum and n.  Stated on the columns w = sqrt(b) z, b = psi / (1 + 2 psi), of PLDA-space rows (vm_plda_project with quad):
+ *   beta[n][d] = psi_d / (1 + n psi_d),  A[n][d] = (1 + n psi_d) / (2 b_d (1 + (n + 1) psi_d)),  G[d] = 1 / (2 b_d (1 + psi_d)),
+ *   C[n] = 1/2 sum_d log((1 + psi_d)(1 + n psi_d) / (1 + (n + 1) psi_d)),
+ *   score(m, s) = -llr = sum_d A[n][d] (w_md - beta[n][d] Sigma_sd)^2 - sum_d G[d] w_md^2 - C[n],  lower = more alike;
+ * at n = 1 it is VM_SCORE_PLDA's quantity.  The entry points take the tables as they are (PldaModel.model_tables makes them); nothing
+ * here depends on their coming from a psi.
+ * Inputs.  q (M, P) fp32 PLDA-space rows, of which only columns 0 .. D - 1 are read; q_label (M) as in vm_speaker_identify.  sums (S, P)
+ * float64 and count (S) int32: vm_speaker_sums' with VM_DIST_EUCLIDEAN on the enrolled PLDA-space rows (E = P); columns >= D are ignored.
+ * A, beta: (n_max + 1, D) float64 row-major, C: (n_max + 1), G: (D) float64, all on the device; row 0 is never read.
+ * Arithmetic, float64 until ONE rounding to fp32, every operation rounded on its own unless it is written as fma:
+ *   n = count_s, Sigma = sum_s; with leave_one_out != 0 and q_label[m] == s: n = count_s - 1 and Sigma_d = sum_sd - (double)w_md.
+ *   (m, s) is NOT A TRIAL, and is counted nowhere, unless 1 <= n <= n_max (the launcher cannot see count).
+ *   mu_d = beta[n][d] * Sigma_d;  t = (double)w_md - mu_d;  u = A[n][d] * t;  acc = fma(u, t, acc), ascending d from 0.0;
+ *   g_m = fma(G[d], (double)w_md * (double)w_md, g_m), ascending d from 0.0;
+ *   score = (float)((acc - g_m) - C[n]).
+ * Outputs and order: exactly vm_speaker_identify's (scores (M, S) may be NULL and holds NaN where (m, s) is not a trial; the order of the
+ * trials of one query is (uint32 key, speaker) with NaN last; rank, best_idx, best_val, true_score) and vm_speaker_trial_hist's (window,
+ * slot and NaN-slot conventions and limits; hist is ACCUMULATED).  The two entry points score bit-identically; no float atomics: the
+ * outputs are a function of the inputs alone.
+ * Limits.  1 <= D < P <= 256, P % 4 == 0, M, S < 2^31, S >= 1, n_max >= 1; q 16-byte aligned, sums and the tables 8-byte aligned.  A bad
+ * argument is an error before any launch.  M == 0 returns without a launch.  ws >= the matching *_workspace_bytes(M, D, S).
+ * Launches: the per-speaker operands mu_s, A[count_s], C[count_s] (one workgroup per speaker); g_m and the own-speaker score (one thread
+ * per row); the tile kernel, 64 rows x 64 models per step with w, mu and A staged through LDS as float64 in chunks of 16 components. */
+int64_t vm_plda_speaker_identify_workspace_bytes(int64_t M, int D, int64_t S);
+int vm_plda_speaker_identify(const float* q, const int32_t* q_label, int64_t M, int P, int D, const double* sums, const int32_t* count,
+                             int64_t S, const double* A, const double* beta, const double* C, const double* G, int n_max,
+                             int leave_one_out, float* scores, float* true_score, int32_t* rank, float* best_val, int32_t* best_idx,
+                             void* ws, void* stream);
+int64_t vm_plda_speaker_trial_hist_workspace_bytes(int64_t M, int D, int64_t S);
+int vm_plda_speaker_trial_hist(const float* q, const int32_t* q_label, int64_t M, int P, int D, const double* sums, const int32_t* count,
+                               int64_t S, const double* A, const double* beta, const double* C, const double* G, int n_max,
+                               int leave_one_out, const int64_t* host_windows, int n_windows, int bins, uint64_t* hist, void* ws,
+                               void* stream);
 
 /* ---- a10 / f4: log-mel front-end and the 2-D CNN encoder variant (BASELINE.json config 4) -------------------
  * NOT in the reference (nothing to cite under /root/reference); the specification is DESIGN.md section 9 and the

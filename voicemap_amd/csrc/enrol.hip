@@ -25,20 +25,12 @@
 // one and the best (key, speaker) -- integer sums and minima kept in registers over all model tiles and merged over the 16 lanes of a
 // row at the end.  HIST = true: the counts by class, exactly as pair_hist_kernel (verif.hip) keeps them: u32 LDS bins, per-lane
 // under / over / NaN counts, one flush of 64-bit integer atomics per workgroup.  One template, one en_acc / en_finish (enrol_score.hpp,
-// shared with reseg.hip): the two entry points score bit-identically.
-#include "enrol_score.hpp"
-#include "score_tile.hpp"
+// shared with reseg.hip): the two entry points score bit-identically.  What happens to a finished score -- EN_TILE_STATE / EN_TILE_CELL /
+// EN_TILE_FINISH -- and the launchers' window parsing and splits live in enrol_tile.hpp, shared with plda_enrol.hip (multi-session PLDA
+// models): as text, so that this kernel's instruction stream is what it was.
+#include "enrol_tile.hpp"
 
 namespace vm {
-
-constexpr int EN_TQ = 64, EN_TS = 64, EN_EC = 32, EN_LD = 66, EN_MAX_WIN = 4;
-constexpr int EN_LDS_HIST_WORDS = 2 * 4 * (1024 + 3);   // = VH_LDS_HIST_WORDS (verif.hip): the same limits on windows and bins
-typedef __attribute__((ext_vector_type(2))) double f64x2;
-
-struct EnWindows {
-    uint32_t lo[EN_MAX_WIN];
-    uint32_t shift[EN_MAX_WIN];
-};
 
 __global__ __launch_bounds__(256) void en_rownorm_kernel(const float* __restrict__ x, int64_t rows, int E, double* __restrict__ out) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -196,12 +188,7 @@ __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ 
         ownv[i] = okm[i] ? own[m] : nanf_;
         okey[i] = score_key_nan_last(ownv[i]);
     }
-    uint32_t before[4] = {0u, 0u, 0u, 0u};
-    unsigned long long best[4] = {~0ull, ~0ull, ~0ull, ~0ull};
-    float bestf[4] = {nanf_, nanf_, nanf_, nanf_};
-    uint32_t und[EN_MAX_WIN][2], ovr[EN_MAX_WIN][2], nanc[2] = {0u, 0u};
-#pragma unroll
-    for (int v = 0; v < EN_MAX_WIN; ++v) und[v][0] = und[v][1] = ovr[v][0] = ovr[v][1] = 0u;
+    EN_TILE_STATE;
 
     const int nchunk = (E + EN_EC - 1) / EN_EC;
     const int n_stage = (t_hi - t_lo) * nchunk;
@@ -289,90 +276,16 @@ __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ 
                 const bool trial = okm[i] && (is_own ? own_ok[i] : has_model);
                 float d = en_finish<KIND>(acc[i][j], qnv[i], pnv);
                 if (is_own) d = ownv[i];
-                if (!HIST) {
-                    if (scores != nullptr && okm[i] && oks) scores[m * S + s] = trial ? d : nanf_;
-                    if (trial) {
-                        const uint32_t k = score_key_nan_last(d);
-                        const unsigned long long cand = ((unsigned long long)k << 32) | (uint32_t)s;
-                        if (cand < best[i]) {
-                            best[i] = cand;
-                            bestf[i] = d;
-                        }
-                        if (!is_own && (k < okey[i] || (k == okey[i] && s < (int64_t)ql[i]))) before[i] += 1u;
-                    }
-                } else if (trial) {
-                    const int cls = is_own ? 0 : 1;
-                    if (d != d) {
-                        nanc[cls] += 1u;
-                        continue;
-                    }
-                    const uint32_t k = score_key_nan_last(d);
-#pragma unroll
-                    for (int v = 0; v < EN_MAX_WIN; ++v) {
-                        if (v >= n_win) break;
-                        const bool under = k < win.lo[v];
-                        const uint32_t b = (k - win.lo[v]) >> win.shift[v];
-                        const bool over = !under && b >= (uint32_t)bins;
-                        und[v][cls] += under;
-                        ovr[v][cls] += over;
-                        if (!under && !over) atomicAdd(&hist[(v * 2 + cls) * slots + b], 1u);
-                    }
-                }
+                EN_TILE_CELL(d)
             }
         }
     }
-    if (!HIST) {
-        // merge over the 16 lanes of a query row: integer sums and minima, any order gives the same result
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-#pragma unroll
-            for (int o = 1; o < 16; o <<= 1) {
-                before[i] += __shfl_xor(before[i], o, 64);
-                const unsigned long long ob = __shfl_xor(best[i], o, 64);
-                const float of = __shfl_xor(bestf[i], o, 64);
-                if (ob < best[i]) {
-                    best[i] = ob;
-                    bestf[i] = of;
-                }
-            }
-            const int64_t m = mb + tq * 4 + i;
-            if (ts == 0 && okm[i]) {
-                rank[m] = own_ok[i] ? (int32_t)before[i] : -1;
-                true_score[m] = own_ok[i] ? ownv[i] : nanf_;
-                best_idx[m] = best[i] == ~0ull ? -1 : (int32_t)(uint32_t)best[i];
-                best_val[m] = bestf[i];
-            }
-        }
-        return;
-    }
-    auto wave_sum_u = [](uint32_t x) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        return x;
-    };
-    const uint32_t nan0 = wave_sum_u(nanc[0]), nan1 = wave_sum_u(nanc[1]);
-#pragma unroll
-    for (int v = 0; v < EN_MAX_WIN; ++v) {
-        if (v >= n_win) break;
-        const uint32_t c[6] = {wave_sum_u(und[v][0]), wave_sum_u(ovr[v][0]), nan0, wave_sum_u(und[v][1]), wave_sum_u(ovr[v][1]), nan1};
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-                if (c[k] != 0u) atomicAdd(&hist[(v * 2 + k / 3) * slots + bins + k % 3], c[k]);
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < n_words; i += 256) {
-        const uint32_t c = hist[i];
-        if (c != 0u) __hip_atomic_fetch_add(&ghist[i], (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    EN_TILE_FINISH
 }
 
 void launch_en_rownorm(const float* x, int64_t rows, int E, double* out, hipStream_t st) {
     hipLaunchKernelGGL(en_rownorm_kernel, dim3((unsigned)cdiv(rows, 256)), dim3(256), 0, st, x, rows, E, out);
 }
-
-static inline char* en_align(void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 
 static int en_check_models(const char* what, const void* q, const void* q_label, int64_t M, int E, const void* sums, const void* msum,
                            const void* count, int64_t S, int kind, const void* ws) {
@@ -484,29 +397,13 @@ extern "C" int vm_speaker_trial_hist(const float* q, const int32_t* q_label, int
     using namespace vm;
     const char* what = "vm_speaker_trial_hist";
     if (int rc = en_check_models(what, q, q_label, M, E, sums, msum, count, S, kind, ws)) return rc;
-    VM_REQUIRE(host_windows && hist, "%s: null pointer", what);
-    VM_REQUIRE(n_windows >= 1 && n_windows <= EN_MAX_WIN && bins >= 1, "%s: 1..%d windows, bins >= 1", what, EN_MAX_WIN);
-    VM_REQUIRE((int64_t)n_windows * 2 * (bins + 3) <= EN_LDS_HIST_WORDS, "%s: %d windows x %d bins exceed %d LDS words", what, n_windows, bins,
-               EN_LDS_HIST_WORDS);
     EnWindows win{};
-    for (int v = 0; v < n_windows; ++v) {
-        const int64_t lo = host_windows[2 * v], sh = host_windows[2 * v + 1];
-        VM_REQUIRE(lo >= 0 && lo <= 0xffffffffLL && sh >= 0 && sh <= 31, "%s: window %d: key_lo in [0, 2^32), shift in [0, 31]", what, v);
-        win.lo[v] = (uint32_t)lo;
-        win.shift[v] = (uint32_t)sh;
-    }
+    if (int rc = en_windows(what, host_windows, n_windows, bins, hist, &win)) return rc;
     if (M == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const EnScratch a = en_scratch(ws, M, E, S);
     en_prepare(q, q_label, M, E, sums, msum, count, S, kind, leave_one_out, a, st);
-    // model tiles split over blockIdx.y: a workgroup counts at most 64 x 64 x tiles trials in its u32 LDS bins (2^19 tiles), and a small
-    // M still fills the chip
-    const int64_t qb = cdiv(M, EN_TQ), nt = cdiv(S, EN_TS);
-    int64_t splits = cdiv(2048, qb);
-    const int64_t s_min = cdiv(nt, (1 << 19));
-    if (splits < s_min) splits = s_min;
-    if (splits > nt) splits = nt;
-    if (splits < 1) splits = 1;
+    const int64_t qb = cdiv(M, EN_TQ), splits = en_hist_splits(M, S);
     const dim3 grid((unsigned)qb, (unsigned)splits);
 #define VM_EN_H(K)                                                                                                                  \
     hipLaunchKernelGGL((en_tile_kernel<K, true>), grid, dim3(256), 0, st, q, q_label, M, E, a.P, a.pn, count, S, leave_one_out, a.qn, \

@@ -30,6 +30,14 @@ cosine 1, dot_product 2.
   identified), -1 if ``q_label[m] < 0`` or the own speaker has no model for the row (one file under leave-one-out); ``true_score[m]`` the
   score against the own speaker (NaN where rank is -1).
 
+Multi-session PLDA models (``enrol(projected_cache, plda=model)``).  On a cache projected by a ``plda.PldaModel`` a speaker model is
+scored by the book: minus the two-covariance log-likelihood ratio of the row against ALL enrolment rows of the speaker together, which
+needs only their sum (``sums`` of the projected rows, euclidean kind) and their number (``plda`` module docstring; include/voicemap_hip.h
+vm_plda_speaker_identify; the numpy twin is ``plda.trial_scores_plda_numpy``).  The models then carry ``distance == "plda"`` and the
+coefficient tables for 1 .. the largest count rows, and ``identify`` / ``model_trial_metrics`` / ``model_trial_accuracy_at_threshold``
+mean what they mean above -- trials, order, leave-one-out, ``per_speaker``, ``rows`` -- with that score.  ``plda=`` is the switch:
+"plda" is not one of the ``distance`` names.  The cache must already be projected (its width is ``model.P``); a raw cache is refused.
+
 Under torchrun every rank computes the sums over all rows itself (N x E reads; the models are then bit-identical everywhere), takes its
 ``parallel.shard_range`` of the query rows, and the integer rank histogram / trial histograms are summed over ranks.
 """
@@ -211,15 +219,75 @@ def speaker_trial_hist(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count
     return hist
 
 
+def _plda_call(name, q, q_label, sums, count, tables, leave_one_out, *tail_args):
+    """One of the two vm_plda_speaker_* entry points on a (M, P) query block."""
+    lib = _lib.lib()
+    dev = q.device
+    M, P = q.shape
+    S, D, n_max = int(count.shape[0]), int(tables["G"].shape[0]), int(tables["C"].shape[0]) - 1
+    if int(sums.shape[1]) != P:
+        raise ValueError("the sums are %d wide and the rows %d" % (int(sums.shape[1]), P))
+    ws = lib.workspace(name + "_workspace_bytes", M, D, S, device=dev)
+    lib.call(name, q.data_ptr(), q_label.data_ptr(), M, P, D, sums.data_ptr(), count.data_ptr(), S, tables["A"].data_ptr(),
+             tables["beta"].data_ptr(), tables["C"].data_ptr(), tables["G"].data_ptr(), n_max, 1 if leave_one_out else 0, *tail_args,
+             ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+
+
+def plda_tables_to(tables, dev) -> Dict[str, torch.Tensor]:
+    """``PldaModel.model_tables``' dict as contiguous float64 tensors on ``dev``."""
+    return {k: torch.as_tensor(np.ascontiguousarray(np.asarray(tables[k], dtype=np.float64))).to(dev) for k in ("A", "beta", "C", "G")}
+
+
+def plda_speaker_identify(q: torch.Tensor, q_label: torch.Tensor, sums, count, tables, leave_one_out: bool,
+                          return_scores: bool = False) -> Dict[str, torch.Tensor]:
+    """``vm_plda_speaker_identify``: the outputs of ``speaker_identify`` for PLDA-space rows ``q`` (M, P) against the models of ``sums``
+    (S, P) float64 / ``count`` (``speaker_sums`` of the enrolled PLDA-space rows, euclidean kind); ``tables``: ``plda_tables_to``'s."""
+    q = q.contiguous()
+    dev = q.device
+    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
+    M, S = int(q.shape[0]), int(count.shape[0])
+    out = {"true_score": torch.empty(M, dtype=torch.float32, device=dev), "rank": torch.empty(M, dtype=torch.int32, device=dev),
+           "best_val": torch.empty(M, dtype=torch.float32, device=dev), "best_idx": torch.empty(M, dtype=torch.int32, device=dev)}
+    if return_scores:
+        out["scores"] = torch.empty(M, S, dtype=torch.float32, device=dev)
+    if M > 0:
+        _plda_call("vm_plda_speaker_identify", q, q_label, sums, count, tables, leave_one_out,
+                   out["scores"].data_ptr() if return_scores else None, out["true_score"].data_ptr(), out["rank"].data_ptr(),
+                   out["best_val"].data_ptr(), out["best_idx"].data_ptr())
+    return out
+
+
+def plda_speaker_trial_hist(q: torch.Tensor, q_label: torch.Tensor, sums, count, tables, leave_one_out: bool,
+                            windows: Sequence[Tuple[int, int]], bins: int, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``vm_plda_speaker_trial_hist``: ``speaker_trial_hist`` with the multi-session PLDA score."""
+    V.check_windows(windows, bins)
+    q = q.contiguous()
+    dev = q.device
+    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
+    if hist is None:
+        hist = torch.zeros(len(windows), 2, bins + 3, dtype=torch.int64, device=dev)
+    if q.shape[0] > 0:
+        win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
+        _plda_call("vm_plda_speaker_trial_hist", q, q_label, sums, count, tables, leave_one_out, win.ctypes.data, len(windows), bins,
+                   hist.data_ptr())
+    return hist
+
+
 # ---- speaker models of an EmbeddingCache -------------------------------------------------------------------------------------------
 class SpeakerModels:
     """The enrolled speakers of a cache: ``sums`` (S, E) / ``msum`` (S) float64 and ``count`` (S) int32 on the device, the ``distance``
     they were summed for, ``speakers`` (dense index -> the cache's speaker code), ``label`` (N) int32 (the dense index of every enrolled
-    row of the cache, -1 for the rows left out by ``per_speaker``) and the ``cache`` itself."""
+    row of the cache, -1 for the rows left out by ``per_speaker``) and the ``cache`` itself.  Multi-session PLDA models (``distance``
+    "plda") also hold the ``plda`` model and its ``tables`` (float64, on the device) for 1 .. ``n_max`` = the largest count rows."""
 
-    def __init__(self, sums, msum, count, distance, speakers, label, cache, per_speaker):
+    def __init__(self, sums, msum, count, distance, speakers, label, cache, per_speaker, plda=None, tables=None):
         self.sums, self.msum, self.count = sums, msum, count
         self.distance, self.speakers, self.label, self.cache, self.per_speaker = distance, speakers, label, cache, per_speaker
+        self.plda, self.tables = plda, tables
+
+    @property
+    def n_max(self) -> Optional[int]:
+        return None if self.tables is None else int(self.tables["C"].shape[0]) - 1
 
     @property
     def S(self) -> int:
@@ -232,11 +300,22 @@ class SpeakerModels:
         return np.where(self.speakers[pos] == codes, pos, -1).astype(np.int32)
 
 
-def enrol(cache, distance: str = "euclidean", per_speaker: Optional[int] = None, seed: int = 0) -> SpeakerModels:
+def enrol(cache, distance: Optional[str] = None, per_speaker: Optional[int] = None, seed: int = 0, plda=None) -> SpeakerModels:
     """Enrol the speakers of ``cache`` (dense labels from ``np.unique(cache.speaker)``).  ``per_speaker=n``: a seeded choice of n rows of
     every speaker is enrolled (a speaker with fewer than n + 1 rows enrols all but one) and the other rows are the queries of
-    ``identify`` / ``model_trial_metrics`` -- the exhaustive n-shot S-way task.  Every rank sums all rows itself."""
-    kind = _kind(distance)
+    ``identify`` / ``model_trial_metrics`` -- the exhaustive n-shot S-way task.  Every rank sums all rows itself.  ``distance``
+    defaults to "euclidean".  ``plda=model`` (a ``plda.PldaModel``): multi-session PLDA models of a cache that ``model.project`` made
+    (module docstring); ``distance`` is then left out.  A cache whose width is not ``model.P`` -- a raw, unprojected one -- is refused."""
+    if plda is not None:
+        if distance not in (None, "plda"):
+            raise ValueError("plda= is the switch: leave distance out (got %r)" % (distance,))
+        if cache.emb.dim() != 2 or int(cache.emb.shape[1]) != plda.P:
+            raise ValueError("enrol(plda=) takes a cache projected by the model -- rows of width %d, got %d: pass model.project(cache)"
+                             % (plda.P, int(cache.emb.shape[-1])))
+        kind = _lib.VM_DIST_EUCLIDEAN   # the sums of the projected rows themselves
+    else:
+        distance = "euclidean" if distance is None else distance
+        kind = _kind(distance)
     speakers, dense = np.unique(cache.speaker, return_inverse=True)
     label = dense.astype(np.int32).reshape(-1)
     if per_speaker is not None:
@@ -253,6 +332,10 @@ def enrol(cache, distance: str = "euclidean", per_speaker: Optional[int] = None,
                 keep[rng.choice(rows, take, replace=False)] = True
         label = np.where(keep, label, -1).astype(np.int32)
     sums, msum, count = speaker_sums(cache.emb, torch.as_tensor(label), len(speakers), kind)
+    if plda is not None:
+        n_max = max(1, int(count.max().item()))
+        return SpeakerModels(sums, msum, count, "plda", speakers, label, cache, per_speaker, plda=plda,
+                             tables=plda_tables_to(plda.model_tables(n_max), cache.emb.device))
     return SpeakerModels(sums, msum, count, distance, speakers, label, cache, per_speaker)
 
 
@@ -291,7 +374,10 @@ def identify(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None,
     ``leave_one_out`` defaults to "the cache is the one that was enrolled and per_speaker is None".  With ``per_speaker`` models and
     the enrolled cache, the queries are the rows that were not enrolled."""
     q, q_label, loo, (lo, hi), n_q, idx = _shard(models, cache, leave_one_out, rows)
-    out = speaker_identify(q, q_label, models.sums, models.msum, models.count, models.distance, loo)
+    if models.tables is not None:
+        out = plda_speaker_identify(q, q_label, models.sums, models.count, models.tables, loo)
+    else:
+        out = speaker_identify(q, q_label, models.sums, models.msum, models.count, models.distance, loo)
     S = models.S
     rk = out["rank"].long()
     hist = torch.bincount(torch.where(rk < 0, torch.full_like(rk, S), rk), minlength=S + 1)[:S + 1]
@@ -320,6 +406,8 @@ def _prototypes(models: SpeakerModels) -> torch.Tensor:
 def _pass1(models: SpeakerModels, q: torch.Tensor, n_sample: int = 1 << 16) -> Tuple[int, int]:
     """``verification.place_window`` for the model trials of rank 0's rows ``q``: bounds from the largest row and model norms, and a
     seeded sample of (row, model) pairs, those of a speaker without a model left out."""
+    if models.tables is not None:
+        return _pass1_plda(models, q, n_sample)
     kind = _kind(models.distance)
 
     def sample():
@@ -343,11 +431,44 @@ def _pass1(models: SpeakerModels, q: torch.Tensor, n_sample: int = 1 << 16) -> T
     return V.place_window(sample)
 
 
+def _pass1_plda(models: SpeakerModels, q: torch.Tensor, n_sample: int) -> Tuple[int, int]:
+    """``_pass1`` for multi-session PLDA models: the shared models' operands in torch float64 (mu = beta[n] Sigma, A[n], C[n]), bounds
+    from the largest terms -- the score is sum A (w - mu)^2 - g - C with g = sum G w^2 >= 0 -- and a seeded sample of (row, model)
+    pairs.  Only the window's place depends on any of it."""
+    def sample():
+        t, D = models.tables, int(models.tables["G"].shape[0])
+        n = models.count.long()
+        ok = (n >= 1) & (n <= models.n_max)
+        n = torch.where(ok, n, torch.zeros_like(n))
+        mu, A, C = t["beta"][n] * models.sums[:, :D], t["A"][n], t["C"][n]
+        w = q[:, :D].double()
+        g = (w * w) @ t["G"]
+        fin = lambda x: x if math.isfinite(x) else 1.0
+        qr = fin(float(torch.linalg.vector_norm(w, dim=1).max().item())) if q.shape[0] else 0.0
+        mr = fin(float(torch.linalg.vector_norm(mu[ok], dim=1).max().item())) if bool(ok.any()) else 0.0
+        cm = fin(float(C.abs().max().item()))
+        gm = fin(float(g.abs().max().item())) if q.shape[0] else 0.0
+        lo = -(gm + cm) * 1.001 - 1e-30
+        hi = (fin(float(A.max().item())) * (qr + mr) ** 2 + gm + cm) * 1.001 + 1e-30
+        if q.shape[0] < 1 or not bool(ok.any()):
+            return lo, hi, None
+        gen = torch.Generator().manual_seed(0)
+        i = torch.randint(0, q.shape[0], (n_sample,), generator=gen).to(q.device)
+        s = torch.randint(0, models.S, (n_sample,), generator=gen).to(q.device)
+        d = w[i] - mu[s]
+        sc = ((A[s] * d * d).sum(1) - g[i]) - C[s]
+        return lo, hi, sc.masked_fill(~ok[s], float("nan"))   # no model: no trial, dropped as not finite
+    return V.place_window(sample)
+
+
 def _hist_source(models, cache, leave_one_out):
     q, q_label, loo, _, _, _ = _shard(models, cache, leave_one_out, None)
 
     def hist_fn(windows, bins):
-        h = speaker_trial_hist(q, q_label, models.sums, models.msum, models.count, models.distance, loo, windows, bins)
+        if models.tables is not None:
+            h = plda_speaker_trial_hist(q, q_label, models.sums, models.count, models.tables, loo, windows, bins)
+        else:
+            h = speaker_trial_hist(q, q_label, models.sums, models.msum, models.count, models.distance, loo, windows, bins)
         return parallel.sum_ranks(h).cpu().numpy()
     return hist_fn, q
 

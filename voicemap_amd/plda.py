@@ -22,10 +22,23 @@ rows are projected on the chip (vm_plda_project), with length normalisation.  St
 for the two-covariance model on the sufficient statistics alone (per-speaker count and mean, the total within scatter); diagonalise.
 Rows with a negative label take no part.
 
-Multi-session scoring of speaker MODELS by the book (several enrolment rows per model) is out of scope: the speaker-model entry
-points (``enrolment``) do not take the kind.  What is checked: the diagonal form against the joint Gaussian densities, EM's monotone
-likelihood and fixed point, the kernels against the float64 statements here, and a synthetic two-covariance corpus end to end.  NO
-claim about the EER of a trained encoder on real LibriSpeech is made: that has not been measured.
+Speaker MODELS of several enrolment rows.  The mean of PLDA-space rows is not a PLDA-space row, so the score kind above does not serve
+``enrolment``'s speaker models.  By the book, the log-likelihood ratio of a test row against the n enrolment rows of one speaker
+TOGETHER ("the n + 1 rows share a speaker" against "the n rows share one and the test row has its own") has a closed form that needs
+only the SUM of the enrolment rows and n.  Per component the speaker variable's posterior after the n rows has mean
+psi Sz / (1 + n psi) and variance psi / (1 + n psi); stated on w = sqrt(b) z and Sigma = the sum of the enrolment rows' w:
+
+    beta[n][d] = psi_d / (1 + n psi_d)                       A[n][d] = (1 + n psi_d) / (2 b_d (1 + (n + 1) psi_d))
+    G[d]       = 1 / (2 b_d (1 + psi_d))                     C[n]    = 1/2 sum_d log((1 + psi_d)(1 + n psi_d) / (1 + (n + 1) psi_d))
+    score(m, s) = -llr = sum_d A[n][d] (w_md - beta[n][d] Sigma_sd)^2 - sum_d G[d] w_md^2 - C[n]
+
+(``PldaModel.model_tables``; at n = 1 it is s_ij above).  vm_plda_speaker_identify / vm_plda_speaker_trial_hist (csrc/plda_enrol.hip)
+score every row against every model this way from vm_speaker_sums' sums of the projected rows; ``trial_scores_plda_numpy`` is their
+numpy twin and ``enrolment.enrol(projected_cache, plda=model)`` the way in.
+
+What is checked: the diagonal form and the multi-session form against the joint Gaussian densities, EM's monotone likelihood and fixed
+point, the kernels against the float64 statements here, and a synthetic two-covariance corpus end to end.  NO claim about the EER or
+the identification accuracy of a trained encoder on real LibriSpeech is made: that has not been measured.
 """
 from __future__ import annotations
 
@@ -102,6 +115,55 @@ def plda_scores_numpy(Zq, Zr=None) -> np.ndarray:
     bad = ~np.isfinite(hq)[:, None] | ~np.isfinite(hr)[None, :]
     s[bad] = np.float32(np.nan)
     return s
+
+
+def trial_scores_plda_numpy(proj, label, q, q_label, tables, leave_one_out: bool, S: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """vm_plda_speaker_identify's score matrix in numpy, with the shape and conventions of ``enrolment.trial_scores_numpy``: (scores
+    (M, S) float64, trial (M, S) bool) of the PLDA-space query rows ``q`` (M, P) against the speaker models of the enrolled PLDA-space
+    rows ``proj`` (N, P) / ``label`` (N; anything outside [0, S) enrols nowhere).  ``tables``: ``PldaModel.model_tables``' dict (any
+    float64 arrays of those shapes do); D = the width of ``G``; only the columns 0 .. D - 1 of the rows are read.  Follows the kernel's
+    chain (include/voicemap_hip.h): Sigma = the float64 sum of the speaker's rows in ascending row order, n their number; with
+    ``leave_one_out`` and q_label[m] == s, n - 1 and Sigma - w_m; no trial unless 1 <= n <= n_max (the score there is NaN and means
+    nothing); mu = beta[n] Sigma, t = w - mu, acc = sum_d (A[n] t) t, g = sum_d G (w w), score = (acc - g) - C[n], every operation
+    rounded on its own where the kernel has an fma (so: bit for bit where every value is exact, within the counted roundings
+    otherwise)."""
+    A, beta, C, G = (np.asarray(tables[k], dtype=np.float64) for k in ("A", "beta", "C", "G"))
+    D, n_max = int(G.shape[0]), int(A.shape[0]) - 1
+    if A.shape != (n_max + 1, D) or beta.shape != A.shape or C.shape != (n_max + 1,) or n_max < 1:
+        raise ValueError("tables: A and beta (n_max + 1, D), C (n_max + 1), G (D), n_max >= 1")
+    proj, q = np.asarray(proj, dtype=np.float32), np.asarray(q, dtype=np.float32)
+    if proj.ndim != 2 or q.ndim != 2 or proj.shape[1] != q.shape[1] or not D < q.shape[1]:
+        raise ValueError("rows must be (N, P) and (M, P) PLDA-space rows with P > D = %d" % D)
+    label, q_label = np.asarray(label), np.asarray(q_label)
+    if S is None:
+        S = int(label.max()) + 1
+    sums, count = np.zeros((S, D)), np.zeros(S, dtype=np.int64)
+    p64 = proj[:, :D].astype(np.float64)
+    for s in range(S):
+        rows = np.flatnonzero(label == s)
+        count[s] = len(rows)
+        for u in rows:
+            sums[s] += p64[u]
+    w = q[:, :D].astype(np.float64)
+    M = len(w)
+    out = np.full((M, S), np.nan)
+    trial = np.zeros((M, S), dtype=bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for m in range(M):
+            n, sg = count.copy(), sums
+            own = int(q_label[m])
+            if leave_one_out and 0 <= own < S:
+                sg = sums.copy()
+                n[own] -= 1
+                sg[own] -= w[m]
+            ok = (n >= 1) & (n <= n_max)
+            trial[m] = ok
+            nn = np.where(ok, n, 0)
+            t = w[m][None, :] - beta[nn] * sg
+            acc = ((A[nn] * t) * t).sum(1)
+            g = (G * (w[m] * w[m])).sum()
+            out[m, ok] = ((acc - g) - C[nn])[ok]
+    return out, trial
 
 
 # ---- the two-covariance model on the host (float64) ----------------------------------------------------------------------------------
@@ -257,20 +319,52 @@ class PldaModel:
         """The (len(a), len(b)) float64 log-likelihood ratios of raw rows ``a`` against ``b`` (default ``a``) through the diagonal form,
         nothing rounded to fp32 on the way: z = V^T (y - mean2) of the float64 stage-1 rows y."""
         t = llr_terms(self.psi)
-
-        def z_of(x):
-            x = np.asarray(x, dtype=np.float64)
-            y = (x - self.mean1[None, :]) @ self.A1.T
-            if self.length_norm:
-                nrm = np.sqrt((y * y).sum(1))
-                ok = nrm != 0.0
-                y[ok] = y[ok] * np.sqrt(float(y.shape[1])) / nrm[ok, None]
-            return ((y - self.mean2[None, :]) @ self.A2.T) / np.sqrt(t["b"])[None, :]
-
-        za = z_of(a)
-        zb = za if b is None else z_of(b)
+        za = self.z_numpy(a)
+        zb = za if b is None else self.z_numpy(b)
         sq = lambda z: 0.5 * ((z * z) @ t["a"])
         return (za * t["b"][None, :]) @ zb.T - sq(za)[:, None] - sq(zb)[None, :] + t["c"]
+
+    def z_numpy(self, x) -> np.ndarray:
+        """z = V^T (y - mean2) of the float64 stage-1 rows y of raw rows ``x``, (N, D) float64: nothing is rounded to fp32."""
+        x = np.asarray(x, dtype=np.float64)
+        y = (x - self.mean1[None, :]) @ self.A1.T
+        if self.length_norm:
+            nrm = np.sqrt((y * y).sum(1))
+            ok = nrm != 0.0
+            y[ok] = y[ok] * np.sqrt(float(y.shape[1])) / nrm[ok, None]
+        return ((y - self.mean2[None, :]) @ self.A2.T) / np.sqrt(llr_terms(self.psi)["b"])[None, :]
+
+    # ---- speaker models of several enrolment rows (module docstring)
+    def model_tables(self, n_max: int) -> Dict[str, np.ndarray]:
+        """The coefficient tables of multi-session scoring for models of 1 .. ``n_max`` rows, float64: ``A`` and ``beta``
+        (n_max + 1, D), ``C`` (n_max + 1), ``G`` (D).  Row 0 is unused (zeros)."""
+        n_max = int(n_max)
+        if n_max < 1:
+            raise ValueError("n_max must be >= 1")
+        psi = self.psi[None, :]
+        b = llr_terms(self.psi)["b"][None, :]
+        n = np.arange(n_max + 1, dtype=np.float64)[:, None]
+        beta = psi / (1.0 + n * psi)
+        A = (1.0 + n * psi) / (2.0 * b * (1.0 + (n + 1.0) * psi))
+        C = 0.5 * np.log((1.0 + psi) * (1.0 + n * psi) / (1.0 + (n + 1.0) * psi)).sum(1)
+        beta[0], A[0], C[0] = 0.0, 0.0, 0.0
+        return {"A": np.ascontiguousarray(A), "beta": np.ascontiguousarray(beta), "C": np.ascontiguousarray(C),
+                "G": np.ascontiguousarray(1.0 / (2.0 * b[0] * (1.0 + self.psi)))}
+
+    def model_llr_numpy(self, enrol_rows, test_rows) -> np.ndarray:
+        """The float64 log-likelihood ratios (len(test_rows)) of raw rows ``test_rows`` against ONE speaker model enrolled from all the
+        raw rows ``enrol_rows`` (n >= 1 of them): per component the predictive density of the test row after the n rows -- mean
+        psi Sz / (1 + n psi), variance 1 + psi / (1 + n psi) -- against its marginal density, variance 1 + psi.  Stated in z, with
+        nothing rounded to fp32 and none of the tables: the independent statement ``model_tables`` is held to."""
+        ze, zt = self.z_numpy(enrol_rows), self.z_numpy(test_rows)
+        n = float(len(ze))
+        if n < 1:
+            raise ValueError("a speaker model needs at least one enrolment row")
+        psi = self.psi
+        mean = psi * ze.sum(0) / (1.0 + n * psi)
+        var = 1.0 + psi / (1.0 + n * psi)
+        d = zt - mean[None, :]
+        return (-0.5 * (np.log(var) + d * d / var) + 0.5 * (np.log(1.0 + psi) + zt * zt / (1.0 + psi))).sum(1)
 
     # ---- the device path
     def _on(self, dev):
