@@ -21,6 +21,12 @@ Pauses, speech gating and resegmentation, all off by default:
     --reseg --switch-cost C --reseg-iters N [--reseg-hop-seconds H]
                                            Viterbi resegmentation of the cluster labels (vm_reseg), at a finer hop H if given; the
                                            line then carries the error before ("ahc_*") and after it
+    --vbx [--vbx-loop-prob P --vbx-fa A --vbx-fb B --vbx-iters N --vbx-hop-seconds H --vbx-init-threshold T]
+                                           VBx behind the clustering (vm_vbx; --distance plda only, not with --reseg): a Bayesian HMM
+                                           over the PLDA-space rows, started from the cluster labels.  With T the start is the
+                                           clustering stopped at height T (meant to leave too many clusters: VBx drops speakers, it
+                                           adds none) and the "before" figures are those of the stop rule chosen; the line carries the
+                                           error and the speakers found before ("ahc_*") and after
 With --tune-conversations the threshold is tuned on the clustering alone and the resegmentation runs on the labels it cuts (no
 --reseg-hop-seconds there: the tuned cut has no finer rows)."""
 import argparse
@@ -86,6 +92,14 @@ def _parser():
     p.add_argument("--switch-cost", type=float, default=0.5, help="--reseg: the cost of a speaker change, in units of the distance")
     p.add_argument("--reseg-iters", type=int, default=3)
     p.add_argument("--reseg-hop-seconds", type=float, default=None, help="--reseg: cut, embed and decode at this finer hop")
+    p.add_argument("--vbx", action="store_true", help="VBx behind the clustering (vm_vbx); needs --distance plda")
+    p.add_argument("--vbx-loop-prob", type=float, default=0.99)
+    p.add_argument("--vbx-fa", type=float, default=0.3)
+    p.add_argument("--vbx-fb", type=float, default=17.0)
+    p.add_argument("--vbx-iters", type=int, default=20)
+    p.add_argument("--vbx-hop-seconds", type=float, default=None, help="--vbx: cut, embed and model at this finer hop")
+    p.add_argument("--vbx-init-threshold", type=float, default=None, metavar="T",
+                   help="--vbx: the clustering that starts VBx stops at height T instead of at the stop rule chosen")
     stop = p.add_mutually_exclusive_group(required=True)
     stop.add_argument("--threshold", type=float, default=None)
     stop.add_argument("--oracle-speakers", action="store_true")
@@ -178,6 +192,14 @@ def main(argv=None):
         reseg = DZ.ResegPolicy(a.switch_cost, a.reseg_iters, a.reseg_hop_seconds) if a.reseg else None
     except ValueError as e:
         p.error("--reseg: %s" % e)
+    vbx = None
+    if a.vbx:
+        if a.distance != "plda" or a.reseg or a.tune_conversations:
+            p.error("--vbx needs --distance plda and goes with neither --reseg nor --tune-conversations")
+        try:
+            vbx = DZ.VbxPolicy(a.vbx_loop_prob, a.vbx_fa, a.vbx_fb, iters=a.vbx_iters, hop_seconds=a.vbx_hop_seconds)
+        except ValueError as e:
+            p.error("--vbx: %s" % e)
     kw = dict(distance=a.distance, linkage=a.linkage, vad=policy, min_voiced=a.min_voiced)
     if a.distance == "plda":
         from voicemap_amd import plda, retrieval
@@ -198,10 +220,20 @@ def main(argv=None):
         out.update(threshold=threshold, tuned_on=len(dev), dev_mean_der=score(conv, dev, segments_at(conv, res, dev, threshold)[0])["mean_der"])
     else:
         n_speakers = conv.speakers if a.oracle_speakers else None
-        segments, res = DZ.diarize(net, conv.audio, conv.offsets, conv.lens, pre, a.window_seconds, a.hop_seconds, threshold=a.threshold,
-                                   n_speakers=n_speakers, reseg=reseg, **kw)
+        stop = dict(threshold=a.threshold, n_speakers=n_speakers)
+        if vbx is not None and a.vbx_init_threshold is not None:
+            stop = dict(threshold=a.vbx_init_threshold, n_speakers=None)
+        segments, res = DZ.diarize(net, conv.audio, conv.offsets, conv.lens, pre, a.window_seconds, a.hop_seconds, reseg=reseg, vbx=vbx,
+                                   **stop, **kw)
         found = res.host().n_clusters.tolist()
-        before = ahc_segments(conv, res, rows) if reseg is not None else None
+        before = ahc_segments(conv, res, rows) if reseg is not None or vbx is not None else None
+        if vbx is not None:
+            found_before, lab, row0 = found, res.vbx.host().labels, res.window_row0
+            found = [len(np.unique(lab[row0[r]:row0[r + 1]])) for r in rows]
+            if a.vbx_init_threshold is not None:   # "before" = the stop rule chosen, without VBx
+                _, plain = DZ.diarize(net, conv.audio, conv.offsets, conv.lens, pre, a.window_seconds, a.hop_seconds, threshold=a.threshold,
+                                      n_speakers=n_speakers, **kw)
+                before, found_before = ahc_segments(conv, plain, rows), plain.host().n_clusters.tolist()
         out.update(threshold=a.threshold, oracle_speakers=bool(a.oracle_speakers))
     out.update(score(conv, rows, segments), scored=len(rows), windows=int(res.row0[-1]))
     if policy is not None:
@@ -209,6 +241,12 @@ def main(argv=None):
     if reseg is not None:
         out.update({"ahc_" + k: v for k, v in score(conv, rows, before).items()}, reseg=True, switch_cost=reseg.switch_cost,
                    reseg_iters=reseg.iters, reseg_hop_seconds=reseg.hop_seconds, windows_decoded=int(res.window_row0[-1]))
+    if vbx is not None:
+        out.update({"ahc_" + k: v for k, v in score(conv, rows, before).items()}, vbx=True, vbx_loop_prob=vbx.loop_prob, vbx_fa=vbx.fa,
+                   vbx_fb=vbx.fb, vbx_iters=vbx.iters, vbx_hop_seconds=vbx.hop_seconds, vbx_init_threshold=a.vbx_init_threshold,
+                   windows_decoded=int(res.window_row0[-1]), ahc_speakers_found=[int(c) for c in found_before],
+                   speakers_found=[int(c) for c in found],
+                   vbx_iters_run=[int(i) for i in res.vbx.host().iters_run])
     table = {}
     for r, c in zip(rows, found):
         table.setdefault(int(conv.speakers[r]), {}).setdefault(int(c), 0)

@@ -950,6 +950,57 @@ int64_t vm_reseg_workspace_bytes(int64_t N, int E, int64_t R, int64_t em_total);
 int vm_reseg(const float* emb, int64_t N, int E, const int64_t* row0, const int64_t* em0, int64_t R, int64_t em_total,
              const int32_t* n_models, const int32_t* labels_in, const int32_t* chain_start, int kind, double switch_cost, int iters,
              int32_t* labels_out, double* path_cost, int32_t* iters_run, int32_t* n_changed, float* emis, void* ws, void* stream);
+/* vm_vbx: VBx, variational-Bayes HMM diarization over PLDA-space rows (csrc/vbx.hip, voicemap_amd/diarization.py vbx; vbx_reference there
+ * is the numpy statement; Landini et al., "Bayesian HMM clustering of x-vector sequences", 2022).  The resegmentation that goes with a
+ * PLDA back end: the states of the HMM are speakers, a speaker is a Gaussian posterior over its mean in the diagonalised space (within
+ * covariance I, between covariance diag(psi)), the assignments are soft and the speaker priors may shrink to nothing.
+ * Inputs.  rows (N, P) fp32: PLDA-space rows as vm_plda_project with `quad` writes them, IN TIME ORDER; only the columns w = 0 .. D - 1
+ * are read.  row0, em0, n_models, labels_in, chain_start: vm_reseg's tables and conventions (K_r = n_models[r] speakers, a label
+ * outside [0, K_r) = no cluster, em0 the cumulative sums of n_r K_r).  psi, r, ib (D) float64 on the device: r_d = sqrt(1 + 2 psi_d), so
+ * that rho = r w = sqrt(psi) z; ib_d = 1 / b_d = (1 + 2 psi_d) / psi_d, so that |z|^2 = sum ib_d w_d^2.  The tables are taken as they
+ * are: nothing here depends on their coming from a psi.  gamma_in (em_total float64) and pi_in (R x 64 float64), each may be NULL: a
+ * warm start.
+ * Per recording, its rows renumbered 0 .. n - 1, everything float64, every operation rounded on its own unless it is written as fma:
+ *   Start.  gamma = gamma_in, or with q = exp(-init_smooth) (taken on the host) and den = 1 + (K - 1) q:  gamma[t][k] = 1 / den where
+ *   labels_in[t] == k, q / den for the other k, 1 / K in a row of no cluster.  pi_k = pi_in, or 1 / K.  F = fa / fb.
+ *   For it = 1 .. iters:
+ *   Speaker posteriors.  N_k = sum_t gamma[t][k];  F_kd = fma(gamma[t][k], rho_td, .), rho_td = r_d * (double)w_td;  both over ascending
+ *   t from 0.0.  invL_kd = 1 / (1 + (F * N_k) * psi_d);  alpha_kd = (F * invL_kd) * F_kd;  over ascending d from 0.0:
+ *   q_k = fma(invL_kd + alpha_kd^2, psi_d, q_k),  ent_k = ent_k + (((log(invL_kd) - invL_kd) - alpha_kd^2) + 1).
+ *   Emissions.  G_t = -0.5 * (fma(ib_d, w_td^2, .) over ascending d + (double)D * 1.8378770664093453);
+ *   lp[t][k] = fa * ((fma(rho_td, alpha_kd, .) over ascending d - 0.5 * q_k) + G_t);  m_t = max_k lp[t][k];  p[t][k] = exp(lp[t][k] - m_t).
+ *   Forward.  lambda_t = loop_prob, but 0 at t = 0 and at every chain start.  at[k] = p[t][k] * (lambda_t * a[t-1][k] + (1 - lambda_t) *
+ *   pi_k);  c_t = SUM_k at[k];  a[t][k] = at[k] / c_t.  SUM_k: the terms padded with zeros to the next power of two K', then for
+ *   o = 1, 2, 4, .., K'/2:  v[k] = v[k] + v[k ^ o] for all k at once;  the sum is v[0].
+ *   Backward.  b[n-1][k] = 1;  pb[k] = p[t+1][k] * b[t+1][k];  s = SUM_k (pi_k * pb[k]);
+ *   b[t][k] = (lambda_{t+1} * pb[k] + (1 - lambda_{t+1}) * s) / c_{t+1}.   gamma[t][k] = a[t][k] * b[t][k].
+ *   Priors.  pi'_k = sum over ascending t of ((((1 - lambda_t) * pi_k) * p[t][k]) * b[t][k]) / c_t;  pi_k = pi'_k / (sum over ascending
+ *   j of pi'_j).
+ *   Bound.  log_pX = sum over ascending t of (log(c_t) + m_t);  ELBO_it = log_pX + (fb * 0.5) * (sum over ascending k of ent_k).  After
+ *   the prior update: stop if it > 1 and ELBO_it - ELBO_{it-1} < epsilon; the iteration that stops is counted and its results are kept.
+ *   Degenerate.  A c_t that is 0 or not finite (a prior has underflowed to exactly 0 under the best-emitting speaker) stops the
+ *   recording: iters_run = -2, labels_out = labels_in, everything else as the last complete iteration (or the start) left it.
+ * Outputs, on the device.  labels_out (N) int32: the first maximum of gamma[t][.], never renumbered.  gamma (em_total float64, also the
+ * working copy: it must not be gamma_in).  pi (R x 64 float64; the entries past K_r are 0).  elbo (R x iters float64, NaN past
+ * iters_run).  iters_run (R) int32: 0 for an empty recording (nothing else is written), -1 for tables the caller should have refused
+ * (voicemap_amd/diarization.py vbx refuses them; nothing else is touched, as in vm_reseg), -2 as above.
+ * The outputs are a function of the inputs alone -- no atomics, every sum in a fixed order, bit-identical from run to run.
+ * Limits.  1 <= K_r <= VM_VBX_MAX_K, 1 <= D <= 255, D <= P, N < 2^31, 0 <= loop_prob < 1, fa, fb finite and > 0, init_smooth finite and
+ * >= 0, epsilon not NaN (-inf: never stop), 1 <= iters <= 64; ws 16-byte aligned; a bad argument is an error before any launch; R == 0
+ * returns without a launch.
+ * Launches: G_t of all N rows, ceil(N / 256) workgroups of 256 threads; then R workgroups of 256 threads, one per recording, for the
+ * whole loop.  alpha lives in LDS as float64, VM_VBX_MAX_K (D + 1) x 8 bytes (131 KB at D = 255: the entry point compares it with the
+ * device's per-block limit, as vm_reseg does).  O(n K D) per iteration for the sums and the emissions, 2 n sequential steps of one wave
+ * for the forward-backward, n more of one lane per speaker for the priors.
+ * ws >= vm_vbx_workspace_bytes(N, D, R, em_total): three float64 per row (G, c, m) and three per emission (p, a, b), each table rounded
+ * up to 256 bytes: 3 pad(8 N) + 3 pad(8 em_total). */
+enum { VM_VBX_MAX_K = 64 };
+int64_t vm_vbx_workspace_bytes(int64_t N, int D, int64_t R, int64_t em_total);
+int vm_vbx(const float* rows, int64_t N, int P, int D, const int64_t* row0, const int64_t* em0, int64_t R, int64_t em_total,
+           const int32_t* n_models, const int32_t* labels_in, const int32_t* chain_start, const double* psi, const double* r,
+           const double* ib, double loop_prob, double fa, double fb, double init_smooth, double epsilon, int iters,
+           const double* gamma_in, const double* pi_in, int32_t* labels_out, double* gamma, double* pi, double* elbo,
+           int32_t* iters_run, void* ws, void* stream);
 
 /* ---- the PLDA back end (csrc/plda.hip, voicemap_amd/plda.py): the statistics of the fit and the projection into PLDA space -----------
  * vm_scatter_f64: out (D, D) float64 = sum over the rows r of x (N, D) fp32 with label[r] >= 0 (label NULL: all rows) of

@@ -43,6 +43,9 @@ MAX_K = 64     # VM_RESEG_MAX_K: a decode step is one lane per model
 MAX_ITERS = 16
 Ahc = namedtuple("Ahc", "merge_a merge_b merge_h merge_size labels n_clusters")
 Reseg = namedtuple("Reseg", "labels path_cost iters_run n_changed emis")
+VBX_MAX_ITERS = 64
+LOG_2PI = 1.8378770664093453   # the float64 next to log(2 pi): the constant of vm_vbx's G_t
+Vbx = namedtuple("Vbx", "labels gamma pi elbo iters_run")
 
 
 # ---- the contract --------------------------------------------------------------------------------------------------------------------
@@ -404,6 +407,266 @@ def resegment(emb, row0, labels, n_models, chain_start=None, distance: str = "co
     return res
 
 
+# ---- VBx: the contract of vm_vbx and the device call ---------------------------------------------------------------------------------
+def vbx_tables(plda_model) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(psi, r, ib) of a fitted ``plda.PldaModel`` for ``vm_vbx``, on the columns w = sqrt(b) z, b = psi / (1 + 2 psi), of its PLDA-space
+    rows: r = sqrt(psi / b) = sqrt(1 + 2 psi), so that rho = r w = sqrt(psi) z; ib = 1 / b, so that |z|^2 = sum ib w^2."""
+    psi = np.ascontiguousarray(np.asarray(plda_model.psi, dtype=np.float64).reshape(-1))
+    return psi, np.sqrt(1.0 + 2.0 * psi), (1.0 + 2.0 * psi) / psi
+
+
+def _vbx_sum(v, stages):
+    """SUM_k of vm_vbx: the butterfly over the next power of two, which is what one lane per speaker of a wave adds."""
+    if len(stages) == 0:
+        return v[0]
+    x = np.zeros(len(stages[0]), v.dtype)
+    x[:len(v)] = v
+    for partner in stages:
+        x = x + x[partner]
+    return x[0]
+
+
+def _check_vbx(loop_prob, fa, fb, init_smooth, iters, epsilon):
+    if not 0.0 <= loop_prob < 1.0:
+        raise ValueError("loop_prob must be in [0, 1)")
+    if not (np.isfinite(fa) and fa > 0 and np.isfinite(fb) and fb > 0):
+        raise ValueError("fa and fb must be finite and > 0")
+    if not (np.isfinite(init_smooth) and init_smooth >= 0):
+        raise ValueError("init_smooth must be finite and >= 0")
+    if not 1 <= int(iters) <= VBX_MAX_ITERS:
+        raise ValueError("iters must be in [1, %d]" % VBX_MAX_ITERS)
+    if np.isnan(epsilon):
+        raise ValueError("epsilon must not be NaN")
+
+
+def vbx_reference(rows, row0, n_models, labels, chain_start, psi, loop_prob, fa, fb, init_smooth, iters, epsilon, gamma=None, pi=None,
+                  dtype=np.float64) -> Vbx:
+    """The numpy statement of ``vm_vbx`` (include/voicemap_hip.h), in the scaled form and with the sums in the order stated there; every
+    operation is rounded on its own where the kernel has an fma.  ``rows`` (N, P) PLDA-space rows of which the columns 0 .. D - 1, D =
+    len(psi), are read; ``psi`` alone, or the triple (psi, r, ib) when the tables are not ``vbx_tables``'.  ``gamma`` (sum n_r K_r,) /
+    ``pi`` (R, 64): a warm start.  ``dtype=np.longdouble`` runs the same statement in extended precision (the inputs are the same
+    float64 / fp32 numbers).  Returns ``Vbx(labels (N,) int32, gamma (sum n_r K_r,), pi (R, 64), elbo (R, iters), iters_run (R,)
+    int32)``; an empty recording leaves zeros / NaN."""
+    T = np.dtype(dtype).type
+    if isinstance(psi, (tuple, list)):
+        psi, rr, ib = (np.asarray(v, dtype=np.float64).reshape(-1) for v in psi)
+    else:
+        psi = np.asarray(psi, dtype=np.float64).reshape(-1)
+        rr, ib = np.sqrt(1.0 + 2.0 * psi), (1.0 + 2.0 * psi) / psi
+    D = len(psi)
+    psi, rr, ib = psi.astype(T), rr.astype(T), ib.astype(T)
+    rows, row0 = np.asarray(rows, dtype=np.float32), np.asarray(row0, dtype=np.int64)
+    labels_in, R, iters = np.asarray(labels).astype(np.int32), len(row0) - 1, int(iters)
+    n_models = np.broadcast_to(np.asarray(n_models, dtype=np.int64), (R,))
+    _check_vbx(loop_prob, fa, fb, init_smooth, iters, epsilon)
+    n_r = np.diff(row0)
+    em0 = np.concatenate([[0], np.cumsum(n_r * np.where(n_r > 0, n_models, 0))]).astype(np.int64)
+    out_lab, out_gamma = np.full(len(rows), -1, np.int32), np.zeros(int(em0[-1]), T)
+    out_pi, out_elbo, run = np.zeros((R, MAX_K), T), np.full((R, iters), np.nan, T), np.zeros(R, np.int32)
+    lam0, fa_, fb_, one, half_ = T(loop_prob), T(fa), T(fb), T(1.0), T(0.5)
+    Fr, q0 = fa_ / fb_, T(np.exp(-np.float64(init_smooth)))
+    for r in range(R):
+        lo, hi, K = int(row0[r]), int(row0[r + 1]), int(n_models[r])
+        n = hi - lo
+        if n == 0:
+            continue
+        if not 1 <= K <= MAX_K:
+            raise ValueError("recording %d has %d speakers: 1 .. %d can be modelled" % (r, K, MAX_K))
+        w = rows[lo:hi, :D].astype(T)
+        lab = labels_in[lo:hi]
+        start = _chain_table(None if chain_start is None else np.asarray(chain_start)[lo:hi], n)
+        lam = np.where(start, T(0.0), lam0).astype(T)
+        Kp = 1
+        while Kp < K:
+            Kp *= 2
+        stages, o = [], 1
+        while o < Kp:
+            stages.append(np.arange(Kp) ^ o)
+            o *= 2
+        if gamma is not None:
+            g = np.asarray(gamma).reshape(-1)[int(em0[r]):int(em0[r + 1])].astype(T).reshape(n, K)
+        else:
+            den = one + T(K - 1) * q0
+            g = np.where(lab[:, None] == np.arange(K)[None, :], one / den, q0 / den).astype(T)
+            g[(lab < 0) | (lab >= K)] = one / T(K)
+        pk = np.asarray(pi)[r, :K].astype(T) if pi is not None else np.full(K, one / T(K), T)
+        rho = rr[None, :] * w
+        acc = np.zeros(n, T)
+        for d in range(D):
+            acc = ib[d] * (w[:, d] * w[:, d]) + acc
+        G = T(-0.5) * (acc + T(np.float64(D) * LOG_2PI))
+        out_pi[r, :K] = pk
+        labels_now, prev = None, T(0.0)
+        for it in range(1, iters + 1):
+            # speaker posteriors
+            Nk, F = np.zeros(K, T), np.zeros((K, D), T)
+            for t in range(n):
+                Nk = Nk + g[t]
+                F = g[t][:, None] * rho[t][None, :] + F
+            invL = one / (one + (Fr * Nk)[:, None] * psi[None, :])
+            alpha = (Fr * invL) * F
+            q, ent = np.zeros(K, T), np.zeros(K, T)
+            for d in range(D):
+                a2 = alpha[:, d] * alpha[:, d]
+                q = (invL[:, d] + a2) * psi[d] + q
+                ent = ent + (((np.log(invL[:, d]) - invL[:, d]) - a2) + one)
+            # emissions
+            dot = np.zeros((n, K), T)
+            for d in range(D):
+                dot = rho[:, d][:, None] * alpha[:, d][None, :] + dot
+            lp = fa_ * ((dot - half_ * q[None, :]) + G[:, None])
+            m = lp.max(axis=1)
+            p = np.exp(lp - m[:, None])
+            # forward
+            a, c, ap = np.zeros((n, K), T), np.zeros(n, T), np.zeros(K, T)
+            ok = True
+            for t in range(n):
+                at = p[t] * (lam[t] * ap + (one - lam[t]) * pk)
+                ct = _vbx_sum(at, stages)
+                if not (ct > 0 and np.isfinite(ct)):
+                    ok = False
+                    break
+                ap = at / ct
+                a[t], c[t] = ap, ct
+            if not ok:
+                run[r], labels_now = -2, lab
+                break
+            # backward
+            b = np.ones((n, K), T)
+            for t in range(n - 2, -1, -1):
+                pb = p[t + 1] * b[t + 1]
+                s = _vbx_sum(pk * pb, stages)
+                b[t] = (lam[t + 1] * pb + (one - lam[t + 1]) * s) / c[t + 1]
+            g = a * b
+            labels_now = g.argmax(axis=1).astype(np.int32)
+            # priors, bound, stop
+            pin, lpx = np.zeros(K, T), T(0.0)
+            for t in range(n):
+                pin = pin + ((((one - lam[t]) * pk) * p[t]) * b[t]) / c[t]
+                lpx = lpx + (np.log(c[t]) + m[t])
+            tot, es = T(0.0), T(0.0)
+            for k in range(K):
+                tot, es = tot + pin[k], es + ent[k]
+            pk = pin / tot
+            e = lpx + (fb_ * half_) * es
+            out_elbo[r, it - 1], run[r] = e, it
+            out_pi[r, :K] = pk
+            if it > 1 and e - prev < epsilon:
+                break
+            prev = e
+        out_lab[lo:hi] = labels_now
+        out_gamma[int(em0[r]):int(em0[r + 1])] = g.ravel()
+    return Vbx(out_lab, out_gamma, out_pi, out_elbo, run)
+
+
+class VbxResult:
+    """What ``vbx`` leaves on the device: ``labels`` (N,) int32, ``gamma`` (sum n_r K_r,) float64 with recording r's (n_r, K_r)
+    posteriors at ``em0[r]``, ``pi`` (R, 64) float64, ``elbo`` (R, iters) float64 (NaN past ``iters_run``), ``iters_run`` (R,) int32;
+    ``row0`` / ``em0`` / ``n_models`` are the host's tables.  ``host()`` is all of it as numpy arrays (one read-back), ``recording(r)``
+    recording r's part."""
+
+    def __init__(self, row0, em0, n_models, labels, gamma, pi, elbo, iters_run):
+        self.row0, self.em0, self.n_models = row0, em0, n_models
+        self.labels, self.gamma, self.pi, self.elbo, self.iters_run = labels, gamma, pi, elbo, iters_run
+        self._host = None
+
+    def host(self) -> Vbx:
+        if self._host is None:
+            self._host = Vbx(*(t.cpu().numpy() for t in (self.labels, self.gamma, self.pi, self.elbo, self.iters_run)))
+        return self._host
+
+    def recording(self, r: int) -> Vbx:
+        h, lo, hi, K = self.host(), int(self.row0[r]), int(self.row0[r + 1]), int(self.n_models[r])
+        return Vbx(h.labels[lo:hi], h.gamma[int(self.em0[r]):int(self.em0[r + 1])].reshape(hi - lo, K) if hi > lo
+                   else np.zeros((0, K), np.float64), h.pi[r, :K], h.elbo[r], int(h.iters_run[r]))
+
+
+class VbxPolicy:
+    """How ``diarize`` runs VBx behind the clustering: the loop probability, the acoustic and speaker-regularisation factors fa / fb,
+    the smoothing of the initial posteriors, the iteration cap and the ELBO gain below which a recording stops (the defaults are the
+    VBx paper's), and -- optionally -- a finer hop at which the windows are cut, embedded and modelled while the clustering keeps the
+    coarse one."""
+
+    def __init__(self, loop_prob: float = 0.99, fa: float = 0.3, fb: float = 17.0, init_smooth: float = 5.0, iters: int = 20,
+                 epsilon: float = 1e-4, hop_seconds: Optional[float] = None):
+        self.loop_prob, self.fa, self.fb, self.init_smooth = float(loop_prob), float(fa), float(fb), float(init_smooth)
+        self.iters, self.epsilon, self.hop_seconds = int(iters), float(epsilon), None if hop_seconds is None else float(hop_seconds)
+        _check_vbx(self.loop_prob, self.fa, self.fb, self.init_smooth, self.iters, self.epsilon)
+        if self.hop_seconds is not None and not self.hop_seconds > 0:
+            raise ValueError("hop_seconds must be positive")
+
+
+def vbx(rows, row0, labels, n_models, plda, chain_start=None, loop_prob: float = 0.99, fa: float = 0.3, fb: float = 17.0,
+        init_smooth: float = 5.0, iters: int = 20, epsilon: float = 1e-4, gamma=None, pi=None) -> VbxResult:
+    """VBx over the windows of R recordings in one ``vm_vbx`` call.  ``rows``: (N, P) fp32 device tensor of PLDA-space rows
+    (``plda.project``), recording r's windows IN TIME ORDER at rows ``row0[r] .. row0[r + 1]``; ``labels`` (N,): the speaker (cluster)
+    every row starts in, -1 for a row of none; ``n_models``: one count or one per recording, 1 .. 64 wherever the recording has rows;
+    ``plda``: the fitted ``plda.PldaModel`` the rows were projected by (or the tables (psi, r, ib) themselves); ``chain_start`` (N,),
+    optional: non-zero where a row must not be tied to the row before it.  ``gamma`` (sum n_r K_r,) / ``pi`` (R, 64) float64: a warm
+    start in place of the labels / of uniform priors.  Any number of windows per recording."""
+    import torch
+    from . import _lib
+    _check_vbx(float(loop_prob), float(fa), float(fb), float(init_smooth), int(iters), float(epsilon))
+    if rows.dim() != 2 or rows.dtype != torch.float32:
+        raise TypeError("rows must be an (N, P) fp32 tensor")
+    rows = rows.contiguous()
+    N, P, dev = int(rows.shape[0]), int(rows.shape[1]), rows.device
+    tabs = vbx_tables(plda) if hasattr(plda, "psi") else tuple(np.asarray(v, dtype=np.float64).reshape(-1) for v in plda)
+    D = len(tabs[0])
+    if len(tabs) != 3 or any(len(v) != D for v in tabs) or not 1 <= D <= min(P, 255):
+        raise ValueError("the tables psi, r, ib hold one value per column read: 1 .. min(P, 255) of them, not %d" % D)
+    if not all(np.isfinite(v).all() for v in tabs):
+        raise ValueError("the tables psi, r, ib must be finite")
+    row0 = _row_table(row0, N, cap=None)
+    R, n_r = row0.size - 1, np.diff(row0)
+    K = np.asarray(n_models.cpu() if hasattr(n_models, "cpu") else n_models, dtype=np.int64)
+    K = np.broadcast_to(K, (R,)).copy() if K.ndim == 0 else K.reshape(-1)
+    if K.shape != (R,):
+        raise ValueError("n_models must be one number or one per recording")
+    bad = np.flatnonzero((n_r > 0) & ((K < 1) | (K > MAX_K)))
+    if bad.size:
+        raise ValueError("recording %d has %d speakers: 1 .. %d can be modelled" % (int(bad[0]), int(K[bad[0]]), MAX_K))
+    K = np.where(n_r > 0, K, 0)
+
+    def per_row(t, name):
+        t = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t).reshape(-1)))
+        if t.numel() != N:
+            raise ValueError("%s must hold one value per row (%d), not %d" % (name, N, t.numel()))
+        return t.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+
+    def f64(t, count, name):
+        t = t if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(np.asarray(t, dtype=np.float64)))
+        if t.numel() != count:
+            raise ValueError("%s must hold %d values, not %d" % (name, count, t.numel()))
+        return t.reshape(-1).to(device=dev, dtype=torch.float64).contiguous()
+    lab = per_row(labels, "labels")
+    cs = None if chain_start is None else per_row(chain_start, "chain_start")
+    em0 = np.concatenate([[0], np.cumsum(n_r * K)]).astype(np.int64)
+    total = int(em0[-1])
+    g_in = None if gamma is None else f64(gamma, total, "gamma")
+    pi_in = None if pi is None else f64(pi, R * MAX_K, "pi")
+    res = VbxResult(row0, em0, K, torch.full((N,), -1, dtype=torch.int32, device=dev),
+                    torch.zeros(total, dtype=torch.float64, device=dev), torch.zeros((R, MAX_K), dtype=torch.float64, device=dev),
+                    torch.full((R, int(iters)), float("nan"), dtype=torch.float64, device=dev),
+                    torch.zeros(R, dtype=torch.int32, device=dev))
+    if R == 0 or N == 0:
+        return res
+    tab = torch.from_numpy(np.concatenate([row0, em0])).to(dev)   # one upload
+    mod = torch.from_numpy(np.concatenate(tabs)).to(dev)
+    km = torch.from_numpy(K.astype(np.int32)).to(dev)
+    lib = _lib.lib()
+    ws = lib.workspace("vm_vbx_workspace_bytes", N, D, R, total, device=dev)
+    lib.call("vm_vbx", rows.data_ptr(), N, P, D, tab.data_ptr(), tab[R + 1:].data_ptr(), R, total, km.data_ptr(), lab.data_ptr(),
+             None if cs is None else cs.data_ptr(), mod.data_ptr(), mod[D:].data_ptr(), mod[2 * D:].data_ptr(), float(loop_prob), float(fa),
+             float(fb), float(init_smooth), float(epsilon), int(iters), None if g_in is None else g_in.data_ptr(),
+             None if pi_in is None else pi_in.data_ptr(), res.labels.data_ptr(), res.gamma.data_ptr(), res.pi.data_ptr(),
+             res.elbo.data_ptr(), res.iters_run.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    return res
+
+
+_run_vbx = vbx   # diarize's own argument is called vbx too
+
+
 # ---- windows and segments ------------------------------------------------------------------------------------------------------------
 def sliding_windows(lens, window: int, hop: int) -> List[np.ndarray]:
     """Per recording the start offsets 0, hop, 2 hop, ... of every window of ``window`` samples that fits, plus one last window flush
@@ -672,7 +935,7 @@ def make_conversations(dataset, n: int, speakers: Tuple[int, int] = (2, 4), turn
 # ---- the whole path --------------------------------------------------------------------------------------------------------------------
 def diarize(model, audio, offsets, lens, preprocessor, window_seconds: float, hop_seconds: float, network_type: str = "siamese",
             distance: str = "cosine", linkage: str = "average", threshold: Optional[float] = None, n_speakers=None, batch: int = 256,
-            plda=None, vad=None, min_voiced: float = 0.5, reseg: Optional[ResegPolicy] = None):
+            plda=None, vad=None, min_voiced: float = 0.5, reseg: Optional[ResegPolicy] = None, vbx: Optional[VbxPolicy] = None):
     """Diarize the recordings ``audio[offsets[r] : offsets[r] + lens[r]]`` of a resident int16 buffer: sliding windows, every window
     embedded alone (``embed_from_offsets(..., windows_per_tower=1)``, ``batch`` windows per call), ``cluster``, ``window_segments``.
     Returns (segments per recording, the ``Clustering``); the clustering also carries ``emb`` (N, E), ``starts`` (per recording, relative
@@ -688,11 +951,15 @@ def diarize(model, audio, offsets, lens, preprocessor, window_seconds: float, ho
     chain break wherever gating dropped a window) and the segments are made from the decoded labels.  With ``reseg.hop_seconds`` = h
     (``hop_seconds`` a multiple of it) the windows are cut and embedded at hop h, the ones ``lattice_windows`` marks are clustered as
     without it, and every other row enters the decode with label -1.  distance="plda" is refused with ``reseg``.
+    ``vbx``: a ``VbxPolicy``; needs distance="plda" and is refused together with ``reseg``.  The cluster labels start a VBx run on the
+    projected rows (``vbx``: ``vm_vbx``, ``n_models`` = the clustering's ``n_clusters``, so the clustering should stop early: VBx drops
+    speakers, it does not add any) over the same fine-hop lattice and chain breaks as ``reseg``, rows that were not clustered entering
+    with label -1; the segments are made from its labels, and the clustering carries the ``VbxResult`` as ``vbx``.
     With either, the clustering also carries ``window_row0`` (the row table of ``emb``; ``row0`` is that of the clustered rows),
     ``kept`` (per recording, one bool per window of the lattice: embedded or not), ``clustered`` (per recording, one bool per embedded
     window), ``chain_start``, ``vad`` (the ``VadResult``), ``voiced`` (per recording, its frames' mask as read back) and ``reseg`` (the
     ``Resegmentation``); ``starts`` are the embedded windows'.
-    With neither, the calls and the results are what they were without the two options."""
+    With none of them, the calls and the results are what they were without the options."""
     import torch
     from .engine_core import require_resident_input
     from .retrieval import _encoder_engine
@@ -718,6 +985,14 @@ def diarize(model, audio, offsets, lens, preprocessor, window_seconds: float, ho
             raise ValueError('diarize: reseg is refused with distance="plda": the mean of PLDA-space rows is not a PLDA-space row')
         if reseg.hop_seconds is not None:
             fine_hop = int(round(reseg.hop_seconds * SAMPLING_RATE))
+    vbx_policy = vbx
+    if vbx_policy is not None:
+        if reseg is not None:
+            raise ValueError("diarize: vbx and reseg are two resegmentations: one of them")
+        if distance != "plda":
+            raise ValueError('diarize: vbx needs distance="plda": its speaker models live in the PLDA space')
+        if vbx_policy.hop_seconds is not None:
+            fine_hop = int(round(vbx_policy.hop_seconds * SAMPLING_RATE))
     if not 0.0 <= min_voiced <= 1.0:
         raise ValueError("min_voiced is a share of a window's frames, in [0, 1]")
     R = len(lens)
@@ -748,16 +1023,23 @@ def diarize(model, audio, offsets, lens, preprocessor, window_seconds: float, ho
     res = cluster(rows if pick is None else rows[pick], crow0, distance, linkage, threshold, n_speakers)
     res.emb, res.rows, res.starts, res.window = emb, rows, starts, window
     res.window_row0, res.kept, res.clustered, res.vad, res.voiced, res.reseg = row0, kept, coarse, det, masks, None
+    res.vbx = None
     res.chain_start = np.concatenate([chain_starts(k) for k in kept]) if vad is not None and R else None
-    if reseg is None:
+    if reseg is None and vbx_policy is None:
         labels = res.host().labels
     else:
         lab_in = res.labels
         if pick is not None:
             lab_in = torch.full((len(flat),), -1, dtype=torch.int32, device=emb.device)
             lab_in[pick] = res.labels
-        res.reseg = resegment(emb, row0, lab_in, res.host().n_clusters, res.chain_start, distance, reseg.switch_cost, reseg.iters)
-        labels = res.reseg.host().labels
+        if reseg is not None:
+            res.reseg = resegment(emb, row0, lab_in, res.host().n_clusters, res.chain_start, distance, reseg.switch_cost, reseg.iters)
+            labels = res.reseg.host().labels
+        else:
+            v = vbx_policy
+            res.vbx = _run_vbx(rows, row0, lab_in, res.host().n_clusters, plda, res.chain_start, v.loop_prob, v.fa, v.fb,
+                               v.init_smooth, v.iters, v.epsilon)
+            labels = res.vbx.host().labels
     segments = []
     for r in range(R):
         seg = np.zeros((0, 3), np.int64)
