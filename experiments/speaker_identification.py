@@ -6,6 +6,7 @@ EER and thresholds.
         [--per-speaker N] [--distance euclidean|cosine|dot_product] [--whole-utterance] [--synthetic]
         [--vad --vad-threshold-db 25 --vad-hang 10 --vad-min-run 3 --vad-frame-ms 10]
         [--backend plda --plda-train train|validation --plda-train-set train-clean-100 --lda-dim D --no-length-norm]
+        [--score-norm none|s-norm|as-norm --cohort-set train-clean-100 --cohort-size 5000 --top-k 300]
 Without --test-set (or with the same set) the enrolled set is also the test set: leave-one-out (every utterance is scored against its own
 speaker's model built from the speaker's OTHER utterances), or with --per-speaker N a seeded choice of N utterances per speaker is
 enrolled and the others are the queries.  With another --test-set its utterances are scored against the enrolled set's models (its
@@ -15,7 +16,12 @@ torchrun the query rows are sharded like the other evaluation scripts.  With --v
 --backend plda (off by default) puts a PLDA back end (voicemap_amd/plda.py) in front, as experiments/verification_accuracy.py does: it is
 fitted on the training set (--plda-train train: --plda-train-set, a further generated set with --synthetic) or on the enrolled set itself
 (--plda-train validation), both sets are projected by it, and every speaker model is scored by the book from ALL its enrolment rows
-(multi-session PLDA, enrolment.enrol(plda=...)); --distance is then not used and the row says distance "plda"."""
+(multi-session PLDA, enrolment.enrol(plda=...)); --distance is then not used and the row says distance "plda".
+--score-norm s-norm / as-norm (off by default; the options of experiments/verification_accuracy.py) normalises the model-trial scores
+against a cohort (enrolment.model_score_norm): a seeded random subset of --cohort-set's files (a third generated set with --synthetic),
+as-norm over the --top-k most alike per side; with --backend plda the cohort is projected by the same model.  The trial figures and
+thresholds of the row are then those of the normalised scores and the row gains score_norm / top_k / cohort_size; the identification
+figures rank by the raw score.  Without it the printed row is what it was."""
 import argparse
 import json
 
@@ -26,11 +32,13 @@ from voicemap_amd.vad import add_vad_args, policy_from_args
 
 
 def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=None, whole_utterance=False, seed=0, vad=None,
-             backend="none", plda_train=None, lda_dim=None, length_norm=True):
+             backend="none", plda_train=None, lda_dim=None, length_norm=True, score_norm="none", cohort=None, top_k=300):
     """The result row: identification and model-trial figures of ``test_set`` (None: the enrolled set itself) against the models of
     ``enrol_set``.  ``vad`` (a ``vad.VadPolicy``): both sets are embedded with their pauses trimmed out.  ``backend`` "plda": a
     ``plda.PldaModel`` is fitted on the embeddings of ``plda_train`` (a dataset; None: the enrolled set) with ``lda_dim`` /
-    ``length_norm``, both sets are projected by it and the models are multi-session PLDA models (``distance`` is not used)."""
+    ``length_norm``, both sets are projected by it and the models are multi-session PLDA models (``distance`` is not used).
+    ``score_norm`` "s-norm" / "as-norm": the model trials are normalised against the embeddings of ``cohort`` (a dataset; projected by
+    the back end where there is one), as-norm over the ``top_k`` most alike per side."""
     wu = {"whole_utterance": True} if whole_utterance else {}
     if vad is not None:
         wu["vad"] = vad
@@ -50,7 +58,14 @@ def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=No
     if back is not None and test_set is not None:
         ct = back.project(ct)
     ident = enrolment.identify(models, ct)
-    mt = enrolment.model_trial_metrics(models, ct)
+    cc, k, nt = None, None, None
+    if score_norm != "none":
+        cc = retrieval.embed_corpus(net, cohort, pre, "siamese", **wu)
+        if back is not None:
+            cc = back.project(cc)
+        k = None if score_norm == "s-norm" else top_k
+        nt = enrolment.model_score_norm(models, ct, cc, top_k=k)
+    mt = enrolment.model_trial_metrics(models, ct, norm=nt)
     cmc = ident["cmc"]
     row = {"distance": distance, "speakers": models.S, "per_speaker": per_speaker, "leave_one_out": ident["leave_one_out"],
            "queries": ident["n_queries"], "unranked": ident["n_unranked"], "rank1_accuracy": ident["rank1_accuracy"],
@@ -59,16 +74,19 @@ def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=No
            "trial_best_threshold": mt["best_threshold"], "target_trials": mt["n_target"], "nontarget_trials": mt["n_nontarget"],
            "whole_utterance": bool(whole_utterance)}
     if test_set is not None:   # the enrolled set's own threshold applied to the test set, as verification_accuracy.py does for pairs
-        me = enrolment.model_trial_metrics(models, ce)
-        at = enrolment.model_trial_accuracy_at_threshold(models, ct, me["best_threshold"])
+        ne = enrolment.model_score_norm(models, ce, cc, top_k=k) if cc is not None else None
+        me = enrolment.model_trial_metrics(models, ce, norm=ne)
+        at = enrolment.model_trial_accuracy_at_threshold(models, ct, me["best_threshold"], norm=nt)
         row.update(enrol_best_threshold=me["best_threshold"], test_balanced_accuracy_at_enrol_threshold=at["balanced_accuracy"],
                    test_far=at["far"], test_frr=at["frr"])
     if back is not None:
         row.update(backend="plda", plda_dim=back.D, lda_dim=back.A1.shape[0], length_norm=back.length_norm,
                    plda_train="validation" if plda_train is None else "train", model_rows_max=models.n_max)
+    if score_norm != "none":
+        row.update(score_norm=score_norm, top_k=top_k if score_norm == "as-norm" else None, cohort_size=len(cohort))
     if vad is not None:
         from voicemap_amd.vad import summarise
-        summary = summarise([c.vad_counts for c in ((ce,) if test_set is None else (ce, ct))])
+        summary = summarise([c.vad_counts for c in ((ce,) if test_set is None else (ce, ct)) + ((cc,) if cc is not None else ())])
         print("--vad:", summary)
         row.update({"vad_" + k: v for k, v in summary.items()})
     return row
@@ -91,7 +109,11 @@ def _parser():
     p.add_argument("--plda-train-set", default="train-clean-100", help="the training subset of --plda-train train")
     p.add_argument("--lda-dim", type=int, default=None, help="LDA directions kept in front of PLDA (default: all)")
     p.add_argument("--no-length-norm", action="store_true", help="no length normalisation between LDA and PLDA")
-    add_vad_args(p)   # --vad ...: off by default; both sets are trimmed first
+    p.add_argument("--score-norm", default="none", choices=["none", "s-norm", "as-norm"], help="cohort score normalisation of the model trials")
+    p.add_argument("--cohort-set", default="train-clean-100", help="the cohort's subset (a third generated set with --synthetic)")
+    p.add_argument("--cohort-size", type=int, default=5000, help="files of the cohort set taken (seeded random subset)")
+    p.add_argument("--top-k", type=int, default=300, help="as-norm: cohort models / rows per side")
+    add_vad_args(p)   # --vad ...: off by default; every set embedded, the cohort included, is trimmed first
     return p
 
 
@@ -125,9 +147,16 @@ def main(argv=None):
         plda_train = (SyntheticSpeechDataset(num_speakers=20, files_per_speaker=8, seconds=a.n_seconds, stochastic=False, seed=4,
                                              subset="synthetic-train")
                       if a.synthetic else LibriSpeechDataset(a.plda_train_set, a.n_seconds, stochastic=False))
+    cohort = None
+    if a.score_norm != "none":
+        from experiments.verification_accuracy import cohort_subset
+        cohort = cohort_subset(SyntheticSpeechDataset(num_speakers=20, files_per_speaker=8, seconds=a.n_seconds, stochastic=False, seed=3,
+                                                      subset="synthetic-cohort")
+                               if a.synthetic else LibriSpeechDataset(a.cohort_set, a.n_seconds, stochastic=False), a.cohort_size)
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
     row = evaluate(net, enrol_set, test_set, pre, a.distance, a.per_speaker, a.whole_utterance, a.seed, vad=vad, backend=a.backend,
-                   plda_train=plda_train, lda_dim=a.lda_dim, length_norm=not a.no_length_norm)
+                   plda_train=plda_train, lda_dim=a.lda_dim, length_norm=not a.no_length_norm, score_norm=a.score_norm, cohort=cohort,
+                   top_k=a.top_k)
     row.update(enrol_set="synthetic" if a.synthetic else a.enrol_set,
                test_set=("synthetic" if a.synthetic else a.enrol_set) if same else a.test_set)
     if rank == 0:

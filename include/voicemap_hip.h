@@ -64,7 +64,7 @@ enum { VM_SCORE_WEIGHTED_L1 = 3, VM_SCORE_NEG_EUCLIDEAN = 4, VM_SCORE_PLDA = 6 }
  * models are scored by the book by vm_plda_speaker_identify / vm_plda_speaker_trial_hist below. */
 
 const char* vm_last_error(void);
-/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms), vm_cohort_topk_stats / vm_cohort_stats_workspace_bytes / vm_pair_score_hist_norm (cohort score normalisation, S-norm / AS-norm), the *_varlen forward entry points (whole utterances in length-masked buckets: vm_crop_decimate_whiten_varlen, vm_conv1_fused_fwd_varlen, vm_conv_fwd_pool_varlen, vm_bn_drop_pool_fwd_varlen, vm_bn_drop_pool_gmax_fwd_varlen, vm_global_maxpool_fwd_varlen), VM_SCORE_PLDA / vm_scatter_f64[_workspace_bytes, _chunk_rows] / vm_plda_project (the PLDA back end), vm_plda_speaker_identify / vm_plda_speaker_trial_hist[_workspace_bytes] (multi-session PLDA speaker models); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
+/* 11.  History: 11 = vm_program_run / vm_program_table_hash, the native runner of a recorded step (round 6), and since then, additive within 11: vm_pair_score_hist[_workspace_bytes] (all-pairs verification histograms), vm_cohort_topk_stats / vm_cohort_stats_workspace_bytes / vm_pair_score_hist_norm (cohort score normalisation, S-norm / AS-norm), the *_varlen forward entry points (whole utterances in length-masked buckets: vm_crop_decimate_whiten_varlen, vm_conv1_fused_fwd_varlen, vm_conv_fwd_pool_varlen, vm_bn_drop_pool_fwd_varlen, vm_bn_drop_pool_gmax_fwd_varlen, vm_global_maxpool_fwd_varlen), VM_SCORE_PLDA / vm_scatter_f64[_workspace_bytes, _chunk_rows] / vm_plda_project (the PLDA back end), vm_plda_speaker_identify / vm_plda_speaker_trial_hist[_workspace_bytes] (multi-session PLDA speaker models), vm_speaker_loo_sums / vm_[plda_]speaker_cohort_stats / vm_[plda_]speaker_trial_hist_norm[_workspace_bytes] (S-norm / AS-norm of speaker-model trials); 10 = config 4's log-mel image at twice the storage significand (vm_stft_logmel_f16s_split, vm_conv2d_first_fwd_split, vm_conv2d_first_bn_pool_stack, vm_bn_pool2d_stack_fwd_split) (round 6); 9 = the last block in pair form (vm_bn_drop_pool_gmax_partials_e, vm_bn_bwd_gmax_finalize_e, vm_bn_pool_bwd_apply_pairs_gmax) (round 6); 8 = vm_mfma_rate_probe[_flops], vm_bn_bwd_gmax_finalize; vm_pairdist_workspace_bytes grew by the scalar-path copy of the queries (round 6); 7 = the fused tail (vm_tail_fwd_bwd, vm_tail_param_grads, vm_bn_drop_pool_gmax_partials), vm_event_* / vm_stream_wait_event, centred tiles (`ctr_out` of vm_fold_bn_weights, `e_center` of vm_conv_fwd_fold / vm_bn_pool_bwd_apply_pairs, `tile_center` of vm_bn_finalize) (round 5); 6 = packed weights (vm_pack_nt_weights[_batch]; the `*_packed` argument of vm_conv_fwd_fold / vm_conv_fwd_pool /
  * vm_conv_dgrad_bnred; `bias`, `wf_packed` and the fourth hb row of vm_fold_bn_weights), the centred block-1 extreme (`center_bias` /
  * `shift_adj` / `mean_adj` of vm_bn_finalize) (round 4).  Earlier: 1 = round 1; 2 = vm_bn_finalize gained the zero-debias arguments (round 2); 3 = VM_F16, `dtype` in vm_conv1_fused_*,
  * `grad_scale` in the loss entry points, `skip_nonfinite` in vm_adam_clip_step, vm_embed_* / vm_pairdist_* (round 3); 4 = the folded-BatchNorm training forward
@@ -1059,6 +1059,64 @@ int vm_plda_speaker_trial_hist(const float* q, const int32_t* q_label, int64_t M
                                int64_t S, const double* A, const double* beta, const double* C, const double* G, int n_max,
                                int leave_one_out, const int64_t* host_windows, int n_windows, int bins, uint64_t* hist, void* ws,
                                void* stream);
+/* Score normalisation of speaker-model trials: S-norm / AS-norm (csrc/enrol_norm.hip, voicemap_amd/enrolment.py model_score_norm).
+ * Notation of the two blocks above (vm_speaker_sums ... vm_plda_speaker_trial_hist).  score(r, model) is the fp32 trial score of that
+ * block for the back end in use -- float64, rounded once -- and NaN where the model has no rows: n == 0, or for PLDA n outside 1..n_max.
+ * Cohort.  A set of C rows other than the query rows and the enrolled rows, used two ways: as C cohort ROWS, and as S_c cohort MODELS
+ * (vm_speaker_sums over all of its rows, with the kind / the PLDA tables of the enrolled models).
+ * Three sets of statistics, each selected and reduced by exactly vm_cohort_topk_stats' rules: NaN scores are skipped; K' = min(K,
+ * remaining); the K' smallest by (uint32 score key with -0.0 as +0.0, index) ascending; mu the mean and sigma the population standard
+ * deviation, accumulated in float64 in a fixed order and rounded to fp32 once; rsig = (float)(1.0 / (double)sigma); K' = 0 gives NaN,
+ * sigma = 0 gives rsig = +inf; count = K'; the optional topk_idx (lines, K) int32 in (key, index) order, padded with -1.
+ *   1. Query side: for every query row m, over the cohort models s_c, score(q_m, cohort model s_c): mu_q, rsig_q (M).
+ *   2. Model side: for every enrolled model s, over the cohort rows c, score(cohort row c, model s): mu_s, rsig_s (S).
+ *   3. Own side, leave-one-out only: query row m sees its own speaker's model without itself -- Sigma = sum_s - c_m, msum likewise,
+ *      n = count_s - 1 -- and that VIRTUAL model has its own statistics over the cohort rows: mu_own, rsig_own (M), NaN where the row
+ *      has no own model.
+ *   The scores of sets 1 and 2 are bit-identical to vm_speaker_identify's (vm_plda_speaker_identify's) `scores` matrix for the same
+ *   operands with leave_one_out = 0; those of set 3 to that matrix with the virtual models as the models.
+ * Normalised trial score, fp32, every operation rounded on its own (no contraction into fma), as vm_pair_score_hist_norm:
+ *   a = s - mu_q[m];  b = s - mu_M;  s' = 0.5f * (a * rsig_q[m] + b * rsig_M)
+ * with (mu_M, rsig_M) = (mu_own[m], rsig_own[m]) when leave_one_out != 0 and s == q_label[m], and (mu_s[s], rsig_s[s]) otherwise.
+ * Trials, classes, windows, slots, the NaN slot, accumulation and limits are exactly vm_speaker_trial_hist's.
+ * vm_speaker_loo_sums: the virtual model of every row of q (M, E) / q_label (M): out_sums (M, E) f64, out_msum (M) f64, out_count (M)
+ *   int32.  c_m and |e_m| are formed exactly as vm_speaker_sums forms them; one float64 subtraction per component.  A row whose q_label
+ *   is outside [0, S), or whose speaker has count <= 1, gets count 0 and zeros.  With kind = VM_DIST_EUCLIDEAN and E = P it serves
+ *   PLDA-space rows (Sigma_d = sum_sd - (double)w_md).  ws >= vm_speaker_loo_sums_workspace_bytes(M, E).
+ * vm_speaker_cohort_stats: rows q (M, E) against the models sums / msum / count (S).  side = 0: per row over the S models (outputs of
+ *   length M); side = 1: per model over the M rows (outputs of length S).  topk_idx may be NULL.  K >= 1.  The scores are written a
+ *   chunk of lines at a time by vm_speaker_identify itself into a tile of at most ~192 MB in ws (vm_cohort_topk_stats' cap) and
+ *   selected down its rows (side 0) or its columns (side 1).  ws >= vm_speaker_cohort_stats_workspace_bytes(M, E, S, side).
+ * vm_plda_speaker_cohort_stats: the same with P, D and the tables A, beta, C, G, n_max in place of msum and kind, as
+ *   vm_plda_speaker_identify takes them.  ws >= vm_plda_speaker_cohort_stats_workspace_bytes(M, D, S, side).
+ * vm_speaker_trial_hist_norm / vm_plda_speaker_trial_hist_norm: the histograms of s'.  mu_q, rsig_q (M, indexed like q), mu_s, rsig_s (S)
+ *   fp32 on the device; mu_own, rsig_own (M) are NULL together, must be NULL when leave_one_out == 0 and are needed when it is not.
+ *   ws >= the matching *_workspace_bytes (those of the plain histograms).
+ * Every bad argument is an error before any launch, outputs untouched; M == 0 returns without a launch.  No float atomics: every output
+ * is bit-identical from run to run. */
+int64_t vm_speaker_loo_sums_workspace_bytes(int64_t M, int E);
+int vm_speaker_loo_sums(const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
+                        const int32_t* count, int64_t S, int kind, double* out_sums, double* out_msum, int32_t* out_count, void* ws,
+                        void* stream);
+int64_t vm_speaker_cohort_stats_workspace_bytes(int64_t M, int E, int64_t S, int side);
+int vm_speaker_cohort_stats(const float* q, int64_t M, int E, const double* sums, const double* msum, const int32_t* count, int64_t S,
+                            int kind, int side, int64_t K, float* mu, float* sigma, float* rsig, int32_t* cnt, int32_t* topk_idx, void* ws,
+                            void* stream);
+int64_t vm_plda_speaker_cohort_stats_workspace_bytes(int64_t M, int D, int64_t S, int side);
+int vm_plda_speaker_cohort_stats(const float* q, int64_t M, int P, int D, const double* sums, const int32_t* count, int64_t S,
+                                 const double* A, const double* beta, const double* C, const double* G, int n_max, int side, int64_t K,
+                                 float* mu, float* sigma, float* rsig, int32_t* cnt, int32_t* topk_idx, void* ws, void* stream);
+int64_t vm_speaker_trial_hist_norm_workspace_bytes(int64_t M, int E, int64_t S);
+int vm_speaker_trial_hist_norm(const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
+                               const int32_t* count, int64_t S, int kind, int leave_one_out, const int64_t* host_windows, int n_windows,
+                               int bins, const float* mu_q, const float* rsig_q, const float* mu_s, const float* rsig_s,
+                               const float* mu_own, const float* rsig_own, uint64_t* hist, void* ws, void* stream);
+int64_t vm_plda_speaker_trial_hist_norm_workspace_bytes(int64_t M, int D, int64_t S);
+int vm_plda_speaker_trial_hist_norm(const float* q, const int32_t* q_label, int64_t M, int P, int D, const double* sums,
+                                    const int32_t* count, int64_t S, const double* A, const double* beta, const double* C, const double* G,
+                                    int n_max, int leave_one_out, const int64_t* host_windows, int n_windows, int bins, const float* mu_q,
+                                    const float* rsig_q, const float* mu_s, const float* rsig_s, const float* mu_own,
+                                    const float* rsig_own, uint64_t* hist, void* ws, void* stream);
 
 /* ---- a10 / f4: log-mel front-end and the 2-D CNN encoder variant (BASELINE.json config 4) -------------------
  * NOT in the reference (nothing to cite under /root/reference); the specification is DESIGN.md section 9 and the

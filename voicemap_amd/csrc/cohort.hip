@@ -11,6 +11,7 @@
 //    radix select finds the K'-th smallest key T (per-wave 256-bin sub-histograms, wave-aggregated adds for the common digit, one wave
 //    scans); the ties at T are cut in index order by a ballot / popcount prefix count.  The selected scores are reduced in float64 in a
 //    fixed order (per-thread ascending index, a shuffle tree, then the waves in order): no float atomics, bit-identical from run to run.
+//    launch_cohort_select (score_tile.hpp) is its launcher, shared with enrol_norm.hip, which also selects down the COLUMNS of a tile.
 #include "score_tile.hpp"
 
 namespace vm {
@@ -83,9 +84,11 @@ __global__ __launch_bounds__(512) void cohort_score_kernel(const float* __restri
 
 // One workgroup per row r of the score tile sc (rows, C).  CAP > 0: the keys are staged in LDS (C <= CAP); CAP == 0: every pass re-reads
 // the row from the tile.  Writes mu / sigma / rsig / count of row row0 + r and, if topk_idx, its K slots; list (rows, C) int32 is the
-// scratch of the selected indices in index order (used only with topk_idx).
-template <int CAP>
+// scratch of the selected indices in index order (used only with topk_idx).  COL (the speaker-model statistics per MODEL,
+// enrol_norm.hip): line r is COLUMN r of a tile (C, ld) -- entry c at sc[c * ld + r] -- staged into the keys with a strided read.
+template <int CAP, bool COL>
 __global__ __launch_bounds__(CS_SEL_THREADS) void cohort_select_kernel(const float* __restrict__ sc, int64_t C, int64_t K, int64_t row0,
+                                                                       int64_t ld,
                                                                        float* __restrict__ mu, float* __restrict__ sigma,
                                                                        float* __restrict__ rsig, int32_t* __restrict__ count,
                                                                        int32_t* __restrict__ topk_idx, int32_t* __restrict__ list) {
@@ -96,11 +99,15 @@ __global__ __launch_bounds__(CS_SEL_THREADS) void cohort_select_kernel(const flo
     __shared__ uint32_t sh_digit, sh_k, sh_eq;
     __shared__ int64_t sh_cut;
     const int64_t r = blockIdx.x;
-    const float* row = sc + r * C;
+    const float* row = COL ? sc + r : sc + r * C;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    auto score_at = [&](int64_t c) -> float {
+        if constexpr (COL) return row[c * ld];
+        else return row[c];
+    };
     auto key_at = [&](int64_t c) -> uint32_t {
         if constexpr (CAP > 0) return keys[c];
-        else return score_key_nan_last(row[c]);
+        else return score_key_nan_last(score_at(c));
     };
     // workgroup sums in a fixed order: a shuffle tree per wave, then the waves in order
     auto block_sum_u = [&](uint32_t x) -> uint32_t {
@@ -132,7 +139,7 @@ __global__ __launch_bounds__(CS_SEL_THREADS) void cohort_select_kernel(const flo
 #pragma unroll
         for (int u = 0; u < CS_LOAD_BATCH; ++u) {
             const int64_t c = c0 + (int64_t)u * CS_SEL_THREADS + tid;
-            v[u] = c < C ? row[c] : 0.f;
+            v[u] = c < C ? score_at(c) : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < CS_LOAD_BATCH; ++u) {
@@ -312,10 +319,28 @@ __global__ __launch_bounds__(CS_SEL_THREADS) void cohort_select_kernel(const flo
 }
 
 // rows of one score tile: the tile stays within CS_TILE_FLOATS
-static int64_t cs_tile_rows(int64_t M, int64_t C) {
+int64_t cs_tile_rows(int64_t M, int64_t C) {
     int64_t R = (CS_TILE_FLOATS / C) / ST_T * ST_T;
     if (R < ST_T) R = ST_T;
     return R < M ? R : M;
+}
+
+// the selection of `lines` lines of C entries each: the rows of a tile (lines, C) (col_ld == 0) or the columns of a tile (C, col_ld)
+void launch_cohort_select(const float* tile, int64_t lines, int64_t C, int64_t K, int64_t row0, int64_t col_ld, float* mu, float* sigma,
+                          float* rsig, int32_t* count, int32_t* topk_idx, int32_t* list, hipStream_t st) {
+    const dim3 sg((unsigned)lines);
+#define VM_CS_SEL(CAP, COL) \
+    hipLaunchKernelGGL((cohort_select_kernel<CAP, COL>), sg, dim3(CS_SEL_THREADS), 0, st, tile, C, K, row0, col_ld, mu, sigma, rsig, count, topk_idx, list)
+    if (col_ld == 0) {
+        if (C <= CS_CAP_SMALL) VM_CS_SEL(CS_CAP_SMALL, false);
+        else if (C <= CS_CAP_LARGE) VM_CS_SEL(CS_CAP_LARGE, false);
+        else VM_CS_SEL(0, false);
+    } else {
+        if (C <= CS_CAP_SMALL) VM_CS_SEL(CS_CAP_SMALL, true);
+        else if (C <= CS_CAP_LARGE) VM_CS_SEL(CS_CAP_LARGE, true);
+        else VM_CS_SEL(0, true);
+    }
+#undef VM_CS_SEL
 }
 
 }  // namespace vm
@@ -372,16 +397,7 @@ extern "C" int vm_cohort_topk_stats(const float* q, int64_t M, const float* coho
             default: VM_CS(VM_SCORE_NEG_EUCLIDEAN); break;
         }
 #undef VM_CS
-        const dim3 sg((unsigned)rows);
-        if (C <= CS_CAP_SMALL)
-            hipLaunchKernelGGL(cohort_select_kernel<CS_CAP_SMALL>, sg, dim3(CS_SEL_THREADS), 0, st, tile, C, K, row0, mu, sigma, rsig, count,
-                               topk_idx, list);
-        else if (C <= CS_CAP_LARGE)
-            hipLaunchKernelGGL(cohort_select_kernel<CS_CAP_LARGE>, sg, dim3(CS_SEL_THREADS), 0, st, tile, C, K, row0, mu, sigma, rsig, count,
-                               topk_idx, list);
-        else
-            hipLaunchKernelGGL(cohort_select_kernel<0>, sg, dim3(CS_SEL_THREADS), 0, st, tile, C, K, row0, mu, sigma, rsig, count, topk_idx,
-                               list);
+        launch_cohort_select(tile, rows, C, K, row0, 0, mu, sigma, rsig, count, topk_idx, list, st);
         const int rc = check_launch("vm_cohort_topk_stats");
         if (rc != 0) return rc;
     }

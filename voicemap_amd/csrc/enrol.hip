@@ -27,7 +27,9 @@
 // under / over / NaN counts, one flush of 64-bit integer atomics per workgroup.  One template, one en_acc / en_finish (enrol_score.hpp,
 // shared with reseg.hip): the two entry points score bit-identically.  What happens to a finished score -- EN_TILE_STATE / EN_TILE_CELL /
 // EN_TILE_FINISH -- and the launchers' window parsing and splits live in enrol_tile.hpp, shared with plda_enrol.hip (multi-session PLDA
-// models): as text, so that this kernel's instruction stream is what it was.
+// models): as text, so that this kernel's instruction stream is what it was.  NORM = true (HIST only; vm_speaker_trial_hist_norm,
+// enrol_norm.hip): the finished score is normalised with the statistics of `nrm` (EN_NORM_*, enrol_tile.hpp) before it is binned; the
+// plain instantiations never read `nrm`.  en_trial_hist is the whole histogram call, with or without the statistics.
 #include "enrol_tile.hpp"
 
 namespace vm {
@@ -144,8 +146,8 @@ __global__ __launch_bounds__(256) void en_own_kernel(const float* __restrict__ q
 }
 
 // grid (query tiles of 64 rows, splits of the model tiles (HIST only)); 256 threads: ts = tid & 15 owns the models
-// {2 ts, 2 ts + 1, 32 + 2 ts, 33 + 2 ts} of a tile, tq = tid >> 4 the queries 4 tq .. 4 tq + 3.
-template <int KIND, bool HIST>
+// {2 ts, 2 ts + 1, 32 + 2 ts, 33 + 2 ts} of a tile, tq = tid >> 4 the queries 4 tq .. 4 tq + 3.  NORM: with HIST only.
+template <int KIND, bool HIST, bool NORM>
 __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ q, const int32_t* __restrict__ q_label, int64_t M, int E,
                                                       const double* __restrict__ P, const double* __restrict__ pn,
                                                       const int32_t* __restrict__ count, int64_t S, int loo,
@@ -153,7 +155,7 @@ __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ 
                                                       float* __restrict__ scores, float* __restrict__ true_score,
                                                       int32_t* __restrict__ rank, float* __restrict__ best_val,
                                                       int32_t* __restrict__ best_idx, EnWindows win, int n_win, int bins, int splits,
-                                                      unsigned long long* __restrict__ ghist) {
+                                                      unsigned long long* __restrict__ ghist, EnNorm nrm) {
     __shared__ __attribute__((aligned(16))) double qs[EN_EC * EN_LD];
     __shared__ __attribute__((aligned(16))) double ps[EN_EC * EN_LD];
     __shared__ uint32_t hist[HIST ? EN_LDS_HIST_WORDS : 1];
@@ -189,6 +191,7 @@ __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ 
         okey[i] = score_key_nan_last(ownv[i]);
     }
     EN_TILE_STATE;
+    EN_NORM_ROWS
 
     const int nchunk = (E + EN_EC - 1) / EN_EC;
     const int n_stage = (t_hi - t_lo) * nchunk;
@@ -269,6 +272,7 @@ __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ 
             const bool oks = s < S;
             const double pnv = (KIND == VM_DIST_COSINE && oks) ? pn[s] : 1.0;
             const bool has_model = oks && count[s] > 0;
+            EN_NORM_MODEL;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int64_t m = mb + tq * 4 + i;
@@ -276,6 +280,7 @@ __global__ __launch_bounds__(256) void en_tile_kernel(const float* __restrict__ 
                 const bool trial = okm[i] && (is_own ? own_ok[i] : has_model);
                 float d = en_finish<KIND>(acc[i][j], qnv[i], pnv);
                 if (is_own) d = ownv[i];
+                EN_NORM_CELL(d)
                 EN_TILE_CELL(d)
             }
         }
@@ -375,8 +380,8 @@ extern "C" int vm_speaker_identify(const float* q, const int32_t* q_label, int64
     const dim3 grid((unsigned)cdiv(M, EN_TQ), 1);
     const EnWindows win{};
 #define VM_EN_ID(K)                                                                                                                  \
-    hipLaunchKernelGGL((en_tile_kernel<K, false>), grid, dim3(256), 0, st, q, q_label, M, E, a.P, a.pn, count, S, leave_one_out, a.qn, \
-                       a.own, scores, true_score, rank, best_val, best_idx, win, 0, 0, 1, (unsigned long long*)nullptr)
+    hipLaunchKernelGGL((en_tile_kernel<K, false, false>), grid, dim3(256), 0, st, q, q_label, M, E, a.P, a.pn, count, S, leave_one_out, \
+                       a.qn, a.own, scores, true_score, rank, best_val, best_idx, win, 0, 0, 1, (unsigned long long*)nullptr, EnNorm{})
     switch (kind) {
         case VM_DIST_EUCLIDEAN: VM_EN_ID(VM_DIST_EUCLIDEAN); break;
         case VM_DIST_COSINE: VM_EN_ID(VM_DIST_COSINE); break;
@@ -394,8 +399,13 @@ extern "C" int64_t vm_speaker_trial_hist_workspace_bytes(int64_t M, int E, int64
 extern "C" int vm_speaker_trial_hist(const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
                                      const int32_t* count, int64_t S, int kind, int leave_one_out, const int64_t* host_windows,
                                      int n_windows, int bins, uint64_t* hist, void* ws, void* stream) {
-    using namespace vm;
-    const char* what = "vm_speaker_trial_hist";
+    return vm::en_trial_hist("vm_speaker_trial_hist", q, q_label, M, E, sums, msum, count, S, kind, leave_one_out, host_windows, n_windows,
+                             bins, hist, nullptr, ws, stream);
+}
+
+int vm::en_trial_hist(const char* what, const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
+                      const int32_t* count, int64_t S, int kind, int leave_one_out, const int64_t* host_windows, int n_windows, int bins,
+                      uint64_t* hist, const EnNorm* norm, void* ws, void* stream) {
     if (int rc = en_check_models(what, q, q_label, M, E, sums, msum, count, S, kind, ws)) return rc;
     EnWindows win{};
     if (int rc = en_windows(what, host_windows, n_windows, bins, hist, &win)) return rc;
@@ -405,14 +415,22 @@ extern "C" int vm_speaker_trial_hist(const float* q, const int32_t* q_label, int
     en_prepare(q, q_label, M, E, sums, msum, count, S, kind, leave_one_out, a, st);
     const int64_t qb = cdiv(M, EN_TQ), splits = en_hist_splits(M, S);
     const dim3 grid((unsigned)qb, (unsigned)splits);
-#define VM_EN_H(K)                                                                                                                  \
-    hipLaunchKernelGGL((en_tile_kernel<K, true>), grid, dim3(256), 0, st, q, q_label, M, E, a.P, a.pn, count, S, leave_one_out, a.qn, \
-                       a.own, (float*)nullptr, (float*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr, win, n_windows, \
-                       bins, (int)splits, (unsigned long long*)hist)
-    switch (kind) {
-        case VM_DIST_EUCLIDEAN: VM_EN_H(VM_DIST_EUCLIDEAN); break;
-        case VM_DIST_COSINE: VM_EN_H(VM_DIST_COSINE); break;
-        default: VM_EN_H(VM_DIST_DOT); break;
+#define VM_EN_H(K, NORM, NRM)                                                                                                              \
+    hipLaunchKernelGGL((en_tile_kernel<K, true, NORM>), grid, dim3(256), 0, st, q, q_label, M, E, a.P, a.pn, count, S, leave_one_out, a.qn, \
+                       a.own, (float*)nullptr, (float*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr, win, n_windows,      \
+                       bins, (int)splits, (unsigned long long*)hist, NRM)
+    if (norm == nullptr) {
+        switch (kind) {
+            case VM_DIST_EUCLIDEAN: VM_EN_H(VM_DIST_EUCLIDEAN, false, EnNorm{}); break;
+            case VM_DIST_COSINE: VM_EN_H(VM_DIST_COSINE, false, EnNorm{}); break;
+            default: VM_EN_H(VM_DIST_DOT, false, EnNorm{}); break;
+        }
+    } else {
+        switch (kind) {
+            case VM_DIST_EUCLIDEAN: VM_EN_H(VM_DIST_EUCLIDEAN, true, *norm); break;
+            case VM_DIST_COSINE: VM_EN_H(VM_DIST_COSINE, true, *norm); break;
+            default: VM_EN_H(VM_DIST_DOT, true, *norm); break;
+        }
     }
 #undef VM_EN_H
     return check_launch(what);

@@ -25,6 +25,35 @@ struct EnWindows {
 
 static inline char* en_align(void* p) { return (char*)(((uintptr_t)p + 255) & ~(uintptr_t)255); }
 
+// The statistics of a NORMALISED trial histogram (enrol_norm.hip: S-norm / AS-norm of model trials), all fp32 on the device: per query
+// row of the call mu_q / rsig_q and, under leave-one-out, mu_own / rsig_own (the row's own speaker WITHOUT the row); per model mu_s /
+// rsig_s.  The plain kernels (NORM = false) never read it.
+struct EnNorm {
+    const float *mu_q, *rsig_q, *mu_s, *rsig_s, *mu_own, *rsig_own;
+};
+
+// NORM only, shared as text like the epilogue below.  EN_NORM_ROWS: the statistics of the thread's four query rows (reads mb, tq, okm,
+// loo, nrm).  EN_NORM_MODEL: those of model s, inside the loop over the thread's models (reads oks, s).  EN_NORM_CELL(d): the finished
+// score d of a cell becomes vh_norm's (score_tile.hpp) s' = 0.5f ((d - mu_q) rsig_q + (d - mu_M) rsig_M), every operation rounded on its
+// own; (mu_M, rsig_M) is the own pair under leave-one-out in the own-speaker cell, the model's everywhere else.
+#define EN_NORM_ROWS                                                     \
+    float n_mq[4], n_rq[4], n_mo[4], n_ro[4];                            \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                      \
+        const int64_t m = mb + tq * 4 + i;                               \
+        n_mq[i] = (NORM && okm[i]) ? nrm.mu_q[m] : 0.f;                  \
+        n_rq[i] = (NORM && okm[i]) ? nrm.rsig_q[m] : 0.f;                \
+        n_mo[i] = (NORM && loo && okm[i]) ? nrm.mu_own[m] : 0.f;         \
+        n_ro[i] = (NORM && loo && okm[i]) ? nrm.rsig_own[m] : 0.f;       \
+    }
+#define EN_NORM_MODEL                                      \
+    const float n_ms = (NORM && oks) ? nrm.mu_s[s] : 0.f;  \
+    const float n_rs = (NORM && oks) ? nrm.rsig_s[s] : 0.f
+#define EN_NORM_CELL(d)                                                                        \
+    if constexpr (NORM) {                                                                      \
+        const bool o_ = loo && is_own;                                                         \
+        d = vh_norm(d, n_mq[i], n_rq[i], o_ ? n_mo[i] : n_ms, o_ ? n_ro[i] : n_rs);            \
+    }
+
 // The per-thread state of a tile kernel's epilogue: per query row i of the thread's four, the number of speakers before the own one
 // and the best (key, speaker) with its score; per window and class the under / over counts, per class the NaN count.  Reads nanf_.
 #define EN_TILE_STATE                                                                        \
@@ -115,6 +144,17 @@ static inline char* en_align(void* p) { return (char*)(((uintptr_t)p + 255) & ~(
     }
 
 // ---- the launchers' side --------------------------------------------------------------------------------------------------------------
+// The whole of a trial-histogram call -- argument checks, windows, the staging launches, the tile kernel -- for the geometric kinds
+// (enrol.hip) and multi-session PLDA (plda_enrol.hip); norm == NULL: the plain histogram.  vm_[plda_]speaker_trial_hist and their
+// _norm forms (enrol_norm.hip) are these two calls.
+int en_trial_hist(const char* what, const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
+                  const int32_t* count, int64_t S, int kind, int leave_one_out, const int64_t* host_windows, int n_windows, int bins,
+                  uint64_t* hist, const EnNorm* norm, void* ws, void* stream);
+int pe_trial_hist(const char* what, const float* q, const int32_t* q_label, int64_t M, int P, int D, const double* sums,
+                  const int32_t* count, int64_t S, const double* A, const double* beta, const double* C, const double* G, int n_max,
+                  int leave_one_out, const int64_t* host_windows, int n_windows, int bins, uint64_t* hist, const EnNorm* norm, void* ws,
+                  void* stream);
+
 // the (key_lo, shift) pairs of a trial-histogram call, checked and packed
 static inline int en_windows(const char* what, const int64_t* host_windows, int n_windows, int bins, const void* hist, EnWindows* win) {
     VM_REQUIRE(host_windows && hist, "%s: null pointer", what);

@@ -18,7 +18,9 @@
 // x 64 models, thread (tq, ts) holding 4 x 4 float64 accumulators -- with THREE float64 operands staged through LDS (w, mu, A), hence in
 // chunks of 16 components rather than 32: 25 KB, and 58 KB with the histogram, so that two workgroups still share a compute unit.  The
 // epilogue -- the order of the trials, rank / best, the class histogram -- is enrol_tile.hpp's, word for word en_tile_kernel's.  One
-// template, one pe_acc / pe_finish: the two entry points score bit-identically.  No float atomics.
+// template, one pe_acc / pe_finish: the two entry points score bit-identically.  No float atomics.  NORM = true (HIST only;
+// vm_plda_speaker_trial_hist_norm, enrol_norm.hip): the finished score is normalised with the statistics of `nrm` (EN_NORM_*,
+// enrol_tile.hpp) before it is binned.  pe_trial_hist is the whole histogram call, with or without the statistics.
 #include "enrol_tile.hpp"
 
 namespace vm {
@@ -107,7 +109,7 @@ __global__ __launch_bounds__(256) void pe_own_kernel(const float* __restrict__ q
 
 // grid (query tiles of 64 rows, splits of the model tiles (HIST only)); 256 threads: ts = tid & 15 owns the models
 // {2 ts, 2 ts + 1, 32 + 2 ts, 33 + 2 ts} of a tile, tq = tid >> 4 the queries 4 tq .. 4 tq + 3 (en_tile_kernel's map).
-template <bool HIST>
+template <bool HIST, bool NORM>
 __global__ __launch_bounds__(256) void pe_tile_kernel(const float* __restrict__ q, const int32_t* __restrict__ q_label, int64_t M, int P, int D,
                                                       const double* __restrict__ mu, const double* __restrict__ As,
                                                       const double* __restrict__ Cs, const int32_t* __restrict__ count, int64_t S,
@@ -115,7 +117,7 @@ __global__ __launch_bounds__(256) void pe_tile_kernel(const float* __restrict__ 
                                                       float* __restrict__ scores, float* __restrict__ true_score,
                                                       int32_t* __restrict__ rank, float* __restrict__ best_val,
                                                       int32_t* __restrict__ best_idx, EnWindows win, int n_win, int bins, int splits,
-                                                      unsigned long long* __restrict__ ghist) {
+                                                      unsigned long long* __restrict__ ghist, EnNorm nrm) {
     __shared__ __attribute__((aligned(16))) double qs[PE_EC * EN_LD];
     __shared__ __attribute__((aligned(16))) double ms[PE_EC * EN_LD];
     __shared__ __attribute__((aligned(16))) double as[PE_EC * EN_LD];
@@ -153,6 +155,7 @@ __global__ __launch_bounds__(256) void pe_tile_kernel(const float* __restrict__ 
         okey[i] = score_key_nan_last(ownv[i]);
     }
     EN_TILE_STATE;
+    EN_NORM_ROWS
 
     const int nchunk = (D + PE_EC - 1) / PE_EC;
     const int n_stage = (t_hi - t_lo) * nchunk;   // workgroup-uniform: every barrier below is reached by all 256 threads
@@ -237,6 +240,7 @@ __global__ __launch_bounds__(256) void pe_tile_kernel(const float* __restrict__ 
             const bool oks = s < S;
             const double cs = oks ? Cs[s] : 0.0;
             const bool has_model = oks && pe_count_ok((int64_t)count[oks ? s : 0], n_max);
+            EN_NORM_MODEL;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int64_t m = mb + tq * 4 + i;
@@ -244,6 +248,7 @@ __global__ __launch_bounds__(256) void pe_tile_kernel(const float* __restrict__ 
                 const bool trial = okm[i] && (is_own ? own_ok[i] : has_model);
                 float d = pe_finish(acc[i][j], gv[i], cs);
                 if (is_own) d = ownv[i];
+                EN_NORM_CELL(d)
                 EN_TILE_CELL(d)
             }
         }
@@ -310,9 +315,9 @@ extern "C" int vm_plda_speaker_identify(const float* q, const int32_t* q_label, 
     pe_prepare(q, q_label, M, P, D, sums, count, S, A, beta, C, G, n_max, leave_one_out, a, st);
     const dim3 grid((unsigned)cdiv(M, EN_TQ), 1);
     const EnWindows win{};
-    hipLaunchKernelGGL((pe_tile_kernel<false>), grid, dim3(256), 0, st, q, q_label, M, P, D, (const double*)a.mu, (const double*)a.As,
+    hipLaunchKernelGGL((pe_tile_kernel<false, false>), grid, dim3(256), 0, st, q, q_label, M, P, D, (const double*)a.mu, (const double*)a.As,
                        (const double*)a.Cs, count, S, n_max, leave_one_out, (const double*)a.gq, (const float*)a.own, scores, true_score,
-                       rank, best_val, best_idx, win, 0, 0, 1, (unsigned long long*)nullptr);
+                       rank, best_val, best_idx, win, 0, 0, 1, (unsigned long long*)nullptr, EnNorm{});
     return check_launch(what);
 }
 
@@ -325,8 +330,14 @@ extern "C" int vm_plda_speaker_trial_hist(const float* q, const int32_t* q_label
                                           const int32_t* count, int64_t S, const double* A, const double* beta, const double* C,
                                           const double* G, int n_max, int leave_one_out, const int64_t* host_windows, int n_windows,
                                           int bins, uint64_t* hist, void* ws, void* stream) {
-    using namespace vm;
-    const char* what = "vm_plda_speaker_trial_hist";
+    return vm::pe_trial_hist("vm_plda_speaker_trial_hist", q, q_label, M, P, D, sums, count, S, A, beta, C, G, n_max, leave_one_out,
+                             host_windows, n_windows, bins, hist, nullptr, ws, stream);
+}
+
+int vm::pe_trial_hist(const char* what, const float* q, const int32_t* q_label, int64_t M, int P, int D, const double* sums,
+                      const int32_t* count, int64_t S, const double* A, const double* beta, const double* C, const double* G, int n_max,
+                      int leave_one_out, const int64_t* host_windows, int n_windows, int bins, uint64_t* hist, const EnNorm* norm, void* ws,
+                      void* stream) {
     if (int rc = pe_check(what, q, q_label, M, P, D, sums, count, S, A, beta, C, G, n_max, ws)) return rc;
     EnWindows win{};
     if (int rc = en_windows(what, host_windows, n_windows, bins, hist, &win)) return rc;
@@ -336,9 +347,13 @@ extern "C" int vm_plda_speaker_trial_hist(const float* q, const int32_t* q_label
     pe_prepare(q, q_label, M, P, D, sums, count, S, A, beta, C, G, n_max, leave_one_out, a, st);
     const int64_t qb = cdiv(M, EN_TQ), splits = en_hist_splits(M, S);
     const dim3 grid((unsigned)qb, (unsigned)splits);
-    hipLaunchKernelGGL((pe_tile_kernel<true>), grid, dim3(256), 0, st, q, q_label, M, P, D, (const double*)a.mu, (const double*)a.As,
-                       (const double*)a.Cs, count, S, n_max, leave_one_out, (const double*)a.gq, (const float*)a.own, (float*)nullptr,
-                       (float*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr, win, n_windows, bins, (int)splits,
-                       (unsigned long long*)hist);
+#define VM_PE_H(NORM, NRM)                                                                                                                \
+    hipLaunchKernelGGL((pe_tile_kernel<true, NORM>), grid, dim3(256), 0, st, q, q_label, M, P, D, (const double*)a.mu, (const double*)a.As, \
+                       (const double*)a.Cs, count, S, n_max, leave_one_out, (const double*)a.gq, (const float*)a.own, (float*)nullptr,     \
+                       (float*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr, win, n_windows, bins, (int)splits,          \
+                       (unsigned long long*)hist, NRM)
+    if (norm == nullptr) VM_PE_H(false, EnNorm{});
+    else VM_PE_H(true, *norm);
+#undef VM_PE_H
     return check_launch(what);
 }

@@ -61,6 +61,15 @@ inline bool plda_width_ok(int kind, int E) { return kind != VM_SCORE_PLDA || (E 
 // wpad[0 .. ST_MAX_E) = w[0 .. E) followed by zeros (all zeros for w == NULL): the weights of VM_SCORE_WEIGHTED_L1
 void launch_pad_weights(const float* w, int E, float* wpad, hipStream_t st);
 
+// ---- the cohort selection (defined in cohort.hip; shared with enrol_norm.hip) ----------------------------------------------------------
+// rows of one score tile of C-entry lines (a multiple of 64 within the tile cap, at most M)
+int64_t cs_tile_rows(int64_t M, int64_t C);
+// vm_cohort_topk_stats' selection and statistics of `lines` lines of C entries: the rows of a tile (lines, C) (col_ld == 0) or the
+// columns of a tile (C, col_ld).  Line r writes mu / sigma / rsig / count [row0 + r] and, if topk_idx, its K slots; list: lines x C int32
+// of scratch (read only with topk_idx).
+void launch_cohort_select(const float* tile, int64_t lines, int64_t C, int64_t K, int64_t row0, int64_t col_ld, float* mu, float* sigma,
+                          float* rsig, int32_t* count, int32_t* topk_idx, int32_t* list, hipStream_t st);
+
 // splits of the reference tiles so that the grid holds at least `target` workgroups (2048 = 8 per CU), one tile per split at the least
 inline int score_splits(int64_t rows, int64_t refs, int64_t target) {
     const int64_t nt = cdiv(refs, ST_RT);

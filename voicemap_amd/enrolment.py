@@ -38,6 +38,24 @@ coefficient tables for 1 .. the largest count rows, and ``identify`` / ``model_t
 mean what they mean above -- trials, order, leave-one-out, ``per_speaker``, ``rows`` -- with that score.  ``plda=`` is the switch:
 "plda" is not one of the ``distance`` names.  The cache must already be projected (its width is ``model.P``); a raw cache is refused.
 
+Score normalisation of model trials: S-norm / AS-norm (``model_score_norm``, ``norm=``; include/voicemap_hip.h and DESIGN 8n state the
+same).  ``score(r, model)`` is the fp32 trial score above for the back end in use, NaN where the model has no rows (n == 0; PLDA: n
+outside 1..n_max).  The cohort is an ``EmbeddingCache`` other than the query cache and ``models.cache``, used two ways: as C cohort
+ROWS, and as S_c cohort MODELS (``enrol(cohort, distance=models.distance)`` / ``enrol(cohort, plda=models.plda)`` over all its rows).
+Three sets of statistics, each selected and reduced by exactly ``vm_cohort_topk_stats``'s rules (``verification.cohort_stats_numpy``: NaN
+scores skipped, K' = min(K, remaining), the K' smallest by (uint32 key with -0.0 as +0.0, index), mu / sigma the float64 mean and
+population standard deviation rounded to fp32 once, rsig = fp32(1 / float64(sigma)), K' = 0: NaN, sigma = 0: rsig = +inf):
+
+1. query side: per query row m over the cohort models, ``score(q_m, cohort model)``: ``mu_q``, ``rsig_q`` (M);
+2. model side: per enrolled model s over the cohort rows, ``score(cohort row, model s)``: ``mu_s``, ``rsig_s`` (S);
+3. own side, leave-one-out only: row m sees its own speaker's model without itself (Sigma = sum_s - c_m, msum likewise, n = count_s - 1)
+   and that virtual model has its own statistics over the cohort rows: ``mu_own``, ``rsig_own`` (M), NaN where the row has no own model.
+
+The trial (m, s) is then scored, in fp32 with every operation rounded on its own, ``a = s - mu_q[m]; b = s - mu_M;
+s' = 0.5 (a rsig_q[m] + b rsig_M)`` with (mu_M, rsig_M) = (mu_own[m], rsig_own[m]) for the own speaker's trial under leave-one-out and
+(mu_s[s], rsig_s[s]) otherwise (``normalise_trials_numpy``); trials, classes and the exact metrics are unchanged.  ``identify`` ranks by
+the raw score: normalised ranking is out of scope, and so is the calibration of model trials.
+
 Under torchrun every rank computes the sums over all rows itself (N x E reads; the models are then bit-identical everywhere), takes its
 ``parallel.shard_range`` of the query rows, and the integer rank histogram / trial histograms are summed over ranks.
 """
@@ -151,6 +169,116 @@ def ranks_numpy(scores, trial, q_label) -> Dict[str, np.ndarray]:
     rank = np.where(ranked, before, -1).astype(np.int32)
     true_score = np.where(ranked, s[rows, own], np.float32(np.nan)).astype(np.float32)
     return {"rank": rank, "best_idx": best_idx, "best_val": best_val, "true_score": true_score}
+
+
+def loo_sums_numpy(q, q_label, sums, msum, count, kind) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """numpy twin of ``vm_speaker_loo_sums``: the virtual model of every row -- (sums (M, E), msum (M), count (M) int32) of the row's own
+    speaker without the row: one float64 subtraction per component; count 0 and zeros where ``q_label`` is outside [0, S) or the
+    speaker has one row or none."""
+    kind = _kind(kind)
+    c, mag = _contrib(q, kind)
+    q_label, count = np.asarray(q_label), np.asarray(count)
+    sums, msum = np.asarray(sums, dtype=np.float64), np.asarray(msum, dtype=np.float64)
+    S = len(count)
+    M = c.shape[0]
+    vs, vm, vc = np.zeros((M, c.shape[1])), np.zeros(M), np.zeros(M, dtype=np.int32)
+    for m in range(M):
+        own = int(q_label[m])
+        if 0 <= own < S and count[own] > 1:
+            vs[m] = sums[own] - c[m]
+            vm[m] = msum[own] - mag[m]
+            vc[m] = count[own] - 1
+    return vs, vm, vc
+
+
+def _scores_from_sums(q, sums, msum, count, kind: int, tables=None) -> np.ndarray:
+    """fp32 (M, S) scores of rows against models given by their sums (``trial_scores_numpy``'s / ``trial_scores_plda_numpy``'s formulas
+    without leave-one-out), NaN where there is no model."""
+    count = np.asarray(count).astype(np.int64)
+    out = np.full((len(q), len(count)), np.nan)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        if tables is not None:
+            A, beta, C, G = (np.asarray(tables[k], dtype=np.float64) for k in ("A", "beta", "C", "G"))
+            D = int(G.shape[0])
+            ok = (count >= 1) & (count <= int(A.shape[0]) - 1)
+            nn = np.where(ok, count, 0)
+            w = np.asarray(q, dtype=np.float32)[:, :D].astype(np.float64)
+            for m in range(len(w)):
+                t = w[m][None, :] - beta[nn] * np.asarray(sums)[:, :D]
+                out[m, ok] = ((((A[nn] * t) * t).sum(1) - (G * (w[m] * w[m])).sum()) - C[nn])[ok]
+            return out.astype(np.float32)
+        ok = count > 0
+        n = count.astype(np.float64)
+        p = np.asarray(sums) / n[:, None]
+        if kind == 2:
+            p = (np.asarray(msum) / n)[:, None] * p
+        q = np.asarray(q, dtype=np.float64)
+        qmag = np.sqrt((q * q).sum(axis=1))
+        for m in range(len(q)):
+            if kind == 0:
+                sc = np.sqrt(((q[m][None, :] - p) ** 2).sum(axis=1))
+            elif kind == 1:
+                sc = 1.0 - (p @ q[m]) / (qmag[m] * np.sqrt((p * p).sum(axis=1)))
+            else:
+                sc = -(p @ q[m])
+            out[m, ok] = sc[ok]
+    return out.astype(np.float32)
+
+
+def model_norm_stats_numpy(emb, label, q, q_label, cohort, cohort_label, kind, top_k: Optional[int], leave_one_out: bool,
+                           S: Optional[int] = None, tables=None, cohort_tables=None) -> Dict[str, np.ndarray]:
+    """numpy twin of ``model_score_norm``: the three sets of statistics of the module docstring for the query rows ``q`` / ``q_label``
+    against the models of the enrolled rows ``emb`` / ``label``, with the cohort rows ``cohort`` and the cohort models of ``cohort`` /
+    ``cohort_label``.  ``tables`` (and ``cohort_tables``, default the same): multi-session PLDA (``kind`` is then not used).  Returns
+    ``mu_q``, ``sigma_q``, ``rsig_q``, ``count_q`` (M); ``mu_s``, ... (S); with ``leave_one_out`` ``mu_own``, ... (M), else None."""
+    from . import plda as _plda
+    label, cohort_label = np.asarray(label), np.asarray(cohort_label)
+    S = int(label.max()) + 1 if S is None else S
+    Sc = int(cohort_label.max()) + 1
+    C = len(cohort)
+    none_q, none_c = np.full(len(q), -1), np.full(C, -1)
+    if tables is not None:
+        kind = 0
+        ctab = tables if cohort_tables is None else cohort_tables
+        sq = _plda.trial_scores_plda_numpy(cohort, cohort_label, q, none_q, ctab, False, Sc)[0]
+        sm = _plda.trial_scores_plda_numpy(emb, label, cohort, none_c, tables, False, S)[0]
+    else:
+        kind = _kind(kind)
+        sq = trial_scores_numpy(cohort, cohort_label, q, none_q, kind, False, Sc)[0]
+        sm = trial_scores_numpy(emb, label, cohort, none_c, kind, False, S)[0]
+    Kq = Sc if top_k is None else min(int(top_k), Sc)
+    Ks = C if top_k is None else min(int(top_k), C)
+    out = {}
+    for name, sc, K in (("q", sq.astype(np.float32), Kq), ("s", sm.astype(np.float32).T, Ks)):
+        st = V.cohort_stats_numpy(sc, K)
+        out.update({k + "_" + name: st[k] for k in ("mu", "sigma", "rsig", "count")})
+    if leave_one_out:
+        sums, msum, count = speaker_sums_numpy(emb, label, S, kind)
+        vs, vm, vc = loo_sums_numpy(q, q_label, sums, msum, count, kind)
+        st = V.cohort_stats_numpy(_scores_from_sums(cohort, vs, vm, vc, kind, tables).T, Ks)
+        out.update({k + "_own": st[k] for k in ("mu", "sigma", "rsig", "count")})
+    else:
+        out.update({k + "_own": None for k in ("mu", "sigma", "rsig", "count")})
+    return out
+
+
+def normalise_trials_numpy(scores, q_label, mu_q, rsig_q, mu_s, rsig_s, mu_own=None, rsig_own=None) -> np.ndarray:
+    """The normalised trial scores of ``vm_speaker_trial_hist_norm`` in fp32 from an (M, S) fp32 score matrix: a = s - mu_q[m];
+    b = s - mu_M; 0.5 (a rsig_q[m] + b rsig_M), each operation rounded on its own; (mu_M, rsig_M) is the own pair in the own-speaker
+    cell when ``mu_own`` / ``rsig_own`` are given (leave-one-out), the model's everywhere else."""
+    s = np.asarray(scores, dtype=np.float32)
+    M, S = s.shape
+    f = lambda x: np.asarray(x, dtype=np.float32)
+    mM, rM = np.broadcast_to(f(mu_s)[None, :], (M, S)).copy(), np.broadcast_to(f(rsig_s)[None, :], (M, S)).copy()
+    if mu_own is not None:
+        ql = np.asarray(q_label)
+        rows = np.flatnonzero((ql >= 0) & (ql < S))
+        mM[rows, ql[rows]] = f(mu_own)[rows]
+        rM[rows, ql[rows]] = f(rsig_own)[rows]
+    with np.errstate(invalid="ignore", over="ignore"):
+        a = s - f(mu_q)[:, None]
+        b = s - mM
+        return np.float32(0.5) * (a * f(rsig_q)[:, None] + b * rM)
 
 
 # ---- the entry points on device tensors --------------------------------------------------------------------------------------------
@@ -273,6 +401,87 @@ def plda_speaker_trial_hist(q: torch.Tensor, q_label: torch.Tensor, sums, count,
     return hist
 
 
+def speaker_loo_sums(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``vm_speaker_loo_sums``: the virtual models (sums (M, E) / msum (M) float64, count (M) int32) of the rows ``q``."""
+    lib = _lib.lib()
+    kind = _kind(kind)
+    q = q.contiguous()
+    dev = q.device
+    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
+    M, E = q.shape
+    vs = torch.zeros(M, E, dtype=torch.float64, device=dev)
+    vm = torch.zeros(M, dtype=torch.float64, device=dev)
+    vc = torch.zeros(M, dtype=torch.int32, device=dev)
+    if M > 0:
+        ws = lib.workspace("vm_speaker_loo_sums_workspace_bytes", M, E, device=dev)
+        lib.call("vm_speaker_loo_sums", q.data_ptr(), q_label.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(),
+                 int(count.shape[0]), kind, vs.data_ptr(), vm.data_ptr(), vc.data_ptr(), ws.data_ptr(),
+                 torch.cuda.current_stream(dev).cuda_stream)
+    return vs, vm, vc
+
+
+def speaker_cohort_stats(q: torch.Tensor, sums, msum, count, kind, side: int, K: int, tables=None,
+                         return_topk: bool = False) -> Dict[str, torch.Tensor]:
+    """``vm_speaker_cohort_stats`` (``tables``: ``vm_plda_speaker_cohort_stats``): ``mu``, ``sigma``, ``rsig`` (fp32), ``count`` (int32)
+    and, with ``return_topk``, ``topk_idx`` (lines, K) of the scores of the rows ``q`` against the models -- per row over the models
+    (``side`` 0) or per model over the rows (``side`` 1)."""
+    lib = _lib.lib()
+    q = q.contiguous()
+    dev = q.device
+    M, E = q.shape
+    S = int(count.shape[0])
+    n = S if side == 1 else M
+    out = {k: torch.full((n,), float("nan"), dtype=torch.float32, device=dev) for k in ("mu", "sigma", "rsig")}
+    out["count"] = torch.zeros(n, dtype=torch.int32, device=dev)
+    if return_topk:
+        out["topk_idx"] = torch.full((n, K), -1, dtype=torch.int32, device=dev)
+    tail = (side, K, out["mu"].data_ptr(), out["sigma"].data_ptr(), out["rsig"].data_ptr(), out["count"].data_ptr(),
+            out["topk_idx"].data_ptr() if return_topk else None)
+    if tables is None:
+        ws = lib.workspace("vm_speaker_cohort_stats_workspace_bytes", M, E, S, side, device=dev)
+        lib.call("vm_speaker_cohort_stats", q.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(), S, _kind(kind), *tail,
+                 ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    else:
+        D, n_max = int(tables["G"].shape[0]), int(tables["C"].shape[0]) - 1
+        if int(sums.shape[1]) != E:
+            raise ValueError("the sums are %d wide and the rows %d" % (int(sums.shape[1]), E))
+        ws = lib.workspace("vm_plda_speaker_cohort_stats_workspace_bytes", M, D, S, side, device=dev)
+        lib.call("vm_plda_speaker_cohort_stats", q.data_ptr(), M, E, D, sums.data_ptr(), count.data_ptr(), S, tables["A"].data_ptr(),
+                 tables["beta"].data_ptr(), tables["C"].data_ptr(), tables["G"].data_ptr(), n_max, *tail, ws.data_ptr(),
+                 torch.cuda.current_stream(dev).cuda_stream)
+    return out
+
+
+def speaker_trial_hist_norm(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind, leave_one_out: bool,
+                            windows: Sequence[Tuple[int, int]], bins: int, stats: Sequence[Optional[torch.Tensor]], tables=None,
+                            hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``vm_speaker_trial_hist_norm`` (``tables``: ``vm_plda_speaker_trial_hist_norm``): ``speaker_trial_hist`` on the normalised scores.
+    ``stats``: (mu_q, rsig_q (M), mu_s, rsig_s (S), mu_own, rsig_own (M) or None, None), fp32 on the device."""
+    lib = _lib.lib()
+    V.check_windows(windows, bins)
+    q = q.contiguous()
+    dev = q.device
+    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
+    M, E = q.shape
+    S = int(count.shape[0])
+    if hist is None:
+        hist = torch.zeros(len(windows), 2, bins + 3, dtype=torch.int64, device=dev)
+    if M > 0:
+        stats = [None if t is None else t.to(device=dev, dtype=torch.float32).contiguous() for t in stats]
+        for t, n in zip(stats, (M, M, S, S, M, M)):
+            if t is not None and int(t.numel()) != n:
+                raise ValueError("a statistics array holds %d entries, not %d" % (int(t.numel()), n))
+        win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
+        tail = (win.ctypes.data, len(windows), bins) + tuple(None if t is None else t.data_ptr() for t in stats) + (hist.data_ptr(),)
+        if tables is None:
+            ws = lib.workspace("vm_speaker_trial_hist_norm_workspace_bytes", M, E, S, device=dev)
+            lib.call("vm_speaker_trial_hist_norm", q.data_ptr(), q_label.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(),
+                     S, _kind(kind), 1 if leave_one_out else 0, *tail, ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            _plda_call("vm_plda_speaker_trial_hist_norm", q, q_label, sums, count, tables, leave_one_out, *tail)
+    return hist
+
+
 # ---- speaker models of an EmbeddingCache -------------------------------------------------------------------------------------------
 class SpeakerModels:
     """The enrolled speakers of a cache: ``sums`` (S, E) / ``msum`` (S) float64 and ``count`` (S) int32 on the device, the ``distance``
@@ -372,7 +581,8 @@ def identify(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None,
     speaker or without a model of it), and of this rank's rows (``rows`` = [lo, hi) of the queries; ``query_index``: their rows in the
     cache) ``rank``, ``pred`` (the best speaker's code; the own code's dtype, -1 / "" where there is no trial) and ``true_score``.
     ``leave_one_out`` defaults to "the cache is the one that was enrolled and per_speaker is None".  With ``per_speaker`` models and
-    the enrolled cache, the queries are the rows that were not enrolled."""
+    the enrolled cache, the queries are the rows that were not enrolled.  The ranking is by the raw score: ranking by the normalised
+    score of ``model_score_norm`` is out of scope."""
     q, q_label, loo, (lo, hi), n_q, idx = _shard(models, cache, leave_one_out, rows)
     if models.tables is not None:
         out = plda_speaker_identify(q, q_label, models.sums, models.count, models.tables, loo)
@@ -403,11 +613,34 @@ def _prototypes(models: SpeakerModels) -> torch.Tensor:
     return p
 
 
-def _pass1(models: SpeakerModels, q: torch.Tensor, n_sample: int = 1 << 16) -> Tuple[int, int]:
+class _Side:
+    """One side's (mu, rsig) as ``verification.norm_bounds`` reads them."""
+
+    def __init__(self, mu, rsig):
+        self.mu, self.rsig = mu, rsig
+
+
+def _normalised_sample(stats, lo, hi, sc=None, i=None, s=None):
+    """A pass-1 sample (bounds lo / hi, float64 scores ``sc`` of the (row i, model s) pairs) after normalisation with ``stats`` (the six
+    arrays of ``speaker_trial_hist_norm``, the per-row ones of the rows sampled from; None: as it is).  The sample is normalised in
+    float64; each half (s - mu) rsig lies within ``verification.norm_bounds`` of its side (the own statistics count as the model
+    side's), and s' is the mean of the two halves.  Only the window's place depends on any of it."""
+    if stats is None:
+        return lo, hi, sc
+    mq, rq, ms, rs, mo, ro = stats
+    l1, h1 = V.norm_bounds(_Side(mq, rq), lo, hi)
+    l2, h2 = V.norm_bounds(_Side(ms if mo is None else torch.cat([ms, mo]), rs if ro is None else torch.cat([rs, ro])), lo, hi)
+    if sc is not None:
+        sc = 0.5 * ((sc - mq.double()[i]) * rq.double()[i] + (sc - ms.double()[s]) * rs.double()[s])
+    return 0.5 * (l1 + l2), 0.5 * (h1 + h2), sc
+
+
+def _pass1(models: SpeakerModels, q: torch.Tensor, n_sample: int = 1 << 16, stats=None) -> Tuple[int, int]:
     """``verification.place_window`` for the model trials of rank 0's rows ``q``: bounds from the largest row and model norms, and a
-    seeded sample of (row, model) pairs, those of a speaker without a model left out."""
+    seeded sample of (row, model) pairs, those of a speaker without a model left out.  ``stats``: the window of the normalised scores
+    (``_normalised_sample``)."""
     if models.tables is not None:
-        return _pass1_plda(models, q, n_sample)
+        return _pass1_plda(models, q, n_sample, stats)
     kind = _kind(models.distance)
 
     def sample():
@@ -423,15 +656,16 @@ def _pass1(models: SpeakerModels, q: torch.Tensor, n_sample: int = 1 << 16) -> T
         else:
             lo, hi = -pr * qr * 1.001 - 1e-30, pr * qr * 1.001 + 1e-30
         if q.shape[0] < 1 or not bool(ok.any()):
-            return lo, hi, None
+            return _normalised_sample(stats, lo, hi)
         g = torch.Generator().manual_seed(0)
         i = torch.randint(0, q.shape[0], (n_sample,), generator=g).to(q.device)
         s = torch.randint(0, models.S, (n_sample,), generator=g).to(q.device)
-        return lo, hi, V.sample_scores(q[i], P[s], kind).masked_fill(~ok[s], float("nan"))   # no model: no trial, dropped as not finite
+        sc = V.sample_scores(q[i], P[s], kind).masked_fill(~ok[s], float("nan"))   # no model: no trial, dropped as not finite
+        return _normalised_sample(stats, lo, hi, sc, i, s)
     return V.place_window(sample)
 
 
-def _pass1_plda(models: SpeakerModels, q: torch.Tensor, n_sample: int) -> Tuple[int, int]:
+def _pass1_plda(models: SpeakerModels, q: torch.Tensor, n_sample: int, stats=None) -> Tuple[int, int]:
     """``_pass1`` for multi-session PLDA models: the shared models' operands in torch float64 (mu = beta[n] Sigma, A[n], C[n]), bounds
     from the largest terms -- the score is sum A (w - mu)^2 - g - C with g = sum G w^2 >= 0 -- and a seeded sample of (row, model)
     pairs.  Only the window's place depends on any of it."""
@@ -451,40 +685,136 @@ def _pass1_plda(models: SpeakerModels, q: torch.Tensor, n_sample: int) -> Tuple[
         lo = -(gm + cm) * 1.001 - 1e-30
         hi = (fin(float(A.max().item())) * (qr + mr) ** 2 + gm + cm) * 1.001 + 1e-30
         if q.shape[0] < 1 or not bool(ok.any()):
-            return lo, hi, None
+            return _normalised_sample(stats, lo, hi)
         gen = torch.Generator().manual_seed(0)
         i = torch.randint(0, q.shape[0], (n_sample,), generator=gen).to(q.device)
         s = torch.randint(0, models.S, (n_sample,), generator=gen).to(q.device)
         d = w[i] - mu[s]
         sc = ((A[s] * d * d).sum(1) - g[i]) - C[s]
-        return lo, hi, sc.masked_fill(~ok[s], float("nan"))   # no model: no trial, dropped as not finite
+        return _normalised_sample(stats, lo, hi, sc.masked_fill(~ok[s], float("nan")), i, s)   # no model: no trial, dropped as not finite
     return V.place_window(sample)
 
 
-def _hist_source(models, cache, leave_one_out):
-    q, q_label, loo, _, _, _ = _shard(models, cache, leave_one_out, None)
+class ModelScoreNorm:
+    """The statistics of ``model_score_norm``: ``mu_q`` / ``rsig_q`` (and ``sigma_q``, ``count_q``) per query row, ``mu_s`` / ``rsig_s``
+    (``sigma_s``, ``count_s``) per enrolled model, ``mu_own`` / ``rsig_own`` (``sigma_own``, ``count_own``) per query row under
+    leave-one-out (else None) -- fp32 / int32 on the device, every rank holding all of them -- with ``top_k`` (None: S-norm), the
+    cohort's sizes ``cohort_rows`` and ``cohort_models``, the ``distance`` of the models and the ``leave_one_out`` flag they were
+    computed for."""
+
+    def __init__(self, stats, top_k, cohort_rows, cohort_models, distance, leave_one_out):
+        for side in ("q", "s", "own"):
+            for k in ("mu", "sigma", "rsig", "count"):
+                setattr(self, k + "_" + side, stats.get(k + "_" + side))
+        self.top_k, self.cohort_rows, self.cohort_models = top_k, cohort_rows, cohort_models
+        self.distance, self.leave_one_out = distance, leave_one_out
+
+    @property
+    def n_queries(self) -> int:
+        return int(self.mu_q.shape[0])
+
+    @property
+    def S(self) -> int:
+        return int(self.mu_s.shape[0])
+
+    def stats(self, lo: int = 0, hi: Optional[int] = None):
+        """The six arrays of ``speaker_trial_hist_norm`` for the query rows [lo, hi)."""
+        cut = lambda t: None if t is None else t[lo:hi].contiguous()
+        return (cut(self.mu_q), cut(self.rsig_q), self.mu_s, self.rsig_s, cut(self.mu_own), cut(self.rsig_own))
+
+
+LOO_CHUNK_BYTES = 64 << 20   # the float64 sums of the virtual models of one chunk of rows
+
+
+def model_score_norm(models: SpeakerModels, cache, cohort, top_k: Optional[int] = 300, leave_one_out: Optional[bool] = None) -> ModelScoreNorm:
+    """The S-norm (``top_k=None``: the whole cohort) or AS-norm (the ``top_k`` most alike, per side ``min(top_k, size)``) statistics of
+    the model trials of ``cache`` against ``models`` (module docstring).  ``cohort``: an ``EmbeddingCache`` that is neither ``cache`` nor
+    ``models.cache`` (for PLDA models: projected by the same model).  Queries and ``leave_one_out`` resolve as in ``identify``.  Under
+    torchrun the per-row statistics are computed on each rank's ``parallel.shard_range`` and all-gathered; the per-model ones on every
+    rank.  The virtual models of the own side are formed ``LOO_CHUNK_BYTES`` of float64 sums at a time."""
+    if cohort is cache or cohort is models.cache or not hasattr(cohort, "emb"):
+        raise ValueError("the cohort must be an EmbeddingCache of its own: neither the query cache nor the enrolled one")
+    if top_k is not None and top_k < 1:
+        raise ValueError("top_k must be >= 1 (or None for S-norm)")
+    if cohort.emb.dim() != 2 or cohort.n < 1 or int(cohort.emb.shape[1]) != int(models.sums.shape[1]):
+        raise ValueError("the cohort must be a non-empty cache of rows %d wide" % int(models.sums.shape[1]))
+    plda_on = models.tables is not None
+    cm = enrol(cohort, plda=models.plda) if plda_on else enrol(cohort, distance=models.distance)
+    kind = _lib.VM_DIST_EUCLIDEAN if plda_on else _kind(models.distance)
+    q, q_label, loo, (lo, hi), n_q, _ = _shard(models, cache, leave_one_out, None)
+    ce = cohort.emb.to(device=q.device, dtype=torch.float32).contiguous()
+    C, Sc = int(ce.shape[0]), cm.S
+    Kq = Sc if top_k is None else min(int(top_k), Sc)
+    Ks = C if top_k is None else min(int(top_k), C)
+    names = ("mu", "sigma", "rsig", "count")
+    sq = speaker_cohort_stats(q, cm.sums, cm.msum, cm.count, kind, 0, Kq, tables=cm.tables)
+    ss = speaker_cohort_stats(ce, models.sums, models.msum, models.count, kind, 1, Ks, tables=models.tables)
+    rows = [sq[k] for k in names]
+    if loo:
+        M, E = q.shape
+        own = {k: torch.full((M,), float("nan"), dtype=torch.float32, device=q.device) for k in names[:3]}
+        own["count"] = torch.zeros(M, dtype=torch.int32, device=q.device)
+        step = max(1, LOO_CHUNK_BYTES // (8 * int(E)))
+        for r0 in range(0, M, step):
+            vs, vm, vc = speaker_loo_sums(q[r0:r0 + step], q_label[r0:r0 + step], models.sums, models.msum, models.count, kind)
+            so = speaker_cohort_stats(ce, vs, vm, vc, kind, 1, Ks, tables=models.tables)
+            for k in names:
+                own[k][r0:r0 + step] = so[k]
+        rows += [own[k] for k in names]
+    if parallel.rank_world()[1] > 1:
+        allr = parallel.all_gather_rows(torch.stack([t.double() for t in rows], 1), n_q)
+        rows = [allr[:, k].to(torch.int32 if k % 4 == 3 else torch.float32).contiguous() for k in range(len(rows))]
+    stats = {k + "_q": t for k, t in zip(names, rows[:4])}
+    stats.update({k + "_s": ss[k] for k in names})
+    stats.update({k + "_own": t for k, t in zip(names, rows[4:])} if loo else {})
+    return ModelScoreNorm(stats, top_k, C, Sc, models.distance, loo)
+
+
+def check_model_norm(models, n_q: int, loo: bool, norm: Optional[ModelScoreNorm]):
+    """``verification.check_norm`` for model trials: the statistics must have been computed for these models, queries and leave-one-out."""
+    if norm is None:
+        return
+    if norm.distance != models.distance:
+        raise ValueError("the ModelScoreNorm was computed for %r models, not %r" % (norm.distance, models.distance))
+    if norm.S != models.S or norm.n_queries != n_q:
+        raise ValueError("the ModelScoreNorm holds %d models and %d query rows, the trials %d and %d" % (norm.S, norm.n_queries, models.S, n_q))
+    if bool(norm.leave_one_out) != bool(loo):
+        raise ValueError("the ModelScoreNorm was computed with leave_one_out=%r, the trials have %r" % (norm.leave_one_out, loo))
+
+
+def _hist_source(models, cache, leave_one_out, norm=None):
+    q, q_label, loo, (lo, hi), n_q, _ = _shard(models, cache, leave_one_out, None)
+    check_model_norm(models, n_q, loo, norm)
+    stats = None if norm is None else norm.stats(lo, hi)
 
     def hist_fn(windows, bins):
-        if models.tables is not None:
+        if norm is not None:
+            h = speaker_trial_hist_norm(q, q_label, models.sums, models.msum, models.count, _lib.VM_DIST_EUCLIDEAN if models.tables is not None
+                                        else models.distance, loo, windows, bins, stats, tables=models.tables)
+        elif models.tables is not None:
             h = plda_speaker_trial_hist(q, q_label, models.sums, models.count, models.tables, loo, windows, bins)
         else:
             h = speaker_trial_hist(q, q_label, models.sums, models.msum, models.count, models.distance, loo, windows, bins)
         return parallel.sum_ranks(h).cpu().numpy()
-    return hist_fn, q
+    return hist_fn, q, stats
 
 
-def model_trial_metrics(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None, dcf_points=()) -> Dict:
+def model_trial_metrics(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None, dcf_points=(),
+                        norm: Optional[ModelScoreNorm] = None) -> Dict:
     """Exact verification metrics of the trials (row of ``cache``, speaker model): the dict of ``verification.exact_sweep`` (``eer``,
     ``eer_threshold``, ``best_balanced_accuracy``, ``best_threshold``, FAR / FRR at both, ``auc``, ``roc``, ``n_target``,
     ``n_nontarget``, ``n_nan``, ``passes``).  A trial is a target iff the model is the row's own speaker; queries and
     ``leave_one_out`` as in ``identify``.  ``dcf_points``: detection-cost points (P_target, C_miss, C_fa), adding ``dcf`` as in
-    ``verification.exact_sweep``."""
-    hist_fn, q = _hist_source(models, cache, leave_one_out)
-    return V.exact_sweep(hist_fn, _pass1(models, q), dcf_points=dcf_points)
+    ``verification.exact_sweep``.  ``norm`` (``model_score_norm`` of the same models, cache and leave-one-out): the metrics of the
+    normalised scores; the thresholds are then in normalised units."""
+    hist_fn, q, stats = _hist_source(models, cache, leave_one_out, norm)
+    return V.exact_sweep(hist_fn, _pass1(models, q, stats=stats), dcf_points=dcf_points)
 
 
-def model_trial_accuracy_at_threshold(models: SpeakerModels, cache, t: float, leave_one_out: Optional[bool] = None) -> Dict:
-    """Balanced accuracy, FAR and FRR of the model trials at a fixed threshold t (accept iff score < t): one pass with key_lo = key(t),
-    whose under slot is exactly {s < t} -- a threshold found on a validation set applied to a test set."""
-    hist_fn, _ = _hist_source(models, cache, leave_one_out)
+def model_trial_accuracy_at_threshold(models: SpeakerModels, cache, t: float, leave_one_out: Optional[bool] = None,
+                                      norm: Optional[ModelScoreNorm] = None) -> Dict:
+    """Balanced accuracy, FAR and FRR of the model trials at a fixed threshold t (accept iff score < t; with ``norm`` in normalised
+    units): one pass with key_lo = key(t), whose under slot is exactly {s < t} -- a threshold found on a validation set applied to a
+    test set."""
+    hist_fn, _, _ = _hist_source(models, cache, leave_one_out, norm)
     return V.counts_at_threshold(hist_fn, t)
