@@ -66,14 +66,16 @@ def _lattice(sizes, E, seed, twins=True):
     return emb[p], label[p].astype(np.int32)
 
 
-@pytest.mark.parametrize("E", [64, 50])
+@pytest.mark.parametrize("E", [1, 3, 4, 31, 32, 33, 50, 64, 65, 100, 255, 256])
 def test_exact_case_equals_the_twin_bit_for_bit(E):
     """Every mean is dyadic (divisors 1, 2, 4, 8), so every squared distance is exact in float64 in any order, with or without fma, and
     the square root is correctly rounded: scores, true_score, rank, best_idx and best_val are the twin's bits.  Without leave-one-out the
     sizes are 1, 2, 4, 8; with it 2, 3, 5, 9 for the OWN speaker's model (divisors 1, 2, 4, 8) -- the other speakers' models then
     divide by 3, 5 and 9, which is not dyadic, so under leave-one-out the whole matrix is compared on a corpus of two-file speakers
     (divisors 1 and 2) and on the 2, 3, 5, 9 corpus the bit-for-bit claim covers true_score and every cell whose divisor is a power of
-    two; its other cells are held to one fp32 ulp and its ranks to the order of the device's own matrix."""
+    two; its other cells are held to one fp32 ulp and its ranks to the order of the device's own matrix.  None of it depends on E: the
+    widths lie on both sides of the 4-wide vector load (1, 3, 4), of the 32-component stage (31, 32, 33) and of the later stages (64,
+    65, 100), up to EN_MAX_E (255, 256)."""
     sizes = [1, 2, 4, 8] * 6 + [4, 4]
     emb, label = _lattice(sizes, E, 1)
     S = len(sizes)
@@ -84,11 +86,14 @@ def test_exact_case_equals_the_twin_bit_for_bit(E):
     _assert_same_bits(got["scores"], sc.astype(np.float32), "scores")
     for k in ("true_score", "rank", "best_idx", "best_val"):
         _assert_same_bits(got[k], ref[k], k)
-    # the planted twins: a query of another speaker scores both alike and the lower index comes first
-    other = label < S - 2
-    assert np.array_equal(got["scores"][other, S - 2], got["scores"][other, S - 1])
-    assert not np.any(got["best_idx"] == S - 1)
-    assert np.all(got["rank"][label == S - 1] >= 1) and np.all(got["rank"][label == S - 2] == 0)   # an own row scores 0 against both
+    # the planted twins: a query of another speaker scores both alike and the lower index comes first.  Properties of this corpus only
+    # where the twin has them: from E = 32 on (checked with trial_scores_numpy / ranks_numpy); narrower random integer rows carry no
+    # speaker structure, and there the equality with the twin above is the whole claim.
+    if E >= 32:
+        other = label < S - 2
+        assert np.array_equal(got["scores"][other, S - 2], got["scores"][other, S - 1])
+        assert not np.any(got["best_idx"] == S - 1)
+        assert np.all(got["rank"][label == S - 1] >= 1) and np.all(got["rank"][label == S - 2] == 0)   # an own row scores 0 against both
 
     sizes = [2] * 30
     emb, label = _lattice(sizes, E, 2)
@@ -193,7 +198,7 @@ def _check_general(emb, label, q, q_label, kind, loo, S, scores_too=True):
 
 @pytest.mark.parametrize("loo", [True, False])
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("E", [64, 50])
+@pytest.mark.parametrize("E", [64, 50, 33, 100])
 def test_general_case_scores_within_one_ulp_and_ranks_within_the_interval(E, kind, loo):
     emb, label = _corpus(3000, 40, E, 10 + E)
     got, sc, trial = _check_general(emb, label, emb, label, kind, loo, 40)

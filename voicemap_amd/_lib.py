@@ -81,11 +81,14 @@ class VoicemapHipError(RuntimeError):
 
 
 class _Lib:
-    def __init__(self):
-        if not os.path.exists(LIB_PATH):
-            from . import build as _build
-            _build.build(verbose=False)  # raises if hipcc is missing too
-        self.cdll = ctypes.CDLL(LIB_PATH)
+    def __init__(self, path=None):
+        if path is None:
+            path = LIB_PATH
+            if not os.path.exists(path):
+                from . import build as _build
+                _build.build(verbose=False)  # raises if hipcc is missing too
+        self.path = path
+        self.cdll = ctypes.CDLL(path)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(self.cdll, name)  # AttributeError if the symbol is not exported
             fn.restype = res
@@ -95,7 +98,7 @@ class _Lib:
         self.abi = self.cdll.vm_abi_version()
         if self.abi != ABI_VERSION:  # a stale prebuilt library: its entry points take different arguments
             raise VoicemapHipError("%s reports ABI %d, this package binds ABI %d -- rebuild it (python -m voicemap_amd.build --force)"
-                                   % (LIB_PATH, self.abi, ABI_VERSION))
+                                   % (path, self.abi, ABI_VERSION))
         # experiments: kernel-selection knobs for a whole process (a pytest run under another knob value): VOICEMAP_TUNE="key=value,..."
         for kv in [t for t in os.environ.get("VOICEMAP_TUNE", "").split(",") if t.strip()]:
             k, v = kv.split("=")
@@ -145,3 +148,15 @@ def lib():
     if _LIB is None:
         _LIB = _Lib()
     return _LIB
+
+
+def load(path):
+    """Another build of the library (A/B tools: the parent commit's), bound from this tree's header like the package's own."""
+    return _Lib(path)
+
+
+def use(other):
+    """Make ``lib()`` -- and with it every wrapper of the package -- return ``other`` (``load``'s or ``lib()``'s); returns the one before."""
+    global _LIB
+    before, _LIB = lib(), other
+    return before

@@ -11,9 +11,10 @@
 //    cohort.hip's radix select runs down the rows of the tile (side 0: a chunk of rows x all models) or down its COLUMNS (side 1: all
 //    rows x a chunk of models; the keys are staged with a strided read, so no second, transposed tile exists).  The tile cap is
 //    cohort.hip's.  No float atomics: bit-identical from run to run.
-//  * vm_[plda_]speaker_trial_hist_norm: the trial histograms on s' = 0.5f ((s - mu_q[m]) rsig_q[m] + (s - mu_M) rsig_M) -- the NORM
-//    instantiation of the tile kernels of enrol.hip / plda_enrol.hip (en_trial_hist / pe_trial_hist, enrol_tile.hpp), so trials,
-//    classes, windows, slots and the raw score are the plain histograms' by construction.
+//  * vm_[plda_]speaker_trial_hist_norm -- the trial histograms on s' = 0.5f ((s - mu_q[m]) rsig_q[m] + (s - mu_M) rsig_M) -- are not
+//    here: they are the NORM instantiation of the one tile kernel and one histogram launcher of enrol_tile.hpp and stand next to their
+//    plain forms in enrol.hip / plda_enrol.hip, so trials, classes, windows, slots and the raw score are the plain histograms' by
+//    construction.
 #include "enrol_tile.hpp"
 
 namespace vm {
@@ -88,14 +89,6 @@ static int mn_stats(const char* what, int64_t M, int64_t S, int side, int64_t K,
         launch_cohort_select(tile, n, p.entries, K, l0, side ? n : 0, mu, sigma, rsig, cnt, topk_idx, list, st);
         if (const int rc2 = check_launch(what)) return rc2;
     }
-    return 0;
-}
-
-static int mn_check_norm(const char* what, const EnNorm& n, int leave_one_out) {
-    VM_REQUIRE(n.mu_q && n.rsig_q && n.mu_s && n.rsig_s, "%s: null pointer", what);
-    VM_REQUIRE((n.mu_own == nullptr) == (n.rsig_own == nullptr), "%s: mu_own and rsig_own go together", what);
-    VM_REQUIRE(leave_one_out != 0 || n.mu_own == nullptr, "%s: mu_own / rsig_own must be NULL without leave_one_out", what);
-    VM_REQUIRE(leave_one_out == 0 || n.mu_own != nullptr, "%s: leave_one_out needs mu_own / rsig_own", what);
     return 0;
 }
 
@@ -182,36 +175,4 @@ extern "C" int vm_plda_speaker_cohort_stats(const float* q, int64_t M, int P, in
                         return vm_plda_speaker_identify(q + r0 * P, lab, nr, P, D, sums + s0 * P, count + s0, ns, A, beta, C, G, n_max, 0, tile,
                                                         u0, u1, u2, u3, inner, stream);
                     });
-}
-
-extern "C" int64_t vm_speaker_trial_hist_norm_workspace_bytes(int64_t M, int E, int64_t S) {
-    return vm_speaker_trial_hist_workspace_bytes(M, E, S);
-}
-
-extern "C" int vm_speaker_trial_hist_norm(const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
-                                          const int32_t* count, int64_t S, int kind, int leave_one_out, const int64_t* host_windows,
-                                          int n_windows, int bins, const float* mu_q, const float* rsig_q, const float* mu_s,
-                                          const float* rsig_s, const float* mu_own, const float* rsig_own, uint64_t* hist, void* ws,
-                                          void* stream) {
-    const char* what = "vm_speaker_trial_hist_norm";
-    const vm::EnNorm n{mu_q, rsig_q, mu_s, rsig_s, mu_own, rsig_own};
-    if (int rc = vm::mn_check_norm(what, n, leave_one_out)) return rc;
-    return vm::en_trial_hist(what, q, q_label, M, E, sums, msum, count, S, kind, leave_one_out, host_windows, n_windows, bins, hist, &n, ws,
-                             stream);
-}
-
-extern "C" int64_t vm_plda_speaker_trial_hist_norm_workspace_bytes(int64_t M, int D, int64_t S) {
-    return vm_plda_speaker_trial_hist_workspace_bytes(M, D, S);
-}
-
-extern "C" int vm_plda_speaker_trial_hist_norm(const float* q, const int32_t* q_label, int64_t M, int P, int D, const double* sums,
-                                               const int32_t* count, int64_t S, const double* A, const double* beta, const double* C,
-                                               const double* G, int n_max, int leave_one_out, const int64_t* host_windows, int n_windows,
-                                               int bins, const float* mu_q, const float* rsig_q, const float* mu_s, const float* rsig_s,
-                                               const float* mu_own, const float* rsig_own, uint64_t* hist, void* ws, void* stream) {
-    const char* what = "vm_plda_speaker_trial_hist_norm";
-    const vm::EnNorm n{mu_q, rsig_q, mu_s, rsig_s, mu_own, rsig_own};
-    if (int rc = vm::mn_check_norm(what, n, leave_one_out)) return rc;
-    return vm::pe_trial_hist(what, q, q_label, M, P, D, sums, count, S, A, beta, C, G, n_max, leave_one_out, host_windows, n_windows, bins,
-                             hist, &n, ws, stream);
 }

@@ -105,6 +105,22 @@ def speaker_sums_numpy(emb, label, S: int, kind) -> Tuple[np.ndarray, np.ndarray
     return sums, msum, count
 
 
+def _models(sg, ms, n, kind: int) -> np.ndarray:
+    """The models of the definition, float64 (S, E), from their sums ``sg`` (S, E), ``ms`` (S) and float64 row numbers ``n`` (S); a row
+    means nothing where ``n`` is 0."""
+    p = sg / n[:, None]
+    return (ms / n)[:, None] * p if kind == 2 else p
+
+
+def _row_scores(qm, qmag, p, kind: int) -> np.ndarray:
+    """The geometric score of the definition, float64 (S): one query row ``qm`` of magnitude ``qmag`` against the models ``p``."""
+    if kind == 0:
+        return np.sqrt(((qm[None, :] - p) ** 2).sum(axis=1))
+    if kind == 1:
+        return 1.0 - (p @ qm) / (qmag * np.sqrt((p * p).sum(axis=1)))
+    return -(p @ qm)
+
+
 def trial_scores_numpy(emb, label, q, q_label, kind, leave_one_out: bool, S: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
     """(scores (M, S) float64, trial (M, S) bool): the score of every query row against every speaker model of the enrolled rows
     ``emb`` / ``label``; where ``trial`` is False there is no model (the score there is NaN and means nothing)."""
@@ -130,16 +146,7 @@ def trial_scores_numpy(emb, label, q, q_label, kind, leave_one_out: bool, S: Opt
                 ms[own] -= qmag[m]
             ok = n > 0
             trial[m] = ok
-            p = sg / n[:, None]
-            if kind == 2:
-                p = (ms / n)[:, None] * p
-            if kind == 0:
-                sc = np.sqrt(((q[m][None, :] - p) ** 2).sum(axis=1))
-            elif kind == 1:
-                sc = 1.0 - (p @ q[m]) / (qmag[m] * np.sqrt((p * p).sum(axis=1)))
-            else:
-                sc = -(p @ q[m])
-            out[m, ok] = sc[ok]
+            out[m, ok] = _row_scores(q[m], qmag[m], _models(sg, ms, n, kind), kind)[ok]
     return out, trial
 
 
@@ -208,20 +215,11 @@ def _scores_from_sums(q, sums, msum, count, kind: int, tables=None) -> np.ndarra
                 out[m, ok] = ((((A[nn] * t) * t).sum(1) - (G * (w[m] * w[m])).sum()) - C[nn])[ok]
             return out.astype(np.float32)
         ok = count > 0
-        n = count.astype(np.float64)
-        p = np.asarray(sums) / n[:, None]
-        if kind == 2:
-            p = (np.asarray(msum) / n)[:, None] * p
         q = np.asarray(q, dtype=np.float64)
         qmag = np.sqrt((q * q).sum(axis=1))
+        p = _models(np.asarray(sums), np.asarray(msum), count.astype(np.float64), kind)
         for m in range(len(q)):
-            if kind == 0:
-                sc = np.sqrt(((q[m][None, :] - p) ** 2).sum(axis=1))
-            elif kind == 1:
-                sc = 1.0 - (p @ q[m]) / (qmag[m] * np.sqrt((p * p).sum(axis=1)))
-            else:
-                sc = -(p @ q[m])
-            out[m, ok] = sc[ok]
+            out[m, ok] = _row_scores(q[m], qmag[m], p, kind)[ok]
     return out.astype(np.float32)
 
 
@@ -300,114 +298,125 @@ def speaker_sums(emb: torch.Tensor, label: torch.Tensor, S: int, kind) -> Tuple[
     return sums, msum, count
 
 
-def speaker_identify(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind, leave_one_out: bool,
-                     return_scores: bool = False) -> Dict[str, torch.Tensor]:
-    """``vm_speaker_identify``: ``true_score``, ``rank``, ``best_val``, ``best_idx`` (M) and, with ``return_scores``, ``scores`` (M, S)
-    (NaN where there is no trial)."""
-    lib = _lib.lib()
-    kind = _kind(kind)
+def plda_tables_to(tables, dev) -> Dict[str, torch.Tensor]:
+    """``PldaModel.model_tables``' dict as contiguous float64 tensors on ``dev``."""
+    return {k: torch.as_tensor(np.ascontiguousarray(np.asarray(tables[k], dtype=np.float64))).to(dev) for k in ("A", "beta", "C", "G")}
+
+
+def _binding(q, sums, msum, count, kind, tables):
+    """What the geometric entry points (``tables`` None) and the multi-session PLDA ones differ in: (the prefix of their names, the
+    model arguments that follow M, the (width, S) that follow M in their workspace queries)."""
+    E, S = int(q.shape[1]), int(count.shape[0])
+    if tables is None:
+        return "vm_speaker_", (E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(), S, _kind(kind)), (E, S)
+    D, n_max = int(tables["G"].shape[0]), int(tables["C"].shape[0]) - 1
+    if int(sums.shape[1]) != E:
+        raise ValueError("the sums are %d wide and the rows %d" % (int(sums.shape[1]), E))
+    return "vm_plda_speaker_", (E, D, sums.data_ptr(), count.data_ptr(), S) + tuple(tables[k].data_ptr() for k in ("A", "beta", "C", "G")) + (
+        n_max,), (D, S)
+
+
+def _call(binding, name, q, head, tail, ws_tail=()):
+    """``<prefix><name>(q, *head, M, <model arguments>, *tail, workspace, stream)``."""
+    prefix, model_args, dims = binding
+    lib, dev, M = _lib.lib(), q.device, int(q.shape[0])
+    ws = lib.workspace(prefix + name + "_workspace_bytes", M, *dims, *ws_tail, device=dev)
+    lib.call(prefix + name, q.data_ptr(), *head, M, *model_args, *tail, ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _rows_labels(q: torch.Tensor, q_label: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Contiguous rows and their int32 labels on the rows' device."""
     q = q.contiguous()
-    dev = q.device
-    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
-    M, E = q.shape
-    S = int(count.shape[0])
+    return q, q_label.to(device=q.device, dtype=torch.int32).contiguous()
+
+
+def _identify_outputs(M: int, S: int, dev, return_scores: bool) -> Dict[str, torch.Tensor]:
     out = {"true_score": torch.empty(M, dtype=torch.float32, device=dev), "rank": torch.empty(M, dtype=torch.int32, device=dev),
            "best_val": torch.empty(M, dtype=torch.float32, device=dev), "best_idx": torch.empty(M, dtype=torch.int32, device=dev)}
     if return_scores:
         out["scores"] = torch.empty(M, S, dtype=torch.float32, device=dev)
-    if M > 0:
-        ws = lib.workspace("vm_speaker_identify_workspace_bytes", M, E, S, device=dev)
-        lib.call("vm_speaker_identify", q.data_ptr(), q_label.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(), S, kind,
-                 1 if leave_one_out else 0, out["scores"].data_ptr() if return_scores else None, out["true_score"].data_ptr(),
-                 out["rank"].data_ptr(), out["best_val"].data_ptr(), out["best_idx"].data_ptr(), ws.data_ptr(),
-                 torch.cuda.current_stream(dev).cuda_stream)
     return out
 
 
-def speaker_trial_hist(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind, leave_one_out: bool,
-                       windows: Sequence[Tuple[int, int]], bins: int, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``vm_speaker_trial_hist``: (n_windows, 2, bins + 3) int64 counts on the device (class 0 = the own speaker's model), added to
-    ``hist`` if one is given."""
-    lib = _lib.lib()
-    kind = _kind(kind)
-    V.check_windows(windows, bins)
-    q = q.contiguous()
-    dev = q.device
-    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
-    M, E = q.shape
-    S = int(count.shape[0])
+def _hist_windows(windows, bins: int, hist: Optional[torch.Tensor], dev) -> Tuple[torch.Tensor, np.ndarray]:
+    """(the (n_windows, 2, bins + 3) int64 counts on ``dev`` -- ``hist`` if one is given --, the windows as the int64 array the entry
+    points read)."""
     if hist is None:
         hist = torch.zeros(len(windows), 2, bins + 3, dtype=torch.int64, device=dev)
+    return hist, np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
+
+
+def _identify(q, q_label, sums, msum, count, kind, tables, leave_one_out, return_scores=False) -> Dict[str, torch.Tensor]:
+    q, q_label = _rows_labels(q, q_label)
+    binding = _binding(q, sums, msum, count, kind, tables)
+    out = _identify_outputs(int(q.shape[0]), int(count.shape[0]), q.device, return_scores)
+    if q.shape[0] > 0:
+        _call(binding, "identify", q, (q_label.data_ptr(),), (1 if leave_one_out else 0, out["scores"].data_ptr() if return_scores else None)
+              + tuple(out[k].data_ptr() for k in ("true_score", "rank", "best_val", "best_idx")))
+    return out
+
+
+def _trial_hist(q, q_label, sums, msum, count, kind, tables, leave_one_out, windows, bins, stats=None, hist=None) -> torch.Tensor:
+    """The plain trial histogram (``stats`` None) or the normalised one of either back end."""
+    V.check_windows(windows, bins)   # refused before anything touches the device
+    q, q_label = _rows_labels(q, q_label)
+    binding = _binding(q, sums, msum, count, kind, tables)
+    hist, win = _hist_windows(windows, bins, hist, q.device)
+    M, S = int(q.shape[0]), int(count.shape[0])
     if M > 0:
-        win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
-        ws = lib.workspace("vm_speaker_trial_hist_workspace_bytes", M, E, S, device=dev)
-        lib.call("vm_speaker_trial_hist", q.data_ptr(), q_label.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(), S, kind,
-                 1 if leave_one_out else 0, win.ctypes.data, len(windows), bins, hist.data_ptr(), ws.data_ptr(),
-                 torch.cuda.current_stream(dev).cuda_stream)
+        ptrs = ()
+        if stats is not None:
+            stats = [None if t is None else t.to(device=q.device, dtype=torch.float32).contiguous() for t in stats]
+            for t, n in zip(stats, (M, M, S, S, M, M)):
+                if t is not None and int(t.numel()) != n:
+                    raise ValueError("a statistics array holds %d entries, not %d" % (int(t.numel()), n))
+            ptrs = tuple(None if t is None else t.data_ptr() for t in stats)
+        _call(binding, "trial_hist" if stats is None else "trial_hist_norm", q, (q_label.data_ptr(),),
+              (1 if leave_one_out else 0, win.ctypes.data, len(windows), bins) + ptrs + (hist.data_ptr(),))
     return hist
 
 
-def _plda_call(name, q, q_label, sums, count, tables, leave_one_out, *tail_args):
-    """One of the two vm_plda_speaker_* entry points on a (M, P) query block."""
-    lib = _lib.lib()
-    dev = q.device
-    M, P = q.shape
-    S, D, n_max = int(count.shape[0]), int(tables["G"].shape[0]), int(tables["C"].shape[0]) - 1
-    if int(sums.shape[1]) != P:
-        raise ValueError("the sums are %d wide and the rows %d" % (int(sums.shape[1]), P))
-    ws = lib.workspace(name + "_workspace_bytes", M, D, S, device=dev)
-    lib.call(name, q.data_ptr(), q_label.data_ptr(), M, P, D, sums.data_ptr(), count.data_ptr(), S, tables["A"].data_ptr(),
-             tables["beta"].data_ptr(), tables["C"].data_ptr(), tables["G"].data_ptr(), n_max, 1 if leave_one_out else 0, *tail_args,
-             ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-
-
-def plda_tables_to(tables, dev) -> Dict[str, torch.Tensor]:
-    """``PldaModel.model_tables``' dict as contiguous float64 tensors on ``dev``."""
-    return {k: torch.as_tensor(np.ascontiguousarray(np.asarray(tables[k], dtype=np.float64))).to(dev) for k in ("A", "beta", "C", "G")}
+def speaker_identify(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind, leave_one_out: bool,
+                     return_scores: bool = False) -> Dict[str, torch.Tensor]:
+    """``vm_speaker_identify``: ``true_score``, ``rank``, ``best_val``, ``best_idx`` (M) and, with ``return_scores``, ``scores`` (M, S)
+    (NaN where there is no trial)."""
+    return _identify(q, q_label, sums, msum, count, kind, None, leave_one_out, return_scores)
 
 
 def plda_speaker_identify(q: torch.Tensor, q_label: torch.Tensor, sums, count, tables, leave_one_out: bool,
                           return_scores: bool = False) -> Dict[str, torch.Tensor]:
     """``vm_plda_speaker_identify``: the outputs of ``speaker_identify`` for PLDA-space rows ``q`` (M, P) against the models of ``sums``
     (S, P) float64 / ``count`` (``speaker_sums`` of the enrolled PLDA-space rows, euclidean kind); ``tables``: ``plda_tables_to``'s."""
-    q = q.contiguous()
-    dev = q.device
-    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
-    M, S = int(q.shape[0]), int(count.shape[0])
-    out = {"true_score": torch.empty(M, dtype=torch.float32, device=dev), "rank": torch.empty(M, dtype=torch.int32, device=dev),
-           "best_val": torch.empty(M, dtype=torch.float32, device=dev), "best_idx": torch.empty(M, dtype=torch.int32, device=dev)}
-    if return_scores:
-        out["scores"] = torch.empty(M, S, dtype=torch.float32, device=dev)
-    if M > 0:
-        _plda_call("vm_plda_speaker_identify", q, q_label, sums, count, tables, leave_one_out,
-                   out["scores"].data_ptr() if return_scores else None, out["true_score"].data_ptr(), out["rank"].data_ptr(),
-                   out["best_val"].data_ptr(), out["best_idx"].data_ptr())
-    return out
+    return _identify(q, q_label, sums, None, count, None, tables, leave_one_out, return_scores)
+
+
+def speaker_trial_hist(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind, leave_one_out: bool,
+                       windows: Sequence[Tuple[int, int]], bins: int, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``vm_speaker_trial_hist``: (n_windows, 2, bins + 3) int64 counts on the device (class 0 = the own speaker's model), added to
+    ``hist`` if one is given."""
+    return _trial_hist(q, q_label, sums, msum, count, kind, None, leave_one_out, windows, bins, hist=hist)
 
 
 def plda_speaker_trial_hist(q: torch.Tensor, q_label: torch.Tensor, sums, count, tables, leave_one_out: bool,
                             windows: Sequence[Tuple[int, int]], bins: int, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``vm_plda_speaker_trial_hist``: ``speaker_trial_hist`` with the multi-session PLDA score."""
-    V.check_windows(windows, bins)
-    q = q.contiguous()
-    dev = q.device
-    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
-    if hist is None:
-        hist = torch.zeros(len(windows), 2, bins + 3, dtype=torch.int64, device=dev)
-    if q.shape[0] > 0:
-        win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
-        _plda_call("vm_plda_speaker_trial_hist", q, q_label, sums, count, tables, leave_one_out, win.ctypes.data, len(windows), bins,
-                   hist.data_ptr())
-    return hist
+    return _trial_hist(q, q_label, sums, None, count, None, tables, leave_one_out, windows, bins, hist=hist)
+
+
+def speaker_trial_hist_norm(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind, leave_one_out: bool,
+                            windows: Sequence[Tuple[int, int]], bins: int, stats: Sequence[Optional[torch.Tensor]], tables=None,
+                            hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``vm_speaker_trial_hist_norm`` (``tables``: ``vm_plda_speaker_trial_hist_norm``): ``speaker_trial_hist`` on the normalised scores.
+    ``stats``: (mu_q, rsig_q (M), mu_s, rsig_s (S), mu_own, rsig_own (M) or None, None), fp32 on the device."""
+    return _trial_hist(q, q_label, sums, msum, count, kind, tables, leave_one_out, windows, bins, stats, hist)
 
 
 def speaker_loo_sums(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``vm_speaker_loo_sums``: the virtual models (sums (M, E) / msum (M) float64, count (M) int32) of the rows ``q``."""
     lib = _lib.lib()
     kind = _kind(kind)
-    q = q.contiguous()
+    q, q_label = _rows_labels(q, q_label)
     dev = q.device
-    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
     M, E = q.shape
     vs = torch.zeros(M, E, dtype=torch.float64, device=dev)
     vm = torch.zeros(M, dtype=torch.float64, device=dev)
@@ -425,61 +434,17 @@ def speaker_cohort_stats(q: torch.Tensor, sums, msum, count, kind, side: int, K:
     """``vm_speaker_cohort_stats`` (``tables``: ``vm_plda_speaker_cohort_stats``): ``mu``, ``sigma``, ``rsig`` (fp32), ``count`` (int32)
     and, with ``return_topk``, ``topk_idx`` (lines, K) of the scores of the rows ``q`` against the models -- per row over the models
     (``side`` 0) or per model over the rows (``side`` 1)."""
-    lib = _lib.lib()
     q = q.contiguous()
     dev = q.device
-    M, E = q.shape
-    S = int(count.shape[0])
-    n = S if side == 1 else M
+    binding = _binding(q, sums, msum, count, kind, tables)
+    n = int(count.shape[0]) if side == 1 else int(q.shape[0])
     out = {k: torch.full((n,), float("nan"), dtype=torch.float32, device=dev) for k in ("mu", "sigma", "rsig")}
     out["count"] = torch.zeros(n, dtype=torch.int32, device=dev)
     if return_topk:
         out["topk_idx"] = torch.full((n, K), -1, dtype=torch.int32, device=dev)
-    tail = (side, K, out["mu"].data_ptr(), out["sigma"].data_ptr(), out["rsig"].data_ptr(), out["count"].data_ptr(),
-            out["topk_idx"].data_ptr() if return_topk else None)
-    if tables is None:
-        ws = lib.workspace("vm_speaker_cohort_stats_workspace_bytes", M, E, S, side, device=dev)
-        lib.call("vm_speaker_cohort_stats", q.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(), S, _kind(kind), *tail,
-                 ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    else:
-        D, n_max = int(tables["G"].shape[0]), int(tables["C"].shape[0]) - 1
-        if int(sums.shape[1]) != E:
-            raise ValueError("the sums are %d wide and the rows %d" % (int(sums.shape[1]), E))
-        ws = lib.workspace("vm_plda_speaker_cohort_stats_workspace_bytes", M, D, S, side, device=dev)
-        lib.call("vm_plda_speaker_cohort_stats", q.data_ptr(), M, E, D, sums.data_ptr(), count.data_ptr(), S, tables["A"].data_ptr(),
-                 tables["beta"].data_ptr(), tables["C"].data_ptr(), tables["G"].data_ptr(), n_max, *tail, ws.data_ptr(),
-                 torch.cuda.current_stream(dev).cuda_stream)
+    _call(binding, "cohort_stats", q, (), (side, K) + tuple(out[k].data_ptr() for k in ("mu", "sigma", "rsig", "count"))
+          + (out["topk_idx"].data_ptr() if return_topk else None,), ws_tail=(side,))
     return out
-
-
-def speaker_trial_hist_norm(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind, leave_one_out: bool,
-                            windows: Sequence[Tuple[int, int]], bins: int, stats: Sequence[Optional[torch.Tensor]], tables=None,
-                            hist: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``vm_speaker_trial_hist_norm`` (``tables``: ``vm_plda_speaker_trial_hist_norm``): ``speaker_trial_hist`` on the normalised scores.
-    ``stats``: (mu_q, rsig_q (M), mu_s, rsig_s (S), mu_own, rsig_own (M) or None, None), fp32 on the device."""
-    lib = _lib.lib()
-    V.check_windows(windows, bins)
-    q = q.contiguous()
-    dev = q.device
-    q_label = q_label.to(device=dev, dtype=torch.int32).contiguous()
-    M, E = q.shape
-    S = int(count.shape[0])
-    if hist is None:
-        hist = torch.zeros(len(windows), 2, bins + 3, dtype=torch.int64, device=dev)
-    if M > 0:
-        stats = [None if t is None else t.to(device=dev, dtype=torch.float32).contiguous() for t in stats]
-        for t, n in zip(stats, (M, M, S, S, M, M)):
-            if t is not None and int(t.numel()) != n:
-                raise ValueError("a statistics array holds %d entries, not %d" % (int(t.numel()), n))
-        win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 2))
-        tail = (win.ctypes.data, len(windows), bins) + tuple(None if t is None else t.data_ptr() for t in stats) + (hist.data_ptr(),)
-        if tables is None:
-            ws = lib.workspace("vm_speaker_trial_hist_norm_workspace_bytes", M, E, S, device=dev)
-            lib.call("vm_speaker_trial_hist_norm", q.data_ptr(), q_label.data_ptr(), M, E, sums.data_ptr(), msum.data_ptr(), count.data_ptr(),
-                     S, _kind(kind), 1 if leave_one_out else 0, *tail, ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        else:
-            _plda_call("vm_plda_speaker_trial_hist_norm", q, q_label, sums, count, tables, leave_one_out, *tail)
-    return hist
 
 
 # ---- speaker models of an EmbeddingCache -------------------------------------------------------------------------------------------
@@ -501,6 +466,12 @@ class SpeakerModels:
     @property
     def S(self) -> int:
         return int(self.count.shape[0])
+
+    @property
+    def backend(self) -> Tuple:
+        """(sums, msum, count, kind, tables) as the entry points above take them: the one place that knows which back end scores
+        these models (the sums of PLDA models are of the euclidean kind)."""
+        return self.sums, self.msum, self.count, _lib.VM_DIST_EUCLIDEAN if self.tables is not None else _kind(self.distance), self.tables
 
     def labels_of(self, speaker_codes) -> np.ndarray:
         """Dense indices of speaker codes (-1: the speaker is not enrolled)."""
@@ -584,10 +555,7 @@ def identify(models: SpeakerModels, cache, leave_one_out: Optional[bool] = None,
     the enrolled cache, the queries are the rows that were not enrolled.  The ranking is by the raw score: ranking by the normalised
     score of ``model_score_norm`` is out of scope."""
     q, q_label, loo, (lo, hi), n_q, idx = _shard(models, cache, leave_one_out, rows)
-    if models.tables is not None:
-        out = plda_speaker_identify(q, q_label, models.sums, models.count, models.tables, loo)
-    else:
-        out = speaker_identify(q, q_label, models.sums, models.msum, models.count, models.distance, loo)
+    out = _identify(q, q_label, *models.backend, loo)
     S = models.S
     rk = out["rank"].long()
     hist = torch.bincount(torch.where(rk < 0, torch.full_like(rk, S), rk), minlength=S + 1)[:S + 1]
@@ -635,63 +603,63 @@ def _normalised_sample(stats, lo, hi, sc=None, i=None, s=None):
     return 0.5 * (l1 + l2), 0.5 * (h1 + h2), sc
 
 
-def _pass1(models: SpeakerModels, q: torch.Tensor, n_sample: int = 1 << 16, stats=None) -> Tuple[int, int]:
-    """``verification.place_window`` for the model trials of rank 0's rows ``q``: bounds from the largest row and model norms, and a
-    seeded sample of (row, model) pairs, those of a speaker without a model left out.  ``stats``: the window of the normalised scores
-    (``_normalised_sample``)."""
-    if models.tables is not None:
-        return _pass1_plda(models, q, n_sample, stats)
+def _geometric_sampler(models: SpeakerModels, q: torch.Tensor):
+    """(lo, hi, ok, score) of the geometric kinds for ``_pass1``: bounds from the largest row and model norms, the models that exist, and
+    ``score(i, s)``: the float64 scores of (row, model) index pairs."""
     kind = _kind(models.distance)
+    P = _prototypes(models)
+    ok = models.count > 0
+    pr = float(torch.linalg.vector_norm(P[ok], dim=1).max().item()) if bool(ok.any()) else 0.0
+    qr = float(torch.linalg.vector_norm(q.double(), dim=1).max().item()) if q.shape[0] else 0.0
+    pr, qr = (x if math.isfinite(x) else 1.0 for x in (pr, qr))
+    if kind == 1:
+        lo, hi = 0.0, 2.0
+    elif kind == 0:
+        lo, hi = 0.0, (pr + qr) * 1.001 + 1e-30
+    else:
+        lo, hi = -pr * qr * 1.001 - 1e-30, pr * qr * 1.001 + 1e-30
+    return lo, hi, ok, lambda i, s: V.sample_scores(q[i], P[s], kind)
+
+
+def _plda_sampler(models: SpeakerModels, q: torch.Tensor):
+    """``_geometric_sampler`` for multi-session PLDA models: the shared models' operands in torch float64 (mu = beta[n] Sigma, A[n],
+    C[n]) and bounds from the largest terms -- the score is sum A (w - mu)^2 - g - C with g = sum G w^2 >= 0."""
+    t, D = models.tables, int(models.tables["G"].shape[0])
+    n = models.count.long()
+    ok = (n >= 1) & (n <= models.n_max)
+    n = torch.where(ok, n, torch.zeros_like(n))
+    mu, A, C = t["beta"][n] * models.sums[:, :D], t["A"][n], t["C"][n]
+    w = q[:, :D].double()
+    g = (w * w) @ t["G"]
+    fin = lambda x: x if math.isfinite(x) else 1.0
+    qr = fin(float(torch.linalg.vector_norm(w, dim=1).max().item())) if q.shape[0] else 0.0
+    mr = fin(float(torch.linalg.vector_norm(mu[ok], dim=1).max().item())) if bool(ok.any()) else 0.0
+    cm = fin(float(C.abs().max().item()))
+    gm = fin(float(g.abs().max().item())) if q.shape[0] else 0.0
+    lo = -(gm + cm) * 1.001 - 1e-30
+    hi = (fin(float(A.max().item())) * (qr + mr) ** 2 + gm + cm) * 1.001 + 1e-30
+
+    def score(i, s):
+        d = w[i] - mu[s]
+        return ((A[s] * d * d).sum(1) - g[i]) - C[s]
+    return lo, hi, ok, score
+
+
+def _pass1(models: SpeakerModels, q: torch.Tensor, n_sample: int = 1 << 16, stats=None) -> Tuple[int, int]:
+    """``verification.place_window`` for the model trials of rank 0's rows ``q``: the back end's bounds and a seeded sample of (row,
+    model) pairs, those of a speaker without a model left out.  ``stats``: the window of the normalised scores
+    (``_normalised_sample``).  Only the window's place depends on any of it."""
+    sampler = _geometric_sampler if models.tables is None else _plda_sampler
 
     def sample():
-        P = _prototypes(models)
-        ok = models.count > 0
-        pr = float(torch.linalg.vector_norm(P[ok], dim=1).max().item()) if bool(ok.any()) else 0.0
-        qr = float(torch.linalg.vector_norm(q.double(), dim=1).max().item()) if q.shape[0] else 0.0
-        pr, qr = (x if math.isfinite(x) else 1.0 for x in (pr, qr))
-        if kind == 1:
-            lo, hi = 0.0, 2.0
-        elif kind == 0:
-            lo, hi = 0.0, (pr + qr) * 1.001 + 1e-30
-        else:
-            lo, hi = -pr * qr * 1.001 - 1e-30, pr * qr * 1.001 + 1e-30
+        lo, hi, ok, score = sampler(models, q)
         if q.shape[0] < 1 or not bool(ok.any()):
             return _normalised_sample(stats, lo, hi)
         g = torch.Generator().manual_seed(0)
         i = torch.randint(0, q.shape[0], (n_sample,), generator=g).to(q.device)
         s = torch.randint(0, models.S, (n_sample,), generator=g).to(q.device)
-        sc = V.sample_scores(q[i], P[s], kind).masked_fill(~ok[s], float("nan"))   # no model: no trial, dropped as not finite
+        sc = score(i, s).masked_fill(~ok[s], float("nan"))   # no model: no trial, dropped as not finite
         return _normalised_sample(stats, lo, hi, sc, i, s)
-    return V.place_window(sample)
-
-
-def _pass1_plda(models: SpeakerModels, q: torch.Tensor, n_sample: int, stats=None) -> Tuple[int, int]:
-    """``_pass1`` for multi-session PLDA models: the shared models' operands in torch float64 (mu = beta[n] Sigma, A[n], C[n]), bounds
-    from the largest terms -- the score is sum A (w - mu)^2 - g - C with g = sum G w^2 >= 0 -- and a seeded sample of (row, model)
-    pairs.  Only the window's place depends on any of it."""
-    def sample():
-        t, D = models.tables, int(models.tables["G"].shape[0])
-        n = models.count.long()
-        ok = (n >= 1) & (n <= models.n_max)
-        n = torch.where(ok, n, torch.zeros_like(n))
-        mu, A, C = t["beta"][n] * models.sums[:, :D], t["A"][n], t["C"][n]
-        w = q[:, :D].double()
-        g = (w * w) @ t["G"]
-        fin = lambda x: x if math.isfinite(x) else 1.0
-        qr = fin(float(torch.linalg.vector_norm(w, dim=1).max().item())) if q.shape[0] else 0.0
-        mr = fin(float(torch.linalg.vector_norm(mu[ok], dim=1).max().item())) if bool(ok.any()) else 0.0
-        cm = fin(float(C.abs().max().item()))
-        gm = fin(float(g.abs().max().item())) if q.shape[0] else 0.0
-        lo = -(gm + cm) * 1.001 - 1e-30
-        hi = (fin(float(A.max().item())) * (qr + mr) ** 2 + gm + cm) * 1.001 + 1e-30
-        if q.shape[0] < 1 or not bool(ok.any()):
-            return _normalised_sample(stats, lo, hi)
-        gen = torch.Generator().manual_seed(0)
-        i = torch.randint(0, q.shape[0], (n_sample,), generator=gen).to(q.device)
-        s = torch.randint(0, models.S, (n_sample,), generator=gen).to(q.device)
-        d = w[i] - mu[s]
-        sc = ((A[s] * d * d).sum(1) - g[i]) - C[s]
-        return _normalised_sample(stats, lo, hi, sc.masked_fill(~ok[s], float("nan")), i, s)   # no model: no trial, dropped as not finite
     return V.place_window(sample)
 
 
@@ -738,9 +706,8 @@ def model_score_norm(models: SpeakerModels, cache, cohort, top_k: Optional[int] 
         raise ValueError("top_k must be >= 1 (or None for S-norm)")
     if cohort.emb.dim() != 2 or cohort.n < 1 or int(cohort.emb.shape[1]) != int(models.sums.shape[1]):
         raise ValueError("the cohort must be a non-empty cache of rows %d wide" % int(models.sums.shape[1]))
-    plda_on = models.tables is not None
-    cm = enrol(cohort, plda=models.plda) if plda_on else enrol(cohort, distance=models.distance)
-    kind = _lib.VM_DIST_EUCLIDEAN if plda_on else _kind(models.distance)
+    cm = enrol(cohort, distance=models.distance, plda=models.plda)   # PLDA models carry distance "plda", which enrol(plda=) accepts
+    sums, msum, count, kind, tables = models.backend
     q, q_label, loo, (lo, hi), n_q, _ = _shard(models, cache, leave_one_out, None)
     ce = cohort.emb.to(device=q.device, dtype=torch.float32).contiguous()
     C, Sc = int(ce.shape[0]), cm.S
@@ -748,7 +715,7 @@ def model_score_norm(models: SpeakerModels, cache, cohort, top_k: Optional[int] 
     Ks = C if top_k is None else min(int(top_k), C)
     names = ("mu", "sigma", "rsig", "count")
     sq = speaker_cohort_stats(q, cm.sums, cm.msum, cm.count, kind, 0, Kq, tables=cm.tables)
-    ss = speaker_cohort_stats(ce, models.sums, models.msum, models.count, kind, 1, Ks, tables=models.tables)
+    ss = speaker_cohort_stats(ce, sums, msum, count, kind, 1, Ks, tables=tables)
     rows = [sq[k] for k in names]
     if loo:
         M, E = q.shape
@@ -756,8 +723,8 @@ def model_score_norm(models: SpeakerModels, cache, cohort, top_k: Optional[int] 
         own["count"] = torch.zeros(M, dtype=torch.int32, device=q.device)
         step = max(1, LOO_CHUNK_BYTES // (8 * int(E)))
         for r0 in range(0, M, step):
-            vs, vm, vc = speaker_loo_sums(q[r0:r0 + step], q_label[r0:r0 + step], models.sums, models.msum, models.count, kind)
-            so = speaker_cohort_stats(ce, vs, vm, vc, kind, 1, Ks, tables=models.tables)
+            vs, vm, vc = speaker_loo_sums(q[r0:r0 + step], q_label[r0:r0 + step], sums, msum, count, kind)
+            so = speaker_cohort_stats(ce, vs, vm, vc, kind, 1, Ks, tables=tables)
             for k in names:
                 own[k][r0:r0 + step] = so[k]
         rows += [own[k] for k in names]
@@ -788,14 +755,7 @@ def _hist_source(models, cache, leave_one_out, norm=None):
     stats = None if norm is None else norm.stats(lo, hi)
 
     def hist_fn(windows, bins):
-        if norm is not None:
-            h = speaker_trial_hist_norm(q, q_label, models.sums, models.msum, models.count, _lib.VM_DIST_EUCLIDEAN if models.tables is not None
-                                        else models.distance, loo, windows, bins, stats, tables=models.tables)
-        elif models.tables is not None:
-            h = plda_speaker_trial_hist(q, q_label, models.sums, models.count, models.tables, loo, windows, bins)
-        else:
-            h = speaker_trial_hist(q, q_label, models.sums, models.msum, models.count, models.distance, loo, windows, bins)
-        return parallel.sum_ranks(h).cpu().numpy()
+        return parallel.sum_ranks(_trial_hist(q, q_label, *models.backend, loo, windows, bins, stats)).cpu().numpy()
     return hist_fn, q, stats
 
 
