@@ -241,7 +241,10 @@ int vm_conv1_fused_fwd(const float* x, const float* w, const float* bias, const 
                        int64_t n_windows, int64_t L, int F, int pool, int inference, int dtype, void* out, float* stat_sum,
                        float* stat_sq, void* stream);
 /* mode 1 (inference) over a length-masked bucket (see vm_crop_decimate_whiten_varlen): lens[n] = the valid positions of window n's
- * input x; pooled rows at or past lens[n] / pool are zero and a 32-position tile past the last valid pool group runs no MFMA. */
+ * input x; pooled rows at or past lens[n] / pool are zero (+0, whatever x holds past the last tap of position (lens[n] / pool) * pool - 1,
+ * NaN included) and a 32-position tile past the last valid pool group runs no MFMA.  lens[n] < pool: the whole window is zero;
+ * lens[n] > L counts as L.  The halo rows 0 and L / pool + 1 are the caller's in every case.  With every lens[n] == L the output is
+ * bit-identical to mode 1 of vm_conv1_fused_fwd. */
 int vm_conv1_fused_fwd_varlen(const float* x, const float* w, const float* bias, const float* scale, const float* shift,
                               const int32_t* lens, int64_t n_windows, int64_t L, int F, int pool, int dtype, void* out, void* stream);
 /* Backward of the same block from dp (n_windows, L/pool, F) `dtype`: recomputes the conv tile on the matrix cores,
@@ -332,7 +335,9 @@ int vm_conv_fwd_pool_supported(int64_t n_windows, int64_t L, int c_in, int c_out
 int vm_conv_fwd_pool(const void* in, const void* wf, const float* bias, const float* scale, const float* shift,
                      int64_t n_windows, int64_t L, int c_in, int c_out, int dtype, void* act, const void* wf_packed, void* stream);
 /* The same over a length-masked bucket (see vm_crop_decimate_whiten_varlen; models.py:22-35): lens[n] = the valid positions of window n.
- * Pooled rows at or past lens[n] / 2 are zero; a 254-row tile with no valid pool group writes its zeros and issues no MFMA.  Served
+ * Pooled rows at or past lens[n] / 2 are zero (+0, whatever `in` holds past row 2 * (lens[n] / 2), NaN included); a 254-row tile with
+ * no valid pool group writes its zeros and issues no MFMA.  lens[n] < 2: the whole window is zero; lens[n] > L counts as L.  The halo
+ * rows of act are the caller's in every case.  With every lens[n] == L the output is bit-identical to vm_conv_fwd_pool's.  Served
  * where vm_conv_fwd_pool_supported() says so. */
 int vm_conv_fwd_pool_varlen(const void* in, const void* wf, const float* bias, const float* scale, const float* shift,
                             const int32_t* lens, int64_t n_windows, int64_t L, int c_in, int c_out, int dtype, void* act,

@@ -612,8 +612,307 @@ def conv1_bwd_case(shape, regime, pool, wpt, drop):
     return Conv1BwdCase(tuple(shape), regime, pool, wpt, bool(drop))
 
 
+# ---- the length-masked fused inference kernels: vm_conv_fwd_pool_varlen and vm_conv1_fused_fwd_varlen --------------------------------------
+# A bucket's windows share the padded length L and carry lens[n]; pooled rows at or past lens[n] // pool are +0.  The cases zero the
+# input at and past lens[n], so the unmasked reference of a window's valid rows is also the reference of that recording ALONE at its
+# own length (a valid row reads at most the zero just past the length: the SAME padding) -- which the host file asserts.
+TROWS = 254         # conv_gemm.hip n2r::TROWS: positions per tile of conv_nt2r_kernel / conv_nt3_kernel
+F1_CHUNK = 256      # conv1_fused.hip: positions per double-buffered chunk ...
+F1_TILE = 32        # ... and per MFMA row tile (the host file reads all three from the sources)
+OVER = 5            # lens[n] = L + OVER: a length past the padded one behaves as L
+
+# (n, L, c_in, c_out), all served by vm_conv_fwd_pool_supported: 254 + 254 + 192 with n * tiles = 72 (8-group swizzle), two column
+# tiles, c_in 128 (conv_nt3_kernel with packed weights); 254 + 254 with n * tiles = 26 (plain division), c_in 256; three full tiles
+# with n * tiles = 57 and c_in 64, which conv_nt3_kernel does not serve
+POOL_VARLEN_SHAPES = [(24, 700, 128, 256), (13, 508, 256, 128), (19, 762, 64, 128)]
+# (n, L, F): CONV1_FUSED_SHAPES' ragged ones with enough windows for the table of either pool
+CONV1_VARLEN_SHAPES = [(32, 700, 16), (28, 532, 40), (28, 300, 160)]
+CONV1_VARLEN_REGIMES = ("small", "lo-x")
+
+
+def mask_rows(full, lens, pool):
+    """The mask helper: full (n, L // pool, c), lens (n,) -> rows q >= lens[n] // pool are +0."""
+    q = np.arange(full.shape[1])[None, :, None]
+    return np.where(q < (np.asarray(lens, dtype=np.int64) // pool)[:, None, None], full, 0.0)
+
+
+def zero_past(x, lens):
+    """x (n, L, ...) with every position at or past lens[n] zeroed."""
+    t = np.arange(x.shape[1]).reshape((1, -1) + (1,) * (x.ndim - 2))
+    return np.where(t < np.asarray(lens, dtype=np.int64).reshape((-1,) + (1,) * (x.ndim - 1)), x, 0.0)
+
+
+def pool_varlen_lens(l):
+    """vm_conv_fwd_pool_varlen: L, L - 1 (odd: the last position is dropped), past L, every tile edge t (the start of a ragged last tile
+    is one) with t - 2 .. t + 3 -- the tile before it one row short and exactly full, the tile behind it dead, and with one pooled row
+    (dq == 1), each at an even and an odd length --, one pooled row (2, 3) and none (0, 1)."""
+    v = {l, l - 1, l + OVER, 0, 1, 2, 3}
+    for t in range(TROWS, l, TROWS):
+        v |= {t + d for d in (-2, -1, 0, 1, 2, 3)}
+    assert all(x <= l or x == l + OVER for x in v)
+    return sorted(v)
+
+
+def conv1_edges(l, pool):
+    """{kind: [32-position tile edges of that kind]}: `tile` an edge inside a whole chunk, `chunk` a 256-position chunk edge,
+    `last-chunk` a tile edge inside the ragged last chunk, `last-tile` the start of the ragged last tile.  An edge counts where the
+    pool group behind it still lies inside the window."""
+    c0, s = (l - 1) // F1_CHUNK * F1_CHUNK, (l - 1) // F1_TILE * F1_TILE
+    ok = lambda e: 0 < e and e + pool <= l // pool * pool
+    out = {"tile": [e for e in range(F1_TILE, c0, F1_TILE) if e % F1_CHUNK and ok(e)],
+           "chunk": [e for e in range(F1_CHUNK, l, F1_CHUNK) if ok(e)],
+           "last-chunk": [e for e in range(c0 + F1_TILE, l, F1_TILE) if l % F1_CHUNK and ok(e)],
+           "last-tile": [s] if l % F1_TILE and ok(s) else []}
+    return out
+
+
+def conv1_varlen_lens(l, pool):
+    """vm_conv1_fused_fwd_varlen: L, L - 1 .. L - pool + 1 (with L: every lens % pool), past L, and for one edge e of every kind of
+    conv1_edges: e (Lv on the edge: a fast tile next to a dead one, no boundary tile), e + 1 .. e + pool - 1 (the same Lv, every
+    remainder), e - pool and e + pool (a boundary tile with one group missing / one group valid); one pooled row (pool) and none
+    (pool - 1, 0)."""
+    v = {l, l + OVER, pool, pool - 1, 0} | {l - r for r in range(1, pool)}
+    for kind, edges in conv1_edges(l, pool).items():
+        for e in edges[len(edges) // 2:len(edges) // 2 + 1]:            # the middle one
+            v |= {e - pool, e + pool} | {e + r for r in range(pool)}
+    assert all(x <= l or x == l + OVER for x in v)
+    return sorted(v)
+
+
+def spread(table, n, seed):
+    """The table's lengths over n >= len(table) windows (the rest repeats it), shuffled: neighbouring windows differ, dead and live
+    tiles interleave in the launch order."""
+    assert n >= len(table), (n, len(table))
+    v = np.array([table[i % len(table)] for i in range(n)], dtype=np.int32)
+    return np.random.default_rng(seed).permutation(v)
+
+
+def pool_tile_class(l, ln, q):
+    """The branch of conv_nt2r_kernel / conv_nt3_kernel (EPI_FWD_POOL) that writes pooled row q of a window of length ln."""
+    t0 = 2 * q // TROWS * TROWS
+    d = (ln >> 1) - (t0 >> 1)
+    if d <= 0:
+        return "dead"                                                   # n2_pool_dead_tile
+    return "live-full" if d >= (min(l - t0, TROWS) >> 1) else "live-partial"    # n2_tile_drain: dq == vq / dq < vq
+
+
+def conv1_tile_class(l, pool, ln, q):
+    """The branch of conv1_fused_fwd_kernel that writes pooled row q of a window of length ln."""
+    t0 = q * pool // F1_TILE * F1_TILE
+    lv = min(ln // pool, l // pool) * pool
+    return "dead" if t0 >= lv else "fast" if t0 + F1_TILE <= lv else "boundary"
+
+
+def varlen_note(lens, klass):
+    """assert_exact's note for a (window, pooled row, channel) index: the window's lens value and the tile class of the row."""
+    return lambda i: "lens[%d] = %d, %s tile" % (i[0], int(lens[i[0]]), klass(int(lens[i[0]]), i[1]))
+
+
+# A host model of the masking: the tiles of a window in launch form, each dead, fast (conv1 only) or drained with dq valid rows.
+# MASK_DEFECTS move one comparison, or the length it reads, in the direction that changes a result; the host file shows that each
+# changes the expected output of a case of the tables.  MASK_NEUTRAL move the dead-tile and the fast-tile comparison the other way:
+# the slower branch they then take masks per row and gives the same bits (asserted as well), so no output can see them.
+MASK_DEFECTS = ("ceil", "positions", "dead-early", "dq+1", "dq-1", "lens-prev", "lens-next", "fast-early")
+MASK_NEUTRAL = ("dead-late", "fast-late")
+
+
+def mask_model(full, lens, l, pool, tile, fast, defect=None):
+    """full (n, L // pool, c) unmasked, lens (n,) -> what the kernel stores.  tile: 254 (the GEMM kernels, fast = False) or 32 (conv1,
+    fast = True).  Defects: `ceil` valid rows = ceil(lens / pool); `positions` lens compared with pooled rows (the shift / the `* POOL`
+    forgotten); `dead-early` a tile with one valid row taken as dead (`<=` in `(t0 >> 1) < (lens >> 1)` read the harmful way: `t0 / pool +
+    1 >= valid`); `dq+1` / `dq-1`; `lens-prev` / `lens-next` the neighbouring window's length; `fast-early` a tile one group short of
+    full taken as fast.  Neutral: `dead-late` (`>` for `>=`: the drain runs with dq = 0), `fast-late` (`<` for `<=`: a full tile takes
+    the boundary branch)."""
+    n, lq, _ = full.shape
+    out = np.full(full.shape, np.nan)
+    for i in range(n):
+        ln = int(lens[(i + {"lens-prev": -1, "lens-next": 1}.get(defect, 0)) % n])
+        nv = -(-ln // pool) if defect == "ceil" else ln if defect == "positions" else ln // pool
+        for t0 in range(0, l, tile):
+            q0, whole = t0 // pool, (t0 + tile) // pool
+            q1 = min(whole, lq)                                         # the pooled rows this tile owns
+            if (q0 + 1 >= nv) if defect == "dead-early" else (q0 > nv) if defect == "dead-late" else (q0 >= nv):
+                out[i, q0:q1] = 0.0
+                continue
+            top = min(nv, lq)
+            if fast and ((whole <= top + 1) if defect == "fast-early" else (whole < top) if defect == "fast-late" else (whole <= top)):
+                out[i, q0:q1] = full[i, q0:q1]
+                continue
+            dq = min(nv - q0, q1 - q0) + {"dq+1": 1, "dq-1": -1}.get(defect, 0)
+            dq = max(min(dq, q1 - q0), 0)
+            out[i, q0:q0 + dq] = full[i, q0:q0 + dq]
+            out[i, q0 + dq:q1] = 0.0
+    assert not np.isnan(out).any(), "a pooled row no tile writes"
+    return out
+
+
+def pool_affine(l, c):
+    """test_fwd_pool's grid: scale +-{0.5, 1, 2, 4}, integer shift."""
+    r = np.random.default_rng(l + c)
+    return r.choice([0.5, 1.0, 2.0, 4.0], c) * r.choice([-1.0, 1.0], c), r.integers(-3, 4, c).astype(np.float64)
+
+
+def pool_forward(x, w, b, scale, shift, dt):
+    """vm_conv_fwd_pool in float64: max over the pair of scale * store(relu(conv + b)) + shift, unrounded."""
+    y = store(np.maximum(conv_same(x, w) + b, 0.0), dt) * scale + shift
+    q = x.shape[1] // 2
+    return np.maximum(y[:, 0:2 * q:2], y[:, 1:2 * q:2])
+
+
+class PoolVarlenCase:
+    """vm_conv_fwd_pool_varlen on `small` operands: x (n, L, c_in) zero at and past lens[n], full (n, L // 2, c_out) the unmasked pooled
+    tensor before its storage rounding (outputs pass 256: bf16 rounds them), want(dt) the masked, stored one."""
+
+    def __init__(self, shape):
+        n, l, cin, cout = shape
+        self.shape = shape
+        r = np.random.default_rng([n, l, cin, cout, 11])
+        self.lens = spread(pool_varlen_lens(l), n, l + cin)
+        self.x_raw = _ints(r, (n, l, cin), 1, 0.25)
+        self.x = zero_past(self.x_raw, self.lens)
+        self.w, self.b = _ints(r, (3, cin, cout), 1, 0.25), _ints(r, (cout,), 3)
+        self.scale, self.shift = pool_affine(l, cout)
+        require_exact_sums(conv_same(np.abs(self.x_raw), np.abs(self.w)) + np.abs(self.b), 1.0, "masked forward")
+        z = np.maximum(conv_same(self.x, self.w) + self.b, 0.0)
+        assert exact_in(z, "bf16") and exact_in(z * self.scale + self.shift, "f32")     # z is stored unrounded; the fma is exact
+        self.full = pool_forward(self.x, self.w, self.b, self.scale, self.shift, "f32")
+
+    def want(self, dt):
+        return mask_rows(store(self.full, dt), self.lens, 2)
+
+    def alone(self, i):
+        """Window i truncated to its own length and run alone: (min(lens, L) // 2, c_out)."""
+        ln = min(int(self.lens[i]), self.shape[1])
+        if ln == 0:
+            return np.zeros((0, self.shape[3]))
+        return pool_forward(self.x_raw[i:i + 1, :ln], self.w, self.b, self.scale, self.shift, "f32")[0]
+
+    def note(self):
+        return varlen_note(self.lens, lambda ln, q: pool_tile_class(self.shape[1], ln, q))
+
+
+@functools.lru_cache(maxsize=3)
+def pool_varlen_case(shape):
+    return PoolVarlenCase(tuple(shape))
+
+
+def conv1_affine(l, f, pool):
+    """test_conv1_fused_fwd's mode-1 grid."""
+    r = np.random.default_rng(l + f + pool)
+    return r.choice([0.5, 1.0, 2.0, 4.0], f) * r.choice([-1.0, 1.0], f), r.integers(-3, 4, f).astype(np.float64)
+
+
+def conv1_forward(x, w, b, scale, shift, pool):
+    """Mode 1 of vm_conv1_fused_fwd in float64, unrounded: fma(pool extreme by sign(scale) of relu(conv + b), scale, shift)."""
+    return pool_extreme(np.maximum(conv32(x, w) + b, 0.0), scale, pool) * scale + shift
+
+
+class Conv1VarlenCase:
+    """vm_conv1_fused_fwd_varlen: a waveform (n, L) zero at and past lens[n], `small` or `lo-x` (a + b * 2^-9: bf16 storage needs x_lo *
+    w_hi), filters and bias as Conv1Case `small`; full (n, L // pool, F) unmasked and unrounded."""
+
+    def __init__(self, shape, regime, pool):
+        n, l, f = shape
+        self.shape, self.pool = shape, pool
+        r = np.random.default_rng([n, l, f, pool, sum(map(ord, regime))])
+        self.lens = spread(conv1_varlen_lens(l, pool), n, l + f + pool)
+        self.x_raw = _lo_operand(r, (n, l)) if regime == "lo-x" else _ints(r, (n, l), 1, 0.25)
+        assert regime in CONV1_VARLEN_REGIMES and exact_in(self.x_raw, "f16")
+        self.x = zero_past(self.x_raw, self.lens)
+        self.w, self.b = _ints(r, (32, 1, f), 1, 0.25), _ints(r, (f,), 3)
+        self.scale, self.shift = conv1_affine(l, f, pool)
+        grid = 2.0 ** -9 if regime == "lo-x" else 1.0
+        require_exact_sums(conv32(np.add(*map(np.abs, bf16_halves(self.x_raw))), np.abs(self.w)) + np.abs(self.b), grid, "masked conv1")
+        self.full = conv1_forward(self.x, self.w, self.b, self.scale, self.shift, pool)
+        assert exact_in(self.full, "f32")                               # the fma is exact: one rounding, to storage
+
+    def want(self, dt):
+        return mask_rows(store(self.full, dt), self.lens, self.pool)
+
+    def alone(self, i):
+        ln = min(int(self.lens[i]), self.shape[1])
+        if ln == 0:
+            return np.zeros((0, self.shape[2]))
+        return conv1_forward(self.x_raw[i:i + 1, :ln], self.w, self.b, self.scale, self.shift, self.pool)[0]
+
+    def note(self):
+        return varlen_note(self.lens, lambda ln, q: conv1_tile_class(self.shape[1], self.pool, ln, q))
+
+
+@functools.lru_cache(maxsize=4)
+def conv1_varlen_case(shape, regime, pool):
+    return Conv1VarlenCase(tuple(shape), regime, pool)
+
+
+def unreached_from(ln, l, kind, pool=2):
+    """The first input position no valid output's taps reach (the reference's own tap range): the k = 3 conv's last valid row 2 * (ln //
+    2) - 1 reads one position further; conv1's last valid position Lv - 1 reads 16 further (pad_wave: 15 before, 16 after)."""
+    ln = min(ln, l)
+    return 2 * (ln // 2) + 1 if kind == "pool" else ln // pool * pool + 16
+
+
+# ---- the hand-off: conv1 -> conv + pool -> global max over one masked bucket against each recording alone --------------------------------
+CHAIN_SHAPE = (12, 800, 128, 128)       # (n, L, F, c_out): L / 2 = 400 = 254 + 146 and L / 4 = 200 are both served by the second layer
+
+
+def chain_lens(n, l, pool):
+    """Mixed lengths of one bucket: full, odd ones, one pooled row at the end (2 pool, 2 pool + 1: lens // pool // 2 == 1; 4 pool - 1: an
+    odd row count at the second layer), the second layer's tile edge where the window reaches it, the rest drawn."""
+    v = [l, l - 1, l - pool - 1, 2 * pool, 2 * pool + 1, 4 * pool - 1]
+    e = TROWS * pool
+    if e + 2 * pool + 1 <= l:
+        v += [e - 1, e, e + 1, e + 2 * pool + 1]
+    r = np.random.default_rng(l + pool)
+    v += [int(k) for k in r.integers(2 * pool, l, n - len(v))]
+    return np.array(v, dtype=np.int32)
+
+
+class ChainCase:
+    """vm_conv1_fused_fwd_varlen -> vm_conv_fwd_pool_varlen (lens // pool) -> vm_global_maxpool_fwd_varlen (lens // pool // 2) in `dt`
+    storage.  Scales +-{0.5, 1, 2}, integer shifts; the first layer's STORED outputs are the second layer's operands, and the
+    precondition is asserted on them."""
+
+    def __init__(self, pool, dt):
+        n, l, f, cout = CHAIN_SHAPE
+        self.pool, self.dt = pool, dt
+        r = np.random.default_rng([n, l, f, cout, pool])
+        self.lens = chain_lens(n, l, pool)
+        self.x_raw = _ints(r, (n, l), 1, 0.25)
+        self.x = zero_past(self.x_raw, self.lens)
+        self.w1, self.b1 = _ints(r, (32, 1, f), 1, 0.25), _ints(r, (f,), 3)
+        self.w2, self.b2 = _ints(r, (3, f, cout), 1, 0.25), _ints(r, (cout,), 3)
+        (self.s1, self.h1), (self.s2, self.h2) = _affine(r, 1, f), _affine(r, 1, cout)
+        self.s1, self.h1, self.s2, self.h2 = self.s1[0], self.h1[0], self.s2[0], self.h2[0]
+        # the bucket as the three launches see it, every precondition on the way
+        require_exact_sums(conv32(np.abs(self.x_raw), np.abs(self.w1)) + np.abs(self.b1), 1.0, "chain: conv1")
+        y1 = conv1_forward(self.x, self.w1, self.b1, self.s1, self.h1, pool)
+        assert exact_in(y1, "f32")
+        self.act1 = mask_rows(store(y1, dt), self.lens, pool)
+        g = dyadic_grid(self.act1)
+        require_exact_sums(conv_same(np.abs(self.act1), np.abs(self.w2)) + np.abs(self.b2), g, "chain: conv2 on conv1's stored outputs")
+        z2 = store(np.maximum(conv_same(self.act1, self.w2) + self.b2, 0.0), dt)
+        assert exact_in(z2 * self.s2 + self.h2, "f32") and np.abs(z2 * self.s2 + self.h2).max() < 60000
+        self.lens1 = self.lens // pool
+        self.act2 = mask_rows(store(pool_forward(self.act1, self.w2, self.b2, self.s2, self.h2, dt), dt), self.lens1, 2)
+        self.lens2 = self.lens1 // 2
+        assert self.lens2.min() == 1
+
+    def alone(self, i):
+        """Recording i alone in float64: truncate, k = 32 conv, floor-pool, affine, round to storage, k = 3 SAME conv over its own rows
+        only, floor-pool, round, first maximum and its row.  -> (act1, act2, gmax, gidx)."""
+        ln, dt = int(self.lens[i]), self.dt
+        a1 = store(conv1_forward(self.x_raw[i:i + 1, :ln], self.w1, self.b1, self.s1, self.h1, self.pool), dt)
+        a2 = store(pool_forward(a1, self.w2, self.b2, self.s2, self.h2, dt), dt)
+        return a1[0], a2[0], a2[0].max(0), a2[0].argmax(0).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=4)
+def chain_case(pool, dt):
+    return ChainCase(pool, dt)
+
+
 # ---- the comparator ------------------------------------------------------------------------------------------------------------------
-LAYOUTS = {"nlc": ("window", "position", "channel"), "kio": ("tap", "c_in", "c_out"), "nc": ("window", "channel"),
+LAYOUTS ={"nlc": ("window", "position", "channel"), "kio": ("tap", "c_in", "c_out"), "nc": ("window", "channel"),
            "tkc": ("tower", "tap", "channel"), "c": ("channel",), "k1f": ("filter tap", "one", "filter"), "tc": ("tower", "channel"),
            "tokc": ("tower", "c_out", "tap", "c_in")}
 
@@ -627,11 +926,12 @@ def _describe(idx, layout, shape):
     return s
 
 
-def assert_exact(got, want, layout, neg_zero=False, what=""):
+def assert_exact(got, want, layout, neg_zero=False, what="", note=None):
     """Bit-pattern equality of `got` (torch tensor, any storage type) with the float64 reference `want`, which must itself be exact in
     got's type.  neg_zero: -0.0 and +0.0 compare equal -- the one allowed difference, for outputs of a ReLU (max(-0.0, 0) may keep the
     sign) and products with an exactly zero factor; everything else is compared as bits.  On a mismatch: the count, the first and the
-    worst element by (window, position, channel), their 128- and 254-position tile indices and the distance from the window edge."""
+    worst element by (window, position, channel), their 128- and 254-position tile indices and the distance from the window edge, and
+    what `note(index)` adds about an element (the length-masked cases: the window's `lens` value and the class of the element's tile)."""
     got = torch.as_tensor(got).detach().cpu().contiguous()
     want64 = np.asarray(want, dtype=np.float64) + 0.0
     assert tuple(got.shape) == want64.shape, (tuple(got.shape), want64.shape)
@@ -649,6 +949,7 @@ def assert_exact(got, want, layout, neg_zero=False, what=""):
     diff = np.where(bad, np.abs(np.nan_to_num(g64, nan=np.inf) - want64), -1.0)
     worst = np.unravel_index(int(np.argmax(diff)), diff.shape)
     first = tuple(idx[0])
-    raise AssertionError("%s: %d of %d elements differ; first at (%s): got %r, want %r; worst at (%s): got %r, want %r" % (
-        what or layout, len(idx), bad.size, _describe(first, layout, bad.shape), g64[first], want64[first],
-        _describe(worst, layout, bad.shape), g64[worst], want64[worst]))
+    more = (lambda i: " {%s}" % note(tuple(int(v) for v in i))) if note is not None else (lambda i: "")
+    raise AssertionError("%s: %d of %d elements differ; first at (%s%s): got %r, want %r; worst at (%s%s): got %r, want %r" % (
+        what or layout, len(idx), bad.size, _describe(first, layout, bad.shape), more(first), g64[first], want64[first],
+        _describe(worst, layout, bad.shape), more(worst), g64[worst], want64[worst]))

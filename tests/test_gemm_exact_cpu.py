@@ -1,6 +1,9 @@
 """Host-side checks of tests/gemm_exact.py (the helper of tests/test_gpu_conv_exact.py): every generated case meets its precondition,
 an fp32 evaluation in another summation order reproduces the float64 reference exactly, and the comparator catches the defects a
 Frobenius ratio at the parity suite's tolerances lets through."""
+import os
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -291,3 +294,168 @@ def test_conv1_bwd_du_is_the_autograd_gradient():
     bound = 2.0 ** -23 * np.abs(B.per_window(scale, wpt)) * (np.abs(B.per_window(c1, wpt)) + np.abs(zhat * B.per_window(c2, wpt))) + 1e-12
     assert want.any() and (np.abs(du - want) <= bound).all(), float(np.abs(du - want).max())
     assert np.abs(du - want).max() < 1e-6 * np.abs(want).max()
+
+
+# ---- the length-masked fused inference kernels ------------------------------------------------------------------------------------------
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "voicemap_amd", "csrc")
+POOL_CASES = [(s,) for s in G.POOL_VARLEN_SHAPES]
+CONV1_CASES = [(s, reg, pool) for s in G.CONV1_VARLEN_SHAPES for reg in G.CONV1_VARLEN_REGIMES for pool in (2, 4)]
+
+
+def _const(fname, name):
+    m = re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, open(os.path.join(CSRC, fname)).read())
+    assert m, (fname, name)
+    return int(m.group(1))
+
+
+def test_varlen_constants_are_the_kernels():
+    """The tile edges of the length tables are the kernels' own: a changed constant fails here and does not silently move them."""
+    assert _const("conv_gemm.hip", "TROWS") == G.TROWS and _const("conv1_fused.hip", "F1_CHUNK") == G.F1_CHUNK
+    src = open(os.path.join(CSRC, "conv1_fused.hip")).read()
+    dead = re.search(r"if \(INFER && t0 \+ (\d+) \* rt >= Lv\)", src)
+    fast = re.search(r"if \(cok && t0 \+ (\d+) \* rt \+ (\d+) <= Lv\)", src)
+    assert dead and fast and {int(dead.group(1)), int(fast.group(1)), int(fast.group(2))} == {G.F1_TILE}
+    assert G.F1_CHUNK % G.F1_TILE == 0 and G.TROWS % 2 == 0 and G.F1_TILE % 4 == 0      # no pool group straddles a tile
+
+
+def test_pool_varlen_table_reaches_every_class():
+    """Per shape: lens == L, L - 1 (odd), past L, 0 .. 3, and at every tile edge t0 > 0 the six (valid pooled rows - t0 / 2, parity of lens)
+    classes of t0 - 2 .. t0 + 3; over the shapes: two full tiles and more, a ragged last tile, both tile-to-window mappings, c_in that
+    conv_nt3_kernel serves and one it does not, two column tiles."""
+    for n, l, cin, cout in G.POOL_VARLEN_SHAPES:
+        lens = G.pool_varlen_case((n, l, cin, cout)).lens
+        assert len(lens) == n and l % 2 == 0 and cout % 128 == 0
+        have = set(int(v) for v in lens)
+        assert {l, l - 1, l + G.OVER, 0, 1, 2, 3} <= have and (l - 1) % 2 == 1
+        tiles = -(-l // G.TROWS)
+        assert tiles >= 2
+        for tl in range(1, tiles):
+            t0 = tl * G.TROWS
+            got = {((v >> 1) - (t0 >> 1), v & 1) for v in have if v <= l}
+            assert {(d, par) for d in (-1, 0, 1) for par in (0, 1)} <= got, (l, tl)
+            # ... which are: the tile before one row short and exactly full, this tile dead, and this tile with dq == 1
+            cls = lambda v, q: G.pool_tile_class(l, v, q)
+            assert cls(t0 - 2, t0 >> 1) == "dead" and cls(t0 - 2, (t0 >> 1) - 1) == "live-partial"      # (the class of the row's TILE)
+            assert cls(t0, (t0 >> 1) - 1) == "live-full" and cls(t0, t0 >> 1) == "dead" and cls(t0 + 1, t0 >> 1) == "dead"
+            assert cls(t0 + 2, t0 >> 1) == "live-partial" and cls(t0 + 3, (t0 >> 1) + 1) == "live-partial"
+        assert all(G.pool_tile_class(l, v, q) == "dead" for v in (0, 1) for q in range(l // 2))
+        assert G.pool_tile_class(l, l + G.OVER, l // 2 - 1) == "live-full" == G.pool_tile_class(l, l, l // 2 - 1)
+    shapes = G.POOL_VARLEN_SHAPES
+    assert any(l % G.TROWS and l > 2 * G.TROWS for _, l, _, _ in shapes) and any(l % G.TROWS == 0 for _, l, _, _ in shapes)
+    groups = [n * -(-l // G.TROWS) for n, l, _, _ in shapes]
+    assert any(g % 8 == 0 for g in groups) and any(g % 8 for g in groups)
+    assert {128, 256} <= {s[2] for s in shapes} and any(s[2] in (32, 64) for s in shapes) and any(s[3] == 256 for s in shapes)
+
+
+@pytest.mark.parametrize("pool", [2, 4])
+def test_conv1_varlen_table_reaches_every_class(pool):
+    """Per shape and pool: lens == L, past L, pool, below pool, every lens % pool, and for every kind of edge the shape has -- a tile edge
+    inside a whole chunk, a chunk edge, a tile edge inside the ragged last chunk, the start of the ragged last tile -- Lv on it and one
+    pool group either side; over the shapes every kind occurs."""
+    kinds = set()
+    for shape in G.CONV1_VARLEN_SHAPES:
+        n, l, f = shape
+        lens = [int(v) for v in G.conv1_varlen_case(shape, "small", pool).lens]
+        assert len(lens) == n and {l, l + G.OVER, pool} <= set(lens) and min(lens) < pool
+        assert {v % pool for v in lens} == set(range(pool))
+        lv = {v // pool * pool for v in lens if v <= l}
+        c0, s = (l - 1) // G.F1_CHUNK * G.F1_CHUNK, (l - 1) // G.F1_TILE * G.F1_TILE
+        is_kind = {"tile": lambda e: e % G.F1_TILE == 0 and e % G.F1_CHUNK and 0 < e < c0,
+                   "chunk": lambda e: e % G.F1_CHUNK == 0 and 0 < e < l,
+                   "last-chunk": lambda e: l % G.F1_CHUNK and e % G.F1_TILE == 0 and c0 < e < l,
+                   "last-tile": lambda e: l % G.F1_TILE and e == s}
+        for kind, edges in G.conv1_edges(l, pool).items():
+            assert all(is_kind[kind](e) for e in edges)
+            if not edges:
+                continue
+            kinds.add(kind)
+            hit = [e for e in edges if {e - pool, e, e + pool} <= lv]
+            assert hit, (shape, kind)
+            e = hit[0]
+            cls = lambda v, t: G.conv1_tile_class(l, pool, v, t // pool)
+            # Lv on the edge: fast next to dead, no boundary tile; one group either side: a boundary tile
+            assert cls(e, e - 1) == "fast" and cls(e, e) == "dead" and cls(e + pool - 1, e) == "dead"
+            assert cls(e - pool, e - pool - 1) == "boundary" and cls(e - pool, e - pool) == "boundary" and cls(e - pool, e) == "dead"
+            assert cls(e + pool, e) == "boundary" and cls(e + pool, e + pool) == "boundary" and cls(e + pool, e - 1) == "fast"
+        assert {"tile", "chunk", "last-tile"} <= {k for k, v in G.conv1_edges(l, pool).items() if v}, shape
+        assert G.conv1_tile_class(l, pool, l + G.OVER, l // pool - 1) == G.conv1_tile_class(l, pool, l, l // pool - 1)
+    assert kinds == {"tile", "chunk", "last-chunk", "last-tile"}
+    assert [s for s in G.CONV1_VARLEN_SHAPES if s[1] + G.OVER >= -(-s[1] // G.F1_TILE) * G.F1_TILE], "no lens past the last tile's end"
+
+
+def _cases(kernel):
+    if kernel == "pool":
+        return [(G.pool_varlen_case(s), s[1], 2, G.TROWS, False) for s in G.POOL_VARLEN_SHAPES]
+    return [(G.conv1_varlen_case(*a), a[0][1], a[2], G.F1_TILE, True) for a in CONV1_CASES]
+
+
+@pytest.mark.parametrize("kernel", ["pool", "conv1"])
+def test_masked_reference_is_each_recording_alone(kernel):
+    """The property embed_varlen promises, on the cases in use: window n truncated to lens[n] and run alone gives the valid rows of the
+    bucket's reference; the rows behind them are +0; the sound host model of the tiles is the mask helper."""
+    for c, l, pool, tile, fast in _cases(kernel):
+        want = c.want("f32")
+        for i, ln in enumerate(c.lens):
+            rows = min(int(ln), l) // pool
+            alone = c.alone(i)
+            assert alone.shape[0] == rows and np.array_equal(alone, want[i, :rows]) and not want[i, rows:].any()
+            assert not np.signbit(want[i, rows:]).any()
+        assert np.array_equal(G.mask_model(c.full, c.lens, l, pool, tile, fast), want)
+        assert (want != c.full).any() and (c.full[c.lens >= l] == want[c.lens >= l]).all()
+        for dt in G.DT16:
+            assert np.array_equal(c.want(dt), G.store(want, dt))         # masking and storage rounding commute
+
+
+@pytest.mark.parametrize("defect", G.MASK_DEFECTS)
+@pytest.mark.parametrize("kernel", ["pool", "conv1"])
+def test_a_planted_mask_defect_changes_the_expected_output(kernel, defect):
+    """Every defect of the host model moves the stored 16-bit expectation of at least one case of the tables -- in both storage types, so
+    the device comparison fails on it.  (`fast-early` has no counterpart in the GEMM kernels: a full tile runs the same drain.)"""
+    if kernel == "pool" and defect == "fast-early":
+        assert all(not fast for _, _, _, _, fast in _cases(kernel))
+        return
+    for dt in G.DT16:
+        moved = 0
+        for c, l, pool, tile, fast in _cases(kernel):
+            bad = G.store(G.mask_model(c.full, c.lens, l, pool, tile, fast, defect), dt)
+            moved += int((bad != c.want(dt)).sum())
+        assert moved > 0, (kernel, defect, dt)
+
+
+@pytest.mark.parametrize("defect", G.MASK_NEUTRAL)
+@pytest.mark.parametrize("kernel", ["pool", "conv1"])
+def test_the_other_direction_of_a_branch_test_changes_no_bit(kernel, defect):
+    """`>` for `>=` in the dead-tile test and `<` for `<=` in the fast-tile test send a tile to the slower branch, which masks per row:
+    the same output, so no comparison of outputs can see it (it costs time, not bits)."""
+    for c, l, pool, tile, fast in _cases(kernel):
+        assert np.array_equal(G.mask_model(c.full, c.lens, l, pool, tile, fast, defect), c.want("f32"))
+
+
+def test_varlen_note_names_lens_and_tile_class():
+    c = G.pool_varlen_case(G.POOL_VARLEN_SHAPES[1])
+    got = c.want("bf16").copy()
+    i = int(np.argmax(c.lens == 256))
+    q, ch = 127, int(np.argmax(got[i, 127] != 0))
+    got[i, q, ch] = 0.0
+    with pytest.raises(AssertionError, match=r"first at \(window %d, position 127, channel %d \[.*\] \{lens\[%d\] = 256, live-partial tile\}\)" % (i, ch, i)):
+        assert_exact(torch.as_tensor(got).to(torch.bfloat16), c.want("bf16"), "nlc", note=c.note())
+
+
+@pytest.mark.parametrize("dt", G.DT16)
+@pytest.mark.parametrize("pool", [2, 4])
+def test_chain_case_meets_its_preconditions(pool, dt):
+    """Constructing the case asserts the exact-sum precondition of both layers (the second on the first's STORED outputs) and that both
+    affines are exact fmas; here: each recording alone reproduces its rows of every tensor of the bucket, the lengths are mixed (odd
+    ones, one pooled row at the end)."""
+    c = G.chain_case(pool, dt)
+    n, l, f, cout = G.CHAIN_SHAPE
+    assert len(c.lens) == n and (c.lens % 2 == 1).any() and (c.lens == l).any() and (c.lens1 % 2 == 1).any()
+    assert (l // pool) % 2 == 0
+    for i in range(n):
+        a1, a2, g, gi = c.alone(i)
+        assert np.array_equal(a1, c.act1[i, :c.lens1[i]]) and not c.act1[i, c.lens1[i]:].any()
+        assert np.array_equal(a2, c.act2[i, :c.lens2[i]]) and not c.act2[i, c.lens2[i]:].any()
+        assert g.shape == (cout,) and (gi < c.lens2[i]).all()
+    if pool == 2:
+        t = G.TROWS
+        assert {t - 1, t, t + 2} <= set(int(v) for v in c.lens1)        # the second layer's tile edge: full, dead behind, dq == 1

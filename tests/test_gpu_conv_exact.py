@@ -30,6 +30,20 @@ Which test reaches which kernel form (vm_set_tuning's GEMM keys; conv_gemm.hip /
                                                      1 / 2 / 3)
   block 1: conv1_fused_bwd_kernel (all_max and       test_conv1_fused_bwd (three grid forms of f1_blocks), test_conv1_fused_bwd_products
   use_min fast tiles, the ragged slow tile, slabs)   (f1_products 1 / 2 / 3), test_conv1_fused_bwd_refuses
+
+The length-masked inference forms (vm_conv_fwd_pool_varlen, vm_conv1_fused_fwd_varlen; tables and tile classes in gemm_exact.py):
+
+  conv_nt2r_kernel EPI_FWD_POOL + valid_len:         test_fwd_pool_varlen, staged weights (every shape; c_in 64 also with the packed
+  dead tile (n2_pool_dead_tile), live-partial        pointer): lens 0 / 1 all dead; t - 2 .. t + 3 at every 254-edge t: the tile before
+  (dq < vq) and live-full (dq == vq) drains, the     one row short and full, the tile behind dead and with dq == 1; L, L - 1, L + 5;
+  8-group swizzle and the plain tile-to-window map   72 tile groups (swizzle) and 26 / 57 (plain); test_masked_chain_.. (layer 2)
+  conv_nt3_kernel, the same three tile classes,      test_fwd_pool_varlen with packed weights on c_in 128 (72 groups, two column tiles)
+  lean prologue and first                            and c_in 256 (26 groups), nt3_lean 3 and 0
+  conv1_fused_fwd_kernel + valid_len: dead, fast     test_conv1_fused_fwd_varlen: Lv on a 32-edge (fast | dead), one pool group either
+  and boundary tiles; per-chunk workgroups and the   side (boundary), at a tile edge, a 256-chunk edge, inside the ragged last chunk and
+  double-buffered chunk loop (f1_fwd_blocks = n)     at the ragged last tile; every lens % pool; lens pool, < pool, L, L + 5 (clamped)
+  rows past the valid length never matter            test_varlen_ignores_what_no_valid_row_reads (NaN behind the last tap)
+  the three masked launches in a row                 test_masked_chain_equals_each_recording_alone
 """
 import numpy as np
 import pytest
@@ -522,3 +536,172 @@ def test_conv1_fused_bwd_refuses(what, l, f, pool, dt):
     torch.cuda.synchronize()
     assert rc != 0, what
     assert torch.isnan(gw).all() and torch.isnan(gb).all(), what + ": the gradients were written"
+
+
+# ---- the length-masked inference forms ---------------------------------------------------------------------------------------------------
+SENTINEL = 7.0
+
+
+def _bits(t):
+    return t.contiguous().view(G.INT_VIEW[t.dtype])
+
+
+def _sentinel(n, rows, c, tdt):
+    """A padded activation buffer (n, rows + 2, c) no row of which is a result: a row the kernel leaves out keeps the sentinel."""
+    return torch.full((n, rows + 2, c), SENTINEL, dtype=tdt, device="cuda")
+
+
+def _check_masked(act, want, lens, pool, what, note):
+    """The masked expectation bit for bit (so the rows at or past lens // pool are +0 in bits: asserted on its own as well) and the
+    halo rows untouched."""
+    assert_exact(act[:, 1:-1], want, "nlc", what=what, note=note)
+    q = torch.arange(want.shape[1], device="cuda")[None, :] >= torch.as_tensor(np.asarray(lens) // pool, device="cuda")[:, None]
+    assert not _bits(act[:, 1:-1])[q].any(), what + ": a masked row is not +0"
+    assert (act[:, 0] == SENTINEL).all() and (act[:, -1] == SENTINEL).all(), what + ": wrote the halo rows"
+
+
+def test_varlen_lists_have_served_shapes():
+    """Nothing below is skipped: every shape of the masked tables is served in both 16-bit types, packed weights exist where
+    conv_nt3_kernel is to be reached, and the hand-off's second layer is served behind either pool."""
+    n, l, f, cout = G.CHAIN_SHAPE
+    for dt in DT16:
+        vm = DTYPES[dt][0]
+        for s in G.POOL_VARLEN_SHAPES:
+            assert _served("vm_conv_fwd_pool_supported", s, dt), (s, dt)
+            assert s[2] not in (128, 256) or L().query("vm_pack_nt_weights_supported", s[3], s[2], vm), (s, dt)
+        for pool in (2, 4):
+            assert l % pool == 0 and _served("vm_conv_fwd_pool_supported", (n, l // pool, f, cout), dt), (pool, dt)
+
+
+def _pool_varlen_call(c, x, lens, dt, wf, wfp, varlen=True):
+    vm, tdt = DTYPES[dt]
+    n, l, cin, cout = c.shape
+    act = _sentinel(n, l // 2, cout, tdt)
+    args = [p(x), p(wf), p(dev(c.b)), p(dev(c.scale)), p(dev(c.shift))] + ([p(dev(lens, torch.int32))] if varlen else [])
+    L().call("vm_conv_fwd_pool_varlen" if varlen else "vm_conv_fwd_pool", *args, n, l, cin, cout, vm, p(act), p(wfp), stream())
+    return act
+
+
+@pytest.mark.parametrize("dt", DT16)
+@pytest.mark.parametrize("n,l,cin,cout", G.POOL_VARLEN_SHAPES)
+def test_fwd_pool_varlen(dt, n, l, cin, cout, nt3_lean):
+    """vm_conv_fwd_pool_varlen on test_fwd_pool's scale / shift grid, the lengths of gemm_exact.pool_varlen_lens mixed in one launch;
+    staged and packed weights, both conv_nt3_kernel prologues.  The masked expectation bit for bit with +0 behind the valid rows, the
+    halo rows untouched, and with every lens[n] == L the bytes of vm_conv_fwd_pool on the same input."""
+    vm, tdt = DTYPES[dt]
+    c = G.pool_varlen_case((n, l, cin, cout))
+    want = c.want(dt)
+    wf, _ = _prep(c.w, cin, cout, vm, tdt)
+    wfp = torch.empty_like(wf)
+    xp = padded(c.x, tdt)
+    for packed, lean in _packed_runs(cout, cin, vm):
+        nt3_lean(lean)
+        if packed:
+            L().call("vm_pack_nt_weights", p(wf), 1, cout, cin, vm, p(wfp), stream())
+        run = "vm_conv_fwd_pool_varlen %s %s packed %d lean %d" % (dt, (n, l, cin, cout), packed, lean)
+        act = _pool_varlen_call(c, xp, c.lens, dt, wf, wfp if packed else None)
+        _check_masked(act, want, c.lens, 2, run, c.note())
+        full = _pool_varlen_call(c, xp, np.full(n, l), dt, wf, wfp if packed else None)
+        plain = _pool_varlen_call(c, xp, None, dt, wf, wfp if packed else None, varlen=False)
+        assert torch.equal(_bits(full), _bits(plain)), run + ": lens == L differs from vm_conv_fwd_pool"
+        assert_exact(plain[:, 1:-1], G.store(c.full, dt), "nlc", what=run + " (vm_conv_fwd_pool on the zero-tailed input)")
+
+
+def _conv1_varlen_call(c, x, lens, dt, varlen=True):
+    vm, tdt = DTYPES[dt]
+    n, l, f = c.shape
+    out = _sentinel(n, l // c.pool, f, tdt)
+    head = [p(x), p(dev(c.w)), p(dev(c.b)), p(dev(c.scale)), p(dev(c.shift))]
+    if varlen:
+        L().call("vm_conv1_fused_fwd_varlen", *head, p(dev(lens, torch.int32)), n, l, f, c.pool, vm, p(out), stream())
+    else:
+        L().call("vm_conv1_fused_fwd", *head, n, l, f, c.pool, 1, vm, p(out), None, None, stream())
+    return out
+
+
+@pytest.mark.parametrize("per_window", [0, 1], ids=["default-grid", "one-workgroup-per-window"])
+@pytest.mark.parametrize("pool", [2, 4])
+@pytest.mark.parametrize("regime", G.CONV1_VARLEN_REGIMES)
+@pytest.mark.parametrize("dt", DT16)
+@pytest.mark.parametrize("n,l,f", G.CONV1_VARLEN_SHAPES)
+def test_conv1_fused_fwd_varlen(dt, regime, n, l, f, pool, per_window, f1_tuning):
+    """vm_conv1_fused_fwd_varlen on test_conv1_fused_fwd's mode-1 grid, the lengths of gemm_exact.conv1_varlen_lens mixed in one launch,
+    on the default grid (a workgroup per chunk) and with one workgroup per window (the double-buffered multi-chunk loop).  The same
+    assertions as test_fwd_pool_varlen; lens == L against mode 1 of vm_conv1_fused_fwd."""
+    if per_window:
+        f1_tuning(b"f1_fwd_blocks", n)
+    c = G.conv1_varlen_case((n, l, f), regime, pool)
+    run = "vm_conv1_fused_fwd_varlen %s %s %s pool %d per-window %d" % (dt, regime, (n, l, f), pool, per_window)
+    xd = dev(G.pad_wave(c.x))
+    out = _conv1_varlen_call(c, xd, c.lens, dt)
+    _check_masked(out, c.want(dt), c.lens, pool, run, c.note())
+    full = _conv1_varlen_call(c, xd, np.full(n, l), dt)
+    plain = _conv1_varlen_call(c, xd, None, dt, varlen=False)
+    assert torch.equal(_bits(full), _bits(plain)), run + ": lens == L differs from mode 1 of vm_conv1_fused_fwd"
+    assert_exact(plain[:, 1:-1], G.store(c.full, dt), "nlc", what=run + " (mode 1 on the zero-tailed input)")
+
+
+@pytest.mark.parametrize("dt", DT16)
+@pytest.mark.parametrize("kernel", ["pool", "conv1"])
+def test_varlen_ignores_what_no_valid_row_reads(kernel, dt):
+    """Pooled rows at or past lens[n] / pool are zero unconditionally: with NaN at every input position no valid output's taps reach
+    (gemm_exact.unreached_from: the reference's own tap range) the whole output, halo rows included, is bit-identical to the clean run."""
+    vm, tdt = DTYPES[dt]
+    if kernel == "pool":
+        c = G.pool_varlen_case(G.POOL_VARLEN_SHAPES[0])
+        n, l, cin, cout = c.shape
+        x = c.x.copy()
+        for i, ln in enumerate(c.lens):
+            x[i, G.unreached_from(int(ln), l, "pool"):] = np.nan
+        assert np.isnan(x).any() and np.array_equal(np.nan_to_num(x), c.x)
+        wf, _ = _prep(c.w, cin, cout, vm, tdt)
+        wfp = torch.empty_like(wf)
+        L().call("vm_pack_nt_weights", p(wf), 1, cout, cin, vm, p(wfp), stream())
+        for packed in (None, wfp):
+            clean = _pool_varlen_call(c, padded(c.x, tdt), c.lens, dt, wf, packed)
+            dirty = _pool_varlen_call(c, padded(x, tdt), c.lens, dt, wf, packed)
+            assert not torch.isnan(clean).any() and torch.equal(_bits(clean), _bits(dirty)), (dt, packed is not None)
+    else:
+        for pool in (2, 4):
+            c = G.conv1_varlen_case(G.CONV1_VARLEN_SHAPES[0], "small", pool)
+            n, l, f = c.shape
+            x = c.x.copy()
+            for i, ln in enumerate(c.lens):
+                x[i, G.unreached_from(int(ln), l, "conv1", pool):] = np.nan
+            assert np.isnan(x).any() and np.array_equal(np.nan_to_num(x), c.x)
+            clean = _conv1_varlen_call(c, dev(G.pad_wave(c.x)), c.lens, dt)
+            dirty = _conv1_varlen_call(c, dev(G.pad_wave(x)), c.lens, dt)
+            assert not torch.isnan(clean).any() and torch.equal(_bits(clean), _bits(dirty)), (dt, pool)
+
+
+@pytest.mark.parametrize("pool", [2, 4])
+@pytest.mark.parametrize("dt", DT16)
+def test_masked_chain_equals_each_recording_alone(dt, pool):
+    """vm_conv1_fused_fwd_varlen -> vm_conv_fwd_pool_varlen (lens // pool) -> vm_global_maxpool_fwd_varlen (lens // pool // 2) on one
+    bucket of mixed lengths against each recording alone in float64 (gemm_exact.ChainCase.alone): the zeros one launch writes are
+    exactly the SAME padding the next one needs.  The buffers between the launches are sentinel-filled except for their halo rows."""
+    vm, tdt = DTYPES[dt]
+    c = G.chain_case(pool, dt)
+    n, l, f, cout = G.CHAIN_SHAPE
+    l1, l2 = l // pool, l // pool // 2
+    tag = "chain %s pool %d" % (dt, pool)
+    act1, act2 = _sentinel(n, l1, f, tdt), _sentinel(n, l2, cout, tdt)
+    act1[:, 0], act1[:, -1] = 0, 0                      # the caller's halo rows: the second layer reads them
+    L().call("vm_conv1_fused_fwd_varlen", p(dev(G.pad_wave(c.x))), p(dev(c.w1)), p(dev(c.b1)), p(dev(c.s1)), p(dev(c.h1)),
+             p(dev(c.lens, torch.int32)), n, l, f, pool, vm, p(act1), stream())
+    wf, _ = _prep(c.w2, f, cout, vm, tdt)
+    L().call("vm_conv_fwd_pool_varlen", p(act1), p(wf), p(dev(c.b2)), p(dev(c.s2)), p(dev(c.h2)), p(dev(c.lens1, torch.int32)), n, l1, f,
+             cout, vm, p(act2), None, stream())
+    ws = torch.empty(L().query("vm_bn_drop_pool_gmax_workspace_bytes", n, cout) // 4, device="cuda")
+    gmax, gidx = _nan(n, cout), torch.full((n, cout), -7, dtype=torch.int32, device="cuda")
+    act2[:, 0], act2[:, -1] = 0, 0
+    L().call("vm_global_maxpool_fwd_varlen", p(act2), p(dev(c.lens2, torch.int32)), n, l2, cout, vm, p(gmax), p(gidx), p(ws), stream())
+    alone = [c.alone(i) for i in range(n)]
+    want1, want2 = np.zeros((n, l1, f)), np.zeros((n, l2, cout))
+    for i, (a1, a2, _, _) in enumerate(alone):
+        want1[i, :len(a1)], want2[i, :len(a2)] = a1, a2
+    assert_exact(act1[:, 1:-1], want1, "nlc", what=tag + " layer 1", note=G.varlen_note(c.lens, lambda ln, q: G.conv1_tile_class(l, pool, ln, q)))
+    assert_exact(act2[:, 1:-1], want2, "nlc", what=tag + " layer 2", note=G.varlen_note(c.lens1, lambda ln, q: G.pool_tile_class(l1, ln, q)))
+    assert_exact(gmax, np.stack([a[2] for a in alone]), "nc", what=tag + " gmax")
+    gi, want_i = gidx.cpu().numpy(), np.stack([a[3] for a in alone])
+    assert np.array_equal(gi, want_i), "%s gidx: first at %s" % (tag, np.argwhere(gi != want_i)[:1])

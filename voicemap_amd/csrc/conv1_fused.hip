@@ -231,8 +231,14 @@ __global__ __launch_bounds__(256) void conv1_fused_fwd_kernel(const float* __res
     const F1Role role = f1_role(wave, CT);
     const int64_t Lq = L / POOL;
     // varlen (inference, vm_conv1_fused_fwd_varlen): positions [0, Lv) form this window's valid pool groups; a pooled row at or past
-    // Lv / POOL is stored as zero (the next conv's SAME padding) and a 32-position tile wholly past Lv runs no MFMA
-    const int64_t Lv = (INFER && valid_len != nullptr) ? (int64_t)(valid_len[n] / POOL) * POOL : Lq * POOL;
+    // Lv / POOL is stored as zero (the next conv's SAME padding) and a 32-position tile wholly past Lv runs no MFMA.  A length past L
+    // counts as L: unclamped, Lv >= the end of a ragged last tile sends that tile down the predicate-free path, which stores all its
+    // 32 / POOL rows -- those past Lq land in the halo row and in the next window (past the buffer for the last one)
+    int64_t Lv = Lq * POOL;
+    if (INFER && valid_len != nullptr) {
+        const int64_t lv = (int64_t)(valid_len[n] / POOL) * POOL;
+        Lv = lv < Lv ? lv : Lv;
+    }
     const int ch_lo = split * cps;
     int ch_hi = ch_lo + cps;
     if (ch_hi > chunks) ch_hi = chunks;
