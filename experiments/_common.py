@@ -88,6 +88,14 @@ def device_resident(a, train):
         a.vad_summary = vad.summarise([ds.vad_counts])
         if rank == 0:
             print("--vad:", a.vad_summary)
+    sp = speed_policy(a)
+    if sp is not None:   # --speed-perturb: a resampled copy of every (trimmed) training file per factor (voicemap_amd/speed.py)
+        before = (len(ds), ds.num_classes())
+        ds = ds.speed_perturbed(sp)
+        a.speed_summary = {"factors": list(sp.factors), "files": [before[0], len(ds)], "speakers": [before[1], ds.num_classes()]}
+        if rank == 0:
+            print("--speed-perturb %s: %d files of %d speakers -> %d files of %d speakers"
+                  % (",".join("%g" % f for f in sp.factors), before[0], before[1], len(ds), ds.num_classes()))
     return ds
 
 
@@ -100,6 +108,20 @@ def add_vad_args(parser):
 def vad_policy(a):
     """The ``vad.VadPolicy`` of the script's ``--vad`` flags, None without them; exits when --vad comes without --device-data."""
     from voicemap_amd.vad import policy_from_args
+    return policy_from_args(a, need_device_data=True)
+
+
+def add_speed_args(parser):
+    """``--speed-perturb`` / ``--speed-same-speaker`` for a training script (off by default; the --device-data path only:
+    ``speed_policy`` checks)."""
+    from voicemap_amd.speed import add_speed_args as add
+    return add(parser)
+
+
+def speed_policy(a):
+    """The ``speed.SpeedPolicy`` of the script's ``--speed-perturb`` flags, None without them; exits when they come without
+    --device-data."""
+    from voicemap_amd.speed import policy_from_args
     return policy_from_args(a, need_device_data=True)
 
 

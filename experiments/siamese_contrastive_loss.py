@@ -13,7 +13,9 @@ def main(argv=None):
     p = C.base_parser(__doc__, batchsize=32, filters=32, embedding_dimension=128, dropout=0.05, epochs=25, pad=False)
     add_augment_args(p)
     C.add_vad_args(p)
+    C.add_speed_args(p)
     a = p.parse_args(argv)
+    C.speed_policy(a)   # --speed-perturb (off by default; needs --device-data): C.device_resident adds the copies; validation stays clean
     C.vad_policy(a)   # --vad (off by default; needs --device-data): C.device_resident trims the resident training set; validation stays as it is
     augment = policy_from_args(a, a.downsampling)   # --augment (off by default; needs --device-data): training batches only
     C.setup()

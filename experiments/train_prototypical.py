@@ -16,7 +16,9 @@ def main(argv=None):
     ap.add_argument("--episode-n", type=int, default=2, help="support windows per speaker")
     ap.add_argument("--episode-q", type=int, default=4, help="query windows per speaker")
     ap.add_argument("--proto-alpha", type=float, default=1.0, help="scale of the squared distance in the logits")
+    C.add_speed_args(ap)
     a = ap.parse_args(argv)
+    C.speed_policy(a)   # --speed-perturb (off by default; needs --device-data): C.device_resident adds the copies; validation stays clean
     if a.hard_fraction > 0:
         raise SystemExit("--hard-fraction mines PAIRS (voicemap_amd/mining.py); episodes are drawn uniformly")
     C.setup()

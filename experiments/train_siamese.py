@@ -15,7 +15,9 @@ def main(argv=None):
                          "on the raw 16 kHz window (BASELINE.json config 4, not in the reference)")
     add_augment_args(ap)
     C.add_vad_args(ap)
+    C.add_speed_args(ap)
     a = ap.parse_args(argv)
+    C.speed_policy(a)   # --speed-perturb (off by default; needs --device-data): C.device_resident adds the copies; validation stays clean
     C.vad_policy(a)   # --vad (off by default; needs --device-data): C.device_resident trims the resident training set; validation stays as it is
     if a.frontend == "logmel":
         a.downsampling = 1   # the front-end works on the raw window: no decimation, no whitening

@@ -18,7 +18,9 @@ def main(argv=None):
     ap.add_argument("--margin", type=float, default=0.2, help="the hinge's margin on the euclidean distances")
     ap.add_argument("--soft-margin", action="store_true", help="softplus(d_ap - d_an) instead of the hinge (--margin is then unused)")
     ap.add_argument("--mining", choices=TripletLoss.MININGS, default="hard", help="batch hard or batch all")
+    C.add_speed_args(ap)
     a = ap.parse_args(argv)
+    C.speed_policy(a)   # --speed-perturb (off by default; needs --device-data): C.device_resident adds the copies; validation stays clean
     if a.hard_fraction > 0:
         raise SystemExit("--hard-fraction mines PAIRS over a cached corpus (voicemap_amd/mining.py); triplets are mined inside every batch")
     C.setup()

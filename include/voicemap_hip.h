@@ -209,6 +209,23 @@ int vm_vad_frames(const void* audio, const int64_t* offsets, const int64_t* lens
 int vm_vad_compact(const void* audio, const int64_t* offsets, const int64_t* lens, const int64_t* frame_base, const void* mask,
                    const int64_t* dst, const int64_t* new_offsets, int64_t n_utts, int frame, void* out, void* stream);
 
+/* ---- speed perturbation of the resident int16 corpus (voicemap_amd/csrc/speed.hip; voicemap_amd/speed.py resample_reference is the
+ * numpy statement, matched bit for bit): an integer polyphase resampler by U / D, U output samples per D input samples.  Utterance u:
+ * the lens[u] >= 0 int16 samples x[0..len-1] at audio[offsets[u]]; taps: U T int32 on the device, c = U T / 2;
+ *   n_out  = ceil(len U / D)
+ *   acc[m] = sum over 0 <= k < len with 0 <= m D + c - k U < U T of taps[m D + c - k U] x[k]                 (int64)
+ *   out[new_offsets[u] + m] = clip((acc[m] + (1 << (shift - 1))) >> shift, -32768, 32767)   (arithmetic shift; shift = 0 adds nothing)
+ * out_base: n_utts + 1 entries ON THE DEVICE, the exclusive cumulative sum of n_out (the host knows every length in closed form: no
+ * read-back); new_offsets[u]: where utterance u's output starts in out, in any order.  phase_abs_max: an upper bound on
+ * max_p sum_i |taps[p + i U]|, below 2^47; the accumulator is 32 bits wide only where it proves that exact (phase_abs_max < 2^16) and 64
+ * bits wide otherwise.  One launch over tiles of the flat output list (a fixed grid in x, a tile's utterance found by binary search of
+ * out_base), no atomics, bit-reproducible; no sample outside [offsets[u], offsets[u] + lens[u]) is read and nothing outside the n_out
+ * outputs of an utterance is written.  1 <= U, D, T <= 64, 0 <= shift <= 30, else an error and no launch; n_utts == 0 returns without a
+ * launch. */
+int vm_resample_i16(const void* audio, const int64_t* offsets, const int64_t* lens, const int64_t* out_base, int64_t n_utts,
+                    int U, int D, const int32_t* taps, int T, int shift, int64_t phase_abs_max,
+                    const int64_t* new_offsets, void* out, void* stream);
+
 /* ---- a1 block 1: Conv1D(filters, 32, padding='same', activation='relu')  (voicemap/models.py:13-16) --
  * x: (n_windows, L + 31) fp32 from vm_decimate_whiten; w: (32, 1, F) fp32 Keras layout; bias (F).
  * z: (n_windows, L, F) `dtype`, = relu(conv + bias).  If stat_sum != NULL also writes per-(window, tile)

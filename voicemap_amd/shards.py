@@ -179,7 +179,17 @@ class ShardedSpeechDataset(LibriSpeechDataset):
 
     _vad = None   # the policy of a ``voiced()`` dataset (then ``_raw_length`` holds the files' lengths in the shards)
 
+    _speed = None   # the policy of a ``speed_perturbed()`` dataset (then ``_speed_base`` is the dataset it was made from, ``_speed_src``
+    #                 each row's file there and ``_speed_k`` its factor's 1-based position, 0 for the originals)
+
     def _pcm(self, index):
+        if self._speed is not None:
+            k, src = int(self._speed_k[index]), int(self._speed_src[index])
+            if k == 0:
+                return self._speed_base._pcm(src)
+            from .speed import resample_reference
+            (U, D), taps = self._speed.ratios[k - 1], self._speed_taps[k - 1]
+            return resample_reference(np.asarray(self._speed_base._pcm(src)), U, D, taps, self._speed.shift)
         r = self.df.iloc[index]
         if self._vad is None:
             return self._maps[int(r['shard'])][int(r['offset']):int(r['offset']) + int(r['length'])]
@@ -195,14 +205,29 @@ class ShardedSpeechDataset(LibriSpeechDataset):
         """Upload all shards once (int16, back to back); returns the 1-D device tensor."""
         import torch
         if self.device_audio is None:
-            if self.speaker_shard is None and self._vad is None:
-                parts = [torch.from_numpy(np.array(m, dtype=np.int16, copy=True)) for m in self._maps]
-            else:
-                # only this rank's recordings (of a voiced() dataset: the trimmed ones), back to back in index order (the layout
-                # global_offset describes)
-                parts = [torch.from_numpy(np.array(self._pcm(i), dtype=np.int16, copy=True)) for i in range(len(self.df))]
+            parts = [torch.from_numpy(p) for p in self._host_parts()]
             self.device_audio = torch.cat(parts).to(device) if parts else torch.zeros(0, dtype=torch.int16, device=device)
         return self.device_audio
+
+    def _host_parts(self):
+        """The int16 arrays whose concatenation is the device buffer ``global_offset`` describes."""
+        if self._speed is not None:
+            # the base dataset's buffer, then the host-built copies in row order
+            n0 = int(np.count_nonzero(self._speed_k == 0))
+            return self._speed_base._host_parts() + [np.array(self._pcm(i), dtype=np.int16, copy=True) for i in range(n0, len(self.df))]
+        if self.speaker_shard is None and self._vad is None:
+            return [np.array(m, dtype=np.int16, copy=True) for m in self._maps]
+        # only this rank's recordings (of a voiced() dataset: the trimmed ones), back to back in index order (the layout
+        # global_offset describes)
+        return [np.array(self._pcm(i), dtype=np.int16, copy=True) for i in range(len(self.df))]
+
+    def _buffer_samples(self) -> int:
+        """The size of the device buffer, resident or not."""
+        if self.device_audio is not None:
+            return int(self.device_audio.numel())
+        if self.speaker_shard is None and self._vad is None:
+            return int(sum(len(m) for m in self._maps))
+        return int(self.file_length.sum())
 
     def voiced(self, policy):
         """This dataset with the pauses trimmed out of every file (voicemap_amd/vad.py): a dataset of the same class and API whose
@@ -214,6 +239,8 @@ class ShardedSpeechDataset(LibriSpeechDataset):
         trimmed files.  The result's ``vad_counts`` are the counts ``vad.summarise`` adds up.  This dataset is left as it is."""
         import copy
         from . import vad
+        if self._speed is not None:
+            raise ValueError('a speed-perturbed dataset cannot be trimmed: trim first (voiced()), then perturb')
         if self._vad is not None:
             raise ValueError('this dataset is already trimmed')
         policy = policy.with_min_keep(self.fragment_length)
@@ -229,6 +256,70 @@ class ShardedSpeechDataset(LibriSpeechDataset):
             new.vad_counts = vad.reference_counts(refs, self.file_length)
         new.global_offset, new.file_length = offsets, lens
         new.df = self.df.assign(length=lens, seconds=lens * 1.0 / LIBRISPEECH_SAMPLING_RATE)
+        new._build_sampling_index()
+        return new
+
+    def speed_perturbed(self, policy):
+        """This dataset with a resampled copy of every file per speed factor of ``policy`` (voicemap_amd/speed.py ``SpeedPolicy``): a
+        dataset of the same class and API.  Rows 0 .. n - 1 are this dataset's files, untouched, with their ids and their
+        ``global_offset`` into the first part of the new buffer (this dataset's buffer, byte for byte); the kept copies of the first
+        factor follow in file order, then the second's.  ``file_length``, ``global_offset`` and the ``length`` / ``seconds`` columns
+        describe the new buffer; a ``speed`` column holds the factor (1.0 for the originals); the ``shard`` / ``offset`` columns of a
+        copy stay its source's.  With ``policy.new_speakers`` a copy's ``speaker_id`` is k B + id -- k the factor's 1-based position, B
+        the smallest power of ten above the largest id -- so ``unique_speakers`` and ``num_classes()`` grow with the copies; without
+        it the ids are kept, and a same-speaker pair may then be a file and its own copy.  Without ``pad`` a copy no longer than the
+        fragment (``seconds > fragment_seconds`` fails) is dropped: the device path cannot pad.  ``_pcm`` / ``_load`` of a copy are
+        ``resample_reference`` of the source file on the host -- bit for bit what the device holds.  With a resident corpus
+        (``to_device()`` before) the copies are made on the device, one launch per factor, straight into the new buffer (while it is
+        built this dataset's buffer and the new one both exist; the result does not hold on to this dataset's); without one
+        the lengths come from the closed form and ``to_device()`` of the result uploads host-built copies.  It works on a ``voiced()``
+        dataset (trim first, then perturb); ``voiced()`` of the result and a second ``speed_perturbed`` are refused.  This dataset is
+        left as it is."""
+        import copy
+        from . import speed
+        if self._speed is not None:
+            raise ValueError('this dataset is already speed-perturbed')
+        n, L = len(self.df), self.file_length
+        ids = self.df['speaker_id'].values
+        B = 1
+        while n and B <= int(ids.max()):
+            B *= 10
+        lens, srcs, ks, taps = [L], [np.arange(n, dtype=np.int64)], [np.zeros(n, dtype=np.int64)], []
+        for k, (U, D) in enumerate(policy.ratios, start=1):
+            nl = speed.output_length(L, U, D)
+            keep = np.flatnonzero((nl > 0) if self.pad else (nl * 1.0 / LIBRISPEECH_SAMPLING_RATE > self.fragment_seconds))
+            lens.append(nl[keep])
+            srcs.append(keep.astype(np.int64))
+            ks.append(np.full(len(keep), k, dtype=np.int64))
+            taps.append(policy.taps(k - 1))
+        base_total = self._buffer_samples()
+        counts = [len(x) for x in lens]
+        new, base = copy.copy(self), copy.copy(self)
+        base.device_audio = None   # the host view of this dataset: the result does not keep this dataset's device buffer alive
+        new._speed, new._speed_base, new._speed_taps, new._cdf_cache = policy, base, taps, None
+        new._speed_src, new._speed_k = np.concatenate(srcs), np.concatenate(ks)
+        new.file_length = np.concatenate(lens).astype(np.int64)
+        copy_lens = new.file_length[n:]
+        new.global_offset = np.concatenate([self.global_offset, base_total + np.cumsum(copy_lens) - copy_lens]).astype(np.int64)
+        if self.device_audio is not None:
+            import torch
+            audio = torch.empty(base_total + int(copy_lens.sum()), dtype=torch.int16, device=self.device_audio.device)
+            audio[:base_total].copy_(self.device_audio)
+            at = base_total
+            for k, (U, D) in enumerate(policy.ratios, start=1):
+                size = int(lens[k].sum())
+                speed.resample(self.device_audio, self.global_offset[srcs[k]], L[srcs[k]], U, D, taps[k - 1], policy.shift,
+                               out=audio[at:at + size])
+                at += size
+            new.device_audio = audio
+        factor = np.concatenate([np.ones(n)] + [np.full(c, f) for c, f in zip(counts[1:], policy.factors)])
+        sid = ids[new._speed_src] + (new._speed_k * B if policy.new_speakers else 0)
+        df = self.df.iloc[new._speed_src].reset_index(drop=True)
+        new.df = df.assign(id=df.index.values, speaker_id=sid, length=new.file_length,
+                           seconds=new.file_length * 1.0 / LIBRISPEECH_SAMPLING_RATE, speed=factor)
+        new.unique_speakers = len(np.unique(sid))
+        d = new.df.to_dict()
+        new.datasetid_to_filepath, new.datasetid_to_speaker_id, new.datasetid_to_sex = d['filepath'], d['speaker_id'], d['sex']
         new._build_sampling_index()
         return new
 
