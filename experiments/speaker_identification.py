@@ -7,6 +7,7 @@ EER and thresholds.
         [--vad --vad-threshold-db 25 --vad-hang 10 --vad-min-run 3 --vad-frame-ms 10]
         [--backend plda --plda-train train|validation --plda-train-set train-clean-100 --lda-dim D --no-length-norm]
         [--score-norm none|s-norm|as-norm --cohort-set train-clean-100 --cohort-size 5000 --top-k 300]
+        [--dcf P[,CMISS,CFA] ...] [--calibrate --calib-prior 0.5]
 Without --test-set (or with the same set) the enrolled set is also the test set: leave-one-out (every utterance is scored against its own
 speaker's model built from the speaker's OTHER utterances), or with --per-speaker N a seeded choice of N utterances per speaker is
 enrolled and the others are the queries.  With another --test-set its utterances are scored against the enrolled set's models (its
@@ -21,24 +22,44 @@ fitted on the training set (--plda-train train: --plda-train-set, a further gene
 against a cohort (enrolment.model_score_norm): a seeded random subset of --cohort-set's files (a third generated set with --synthetic),
 as-norm over the --top-k most alike per side; with --backend plda the cohort is projected by the same model.  The trial figures and
 thresholds of the row are then those of the normalised scores and the row gains score_norm / top_k / cohort_size; the identification
-figures rank by the raw score.  Without it the printed row is what it was."""
+figures rank by the raw score.  Without it the printed row is what it was.
+--dcf P[,CMISS,CFA] (repeatable, off by default; the option of experiments/verification_accuracy.py) adds the exact minimum detection
+cost of the row's model trials at each operating point (trial_min_dcf_<point>, with its threshold).  --calibrate [--calib-prior P]
+(off by default) needs a --test-set other than the enrolled set -- a calibration is fitted on other data than it is judged on -- and
+fits llr = a s + b (enrolment.fit_model_calibration) on the enrolled set's own leave-one-out (or --per-speaker) trials, the trials
+enrol_best_threshold comes from; the row gains calib_a / calib_b / calib_prior / calib_converged / calib_iterations / calib_passes, Cllr
+of both sets (enrol_cllr, test_cllr) and per --dcf point (without one: (P, 1, 1) at the calibration prior) the test set's actDCF at the
+Bayes threshold, that threshold and FAR / FRR there, beside the minimum.  With --backend plda the scores calibrated are the PLDA
+scores; with --score-norm the normalised ones (the fit uses the enrolled set's statistics, the test figures the test set's).  Under
+leave-one-out the fit's models hold n - 1 rows of a speaker and the test's hold all n: the calibration moves between models of
+slightly different sizes, exactly as the threshold transfer above already does.  A fitted slope a >= 0 has no Bayes threshold in
+score units: the script says "no actDCF" and the minimum costs stand alone.  Without these options the printed row is what it was."""
 import argparse
 import json
 
-from voicemap_amd import enrolment, retrieval
+from experiments.verification_accuracy import parse_dcf, point_name
+from voicemap_amd import enrolment, retrieval, verification
 from voicemap_amd.librispeech import LibriSpeechDataset, SyntheticSpeechDataset
 from voicemap_amd.utils import BatchPreProcessor, preprocess_instances
 from voicemap_amd.vad import add_vad_args, policy_from_args
 
 
 def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=None, whole_utterance=False, seed=0, vad=None,
-             backend="none", plda_train=None, lda_dim=None, length_norm=True, score_norm="none", cohort=None, top_k=300):
+             backend="none", plda_train=None, lda_dim=None, length_norm=True, score_norm="none", cohort=None, top_k=300, dcf=(),
+             calibrate=False, calib_prior=0.5):
     """The result row: identification and model-trial figures of ``test_set`` (None: the enrolled set itself) against the models of
     ``enrol_set``.  ``vad`` (a ``vad.VadPolicy``): both sets are embedded with their pauses trimmed out.  ``backend`` "plda": a
     ``plda.PldaModel`` is fitted on the embeddings of ``plda_train`` (a dataset; None: the enrolled set) with ``lda_dim`` /
     ``length_norm``, both sets are projected by it and the models are multi-session PLDA models (``distance`` is not used).
     ``score_norm`` "s-norm" / "as-norm": the model trials are normalised against the embeddings of ``cohort`` (a dataset; projected by
-    the back end where there is one), as-norm over the ``top_k`` most alike per side."""
+    the back end where there is one), as-norm over the ``top_k`` most alike per side.  ``dcf``: detection-cost points for the row's
+    trials; ``calibrate`` (needs a ``test_set``): fit llr = a s + b on the enrolled set's own trials at ``calib_prior`` and report Cllr
+    and, per point, actDCF on the test set (module docstring)."""
+    dcf = verification.as_dcf_points(dcf)
+    if calibrate and test_set is None:
+        raise ValueError("calibrate needs a test set other than the enrolled set")
+    if calibrate and not dcf:
+        dcf = [(float(calib_prior), 1.0, 1.0)]
     wu = {"whole_utterance": True} if whole_utterance else {}
     if vad is not None:
         wu["vad"] = vad
@@ -65,7 +86,7 @@ def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=No
             cc = back.project(cc)
         k = None if score_norm == "s-norm" else top_k
         nt = enrolment.model_score_norm(models, ct, cc, top_k=k)
-    mt = enrolment.model_trial_metrics(models, ct, norm=nt)
+    mt = enrolment.model_trial_metrics(models, ct, dcf_points=dcf, norm=nt)
     cmc = ident["cmc"]
     row = {"distance": distance, "speakers": models.S, "per_speaker": per_speaker, "leave_one_out": ident["leave_one_out"],
            "queries": ident["n_queries"], "unranked": ident["n_unranked"], "rank1_accuracy": ident["rank1_accuracy"],
@@ -79,6 +100,22 @@ def evaluate(net, enrol_set, test_set, pre, distance="euclidean", per_speaker=No
         at = enrolment.model_trial_accuracy_at_threshold(models, ct, me["best_threshold"], norm=nt)
         row.update(enrol_best_threshold=me["best_threshold"], test_balanced_accuracy_at_enrol_threshold=at["balanced_accuracy"],
                    test_far=at["far"], test_frr=at["frr"])
+    costs = mt.get("dcf", [])
+    if calibrate:   # fitted on the enrolled set's own trials (ne), judged on the test set's (nt)
+        cal = enrolment.fit_model_calibration(models, ce, prior=calib_prior, norm=ne)
+        row.update(calib_a=cal.a, calib_b=cal.b, calib_prior=cal.prior, calib_converged=cal.converged, calib_iterations=cal.iterations,
+                   calib_passes=cal.passes, enrol_cllr=cal.cllr_train, test_cllr=enrolment.model_cllr(models, ct, cal, norm=nt))
+        try:
+            costs = enrolment.model_detection_costs(models, ct, cal, dcf, norm=nt, metrics=mt)
+        except ValueError as e:   # a >= 0: there is no Bayes threshold in score units; the minimum costs stand alone
+            print("--calibrate: no actDCF:", e)
+    for d in costs:
+        name = point_name((d["p_target"], d["c_miss"], d["c_fa"]))
+        row["trial_min_dcf_" + name], row["trial_min_dcf_threshold_" + name] = d["min_dcf"], d["min_dcf_threshold"]
+        if calibrate:
+            nan = float("nan")
+            row.update({"test_act_dcf_" + name: d.get("act_dcf", nan), "test_act_threshold_" + name: d.get("act_threshold", nan),
+                        "test_far_at_act_" + name: d.get("far_at_act", nan), "test_frr_at_act_" + name: d.get("frr_at_act", nan)})
     if back is not None:
         row.update(backend="plda", plda_dim=back.D, lda_dim=back.A1.shape[0], length_norm=back.length_norm,
                    plda_train="validation" if plda_train is None else "train", model_rows_max=models.n_max)
@@ -113,6 +150,10 @@ def _parser():
     p.add_argument("--cohort-set", default="train-clean-100", help="the cohort's subset (a third generated set with --synthetic)")
     p.add_argument("--cohort-size", type=int, default=5000, help="files of the cohort set taken (seeded random subset)")
     p.add_argument("--top-k", type=int, default=300, help="as-norm: cohort models / rows per side")
+    p.add_argument("--dcf", action="append", default=[], type=parse_dcf, metavar="P[,CMISS,CFA]",
+                   help="a detection-cost operating point for the model trials (repeatable)")
+    p.add_argument("--calibrate", action="store_true", help="fit llr = a s + b on the enrolled set's trials; Cllr and actDCF on --test-set")
+    p.add_argument("--calib-prior", type=float, default=0.5, help="the target prior of the calibration fit")
     add_vad_args(p)   # --vad ...: off by default; every set embedded, the cohort included, is trimmed first
     return p
 
@@ -121,9 +162,11 @@ def main(argv=None):
     p = _parser()
     a = p.parse_args(argv)
     vad = policy_from_args(a)
+    same = a.test_set is None or a.test_set == a.enrol_set
+    if a.calibrate and same:
+        p.error("--calibrate needs a --test-set other than the enrolled set: a calibration is judged on other data than it is fitted on")
     from experiments._common import setup
     rank, _ = setup()
-    same = a.test_set is None or a.test_set == a.enrol_set
     if a.synthetic:
         from voicemap_amd import models
         enrol_set = SyntheticSpeechDataset(num_speakers=20, files_per_speaker=8, seconds=a.n_seconds, stochastic=False, seed=1,
@@ -156,7 +199,7 @@ def main(argv=None):
     pre = BatchPreProcessor("siamese", preprocess_instances(a.downsampling))
     row = evaluate(net, enrol_set, test_set, pre, a.distance, a.per_speaker, a.whole_utterance, a.seed, vad=vad, backend=a.backend,
                    plda_train=plda_train, lda_dim=a.lda_dim, length_norm=not a.no_length_norm, score_norm=a.score_norm, cohort=cohort,
-                   top_k=a.top_k)
+                   top_k=a.top_k, dcf=a.dcf, calibrate=a.calibrate, calib_prior=a.calib_prior)
     row.update(enrol_set="synthetic" if a.synthetic else a.enrol_set,
                test_set=("synthetic" if a.synthetic else a.enrol_set) if same else a.test_set)
     if rank == 0:

@@ -1139,6 +1139,36 @@ int vm_plda_speaker_trial_hist_norm(const float* q, const int32_t* q_label, int6
                                     int n_max, int leave_one_out, const int64_t* host_windows, int n_windows, int bins, const float* mu_q,
                                     const float* rsig_q, const float* mu_s, const float* rsig_s, const float* mu_own,
                                     const float* rsig_own, uint64_t* hist, void* ws, void* stream);
+/* Calibration of speaker-model trials (csrc/enrol_tile.hpp CALIB mode, csrc/calib_terms.hpp, voicemap_amd/enrolment.py
+ * fit_model_calibration / model_cllr / model_detection_costs): vm_pair_calib_sums' sums over the trials of vm_speaker_trial_hist.
+ * Trials, scores, leave-one-out, the not-a-trial rule and the limits are exactly those of vm_speaker_trial_hist
+ * (vm_plda_speaker_trial_hist): every (m, s) whose model exists is a trial, class 0 (target) iff s == q_label[m], class 1 otherwise; s
+ * is the fp32 score of that entry point, bit-identical to vm_[plda_]speaker_identify's `scores` matrix.  A cell that is not a trial
+ * -- no model, row >= M, model >= S -- adds nothing anywhere.
+ * Statistics.  mu_q, rsig_q, mu_s, rsig_s, mu_own, rsig_own all NULL: the raw scores.  Otherwise they are
+ * vm_[plda_]speaker_trial_hist_norm's, under its rules (mu_own / rsig_own NULL together, NULL without leave_one_out, needed with it),
+ * and s is replaced by its normalised score s', in exactly that fp32 order.
+ * Per-trial terms and the eight sums per class: exactly vm_pair_calib_sums' (float64, every operation rounded on its own); a trial
+ * whose s is NaN or infinite adds to n_skipped alone.  calib (2, 8) float64 on the device is WRITTEN, not accumulated (row ranges and
+ * ranks are added by the caller):  n, n_skipped, L, P0, P1, W0, W1, W2.  The counts are exact.  M == 0 writes zeros.
+ * Determinism.  The grid is the histogram's: ceil(M / 64) query tiles x vm_speaker_trial_calib_sums_splits(M, S) splits of the 64-model
+ * tiles (0 if M or S <= 0; the same for both back ends).  Per-lane float64 accumulators (u32 counts) carried over the workgroup's tiles
+ * in ascending order, a fixed shuffle tree per wave, the four waves in order, one column of partials per workgroup in ws (zeros where a
+ * split holds no tile), and vm_pair_calib_sums' fixed-order final sum in a second launch.  No floating-point atomics: bit-identical
+ * from run to run for the same arguments; a row range cut into several calls sums in another order (within rounding).
+ * a, b, tau finite; calib 8-byte aligned.  Every bad argument is an error before any launch.  ws >= the matching *_workspace_bytes. */
+int64_t vm_speaker_trial_calib_sums_splits(int64_t M, int64_t S);
+int64_t vm_speaker_trial_calib_sums_workspace_bytes(int64_t M, int E, int64_t S);
+int vm_speaker_trial_calib_sums(const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
+                                const int32_t* count, int64_t S, int kind, int leave_one_out, const float* mu_q, const float* rsig_q,
+                                const float* mu_s, const float* rsig_s, const float* mu_own, const float* rsig_own, double a, double b,
+                                double tau, double* calib, void* ws, void* stream);
+int64_t vm_plda_speaker_trial_calib_sums_workspace_bytes(int64_t M, int D, int64_t S);
+int vm_plda_speaker_trial_calib_sums(const float* q, const int32_t* q_label, int64_t M, int P, int D, const double* sums,
+                                     const int32_t* count, int64_t S, const double* A, const double* beta, const double* C,
+                                     const double* G, int n_max, int leave_one_out, const float* mu_q, const float* rsig_q,
+                                     const float* mu_s, const float* rsig_s, const float* mu_own, const float* rsig_own, double a, double b,
+                                     double tau, double* calib, void* ws, void* stream);
 
 /* ---- a10 / f4: log-mel front-end and the 2-D CNN encoder variant (BASELINE.json config 4) -------------------
  * NOT in the reference (nothing to cite under /root/reference); the specification is DESIGN.md section 9 and the

@@ -139,7 +139,9 @@ def cllr_of(sums: np.ndarray) -> float:
 class Calibration:
     """llr = a s + b, fitted at ``prior`` on the scores ``score`` (``normalised``: cohort-normalised).  ``iterations`` Newton steps
     taken in ``passes`` passes over the trials; ``converged``: the stopping rule of ``fit_calibration`` was met, with ``stop`` its
-    constant; ``objective`` = C(a, b) and ``cllr_train`` = Cllr on the trials it was fitted on."""
+    constant; ``objective`` = C(a, b) and ``cllr_train`` = Cllr on the trials it was fitted on.  ``trials``: "pair" (the all-pairs
+    trials of this module) or "model" (the speaker-model trials of ``enrolment.fit_model_calibration``); the evaluators of either kind
+    refuse a calibration of the other."""
     a: float
     b: float
     prior: float
@@ -151,6 +153,7 @@ class Calibration:
     cllr_train: float
     stop: float = NEWTON_STOP
     passes: int = 0
+    trials: str = "pair"
 
 
 def llr(calibration: Calibration, s) -> np.ndarray:
@@ -158,7 +161,8 @@ def llr(calibration: Calibration, s) -> np.ndarray:
     return calibration.a * np.asarray(s, dtype=np.float64) + calibration.b
 
 
-def _fit(sums_fn: Callable[[float, float, float], np.ndarray], prior: float, score: str, normalised: bool, max_iter: int) -> Calibration:
+def _fit(sums_fn: Callable[[float, float, float], np.ndarray], prior: float, score: str, normalised: bool, max_iter: int,
+         trials: str = "pair") -> Calibration:
     if not 0.0 < prior < 1.0:
         raise ValueError("the prior must lie in (0, 1)")
     tau = logit(prior)
@@ -203,7 +207,7 @@ def _fit(sums_fn: Callable[[float, float, float], np.ndarray], prior: float, sco
             break
     S0 = sums_fn(a, b, 0.0)
     passes += 1
-    return Calibration(a, b, prior, score, normalised, it, converged, C, cllr_of(S0), NEWTON_STOP, passes)
+    return Calibration(a, b, prior, score, normalised, it, converged, C, cllr_of(S0), NEWTON_STOP, passes, trials)
 
 
 def fit_calibration_numpy(scores, target, prior: float = 0.5, max_iter: int = 50, score: str = "array") -> Calibration:
@@ -224,7 +228,10 @@ def fit_calibration(cache, prior: float = 0.5, score: str = "euclidean", model=N
 
 
 def cllr(cache, calibration: Calibration, model=None, norm=None) -> float:
-    """Cllr of the calibrated scores of all pair trials of ``cache`` (one pass at tau = 0): 0 is perfect, 1 is what a = b = 0 gives."""
+    """Cllr of the calibrated scores of all pair trials of ``cache`` (one pass at tau = 0): 0 is perfect, 1 is what a = b = 0 gives.
+    A calibration of speaker-model trials (``trials == "model"``) is refused: ``enrolment.model_cllr`` takes those."""
+    if getattr(calibration, "trials", "pair") != "pair":
+        raise ValueError("the calibration was fitted on %s trials, not pair trials" % calibration.trials)
     if (norm is not None) != calibration.normalised:
         raise ValueError("the calibration was fitted on %s scores" % ("normalised" if calibration.normalised else "raw"))
     return cllr_of(calib_sums(cache, calibration.a, calibration.b, 0.0, calibration.score, model, norm))

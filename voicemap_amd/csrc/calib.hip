@@ -7,38 +7,21 @@
 // dist[i][j] of vm_pairdist_argmin, and with mu / rsig it is replaced by vh_norm's normalised score.  Only reference tiles that hold
 // some j > i are visited and the pairs j <= i are masked.
 //
-// Per trial, in float64, every operation rounded on its own (cal_terms: no fma contraction, so numpy's float64 follows it):
+// Per trial, in float64, every operation rounded on its own (cal_terms, calib_terms.hpp -- shared with the speaker-model path of
+// enrol_tile.hpp: no fma contraction, so numpy's float64 follows it):
 //   z = a s + b + tau;  t = -z (target) or +z;  e = exp(-|t|);  loss = max(t, 0) + log1p(e);
 //   p = 1 / (1 + e) if t >= 0 else e / (1 + e);  w = e / (1 + e)^2
 // and per class the eight doubles  n, n_skipped, L = sum loss, P0 = sum p, P1 = sum p s, W0 = sum w, W1 = sum w s, W2 = sum (w s) s.
 // A trial whose s is NaN or infinite adds to n_skipped alone.
 //
 // Reduction, in a fixed order throughout: per-lane double accumulators (u32 counts), a shuffle tree per wave, the eight waves of the
-// workgroup in order, one partial row per workgroup in the workspace; a second launch sums the partials (lane l takes partials l,
-// l + 64, ... ascending, then the shuffle tree).  No floating-point atomics: the (2, 8) result is a function of the inputs and the
-// grid alone, bit-identical from run to run.
+// workgroup in order, one partial row per workgroup in the workspace; a second launch (calib_final_kernel, calib_terms.hpp) sums the
+// partials (lane l takes partials l, l + 64, ... ascending, then the shuffle tree).  No floating-point atomics: the (2, 8) result is a
+// function of the inputs and the grid alone, bit-identical from run to run.
+#include "calib_terms.hpp"
 #include "score_tile.hpp"
 
 namespace vm {
-
-constexpr int CAL_TERMS = 8, CAL_SUMS = 2 * CAL_TERMS;
-
-// the per-trial terms of the file comment; s is finite
-__device__ inline void cal_terms(double s, bool tgt, double a, double b, double tau, double (&x)[6]) {
-#pragma clang fp contract(off)
-    const double z = a * s + b + tau;
-    const double t = tgt ? -z : z;
-    const double e = exp(-fabs(t));
-    const double d = 1.0 + e;
-    const double w = e / (d * d);
-    const double p = t >= 0.0 ? 1.0 / d : e / d;
-    x[0] = fmax(t, 0.0) + log1p(e);
-    x[1] = p;
-    x[2] = p * s;
-    x[3] = w;
-    x[4] = w * s;
-    x[5] = (w * s) * s;
-}
 
 // grid (query blocks of 64 rows of [row_lo, row_lo + M), splits of the block's reference tiles); 512 threads.  part (CAL_SUMS,
 // gridDim.x * gridDim.y) doubles: every workgroup writes its column (zeros where its split holds no tile).
@@ -174,17 +157,6 @@ __global__ __launch_bounds__(512) void pair_calib_kernel(const float* __restrict
         const int64_t n_part = (int64_t)gridDim.x * gridDim.y;
         part[tid * n_part + (int64_t)blockIdx.y * gridDim.x + blockIdx.x] = v;
     }
-}
-
-// one workgroup of CAL_SUMS waves: wave q sums row q of part (CAL_SUMS, n_part) -- lane l the partials l, l + 64, ... ascending, then
-// the shuffle tree -- and lane 0 stores sums[q].  n_part == 0 writes zeros.
-__global__ __launch_bounds__(64 * CAL_SUMS) void calib_final_kernel(const double* __restrict__ part, int64_t n_part,
-                                                                     double* __restrict__ sums) {
-    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
-    double v = 0.0;
-    for (int64_t k = lane; k < n_part; k += 64) v += part[q * n_part + k];
-    v = wave_sum_d(v);
-    if (lane == 0) sums[q] = v;
 }
 
 // the workgroups before the triangle empties the late blocks' ranges: vh_splits' target (verif.hip)

@@ -20,13 +20,13 @@
 // compacted in order (ballot + prefix) and added one after the other, thread e owning component e.  en_proto_kernel: the shared models
 // P (S, E) and their norms.  en_own_kernel: one thread per query row scores the row against its OWN speaker (the leave-one-out model
 // differs from the shared one, so that one score is computed from the sums rather than patched).  The tile kernel is enrol_tile.hpp's
-// model_tile_kernel<EnScore<KIND>, HIST, NORM>, the one kernel of "rows against speaker models", shared with plda_enrol.hip: a tile of 64
+// model_tile_kernel<EnScore<KIND>, MODE, NORM>, the one kernel of "rows against speaker models", shared with plda_enrol.hip: a tile of 64
 // query rows x 64 models, both staged through LDS as float64 in chunks of 32 components, thread (tq, ts) holding 4 x 4 accumulators; the
 // own-speaker cell takes en_own_kernel's score.  This file gives it the score policy EnScore<KIND> -- the operand P, the norms as row
 // and model terms, "a model has n > 0 rows", en_acc / en_finish (enrol_score.hpp, shared with reseg.hip) -- and the launchers of
 // enrol_tile.hpp the call EnCall: the argument checks, the scratch layout and the two staging launches.  vm_speaker_identify,
-// vm_speaker_trial_hist and vm_speaker_trial_hist_norm are model_identify / model_trial_hist on an EnCall: one template, one en_acc /
-// en_finish, so the three entry points score bit-identically.
+// vm_speaker_trial_hist, vm_speaker_trial_hist_norm and vm_speaker_trial_calib_sums are model_identify / model_trial_hist /
+// model_trial_calib on an EnCall: one template, one en_acc / en_finish, so the four entry points score bit-identically.
 #include "enrol_tile.hpp"
 
 namespace vm {
@@ -270,4 +270,22 @@ extern "C" int vm_speaker_trial_hist_norm(const float* q, const int32_t* q_label
     const vm::EnNorm n{mu_q, rsig_q, mu_s, rsig_s, mu_own, rsig_own};
     return vm::model_trial_hist("vm_speaker_trial_hist_norm", vm::EnCall{q, q_label, M, E, sums, msum, count, S, kind, leave_one_out},
                                 host_windows, n_windows, bins, hist, &n, ws, stream);
+}
+
+extern "C" int64_t vm_speaker_trial_calib_sums_splits(int64_t M, int64_t S) {
+    if (M <= 0 || S <= 0) return 0;
+    return vm::en_hist_splits(M, S);
+}
+
+extern "C" int64_t vm_speaker_trial_calib_sums_workspace_bytes(int64_t M, int E, int64_t S) {
+    if (M < 0 || E <= 0 || S <= 0) return 0;
+    return vm::en_scratch_bytes(M, E, S) + vm::en_calib_part_bytes(M, S);
+}
+
+extern "C" int vm_speaker_trial_calib_sums(const float* q, const int32_t* q_label, int64_t M, int E, const double* sums, const double* msum,
+                                           const int32_t* count, int64_t S, int kind, int leave_one_out, const float* mu_q,
+                                           const float* rsig_q, const float* mu_s, const float* rsig_s, const float* mu_own,
+                                           const float* rsig_own, double a, double b, double tau, double* calib, void* ws, void* stream) {
+    return vm::model_trial_calib("vm_speaker_trial_calib_sums", vm::EnCall{q, q_label, M, E, sums, msum, count, S, kind, leave_one_out},
+                                 vm::EnNorm{mu_q, rsig_q, mu_s, rsig_s, mu_own, rsig_own}, a, b, tau, calib, ws, stream);
 }

@@ -1,8 +1,9 @@
-// "Rows against speaker models": the ONE tile kernel behind vm_[plda_]speaker_{identify, trial_hist, trial_hist_norm} and the two
-// launchers of those six entry points.  model_tile_kernel<Score, HIST, NORM> holds, once and as plain statements, the tile geometry and
-// thread map, the row prologue, the prefetch / stash stage pipeline, the accumulate loop, the model loop and everything that happens to a
-// finished fp32 score -- the order of the trials of one query ((uint32 key, speaker), NaN last), rank / best, the class histogram with
-// pair_hist_kernel's (verif.hip) window, slot and NaN conventions.  What differs between the back ends comes from the score policy
+// "Rows against speaker models": the ONE tile kernel behind vm_[plda_]speaker_{identify, trial_hist, trial_hist_norm, trial_calib_sums}
+// and the three launchers of those eight entry points.  model_tile_kernel<Score, MODE, NORM> holds, once and as plain statements, the
+// tile geometry and thread map, the row prologue, the prefetch / stash stage pipeline, the accumulate loop, the model loop and
+// everything that happens to a finished fp32 score -- the order of the trials of one query ((uint32 key, speaker), NaN last), rank /
+// best; the class histogram with pair_hist_kernel's (verif.hip) window, slot and NaN conventions; the calibration sums with
+// pair_calib_kernel's (calib.hip) terms and fixed-order reduction.  What differs between the back ends comes from the score policy
 // `Score` (EnScore<KIND>, enrol.hip: the geometric kinds; PeScore, plda_enrol.hip: multi-session PLDA), passed by value:
 //   EC, NM                       components per stage and float64 model operands staged through LDS beside the query operand
 //   op[NM], width, PADDED[, pitch] the model operands ((S, width) float64) and the components scored; PADDED: q's rows are `pitch`
@@ -16,10 +17,14 @@
 // selects, an unrolled window loop of another shape), which is why the epilogue used to be shared as text macros.  Inside one templated
 // body the same statements are the kernel's own; the policy's members are scalars and a two-element array, and vanish on inlining.
 #pragma once
+#include "calib_terms.hpp"
 #include "enrol_score.hpp"
 #include "score_tile.hpp"
 
 namespace vm {
+
+// what model_tile_kernel does with a finished score: the matrix / rank / best of identify, the class histogram, the calibration sums
+enum class EnMode { IDENTIFY, HIST, CALIB };
 
 constexpr int EN_TQ = 64, EN_TS = 64, EN_LD = 66, EN_MAX_WIN = 4;
 constexpr int EN_LDS_HIST_WORDS = 2 * 4 * (1024 + 3);   // = VH_LDS_HIST_WORDS (verif.hip): the same limits on windows and bins
@@ -39,23 +44,35 @@ struct EnNorm {
     const float *mu_q, *rsig_q, *mu_s, *rsig_s, *mu_own, *rsig_own;
 };
 
-// grid (query tiles of 64 rows, splits of the model tiles (HIST only)); 256 threads: ts = tid & 15 owns the models
+// The calibration mode's arguments: llr = a s + b at the offset tau (cal_terms, calib_terms.hpp) and the workgroups' partial sums
+// part (CAL_SUMS, gridDim.x * gridDim.y) float64, workgroup (x, y) owning column y * gridDim.x + x.  The other modes never read it.
+struct EnCalib {
+    double a, b, tau;
+    double* part;
+};
+
+// grid (query tiles of 64 rows, splits of the model tiles (HIST and CALIB)); 256 threads: ts = tid & 15 owns the models
 // {2 ts, 2 ts + 1, 32 + 2 ts, 33 + 2 ts} of a tile, tq = tid >> 4 the queries 4 tq .. 4 tq + 3, in 4 x 4 float64 accumulators.  `own`: the
 // score of every row against its OWN speaker (under leave-one-out that model differs from the shared one: the cell takes this score
-// rather than a patched one).  HIST false: the score matrix (NaN where the cell is no trial) and, per row, the count of speakers before
+// rather than a patched one).  IDENTIFY: the score matrix (NaN where the cell is no trial) and, per row, the count of speakers before
 // the own one and the best (key, speaker) -- integer sums and minima kept in registers over all model tiles and merged over the 16 lanes
-// of a row at the end.  HIST true: every trial is counted once per window -- under / over in the lane's registers, a bin in the
-// workgroup's u32 LDS histogram -- or, a NaN, once in the lane's NaN count; one flush of 64-bit integer atomics per workgroup.  NORM
-// (HIST only): the finished score becomes vh_norm's (score_tile.hpp) s' = 0.5f ((d - mu_q) rsig_q + (d - mu_M) rsig_M) before it is
-// binned, (mu_M, rsig_M) the own pair under leave-one-out in the own-speaker cell, the model's everywhere else.
-template <class Score, bool HIST, bool NORM>
+// of a row at the end.  HIST: every trial is counted once per window -- under / over in the lane's registers, a bin in the
+// workgroup's u32 LDS histogram -- or, a NaN, once in the lane's NaN count; one flush of 64-bit integer atomics per workgroup.  CALIB:
+// every trial adds its six cal_terms to the lane's float64 accumulators of its class (u32 counts; a NaN or infinite score is counted
+// as skipped and adds nothing else), carried over the workgroup's model tiles in ascending tile order; then the shuffle tree per wave,
+// the four waves in order through LDS, and the workgroup's column of cal.part -- zeros where its split holds no tile; no LDS
+// histogram, no atomics.  NORM (HIST and CALIB): the finished score becomes vh_norm's (score_tile.hpp) s' = 0.5f ((d - mu_q) rsig_q +
+// (d - mu_M) rsig_M) before it is binned or summed, (mu_M, rsig_M) the own pair under leave-one-out in the own-speaker cell, the
+// model's everywhere else.
+template <class Score, EnMode MODE, bool NORM>
 __global__ __launch_bounds__(256) void model_tile_kernel(Score sc, const float* __restrict__ q, const int32_t* __restrict__ q_label, int64_t M,
                                                          const int32_t* __restrict__ count, int64_t S, int loo,
                                                          const float* __restrict__ own, float* __restrict__ scores,
                                                          float* __restrict__ true_score, int32_t* __restrict__ rank,
                                                          float* __restrict__ best_val, int32_t* __restrict__ best_idx, EnWindows win,
                                                          int n_win, int bins, int splits, unsigned long long* __restrict__ ghist,
-                                                         EnNorm nrm) {
+                                                         EnNorm nrm, EnCalib cal) {
+    constexpr bool HIST = MODE == EnMode::HIST, CALIB = MODE == EnMode::CALIB;
     constexpr int EC = Score::EC, NM = Score::NM;
     constexpr int QP = EC / 16, MP = EC / 8;   // per thread and stage: pieces of 4 floats of q, pieces of 2 doubles of each model operand
     __shared__ __attribute__((aligned(16))) double qs[EC * EN_LD];
@@ -69,7 +86,12 @@ __global__ __launch_bounds__(256) void model_tile_kernel(Score sc, const float* 
     const int tps = (n_tiles + splits - 1) / splits;
     const int t_lo = blockIdx.y * tps;
     const int t_hi = min(n_tiles, t_lo + tps);
-    if (t_lo >= t_hi) return;   // workgroup-uniform
+    if (t_lo >= t_hi) {   // workgroup-uniform
+        if constexpr (CALIB) {
+            if (tid < CAL_SUMS) cal.part[(int64_t)tid * gridDim.x * gridDim.y + (int64_t)blockIdx.y * gridDim.x + blockIdx.x] = 0.0;
+        }
+        return;
+    }
     if (HIST) {
         for (int i = tid; i < n_words; i += 256) hist[i] = 0u;
     }
@@ -106,6 +128,13 @@ __global__ __launch_bounds__(256) void model_tile_kernel(Score sc, const float* 
     uint32_t und[EN_MAX_WIN][2], ovr[EN_MAX_WIN][2], nanc[2] = {0u, 0u};
 #pragma unroll
     for (int v = 0; v < EN_MAX_WIN; ++v) und[v][0] = und[v][1] = ovr[v][0] = ovr[v][1] = 0u;
+    // CALIB: per class the six sums of cal_terms, the trials summed and the trials skipped (at most 16 per lane and tile: no overflow)
+    double csum[2][6];
+    uint32_t ccnt[2] = {0u, 0u}, cskp[2] = {0u, 0u};
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) csum[c][k] = 0.0;
 
     const int W = sc.width;
     int pitch = W;
@@ -228,7 +257,22 @@ __global__ __launch_bounds__(256) void model_tile_kernel(Score sc, const float* 
                     const bool o_ = loo && is_own;
                     d = vh_norm(d, n_mq[i], n_rq[i], o_ ? n_mo[i] : n_ms, o_ ? n_ro[i] : n_rs);
                 }
-                if (!HIST) {
+                if constexpr (CALIB) {
+                    // pair_calib_kernel's masked form: the terms of 0.0 where the cell adds nothing, selected away
+                    const bool fin = (__float_as_uint(d) & 0x7f800000u) != 0x7f800000u;   // neither NaN nor infinite
+                    const bool use = trial && fin;
+                    ccnt[0] += use && is_own;
+                    ccnt[1] += use && !is_own;
+                    cskp[0] += trial && !fin && is_own;
+                    cskp[1] += trial && !fin && !is_own;
+                    double x[6];
+                    cal_terms(use ? (double)d : 0.0, is_own, cal.a, cal.b, cal.tau, x);
+#pragma unroll
+                    for (int k = 0; k < 6; ++k) {
+                        csum[0][k] += (use && is_own) ? x[k] : 0.0;
+                        csum[1][k] += (use && !is_own) ? x[k] : 0.0;
+                    }
+                } else if (!HIST) {
                     if (scores != nullptr && okm[i] && oks) scores[m * S + s] = trial ? d : nanf_;
                     if (trial) {
                         const uint32_t k = score_key_nan_last(d);
@@ -261,7 +305,38 @@ __global__ __launch_bounds__(256) void model_tile_kernel(Score sc, const float* 
         }
     }
 
-    // The end of a workgroup, reached by all of its threads (the histogram flush holds a barrier).
+    // The end of a workgroup, reached by all of its threads (the histogram flush and the calibration reduction hold a barrier).
+    auto wave_sum_u = [](uint32_t x) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+        return x;
+    };
+    if constexpr (CALIB) {
+        // the wave's sums (a fixed shuffle tree; the counts are integers), the four waves in order, the workgroup's column of part
+        __shared__ double red[4][CAL_SUMS];
+        const int w = tid >> 6;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const uint32_t n = wave_sum_u(ccnt[c]), ns = wave_sum_u(cskp[c]);
+            if (lane == 0) {
+                red[w][c * CAL_TERMS + 0] = (double)n;
+                red[w][c * CAL_TERMS + 1] = (double)ns;
+            }
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const double v = wave_sum_d(csum[c][k]);
+                if (lane == 0) red[w][c * CAL_TERMS + 2 + k] = v;
+            }
+        }
+        __syncthreads();
+        if (tid < CAL_SUMS) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v += red[k][tid];
+            cal.part[(int64_t)tid * gridDim.x * gridDim.y + (int64_t)blockIdx.y * gridDim.x + blockIdx.x] = v;
+        }
+        return;
+    }
     if (!HIST) {
         // merge over the 16 lanes of a query row -- integer sums and minima, any order gives the same result -- and lane ts == 0 writes
 #pragma unroll
@@ -287,11 +362,6 @@ __global__ __launch_bounds__(256) void model_tile_kernel(Score sc, const float* 
         return;
     }
     // the lanes' under / over / NaN counts join the LDS histogram, which is flushed once with 64-bit integer atomics into ghist
-    auto wave_sum_u = [](uint32_t x) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        return x;
-    };
     const uint32_t nan0 = wave_sum_u(nanc[0]), nan1 = wave_sum_u(nanc[1]);
 #pragma unroll
     for (int v = 0; v < EN_MAX_WIN; ++v) {
@@ -347,10 +417,10 @@ static inline int en_check_norm(const char* what, const EnNorm& n, int leave_one
     return 0;
 }
 
-// The two launchers.  `Call` is a back end's arguments (EnCall, enrol.hip; PeCall, plda_enrol.hip): q, q_label, M, count, S, loo, and
+// The three launchers.  `Call` is a back end's arguments (EnCall, enrol.hip; PeCall, plda_enrol.hip): q, q_label, M, count, S, loo, and
 //   check(what, ws)        its argument checks
 //   stage(ws, st, launch)  its scratch layout in ws and its prepare launches, then launch(score policy, own-speaker scores) once
-// Either runs checks -> windows -> scratch -> prepare -> grid / splits -> kernel.
+// Each runs checks -> windows -> scratch -> prepare -> grid / splits -> kernel (-> the final sum of the calibration partials).
 struct EnOutputs {
     float *scores, *true_score;
     int32_t* rank;
@@ -366,9 +436,9 @@ static int model_identify(const char* what, const Call& a, const EnOutputs& o, v
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)cdiv(a.M, EN_TQ), 1);
     a.stage(ws, st, [&](auto sc, const float* own) {
-        hipLaunchKernelGGL((model_tile_kernel<decltype(sc), false, false>), grid, dim3(256), 0, st, sc, a.q, a.q_label, a.M, a.count, a.S, a.loo,
-                           own, o.scores, o.true_score, o.rank, o.best_val, o.best_idx, EnWindows{}, 0, 0, 1, (unsigned long long*)nullptr,
-                           EnNorm{});
+        hipLaunchKernelGGL((model_tile_kernel<decltype(sc), EnMode::IDENTIFY, false>), grid, dim3(256), 0, st, sc, a.q, a.q_label, a.M, a.count,
+                           a.S, a.loo, own, o.scores, o.true_score, o.rank, o.best_val, o.best_idx, EnWindows{}, 0, 0, 1,
+                           (unsigned long long*)nullptr, EnNorm{}, EnCalib{});
     });
     return check_launch(what);
 }
@@ -391,11 +461,48 @@ static int model_trial_hist(const char* what, const Call& a, const int64_t* host
         auto launch = [&](auto kernel, const EnNorm& n) {
             hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, sc, a.q, a.q_label, a.M, a.count, a.S, a.loo, own, (float*)nullptr,
                                (float*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr, win, n_windows, bins, splits,
-                               (unsigned long long*)hist, n);
+                               (unsigned long long*)hist, n, EnCalib{});
         };
-        if (norm == nullptr) launch(model_tile_kernel<decltype(sc), true, false>, EnNorm{});
-        else launch(model_tile_kernel<decltype(sc), true, true>, *norm);
+        if (norm == nullptr) launch(model_tile_kernel<decltype(sc), EnMode::HIST, false>, EnNorm{});
+        else launch(model_tile_kernel<decltype(sc), EnMode::HIST, true>, *norm);
     });
+    return check_launch(what);
+}
+
+// The calibration sums' partials: the histogram's grid, one column of CAL_SUMS doubles per workgroup, in front of the call's scratch
+static inline int64_t en_calib_parts(int64_t M, int64_t S) { return M > 0 && S > 0 ? cdiv(M, EN_TQ) * en_hist_splits(M, S) : 0; }
+static inline int64_t en_calib_part_bytes(int64_t M, int64_t S) { return en_calib_parts(M, S) * CAL_SUMS * 8 + 256; }
+
+// calib (2, CAL_TERMS) float64 is WRITTEN: the kernel's partials, then calib_final_kernel over them (M == 0: zeros).  The six
+// statistics are NULL all together (raw scores: the plain instantiation) or follow en_check_norm.
+template <class Call>
+static int model_trial_calib(const char* what, const Call& a, const EnNorm& norm, double ca, double cb, double tau, double* calib, void* ws,
+                             void* stream) {
+    const bool normed = norm.mu_q || norm.rsig_q || norm.mu_s || norm.rsig_s || norm.mu_own || norm.rsig_own;
+    if (normed) {
+        if (int rc = en_check_norm(what, norm, a.loo)) return rc;
+    }
+    if (int rc = a.check(what, ws)) return rc;
+    VM_REQUIRE(calib != nullptr, "%s: null pointer", what);
+    VM_REQUIRE((((uintptr_t)calib) & 7) == 0, "%s: calib must be 8-byte aligned", what);
+    VM_REQUIRE(ca - ca == 0.0 && cb - cb == 0.0 && tau - tau == 0.0, "%s: a, b and tau must be finite", what);
+    hipStream_t st = (hipStream_t)stream;
+    double* part = (double*)en_align(ws);
+    const int64_t n_part = en_calib_parts(a.M, a.S);
+    if (a.M > 0) {
+        const int splits = (int)en_hist_splits(a.M, a.S);
+        const dim3 grid((unsigned)cdiv(a.M, EN_TQ), (unsigned)splits);
+        a.stage(part + n_part * CAL_SUMS, st, [&](auto sc, const float* own) {
+            auto launch = [&](auto kernel) {
+                hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, sc, a.q, a.q_label, a.M, a.count, a.S, a.loo, own, (float*)nullptr,
+                                   (float*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int32_t*)nullptr, EnWindows{}, 0, 0, splits,
+                                   (unsigned long long*)nullptr, norm, EnCalib{ca, cb, tau, part});
+            };
+            if (!normed) launch(model_tile_kernel<decltype(sc), EnMode::CALIB, false>);
+            else launch(model_tile_kernel<decltype(sc), EnMode::CALIB, true>);
+        });
+    }
+    hipLaunchKernelGGL(calib_final_kernel, dim3(1), dim3(64 * CAL_SUMS), 0, st, (const double*)part, n_part, calib);
     return check_launch(what);
 }
 

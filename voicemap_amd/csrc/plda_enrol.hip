@@ -14,12 +14,12 @@
 // Kernels.  pe_prep_kernel: per speaker mu_s = beta[count_s] * sum_s, A_s = A[count_s] and C_s = C[count_s] (zeros where the count is
 // out of range: never a trial), so that the tile loop reads two model operands and one query operand.  pe_own_kernel: one thread per
 // query row, g_m and the score against the row's OWN speaker (under leave-one-out that model differs from the shared one: the score is
-// computed from the sums and the tables rather than patched).  The tile kernel is enrol_tile.hpp's model_tile_kernel<PeScore, HIST,
+// computed from the sums and the tables rather than patched).  The tile kernel is enrol_tile.hpp's model_tile_kernel<PeScore, MODE,
 // NORM>, the one kernel shared with enrol.hip -- 64 query rows x 64 models, thread (tq, ts) holding 4 x 4 float64 accumulators -- with
 // the score policy PeScore below: THREE float64 operands staged through LDS (w, mu, A), hence stages of 16 components.  The launchers
 // are enrol_tile.hpp's too, on the call PeCall (checks, scratch layout, the two staging launches): vm_plda_speaker_identify,
-// _trial_hist and _trial_hist_norm are model_identify / model_trial_hist on a PeCall.  One pe_acc / pe_finish: the three entry points
-// score bit-identically.  No float atomics.
+// _trial_hist, _trial_hist_norm and _trial_calib_sums are model_identify / model_trial_hist / model_trial_calib on a PeCall.  One
+// pe_acc / pe_finish: the four entry points score bit-identically.  No float atomics.
 #include "enrol_tile.hpp"
 
 namespace vm {
@@ -204,4 +204,19 @@ extern "C" int vm_plda_speaker_trial_hist_norm(const float* q, const int32_t* q_
     return vm::model_trial_hist("vm_plda_speaker_trial_hist_norm",
                                 vm::PeCall{q, q_label, M, P, D, sums, count, S, A, beta, C, G, n_max, leave_one_out}, host_windows, n_windows,
                                 bins, hist, &n, ws, stream);
+}
+
+extern "C" int64_t vm_plda_speaker_trial_calib_sums_workspace_bytes(int64_t M, int D, int64_t S) {
+    if (M < 0 || D <= 0 || S <= 0) return 0;
+    return vm::pe_scratch_bytes(M, D, S) + vm::en_calib_part_bytes(M, S);
+}
+
+extern "C" int vm_plda_speaker_trial_calib_sums(const float* q, const int32_t* q_label, int64_t M, int P, int D, const double* sums,
+                                                const int32_t* count, int64_t S, const double* A, const double* beta, const double* C,
+                                                const double* G, int n_max, int leave_one_out, const float* mu_q, const float* rsig_q,
+                                                const float* mu_s, const float* rsig_s, const float* mu_own, const float* rsig_own,
+                                                double a, double b, double tau, double* calib, void* ws, void* stream) {
+    return vm::model_trial_calib("vm_plda_speaker_trial_calib_sums",
+                                 vm::PeCall{q, q_label, M, P, D, sums, count, S, A, beta, C, G, n_max, leave_one_out},
+                                 vm::EnNorm{mu_q, rsig_q, mu_s, rsig_s, mu_own, rsig_own}, a, b, tau, calib, ws, stream);
 }

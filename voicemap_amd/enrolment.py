@@ -54,10 +54,19 @@ population standard deviation rounded to fp32 once, rsig = fp32(1 / float64(sigm
 The trial (m, s) is then scored, in fp32 with every operation rounded on its own, ``a = s - mu_q[m]; b = s - mu_M;
 s' = 0.5 (a rsig_q[m] + b rsig_M)`` with (mu_M, rsig_M) = (mu_own[m], rsig_own[m]) for the own speaker's trial under leave-one-out and
 (mu_s[s], rsig_s[s]) otherwise (``normalise_trials_numpy``); trials, classes and the exact metrics are unchanged.  ``identify`` ranks by
-the raw score: normalised ranking is out of scope, and so is the calibration of model trials.
+the raw score: normalised ranking is out of scope.
+
+Calibration of model trials (``fit_model_calibration``, ``model_cllr``, ``model_detection_costs``): the ``calibration`` module's affine
+map llr = a s + b, its objective, Newton fit and Cllr, over the model trials above instead of the pair trials -- a target iff the model
+is the row's own speaker, s the raw or (``norm=``) normalised fp32 trial score, a NaN or infinite s skipped and counted.  One pass of
+``vm_[plda_]speaker_trial_calib_sums`` (``model_calib_sums``; twin ``model_calib_sums_numpy``) gives the (2, 8) float64 sums of
+``calibration.SUM_NAMES``: the third output mode of the tile kernel behind ``identify`` and the histograms, so its scores are theirs
+bit for bit, reduced in a fixed order without float atomics.  A ``Calibration`` fitted here carries ``trials == "model"``; the pair
+evaluators refuse it and these refuse a pair one.
 
 Under torchrun every rank computes the sums over all rows itself (N x E reads; the models are then bit-identical everywhere), takes its
-``parallel.shard_range`` of the query rows, and the integer rank histogram / trial histograms are summed over ranks.
+``parallel.shard_range`` of the query rows, and the integer rank histogram / trial histograms -- and the float64 calibration sums,
+so that every rank takes the same Newton steps -- are summed over ranks.
 """
 from __future__ import annotations
 
@@ -68,6 +77,7 @@ import numpy as np
 import torch
 
 from . import _lib, parallel
+from . import calibration as CAL
 from . import verification as V
 
 KINDS = _lib.DIST
@@ -778,3 +788,109 @@ def model_trial_accuracy_at_threshold(models: SpeakerModels, cache, t: float, le
     test set."""
     hist_fn, _, _ = _hist_source(models, cache, leave_one_out, norm)
     return V.counts_at_threshold(hist_fn, t)
+
+
+# ---- calibration of model trials ---------------------------------------------------------------------------------------------------
+def model_calib_sums_numpy(scores, trial, q_label, a: float, b: float, tau: float) -> np.ndarray:
+    """numpy twin of ``vm_[plda_]speaker_trial_calib_sums`` on an (M, S) fp32 score matrix and its trial mask: ``calibration.
+    calib_sums_numpy`` over the cells where ``trial`` is set, a target iff the column is the row's ``q_label``."""
+    s = np.asarray(scores, dtype=np.float32)
+    trial = np.asarray(trial, dtype=bool)
+    target = np.arange(s.shape[1])[None, :] == np.asarray(q_label).reshape(-1, 1)
+    return CAL.calib_sums_numpy(s[trial], target[trial], a, b, tau)
+
+
+def _trial_calib_sums(q, q_label, sums, msum, count, kind, tables, leave_one_out, a, b, tau, stats=None) -> torch.Tensor:
+    """One pass of ``vm_speaker_trial_calib_sums`` / ``vm_plda_speaker_trial_calib_sums`` (``tables``): the (2, 8) float64 sums on the
+    device.  ``stats``: the six arrays of ``speaker_trial_hist_norm`` (the normalised scores) or None (the raw ones)."""
+    q, q_label = _rows_labels(q, q_label)
+    binding = _binding(q, sums, msum, count, kind, tables)
+    out = torch.zeros(2, 8, dtype=torch.float64, device=q.device)
+    M, S = int(q.shape[0]), int(count.shape[0])
+    if M > 0:
+        ptrs = (None,) * 6
+        if stats is not None:
+            stats = [None if t is None else t.to(device=q.device, dtype=torch.float32).contiguous() for t in stats]
+            for t, n in zip(stats, (M, M, S, S, M, M)):
+                if t is not None and int(t.numel()) != n:
+                    raise ValueError("a statistics array holds %d entries, not %d" % (int(t.numel()), n))
+            ptrs = tuple(None if t is None else t.data_ptr() for t in stats)
+        _call(binding, "trial_calib_sums", q, (q_label.data_ptr(),),
+              (1 if leave_one_out else 0,) + ptrs + (float(a), float(b), float(tau), out.data_ptr()))
+    return out
+
+
+def speaker_trial_calib_sums(q: torch.Tensor, q_label: torch.Tensor, sums, msum, count, kind, leave_one_out: bool, a: float, b: float,
+                             tau: float, stats: Optional[Sequence[Optional[torch.Tensor]]] = None, tables=None) -> torch.Tensor:
+    """``vm_speaker_trial_calib_sums`` (``tables``: ``vm_plda_speaker_trial_calib_sums``): the (2, 8) float64 calibration sums
+    (``calibration.SUM_NAMES``; class 0 = the own speaker's model) of the trials of ``speaker_trial_hist`` at (a, b, tau), on the
+    device.  ``stats``: as ``speaker_trial_hist_norm`` takes them, for the normalised scores."""
+    return _trial_calib_sums(q, q_label, sums, msum, count, kind, tables, leave_one_out, a, b, tau, stats)
+
+
+def _calib_source(models, cache, leave_one_out, norm, rows=None):
+    """``sums_fn(a, b, tau)`` -> (2, 8) numpy over the model trials: ``_hist_source``'s queries, leave-one-out and sharding.  ``rows``
+    given: that range of the queries alone, no communication; otherwise this rank's shard, summed over the ranks."""
+    q, q_label, loo, (lo, hi), n_q, _ = _shard(models, cache, leave_one_out, rows)
+    check_model_norm(models, n_q, loo, norm)
+    stats = None if norm is None else norm.stats(lo, hi)
+
+    def sums_fn(a, b, tau):
+        out = _trial_calib_sums(q, q_label, *models.backend, loo, a, b, tau, stats)
+        return (out if rows is not None else parallel.sum_ranks(out)).cpu().numpy()
+    return sums_fn
+
+
+def model_calib_sums(models: SpeakerModels, cache, a: float, b: float, tau: float, leave_one_out: Optional[bool] = None,
+                     norm: Optional[ModelScoreNorm] = None, rows: Optional[Tuple[int, int]] = None) -> np.ndarray:
+    """The (2, 8) float64 sums (``calibration.SUM_NAMES``; class 0 = target) of the model trials of ``cache`` against ``models`` at
+    (a, b, tau): one pass of ``vm_[plda_]speaker_trial_calib_sums``.  Queries and ``leave_one_out`` as in ``identify``.  ``rows``: only
+    the queries [lo, hi); by default this rank's ``parallel.shard_range``, and under torchrun the sums of all ranks are added.
+    ``norm``: on the normalised scores (``model_score_norm`` of the same models, cache and leave-one-out)."""
+    return _calib_source(models, cache, leave_one_out, norm, rows)(a, b, tau)
+
+
+def fit_model_calibration(models: SpeakerModels, cache, prior: float = 0.5, leave_one_out: Optional[bool] = None,
+                          norm: Optional[ModelScoreNorm] = None, max_iter: int = 50) -> CAL.Calibration:
+    """``calibration.fit_calibration`` on the model trials of ``cache`` against ``models``: the same objective, starting point, Newton
+    steps and stopping rule, one ``vm_[plda_]speaker_trial_calib_sums`` pass per evaluation.  The result carries ``score =
+    models.distance``, ``normalised = norm is not None`` and ``trials = "model"``."""
+    return CAL._fit(_calib_source(models, cache, leave_one_out, norm), prior, models.distance, norm is not None, max_iter, "model")
+
+
+def _check_model_calibration(models, calibration, norm):
+    if calibration.trials != "model":
+        raise ValueError("the calibration was fitted on %s trials, not model trials" % calibration.trials)
+    if calibration.score != models.distance:
+        raise ValueError("the calibration was fitted on %r scores, the models score %r" % (calibration.score, models.distance))
+    if (norm is not None) != bool(calibration.normalised):
+        raise ValueError("the calibration was fitted on %s scores" % ("normalised" if calibration.normalised else "raw"))
+
+
+def model_cllr(models: SpeakerModels, cache, calibration, leave_one_out: Optional[bool] = None,
+               norm: Optional[ModelScoreNorm] = None) -> float:
+    """Cllr of the calibrated scores of the model trials of ``cache`` (one pass at tau = 0): 0 is perfect, 1 is what a = b = 0 gives.
+    ``calibration``: fitted by ``fit_model_calibration`` for the same score, raw or normalised as here."""
+    _check_model_calibration(models, calibration, norm)
+    return CAL.cllr_of(model_calib_sums(models, cache, calibration.a, calibration.b, 0.0, leave_one_out, norm))
+
+
+def model_detection_costs(models: SpeakerModels, cache, calibration, points, leave_one_out: Optional[bool] = None,
+                          norm: Optional[ModelScoreNorm] = None, metrics: Optional[Dict] = None) -> list:
+    """``verification.detection_costs`` for model trials.  Per point (P_target, C_miss, C_fa): the entry of ``model_trial_metrics``'s
+    ``dcf`` (``min_dcf`` and where it is reached) plus ``act_dcf``, the cost at the calibration's Bayes threshold ``act_threshold``
+    (``verification.bayes_threshold``, in score units) counted by ``model_trial_accuracy_at_threshold``, with ``far_at_act`` /
+    ``frr_at_act``.  ``calibration``: fitted (on other data) by ``fit_model_calibration`` for the same score, raw or normalised as here.
+    ``metrics``: the result of ``model_trial_metrics(..., dcf_points=points)`` where it has been computed already."""
+    _check_model_calibration(models, calibration, norm)
+    points = V.as_dcf_points(points)
+    ts = [V.bayes_threshold(calibration, pt) for pt in points]   # raises before any pass
+    if metrics is None:
+        metrics = model_trial_metrics(models, cache, leave_one_out, dcf_points=points, norm=norm)
+    out = [dict(d) for d in metrics["dcf"]]
+    if [(d["p_target"], d["c_miss"], d["c_fa"]) for d in out] != points:
+        raise ValueError("``metrics`` was computed for other detection-cost points")
+    for d, pt, t in zip(out, points, ts):
+        at = model_trial_accuracy_at_threshold(models, cache, t, leave_one_out, norm=norm)
+        d.update(act_dcf=V.dcf_value(pt, at["far"], at["frr"]), act_threshold=t, far_at_act=at["far"], frr_at_act=at["frr"])
+    return out

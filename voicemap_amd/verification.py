@@ -747,7 +747,10 @@ def detection_costs(cache, calibration, points, model=None, norm: Optional[Score
     ``act_dcf``, the cost at the calibration's Bayes threshold ``act_threshold`` (``bayes_threshold``, in score units) counted by
     ``accuracy_at_threshold``, with ``far_at_act`` / ``frr_at_act``.  ``calibration``: a ``calibration.Calibration`` fitted (on other
     data) for the same score; with ``norm`` it must have been fitted on normalised scores.  ``metrics``: the result of
-    ``verification_metrics(cache, ..., dcf_points=points)`` where it has been computed already (the sweep is then not repeated)."""
+    ``verification_metrics(cache, ..., dcf_points=points)`` where it has been computed already (the sweep is then not repeated).
+    A calibration of speaker-model trials (``trials == "model"``) is refused: ``enrolment.model_detection_costs`` takes those."""
+    if getattr(calibration, "trials", "pair") != "pair":
+        raise ValueError("the calibration was fitted on %s trials, not pair trials" % calibration.trials)
     if (norm is not None) != bool(calibration.normalised):
         raise ValueError("the calibration was fitted on %s scores" % ("normalised" if calibration.normalised else "raw"))
     points = as_dcf_points(points)
